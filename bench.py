@@ -13,9 +13,14 @@ work-balanced contiguous row ranges (strong scaling); x is replicated; single-sh
 SpMV needs no collective (each rank owns its slice of y).
 value = 2 * nnz_total * K / max-over-ranks wall time.
 
-Prints ONE JSON line on rank 0 with the driver's contract keys plus
+A plain run sets up, warms up, times the --steps steps, writes the output of the
+last timed step if --dump-outputs DIR is given (DIR/y.npy, float32: y of every row;
+past 64 MB a fixed seeded sample of rows, with their indices in DIR/y_rows.npy) and
+prints ONE JSON line on rank 0 with the driver's contract keys plus
   roofline     : algorithmic bytes of this rank's launch / its average device
                  time (HIP events on the launch stream), vs 8 TB/s HBM peak
+--full adds what takes runs or checks of its own (the keys are null without it):
+  parity       : the timed output against the oracle's gold
   cpu_baseline : the oracle's restatement of the reference gold dot loop
                  (inc/spmv_gold.h:17-26) timed on this host (N=1 only): single thread
                  (the reference is single-threaded) and, under all_cores, row-parallel
@@ -120,6 +125,91 @@ def self_launch(args):
     raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, y, world, rank):
+    """--dump-outputs: y of the last timed step, every row (rank 0 gathers the other ranks' slices), as
+    DIR/y.npy in float32; past DUMP_LIMIT_BYTES a fixed, seeded sample of rows, their indices in DIR/y_rows.npy."""
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(y, parts, dst=0)
+        if rank != 0:
+            return
+        y = np.concatenate(parts)
+    os.makedirs(path, exist_ok=True)
+    y = np.ascontiguousarray(y, np.float32)
+    if y.nbytes > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - 4096) // (4 + 8)
+        rows = np.sort(np.random.default_rng(0x5EED).choice(len(y), k, replace=False))
+        np.save(os.path.join(path, "y_rows.npy"), rows.astype(np.float64))
+        y = y[rows]
+    np.save(os.path.join(path, "y.npy"), y)
+
+
+def oracle_legs(args, rp, ci, va, s_rp, s_ci, s_va, x_host, y, n, nnz_total, rank, world):
+    """--full: this rank's rows of the timed output against the oracle's gold -> (cpu_baseline, parity, mismatches);
+    on a single rank the gold is the timed single-thread / all-cores CPU baseline."""
+    from oracle import oracle as O   # checker + reported CPU baseline only
+    cpu = None
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        gold = np.empty(n, np.float32)
+        times = []
+        for _ in range(3):
+            tc = time.perf_counter()
+            O.gold_dot(rp, ci, va, x_host, 1.0, out=gold)
+            times.append(time.perf_counter() - tc)
+        tmed = sorted(times)[1]
+        # the same loop row-parallel on every host core this process may use (OpenMP, rows still summed sequentially)
+        ncores = usable_host_cores()
+        par = np.empty(n, np.float32)
+        ptimes, used = [], 1
+        for _ in range(3):
+            tc = time.perf_counter()
+            _, used = O.gold_dot_all_cores(rp, ci, va, x_host, 1.0, out=par, threads=ncores)
+            ptimes.append(time.perf_counter() - tc)
+        pmed = sorted(ptimes)[1]
+        model = ""
+        try:
+            model = next(l.split(":", 1)[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name"))
+        except (OSError, StopIteration):
+            pass
+        cpu = {"value": round(2.0 * nnz_total / tmed / 1e9, 4), "unit": "GFLOP/s", "cores": 1, "kind": "port",
+               "sample": f"full {args.workload} matrix ({nnz_total} nnz), median of 3 single-thread runs of the "
+                         f"gold dot loop restatement (oracle_gold_dot_f32), {tmed:.3f} s each",
+               "all_cores": {"value": round(2.0 * nnz_total / pmed / 1e9, 4), "unit": "GFLOP/s", "cores": used,
+                             "sample": f"the same loop, rows dealt to {used} OpenMP threads (oracle_gold_dot_f32_omp), "
+                                       f"median of 3, {pmed:.3f} s each",
+                             "same_bits_as_single_thread": bool(np.array_equal(par.view(np.uint32), gold.view(np.uint32)))},
+               "host_cpus": os.cpu_count(), "cpu_model": model}
+        want = gold
+    else:
+        want = O.gold_dot(s_rp, s_ci, s_va, x_host, 1.0)
+    tol = 1e-5 * np.maximum(1.0, np.abs(want.astype(np.float64)))
+    off = np.nonzero(np.abs(y.astype(np.float64) - want.astype(np.float64)) > tol)[0]
+    # A row whose partial sums pass 2^24 is summed inexactly by the sequential float gold itself
+    # (error ~ n*2^-24); there the GPU's tree order legitimately differs by more than 1e-5.  Such a row
+    # is accepted only if the GPU value is within 1e-5 of the exact (float64) dot AND no farther from it
+    # than the gold is.  Everything else is a mismatch.
+    bad, excused = 0, 0
+    chk_rp, chk_ci, chk_va = (rp, ci, va) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else (s_rp, s_ci, s_va)
+    for r in off:
+        a, b = int(chk_rp[r]), int(chk_rp[r + 1])
+        terms = x_host[chk_ci[a:b]].astype(np.float64) * chk_va[a:b].astype(np.float64)
+        exact = terms.sum()
+        # (non-integer weights: every row rounds, in gold and on the GPU alike; the yardstick is then the exact dot)
+        if ((np.abs(terms).sum() >= 2 ** 24 or args.real_values) and abs(y[r] - exact) <= 1e-5 * max(1.0, abs(exact))
+                and (abs(y[r] - exact) <= abs(want[r] - exact) or args.real_values)):
+            excused += 1
+        else:
+            bad += 1
+    parity = {"checked_rows": len(y), "mismatches_rel_1e-5": bad,
+              "rows_where_gold_itself_is_inexact_and_gpu_is_closer_to_exact": excused,
+              "bit_exact_rows": int((y == want).sum())}
+    return cpu, parity, bad
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -128,9 +218,13 @@ def main():
     ap.add_argument("--workload", default="powerlaw-10M-200M", choices=sorted(WORKLOADS))
     ap.add_argument("--rows", type=int, default=None, help="override size (testing only; makes the number non-headline)")
     ap.add_argument("--nnz", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the output against the oracle and run the extra legs (CPU baseline, other value codings)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/y.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-ablation", action="store_true",
-                    help="skip the extra timing of the same matrix with value coding off (N=1 only)")
+                    help="with --full: skip the extra timing of the same matrix with other value codings (N=1 only)")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc pass (corrected); echoed into roofline.traffic")
     ap.add_argument("--real-values", action="store_true",
@@ -221,69 +315,21 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
 
-    # ---- parity of what was just timed (this rank's rows), against the oracle's gold
-    y = out_t.cpu().numpy()[:s_rows]
-    from oracle import oracle as O   # checker + reported CPU baseline only
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        gold = np.empty(n, np.float32)
-        times = []
-        for _ in range(3):
-            tc = time.perf_counter()
-            O.gold_dot(rp, ci, va, x_host, 1.0, out=gold)
-            times.append(time.perf_counter() - tc)
-        tmed = sorted(times)[1]
-        # the same loop row-parallel on every host core this process may use (OpenMP, rows still summed sequentially)
-        ncores = usable_host_cores()
-        par = np.empty(n, np.float32)
-        ptimes, used = [], 1
-        for _ in range(3):
-            tc = time.perf_counter()
-            _, used = O.gold_dot_all_cores(rp, ci, va, x_host, 1.0, out=par, threads=ncores)
-            ptimes.append(time.perf_counter() - tc)
-        pmed = sorted(ptimes)[1]
-        model = ""
-        try:
-            model = next(l.split(":", 1)[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name"))
-        except (OSError, StopIteration):
-            pass
-        cpu = {"value": round(2.0 * nnz_total / tmed / 1e9, 4), "unit": "GFLOP/s", "cores": 1, "kind": "port",
-               "sample": f"full {args.workload} matrix ({nnz_total} nnz), median of 3 single-thread runs of the "
-                         f"gold dot loop restatement (oracle_gold_dot_f32), {tmed:.3f} s each",
-               "all_cores": {"value": round(2.0 * nnz_total / pmed / 1e9, 4), "unit": "GFLOP/s", "cores": used,
-                             "sample": f"the same loop, rows dealt to {used} OpenMP threads (oracle_gold_dot_f32_omp), "
-                                       f"median of 3, {pmed:.3f} s each",
-                             "same_bits_as_single_thread": bool(np.array_equal(par.view(np.uint32), gold.view(np.uint32)))},
-               "host_cpus": os.cpu_count(), "cpu_model": model}
-        want = gold
-    else:
-        want = O.gold_dot(s_rp, s_ci, s_va, x_host, 1.0)
-    tol = 1e-5 * np.maximum(1.0, np.abs(want.astype(np.float64)))
-    off = np.nonzero(np.abs(y.astype(np.float64) - want.astype(np.float64)) > tol)[0]
-    # A row whose partial sums pass 2^24 is summed inexactly by the sequential float gold itself
-    # (error ~ n*2^-24); there the GPU's tree order legitimately differs by more than 1e-5.  Such a row
-    # is accepted only if the GPU value is within 1e-5 of the exact (float64) dot AND no farther from it
-    # than the gold is.  Everything else is a mismatch.
-    bad, excused = 0, 0
-    chk_rp, chk_ci, chk_va = (rp, ci, va) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else (s_rp, s_ci, s_va)
-    for r in off:
-        a, b = int(chk_rp[r]), int(chk_rp[r + 1])
-        terms = x_host[chk_ci[a:b]].astype(np.float64) * chk_va[a:b].astype(np.float64)
-        exact = terms.sum()
-        # (non-integer weights: every row rounds, in gold and on the GPU alike; the yardstick is then the exact dot)
-        if ((np.abs(terms).sum() >= 2 ** 24 or args.real_values) and abs(y[r] - exact) <= 1e-5 * max(1.0, abs(exact))
-                and (abs(y[r] - exact) <= abs(want[r] - exact) or args.real_values)):
-            excused += 1
-        else:
-            bad += 1
-    parity = {"checked_rows": int(s_rows), "mismatches_rel_1e-5": bad,
-              "rows_where_gold_itself_is_inexact_and_gpu_is_closer_to_exact": excused,
-              "bit_exact_rows": int((y == want).sum())}
+    if args.dump_outputs or args.full:
+        y = out_t.cpu().numpy()[:s_rows]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, world, rank)
+
+    # ---- --full: parity of what was just timed (this rank's rows) against the oracle's gold, the CPU baseline
+    # and the legs with other value codings.  A plain run stops at the timed steps.
+    cpu, parity, bad = None, None, 0
+    if args.full:
+        cpu, parity, bad = oracle_legs(args, rp, ci, va, s_rp, s_ci, s_va, x_host, y, n, nnz_total, rank, world)
 
     # ---- transparency leg (N=1): the same matrix without the one-byte value coding, i.e. the layout a
     # matrix with more than 256 distinct values gets; NOT the reported value
     ablation = None
-    if rank == 0 and world == 1 and not args.no_ablation and "values=dict" in A.describe():
+    if args.full and rank == 0 and world == 1 and not args.no_ablation and "values=dict" in A.describe():
         A_raw = eng.upload_csr(s_rows, n, s_rp, s_ci, s_va, value_coding=-1)
         out2_t = torch.zeros_like(out_t)
         out2 = eng.wrap(out2_t.data_ptr(), s_rows)
@@ -308,7 +354,8 @@ def main():
     # 976 -- i.e. a matrix whose values do not fit the one-byte dictionary: two-byte codes (values=dict16), 4 instead
     # of 6 bytes per entry read by phase 1.  Checked against the oracle's gold on ITS values.
     dict16 = None
-    if rank == 0 and world == 1 and not args.no_ablation and "values=dict" in A.describe():
+    if args.full and rank == 0 and world == 1 and not args.no_ablation and "values=dict" in A.describe():
+        from oracle import oracle as O
         va16 = (s_va + np.float32(16) * (np.arange(len(s_va), dtype=np.int64) % 61).astype(np.float32)).astype(np.float32)
         A16 = eng.upload_csr(s_rows, n, s_rp, s_ci, va16)
         out3_t = torch.zeros_like(out_t)

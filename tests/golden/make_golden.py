@@ -25,9 +25,15 @@ Keys of each <name>.npz (all produced by reference code, see ref_driver.cpp):
   pr_meta, pr_first/final     PageRank app loop on the Lift pr kernel (app/pr.cpp constants)
   scc_row_ptr/col_idx/val     SparseMatrix<int> rows after scc_normalise()
   scc_meta, scc_first/final   SCC app loop on the Lift (max,min) kernel (app/scc.cpp constants)
+
+kernel_configs/<algo>/kernel*.json are the reference's example/<algo>/kernel*.json with
+every setting as it is, except "source": the Lift kernel text is replaced by the list of
+the semiring function names it defines (all the host side reads from it, detect_semiring).
 """
 import glob
+import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -42,7 +48,26 @@ DRIVER = os.path.join(ROOT, "oracle", "_ref", "ref_driver")
 DT = {"i32": np.int32, "f32": np.float32}
 
 
+# the names detect_semiring (sparseharness_amd/host/inc/harness.h) looks for, and the (+,x) ones
+SEMIRING_NAMES = ["mult", "add", "doubleMultiplyAdd", "absadd", "clmin", "bool_and", "bool_or", "doubleAndOr",
+                  "int_min", "int_max", "doubleMinMax"]
+
+
+def kernel_configs():
+    for path in sorted(glob.glob(os.path.join(REF, "example", "*", "kernel*.json"))):
+        algo, name = path.split(os.sep)[-2:]
+        with open(path) as f:
+            cfg = json.load(f)
+        names = [w for w in SEMIRING_NAMES if re.search(r"\b%s\s*\(" % w, cfg["source"])]
+        cfg["source"] = "semiring hint, kernel text not stored: " + " ".join(names)
+        os.makedirs(os.path.join(HERE, "kernel_configs", algo), exist_ok=True)
+        with open(os.path.join(HERE, "kernel_configs", algo, name), "w") as f:
+            json.dump(cfg, f, indent=2)
+            f.write("\n")
+
+
 def main():
+    kernel_configs()
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle", "ref")])
     for name in ["matrix", "matrix2", "matrix3", "matrix4", "matrix5"]:
         src = os.path.join(REF, "example", name + ".mtx")

@@ -83,7 +83,7 @@ def test_plan_options_defaults_and_environment(monkeypatch):
     assert o.or_and_bits == 2
 
 
-def test_tiled_kernels_use_no_scratch_and_spill_nothing():
+def test_tiled_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     """The hand-scheduled loaders keep asm-issued loads in flight across compiler-visible code: only sound while
     hipcc neither spills nor uses scratch in those kernels (make asm-check, sparseharness_amd/csrc)."""
     import subprocess
@@ -94,13 +94,13 @@ def test_tiled_kernels_use_no_scratch_and_spill_nothing():
     # and the prefetch check does bite: a copy of a prefetch register slipped in right behind its load is reported
     import re
     import sys
-    lines = open("/tmp/sh_engine_check.s").read().splitlines()
+    lines = open(os.path.join(ROOT, "sparseharness_amd", "csrc", "build", "sh_engine_check.s")).read().splitlines()
     k = next(i for i, l in enumerate(lines) if l.startswith("_ZN2sh18spmv_tiled_phase2s"))
     j = next(i for i in range(k, len(lines)) if lines[i].strip().startswith("global_load_dwordx4") and "#ASMSTART" in lines[i - 1])
     dst = re.search(r"v\[(\d+):", lines[j]).group(1)
     end = next(i for i in range(j, len(lines)) if "#ASMEND" in lines[i])
     doctored = lines[:end + 1] + [f"\tv_mov_b32_e32 v1, v{dst}"] + lines[end + 1:]
-    open("/tmp/sh_engine_doctored.s", "w").write("\n".join(doctored))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "sparseharness_amd", "csrc", "check_prefetch.py"), "/tmp/sh_engine_doctored.s"],
+    (tmp_path / "sh_engine_doctored.s").write_text("\n".join(doctored))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "sparseharness_amd", "csrc", "check_prefetch.py"), str(tmp_path / "sh_engine_doctored.s")],
                        capture_output=True, text=True)
     assert r.returncode == 1 and "touches in-flight" in r.stdout, r.stdout[-400:]

@@ -115,11 +115,11 @@ def test_experiment_sweep_end_to_end(tmp_path):
 
 
 def test_bench_script_emits_the_contract_line():
-    """bench.py at a reduced size: one JSON line with the driver's fields, roofline and cpu_baseline objects."""
+    """bench.py --full at a reduced size: one JSON line with the driver's fields, roofline and cpu_baseline objects."""
     import json
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "300000", "--nnz", "6000000", "--steps", "3",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-800:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -137,7 +137,40 @@ def test_bench_script_emits_the_contract_line():
     assert d["frac_raw_values"] is None or 0 < d["frac_raw_values"] < 1
 
 
-def test_bench_script_two_ranks_rehearsal():
+def exact_spmv(rp, ci, va, x):
+    """y = A x summed in float64 (exact for the benchmark's integer weights and x)."""
+    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    return np.bincount(rows, weights=x[ci].astype(np.float64) * va.astype(np.float64), minlength=len(rp) - 1)
+
+
+def assert_matches_exact(y, want):
+    assert y.dtype == np.float32 and y.shape == want.shape
+    assert np.all(np.abs(y.astype(np.float64) - want) <= 1e-5 * np.maximum(1.0, np.abs(want)))
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_its_output(tmp_path):
+    """A plain bench.py run (no --full): the contract line with ms_per_step for exactly --steps timed steps, none of
+    the --full legs, and --dump-outputs writes y of the last timed step (every row, float32)."""
+    import json
+    import sys
+    from bench import make_workload
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "300000", "--nnz", "6000000", "--steps", "4",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-800:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"]) == ("spmv_gflops", "GFLOP/s", True, "f32")
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["roofline"]["bound"] == "hbm" and d["roofline"]["avg_launch_ms"] > 0
+    for k in ("cpu_baseline", "parity", "ablation_raw_values", "dict16_values", "frac_raw_values", "frac_dict16_values"):
+        assert d[k] is None, k
+    assert sorted(os.listdir(tmp_path / "out")) == ["y.npy"]
+    rp, ci, va, n, _ = make_workload("powerlaw-10M-200M", 300000, 6000000)
+    assert_matches_exact(np.load(tmp_path / "out" / "y.npy"), exact_spmv(rp, ci, va, (1 + np.arange(n) % 7).astype(np.float32)))
+
+
+def test_bench_script_two_ranks_rehearsal(tmp_path):
     """The N > 1 path of bench.py (row sharding, barriers, max-over-ranks, rank-0 JSON) with two ranks sharing
     GPU 0 over gloo (SH_BENCH_REHEARSAL=1); the driver runs the real thing, one rank per GPU over RCCL."""
     import json
@@ -149,8 +182,8 @@ def test_bench_script_two_ranks_rehearsal():
     env = dict(os.environ, SH_BENCH_REHEARSAL="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "400000",
-                        "--nnz", "8000000", "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=900,
-                       cwd=ROOT, env=env)
+                        "--nnz", "8000000", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-1200:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                   # rank 0 only
@@ -158,6 +191,10 @@ def test_bench_script_two_ranks_rehearsal():
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["nnz"] == 8000000
     assert 0 < d["roofline"]["rank_nnz"] < 8000000 and d["parity"]["mismatches_rel_1e-5"] == 0
     assert d["cpu_baseline"] is None and "rehearsal" in d
+    # rank 0 gathers both slices of y into one dump
+    from bench import make_workload
+    rp, ci, va, n, _ = make_workload("powerlaw-10M-200M", 400000, 8000000)
+    assert_matches_exact(np.load(tmp_path / "y.npy"), exact_spmv(rp, ci, va, (1 + np.arange(n) % 7).astype(np.float32)))
 
 
 def test_bench_script_starts_its_own_ranks():
@@ -168,7 +205,7 @@ def test_bench_script_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["SH_BENCH_REHEARSAL"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "400000", "--nnz", "8000000",
-                        "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-1200:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -204,7 +241,7 @@ def test_headline_sizes_through_the_harness_boundary(spec, workload, expect_corr
         assert sql[0].count('"correct"') == 11 and "badvalues" not in sql[0]
     app_ms = float(perf[0].split("median_ms=")[1].split()[0])
     b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "20", "--warmup", "3",
-                        "--no-cpu-baseline", "--no-ablation"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-ablation"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert b.returncode == 0, b.stderr[-800:]
     d = json.loads([l for l in b.stdout.splitlines() if l.startswith("{")][0])
     bench_ms = d["roofline"]["avg_launch_ms"]

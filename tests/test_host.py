@@ -266,10 +266,11 @@ def test_binary_csr_cache_roundtrip_and_invalidation(tmp_path, monkeypatch):
     assert pr[0] == 20
 
 
-REF_EXAMPLE = os.path.join(os.environ.get("SH_REFERENCE", "/root/reference"), "example")
+# the reference's example/<algo>/kernel*.json, settings unchanged, the kernel text reduced to its semiring names
+# (tests/golden/make_golden.py)
+REF_CONFIGS = os.path.join(GOLDEN, "kernel_configs")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EXAMPLE), reason="reference tree not present (GPU box)")
 def test_reference_kernel_configs_are_accepted_unmodified():
     """The reference's own example/<algo>/kernel*.json (7 Lift strategies x 5 apps) load into KernelConfig and
     drive executorEncodeMatrix with the reference's size rules: MHeight padding A-6, MWidthC = cl_width/splitSize
@@ -278,7 +279,7 @@ def test_reference_kernel_configs_are_accepted_unmodified():
     exe = os.path.join(HOST, "bin", "host_selftest")
     want_sr = {"spmv": "plus-times", "pr": "plus-times", "sssp": "min-plus", "bfs": "or-and", "scc": "max-min"}
     for algo, sr in want_sr.items():
-        files = sorted(glob.glob(os.path.join(REF_EXAMPLE, algo, "kernel*.json")))
+        files = sorted(glob.glob(os.path.join(REF_CONFIGS, algo, "kernel*.json")))
         assert len(files) == 7, algo
         mode = "--encode-int" if algo in ("bfs", "scc") else "--encode"
         r = subprocess.run([exe, mode, mtx("matrix3"), *files], capture_output=True, text=True, timeout=120,

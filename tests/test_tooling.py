@@ -95,3 +95,25 @@ def test_build_query_from_files_gz_and_archives(tmp_path):
     assert rows[0][0] == "time" and len(rows) == 7
     assert rows[1] == ["0.0123", "correct", "csr-stream", "1280", "256", "box", "AMD Instinct MI355X (gfx950)", "m3",
                        "0", "0", "RAW_RESULT", "e1"]
+
+
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py's command line (no GPU needed for --help) and its --dump-outputs writer: every row as float32,
+    past the size limit a fixed seeded sample of rows with their indices (the same sample on every run)."""
+    import numpy as np
+    import bench
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    y = np.arange(10000, dtype=np.float32) * np.float32(0.5)
+    bench.dump_outputs(str(tmp_path / "all"), y, 1, 0)
+    assert sorted(os.listdir(tmp_path / "all")) == ["y.npy"]
+    got = np.load(tmp_path / "all" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 12 * 100)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), y, 1, 0)
+    rows = np.load(tmp_path / "s1" / "y_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 100 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "s1" / "y.npy"), y[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "y_rows.npy"))
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= 4096 + 12 * 100 + 256

@@ -10,7 +10,7 @@ for arm in "$@"; do
   (
     if [ "$lib" != "head" ]; then export SH_LIB=$root/sparseharness_amd/$lib SH_LIB_PARTIAL=1; fi
     for kv in $envs; do export "$kv"; done
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $root/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-ablation $BENCH_ARGS > $out/bench.json 2> $out/err.log
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 $root/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-ablation $BENCH_ARGS > $out/bench.json 2> $out/err.log
   )
   python3 - $out "$name" <<'PY'
 import csv, glob, json, os, sys
