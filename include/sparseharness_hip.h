@@ -266,6 +266,48 @@ int sh_spmv_step(sh_engine *e, sh_semiring sr, const sh_csr *A, const sh_vec *x,
                  const sh_vec *y, const void *alpha, const void *beta, sh_vec *out,
                  int64_t x_row_offset, double delta, int32_t *changed_flag_device);
 
+/* ---- several vectors per launch: extends Harness::executeKernel (inc/harness.h:149-195) and the do/while of
+ *      HarnessSSSP::executeRun (app/sssp.cpp:97-176).  The reference multiplies by ONE vector per launch and runs
+ *      `trials` repetitions of one source; it has no counterpart of the two calls below.
+ *      The matrix stream (8 B per entry) is read once for `width` vectors, and the gather of a column fetches
+ *      4 * width contiguous bytes instead of 4.  Measured on an MI355X (DESIGN.md "Multi-vector products",
+ *      profiles/spmm_*.json), as t_spmm / (width * t_spmv under the default plan):
+ *        - x * width cache-resident (170 998 rows, 0.96 M entries): 0.48 / 0.34 / 0.25 / 0.19 at width 4 / 8 / 16 / 32;
+ *        - a matrix that sh_csr_upload gives the x-tiled plan (R-MAT-23: 8.4 M rows, 134 M entries, scattered columns):
+ *          1.6 at width 4 -- NOT worth calling: four tiled sh_spmv are faster -- then 0.81 / 0.43 / 0.33 at 8 / 16 / 32.
+ *          On the power-law 10 M-row / 200 M-entry matrix (uniform columns): 2.4 and 1.2 at width 4 and 8 -- NOT worth
+ *          calling -- then 0.61 / 0.40 at 16 / 32.
+ *          Against `width` launches on the same CSR-stream arrays it is 3.4 to 21 times faster at every width.
+ *        Rule: call it when the matrix' default plan is the CSR-stream plan; otherwise only from width 16 on.
+ *
+ * K vectors per launch.  X, Y, Out are ordinary sh_vec of >= cols*width (X) / rows*width (Y, Out) elements,
+ * element i of vector j at i*width + j, 16-byte aligned.  width in {4, 8, 16, 32}.  alpha, beta: one element, shared by
+ * the columns.  Y may be NULL where sh_spmv allows it.
+ * The matrix must hold its CSR arrays on the device (uploaded with sh_plan_options::plan = 1, or chosen so by the
+ * size rule); otherwise SH_EINVAL with a message that says how to upload.  Out must not alias X.
+ * One launch (plus the long-row fix-up when the matrix has rows above the schedule's threshold).  kernel_ns as sh_spmv.
+ * NOT covered by the multi-vector path: the x-tiled and the bit-blocked plans, row pieces / `report`
+ * (sh_spmv_step_pieces) and the multi-GPU driver. */
+int sh_spmm(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t width, const sh_vec *X, const sh_vec *Y,
+            const void *alpha, const void *beta, sh_vec *Out, uint64_t *kernel_ns);
+
+/* sh_iterate for `width` independent start vectors at once (multi-source SSSP / BFS / SCC labels).
+ * Column j stops at the first launch in which none of its rows fails the convergence test; from then on it is FROZEN:
+ * later launches carry it through unchanged while the other columns go on.  On return column j of X is bit-identical
+ * to what sh_iterate leaves in x when run on that column alone, iters_of_column[j] equals its *iters and
+ * converged_of_column[j] its *converged.  *launches = max_j iters_of_column[j] (<= max_iters).
+ * (For SH_PLUS_TIMES_F32 "alone" means through this path: a row's sum is taken in another order than under sh_spmv,
+ * so the last bits, and with them a count that hangs on |in - out| < delta by a hair, may differ from sh_iterate's.)
+ * X, Y0, scratch: rows*width elements each (the matrix must be square); scratch is clobbered and must not alias X.
+ * iters_of_column, converged_of_column: `width` words; ns_per_launch (may be NULL): capacity max_iters.
+ * max_iters <= 0: nothing is launched, *launches = 0.  The launches are enqueued ahead of the host as sh_iterate's are:
+ * the per-column flags of launch i live in device memory and launch i + 1 reads them as its live columns; the loop ends
+ * when every column is frozen.  Row pieces / `report` / multi-GPU are out of scope here as for sh_spmm. */
+int sh_iterate_multi(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t width, sh_vec *X, const sh_vec *Y0,
+                     sh_vec *scratch, const void *alpha, const void *beta, double delta, int32_t max_iters,
+                     int32_t *launches, int32_t *iters_of_column, int32_t *converged_of_column,
+                     uint64_t *ns_per_launch, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,9 @@ SIGNATURES = {
     "sh_spmv_step_pieces": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(sh_row_pieces), C.c_double, _vp,
                                    C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32))]),
     "sh_csr_piece_state": (_int, [_vp, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "sh_spmm": (_int, [_vp, _int, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "sh_iterate_multi": (_int, [_vp, _int, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_double, _i32,
+                                C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_u64), C.POINTER(_u64)]),
 }
 
 _lib = None

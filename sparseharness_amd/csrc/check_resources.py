@@ -1,16 +1,21 @@
 #!/usr/bin/env python3
-"""Reads hipcc's -Rpass-analysis=kernel-resource-usage remarks and fails if a kernel of the tiled plan uses scratch
-or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+"""Reads hipcc's -Rpass-analysis=kernel-resource-usage remarks and fails if a kernel of the tiled plan, or one of the
+multi-vector kernels (spmm_csr_kernel / spmm_long_fixup, multi.hip.h), uses scratch or spills VGPRs or SGPRs (see the
+asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen = [], 0
+bad, seen, seen_multi = [], 0, set()
 for blk in text.split("remark: Function Name: ")[1:]:
     name = blk.split()[0]
-    if "spmv_tiled" not in name:
+    multi = "spmm_csr" in name or "spmm_long" in name
+    if "spmv_tiled" not in name and not multi:
         continue
-    seen += 1
+    if multi:
+        seen_multi.add(name)
+    else:
+        seen += 1
     scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blk).group(1))
     spill = int(re.search(r"VGPRs Spill: (\d+)", blk).group(1))
     vgprs = int(re.search(r"VGPRs: (\d+)", blk).group(1))
@@ -20,11 +25,17 @@ for blk in text.split("remark: Function Name: ")[1:]:
     # default kernels must have none.
     # (a spilled SGPR lives in a lane of a VGPR the hand-scheduled loaders might otherwise count on, and costs
     # v_writelane / v_readlane traffic wherever it is used)
+    # The multi-vector kernels run 256-thread workgroups, four per CU by their LDS (40 KB each): 16 waves per CU, four
+    # per SIMD, which 128 VGPRs per lane still allow -- the same bound.
     if spill or sspill or vgprs > 128 or scratch:
         bad.append((name, scratch, spill, vgprs, sspill))
 if not seen:
     sys.exit("no spmv_tiled kernels found in the resource-usage remarks")
+# four semirings x four widths of spmm_csr_kernel, and as many fix-up kernels
+n_csr = sum("spmm_csr" in n for n in seen_multi)
+if n_csr != 16 or len(seen_multi) != 32:
+    sys.exit(f"expected 16 spmm_csr_kernel and 16 spmm_long_fixup instantiations in the remarks, found {n_csr} and {len(seen_multi) - n_csr}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled and {len(seen_multi)} multi-vector kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

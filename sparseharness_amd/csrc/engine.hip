@@ -8,6 +8,7 @@
 #include "../../include/sparseharness_hip.h"
 #include "kernels.hip.h"
 #include "bits.hip.h"
+#include "multi.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -36,6 +37,7 @@ struct sh_engine {
   int32_t *d_flags = nullptr;   // per-iteration convergence flags
   int32_t n_flags = 0;
   int32_t *h_flag = nullptr;    // pinned, 64 B: convergence flags of a batch of iterations, read back
+  int32_t *d_mflags = nullptr, *h_mflags = nullptr;   // sh_iterate_multi: MULTI_FLAG_WORDS per-column flags of a batch (device / pinned copy)
   char name[256] = {0};
   int n_cus = 256;
   std::string err;
@@ -52,6 +54,7 @@ struct sh_csr {
   LongRow *d_long = nullptr;
   int32_t n_long = 0;
   uint32_t *d_partial = nullptr;
+  uint32_t *d_partial_multi = nullptr;   // sh_spmm: SPMM_MAX_WIDTH partials per long-row segment
   // x-tiled two-phase plan (kernels.hip.h); built when plan == PLAN_TILED
   int plan = 0;
   bool tuned = false;           // plan confirmed by timing both at upload (autotune_plan)
@@ -103,6 +106,7 @@ struct sh_csr {
   std::string build_note;                     // why the device builder was not used / fell back (empty: nothing to say)
 };
 enum { PLAN_STREAM = 0, PLAN_TILED = 1 };
+constexpr int SPMM_MAX_WIDTH = 32;   // widest sh_spmm
 
 struct sh_vec {
   void *d = nullptr;
@@ -203,6 +207,8 @@ int sh_engine_destroy(sh_engine *e) {
   (void)hipStreamSynchronize(e->stream);
   if (e->d_flags) (void)hipFree(e->d_flags);
   if (e->h_flag) (void)hipHostFree(e->h_flag);
+  if (e->d_mflags) (void)hipFree(e->d_mflags);
+  if (e->h_mflags) (void)hipHostFree(e->h_mflags);
   if (e->ev0) (void)hipEventDestroy(e->ev0);
   if (e->ev1) (void)hipEventDestroy(e->ev1);
   for (auto ev : e->ev_iter) if (ev) (void)hipEventDestroy(ev);
@@ -281,7 +287,7 @@ static void autotune_plan(sh_engine *e, sh_csr *m) {
   } else {
     m->stream_bytes = 0;
     for (void **p : {(void **)&m->d_row_ptr, (void **)&m->d_col, (void **)&m->d_val, (void **)&m->d_blk_row, (void **)&m->d_segs,
-                     (void **)&m->d_long, (void **)&m->d_partial}) {
+                     (void **)&m->d_long, (void **)&m->d_partial, (void **)&m->d_partial_multi}) {
       if (*p) (void)hipFree(*p);
       *p = nullptr;
     }
@@ -600,6 +606,7 @@ int sh_csr_upload_ex(sh_engine *e, int64_t rows, int64_t cols, int64_t nnz, cons
       DEV_ARRAY(m->d_segs, segs.data(), segs.size() * sizeof(LongSeg), 0);
       DEV_ARRAY(m->d_long, longs.data(), longs.size() * sizeof(LongRow), 0);
       DEV_ARRAY(m->d_partial, (const uint32_t *)nullptr, segs.size() * 4, 0);
+      DEV_ARRAY(m->d_partial_multi, (const uint32_t *)nullptr, segs.size() * 4 * SPMM_MAX_WIDTH, 0);
     }
     HIP_TRY_M(hipStreamSynchronize(e->stream)); // host vectors die at the end of this block
   } else if (csr_on_device) {
@@ -694,6 +701,7 @@ int sh_csr_free(sh_engine *e, sh_csr *m) {
   if (m->d_segs) (void)hipFree(m->d_segs);
   if (m->d_long) (void)hipFree(m->d_long);
   if (m->d_partial) (void)hipFree(m->d_partial);
+  if (m->d_partial_multi) (void)hipFree(m->d_partial_multi);
   for (void *p : {(void *)m->d_bins, (void *)m->d_chunks, (void *)m->d_tval, (void *)m->d_tcol, (void *)m->d_gdest,
                   (void *)m->d_pslot, (void *)m->d_gblk, (void *)m->d_ptab, (void *)m->d_ptile, (void *)m->d_ptab_live, (void *)m->d_tile_live, (void *)m->d_P, (void *)m->d_tlong, (void *)m->d_tpartial, (void *)m->d_lrp,
                   (void *)m->d_tcode, (void *)m->d_vdict, (void *)m->d_obase, (void *)m->d_done, (void *)m->d_pcs, (void *)m->d_bits_items,
@@ -1280,6 +1288,213 @@ int sh_iterate(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_vec *x, const s
   }
   *iters = it;
   *converged = term ? 1 : 0;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- K vectors per launch (multi.hip.h) -----------------------------------------------------------------------------
+template <class SR, int K>
+static int launch_spmm(sh_engine *e, const sh_csr *A, const sh_vec *X, const sh_vec *Y, const void *alpha_p,
+                       const void *beta_p, sh_vec *Out, MultiStep st) {
+  using T = typename SR::T;
+  T alpha, beta;
+  memcpy(&alpha, alpha_p, 4);
+  memcpy(&beta, beta_p, 4);
+  const bool use_y = SR::reads_y(beta);
+  CsrDev dev{A->d_row_ptr, A->d_col, A->d_val, (int32_t)A->rows, (int32_t)A->cols};
+  const uint32_t *yp = use_y ? (const uint32_t *)Y->d : nullptr;
+  const int grid = A->n_stream + A->n_segs;
+  if (grid > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmm_csr_kernel<SR, K>), dim3(grid), dim3(BS), 0, e->stream, dev, (const uint32_t *)X->d, yp,
+                       alpha, beta, use_y ? 1 : 0, (uint32_t *)Out->d, A->d_blk_row, A->n_stream, A->d_segs, A->d_partial_multi, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (A->n_long > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmm_long_fixup<SR, K>), dim3((A->n_long * K + 63) / 64), dim3(64), 0, e->stream, A->d_long,
+                       A->n_long, A->d_partial_multi, yp, alpha, beta, use_y ? 1 : 0, (uint32_t *)Out->d, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  return SH_OK;
+}
+
+template <class SR>
+static int launch_spmm_width(sh_engine *e, const sh_csr *A, int32_t width, const sh_vec *X, const sh_vec *Y, const void *alpha,
+                             const void *beta, sh_vec *Out, MultiStep st) {
+  switch (width) {
+  case 4: return launch_spmm<SR, 4>(e, A, X, Y, alpha, beta, Out, st);
+  case 8: return launch_spmm<SR, 8>(e, A, X, Y, alpha, beta, Out, st);
+  case 16: return launch_spmm<SR, 16>(e, A, X, Y, alpha, beta, Out, st);
+  case 32: return launch_spmm<SR, 32>(e, A, X, Y, alpha, beta, Out, st);
+  default: return fail(e, SH_EINVAL, "width %d: sh_spmm serves 4, 8, 16 or 32 vectors per launch", (int)width);
+  }
+}
+
+static int dispatch_spmm(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t width, const sh_vec *X, const sh_vec *Y,
+                         const void *alpha, const void *beta, sh_vec *Out, MultiStep st) {
+  switch (sr) {
+  case SH_PLUS_TIMES_F32: return launch_spmm_width<PlusTimesF32>(e, A, width, X, Y, alpha, beta, Out, st);
+  case SH_MIN_PLUS_F32: return launch_spmm_width<MinPlusF32>(e, A, width, X, Y, alpha, beta, Out, st);
+  case SH_OR_AND_I32: return launch_spmm_width<OrAndI32>(e, A, width, X, Y, alpha, beta, Out, st);
+  case SH_MAX_MIN_I32: return launch_spmm_width<MaxMinI32>(e, A, width, X, Y, alpha, beta, Out, st);
+  default: return fail(e, SH_EINVAL, "unknown semiring %d", (int)sr);
+  }
+}
+
+static bool reads_y(sh_semiring sr, const void *beta_p) {
+  float bf;
+  int32_t bi;
+  memcpy(&bf, beta_p, 4);
+  memcpy(&bi, beta_p, 4);
+  switch (sr) {
+  case SH_PLUS_TIMES_F32: return PlusTimesF32::reads_y(bf);
+  case SH_MIN_PLUS_F32: return MinPlusF32::reads_y(bf);
+  case SH_OR_AND_I32: return OrAndI32::reads_y(bi);
+  default: return MaxMinI32::reads_y(bi);
+  }
+}
+
+// What sh_spmm and sh_iterate_multi ask of their operands (Y == NULL is legal where the epilogue does not read it).
+static int check_multi(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t width, const sh_vec *X, const sh_vec *Y,
+                       const void *alpha, const void *beta, const sh_vec *Out, const char *who) {
+  if (!e || !A || !X || !alpha || !beta || !Out)
+    return fail(e, SH_EINVAL, "%s: NULL argument", who);
+  if ((int)sr < SH_PLUS_TIMES_F32 || (int)sr > SH_MAX_MIN_I32)
+    return fail(e, SH_EINVAL, "%s: unknown semiring %d", who, (int)sr);
+  if (width != 4 && width != 8 && width != 16 && width != 32)
+    return fail(e, SH_EINVAL, "%s: width %d, must be 4, 8, 16 or 32", who, (int)width);
+  if (!A->d_row_ptr || !A->d_blk_row)
+    return fail(e, SH_EINVAL, "%s: the matrix does not hold its CSR arrays on the device (it runs the tiled or the bit-blocked "
+                "plan); upload it with sh_plan_options::plan = 1 (SH_PLAN=stream)", who);
+  const bool use_y = reads_y(sr, beta);
+  if (use_y && !Y)
+    return fail(e, SH_EINVAL, "%s: Y is NULL but the epilogue reads it (beta != 0 or min-plus)", who);
+  if (X->n < A->cols * width)
+    return fail(e, SH_ESHAPE, "%s: X has %lld elements, needs cols * width = %lld", who, (long long)X->n, (long long)(A->cols * width));
+  if (Out->n < A->rows * width)
+    return fail(e, SH_ESHAPE, "%s: Out has %lld elements, needs rows * width = %lld", who, (long long)Out->n, (long long)(A->rows * width));
+  if (use_y && Y->n < A->rows * width)
+    return fail(e, SH_ESHAPE, "%s: Y has %lld elements, needs rows * width = %lld", who, (long long)Y->n, (long long)(A->rows * width));
+  if (Out->d == X->d && A->rows > 0)
+    return fail(e, SH_EINVAL, "%s: Out must not alias X", who);
+  for (const sh_vec *v : {X, use_y ? Y : X, Out})
+    if ((uintptr_t)v->d % 16 != 0)
+      return fail(e, SH_EINVAL, "%s: vectors must be 16-byte aligned (a lane moves four columns at a time)", who);
+  return SH_OK;
+}
+
+extern "C" {
+
+int sh_spmm(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t width, const sh_vec *X, const sh_vec *Y,
+            const void *alpha, const void *beta, sh_vec *Out, uint64_t *kernel_ns) {
+  int rc = check_multi(e, sr, A, width, X, Y, alpha, beta, Out, "sh_spmm");
+  if (rc)
+    return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  if (kernel_ns)
+    HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  rc = dispatch_spmm(e, sr, A, width, X, Y, alpha, beta, Out, MultiStep{nullptr, nullptr, 0.0, nullptr});
+  if (rc)
+    return rc;
+  if (kernel_ns) {
+    HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+    HIP_TRY(e, hipEventSynchronize(e->ev1));
+    float ms = 0.f;
+    HIP_TRY(e, hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    *kernel_ns = (uint64_t)((double)ms * 1e6);
+  }
+  return SH_OK;
+}
+
+int sh_iterate_multi(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t width, sh_vec *X, const sh_vec *Y0,
+                     sh_vec *scratch, const void *alpha, const void *beta, double delta, int32_t max_iters,
+                     int32_t *launches, int32_t *iters_of_column, int32_t *converged_of_column,
+                     uint64_t *ns_per_launch, uint64_t *total_ns) {
+  if (!Y0 || !scratch || !launches || !iters_of_column || !converged_of_column)
+    return fail(e, SH_EINVAL, "sh_iterate_multi: NULL argument");
+  int rc = check_multi(e, sr, A, width, X, Y0, alpha, beta, scratch, "sh_iterate_multi");
+  if (rc)
+    return rc;
+  if (A->rows != A->cols)
+    return fail(e, SH_ESHAPE, "sh_iterate_multi: matrix must be square (inc/common.h:49-52)");
+  if (Y0->n < A->rows * width)
+    return fail(e, SH_ESHAPE, "sh_iterate_multi: Y0 has %lld elements, needs rows * width = %lld", (long long)Y0->n, (long long)(A->rows * width));
+  if ((uintptr_t)Y0->d % 16 != 0)
+    return fail(e, SH_EINVAL, "sh_iterate_multi: vectors must be 16-byte aligned (a lane moves four columns at a time)");
+  *launches = 0;
+  for (int j = 0; j < width; j++) iters_of_column[j] = 0, converged_of_column[j] = 0;
+  if (total_ns)
+    *total_ns = 0;
+  if (max_iters <= 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  // As sh_iterate: launches are enqueued MULTI_BATCH ahead of the host.  Slot k + 1 of d_mflags holds the per-column flags
+  // of launch k of the batch, which launch k + 1 reads as its live columns; slot 0 holds the flags of the previous batch's
+  // last launch.  A column's count = index of its first flag that stayed 0, plus one (the confirming launch included).
+  constexpr int MULTI_BATCH = 8, SLOT = SPMM_MAX_WIDTH, MULTI_FLAG_WORDS = (MULTI_BATCH + 1) * SLOT;
+  if (!e->d_mflags)
+    HIP_TRY(e, hipMalloc((void **)&e->d_mflags, MULTI_FLAG_WORDS * 4));
+  if (!e->h_mflags)
+    HIP_TRY(e, hipHostMalloc((void **)&e->h_mflags, MULTI_FLAG_WORDS * 4, hipHostMallocDefault));
+  if (!e->ev_iter[0])
+    for (auto &ev : e->ev_iter) HIP_TRY(e, hipEventCreate(&ev));
+  sh_vec *in = X, *out = scratch;
+  const sh_vec *y = Y0;
+  int32_t it = 0, n_live = width;
+  uint64_t total = 0;
+  int last_slot = -1;   // slot of the latest launch that ran (-1: none yet, every column is live)
+  while (n_live > 0 && it < max_iters) {
+    const int nb = std::min<int32_t>(MULTI_BATCH, max_iters - it);
+    if (last_slot > 0)
+      HIP_TRY(e, hipMemcpyAsync(e->d_mflags, e->d_mflags + last_slot * SLOT, SLOT * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(e, hipMemsetAsync(e->d_mflags + SLOT, 0, MULTI_BATCH * SLOT * 4, e->stream));
+    HIP_TRY(e, hipEventRecord(e->ev_iter[0], e->stream));
+    for (int k = 0; k < nb; k++) {
+      const int32_t *active = (k == 0 && last_slot < 0) ? nullptr : e->d_mflags + k * SLOT;
+      MultiStep st{e->d_mflags + (k + 1) * SLOT, (const uint32_t *)in->d, delta, active};
+      rc = dispatch_spmm(e, sr, A, width, in, y, alpha, beta, out, st);
+      if (rc)
+        return rc;
+      HIP_TRY(e, hipEventRecord(e->ev_iter[k + 1], e->stream));
+      std::swap(in, out);   // std::swap(input, output), app/sssp.cpp:143
+      y = in;               // setGlobalArg(3, input_mem_ptr), :150
+    }
+    HIP_TRY(e, hipMemcpyAsync(e->h_mflags, e->d_mflags, MULTI_FLAG_WORDS * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    int ran = 0;   // launches of this batch that did run: every one up to the first that left no column live
+    while (ran < nb && n_live > 0) {
+      const int32_t *f = e->h_mflags + (ran + 1) * SLOT;
+      for (int j = 0; j < width; j++)
+        if (!converged_of_column[j] && f[j] == 0) {
+          converged_of_column[j] = 1;
+          iters_of_column[j] = it + ran + 1;
+          n_live--;
+        }
+      ran++;
+    }
+    for (int k = 0; k < ran; k++) {
+      float ms = 0.f;
+      HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_iter[k], e->ev_iter[k + 1]));
+      const uint64_t ns = (uint64_t)((double)ms * 1e6);
+      if (ns_per_launch)
+        ns_per_launch[it + k] = ns;
+      total += ns;
+    }
+    // the gated launches behind the last one that ran wrote nothing: the result is what launch `ran` produced
+    if ((nb - ran) % 2) std::swap(in, out);
+    last_slot = ran;
+    it += ran;
+  }
+  for (int j = 0; j < width; j++)
+    if (!converged_of_column[j])
+      iters_of_column[j] = it;
+  if (in != X) {   // the final vectors live in `scratch`: hand them back in X
+    HIP_TRY(e, hipMemcpyAsync(X->d, in->d, (size_t)A->rows * width * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+  }
+  *launches = it;
   if (total_ns)
     *total_ns = total;
   return SH_OK;

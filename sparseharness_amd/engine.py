@@ -47,11 +47,14 @@ class Vec:
         self.engine._chk(abi.load().sh_vec_upload(self.engine.h, self.h, _ptr(host), host.size))
         return self
 
-    def download(self, dtype=np.float32, n=None):
+    def download(self, dtype=np.float32, n=None, shape=None):
+        """shape=(rows, width): the interleaved vectors of Engine.spmm as a C-contiguous 2-D array."""
+        if shape is not None:
+            n = int(np.prod(shape))
         n = len(self) if n is None else n
         out = np.empty(n, dtype)
         self.engine._chk(abi.load().sh_vec_download(self.engine.h, self.h, _ptr(out), n))
-        return out
+        return out if shape is None else out.reshape(shape)
 
     def fill(self, value, dtype=np.float32):
         pat = int(np.array([value], dtype).view(np.uint32)[0])
@@ -222,3 +225,25 @@ class Engine:
                                         delta, max_iters, None, C.byref(iters), C.byref(conv), per,
                                         C.byref(total)))
         return iters.value, bool(conv.value), list(per[:iters.value]), total.value
+
+    # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
+    def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
+        dt = elem_dtype(semiring)
+        a, b = np.array([alpha], dt), np.array([beta], dt)
+        ns = C.c_uint64()
+        self._chk(abi.load().sh_spmm(self.h, semiring, A.h, width, X.h, None if Y is None else Y.h, _ptr(a), _ptr(b),
+                                     Out.h, C.byref(ns) if timed else None))
+        return ns.value if timed else None
+
+    def iterate_multi(self, semiring, A, X, Y0, scratch, alpha, beta, width, delta=1e-4, max_iters=10000):
+        """-> (launches, iters_of_column, converged_of_column, ns_per_launch, total_ns)"""
+        dt = elem_dtype(semiring)
+        a, b = np.array([alpha], dt), np.array([beta], dt)
+        launches, total = C.c_int32(), C.c_uint64()
+        cap = max(int(width), 1)   # (a width the engine refuses still gets buffers it could not overrun)
+        iters, conv = (C.c_int32 * cap)(), (C.c_int32 * cap)()
+        per = (C.c_uint64 * max(max_iters, 1))()
+        self._chk(abi.load().sh_iterate_multi(self.h, semiring, A.h, width, X.h, None if Y0 is None else Y0.h, scratch.h,
+                                              _ptr(a), _ptr(b), delta, max_iters, C.byref(launches), iters, conv, per,
+                                              C.byref(total)))
+        return launches.value, list(iters[:width]), [bool(c) for c in conv[:width]], list(per[:launches.value]), total.value
