@@ -308,6 +308,68 @@ int sh_iterate_multi(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t widt
                      int32_t *launches, int32_t *iters_of_column, int32_t *converged_of_column,
                      uint64_t *ns_per_launch, uint64_t *total_ns);
 
+/* ---- (or,and) on packed bits: extends Harness::executeKernel (inc/harness.h:149-195) and the BFS loop of
+ *      HarnessBFS::executeRun (app/bfs.cpp:94-174).  The reference runs `trials` repetitions of ONE source, one int32
+ *      per vertex; it has no counterpart of the four calls below.
+ *      The (or,and) semiring only has the values 0 and 1, so a vertex carries `words` 32-bit words for 32 * words
+ *      sources: word w of vertex v is element v*words + w of an ordinary sh_vec, source s is bit s % 32 of word s / 32.
+ *      One launch reads the matrix stream once and gathers 4 * words contiguous bytes per entry -- the gathers and, at
+ *      words = 1, the bytes of ONE sh_spmv -- for all 32 * words sources:
+ *        Out[r*words + w] = ( OR over entries e of row r with val_e != 0 and 0 <= col_e < cols of X[col_e*words + w]  &  amask )
+ *                         | ( Y[r*words + w] & bmask ),     amask = alpha != 0 ? ~0 : 0, bmask likewise from beta
+ *      which is SH_OR_AND_I32's mul / add / epilogue on every bit on its own.
+ *      Measured on an MI355X (DESIGN.md "Bit-parallel multi-source BFS", profiles/msbfs_*.json): as t_bits_iterate / (cost of the same
+ *      32 * words sources another way), alpha = beta = 1 from random sources to convergence, at words = 1 / 2 / 4 / 8:
+ *        - against 32 * words single-source sh_iterate runs under the matrix' default plan:
+ *            x cache-resident (170 998 rows, 0.96 M entries, stream plan):        0.042 / 0.024 / 0.014 / 0.012
+ *            R-MAT-23 (8.4 M rows, 134 M entries, x-tiled plan):                  0.25  / 0.29  / 0.13  / 0.060
+ *            power-law 10 M rows / 200 M entries (x-tiled plan):                  0.26  / 0.14  / 0.074 / 0.041
+ *        - against words x sh_iterate_multi at width 32 on the same CSR arrays:  0.20 / 0.11 / 0.065 / 0.055,
+ *            0.42 / 0.23 / 0.14 / 0.074 and 0.58 / 0.31 / 0.16 / 0.090 on the same three matrices.
+ *        A launch costs what one sh_spmv on the CSR arrays costs (R-MAT-23: 1.62 ms at words = 1, 2.26 ms at words = 8).
+ *        Rule: with 32 or more (or,and) start vectors call it, on a plan = 1 upload, whatever the matrix' default plan,
+ *        with the largest `words` the sources fill; every `words` pays on every matrix class measured.  With fewer than
+ *        about 8 sources on a matrix whose default plan is x-tiled, single-source sh_iterate runs stay cheaper.
+ *
+ * words in {1, 2, 4, 8}.  alpha, beta: one int32 each, as for SH_OR_AND_I32 in sh_spmv, shared by all sources.
+ * X >= cols*words, Y / Out >= rows*words elements, 16-byte aligned; Y may be NULL when beta == 0; Out must not alias X.
+ * The matrix must hold its CSR arrays on the device (uploaded with sh_plan_options::plan = 1, or chosen so by the
+ * size rule); otherwise SH_EINVAL with a message that says how to upload.  A matrix without rows launches nothing.
+ * One launch (plus the long-row fix-up when the matrix has rows above the schedule's threshold).  kernel_ns as sh_spmv.
+ * NOT covered by the packed path: the x-tiled and the bit-blocked plans, row pieces / `report` (sh_spmv_step_pieces),
+ * the multi-GPU driver and the C++ harness apps. */
+int sh_bits_spmv(sh_engine *e, const sh_csr *A, int32_t words, const sh_vec *X, const sh_vec *Y,
+                 const void *alpha, const void *beta, sh_vec *Out, uint64_t *kernel_ns);
+
+/* sh_iterate(SH_OR_AND_I32) for 32 * words start vectors at once (bit-parallel multi-source BFS).
+ * Source s stops at the first launch that changes none of its bits; from then on it is FROZEN: later launches carry
+ * its bits through while the other sources go on.  (Needed, not only an optimisation: launch 0 reads Y0 and later
+ * launches the previous vector, so a source confirmed at launch 0 is not necessarily a fixed point of the later
+ * launches; and with beta == 0 a source may oscillate and never converge.)  On return bit s of X equals, for every
+ * vertex, (x != 0) of what sh_iterate(SH_OR_AND_I32) leaves when run alone on the 0/1 vector of source s with the same
+ * alpha, beta, max_iters and bit s of Y0 as its y0; iters_of_source[s] equals its *iters, converged_of_source[s] its
+ * *converged; *launches = max_s iters_of_source[s] (<= max_iters).
+ * X, Y0, scratch: rows*words elements each (the matrix must be square); scratch is clobbered and must not alias X.
+ * iters_of_source, converged_of_source: 32 * words entries; ns_per_launch (may be NULL): capacity max_iters.
+ * newly_set (may be NULL): host memory of max_iters * 32*words words; entry l * 32*words + s receives the number of
+ * vertices whose bit s was 0 before launch l and 1 after it (0 for a frozen source and for launches that did not
+ * run).  With alpha = beta = 1 and Y0 = X this is the number of vertices at BFS distance l + 1 from source s:
+ * eccentricity and closeness of 32 to 256 sources from one sweep, without unpacking a vector.
+ * max_iters <= 0: nothing is launched, *launches = 0.  The launches are enqueued ahead of the host as sh_iterate_multi's
+ * are: the changed words of launch i live in device memory and launch i + 1 reads them as its live mask; the loop
+ * ends when every source is frozen. */
+int sh_bits_iterate(sh_engine *e, const sh_csr *A, int32_t words, sh_vec *X, const sh_vec *Y0, sh_vec *scratch,
+                    const void *alpha, const void *beta, int32_t max_iters, int32_t *launches,
+                    int32_t *iters_of_source, int32_t *converged_of_source, uint32_t *newly_set,
+                    uint64_t *ns_per_launch, uint64_t *total_ns);
+
+/* Between the packed form and the 0/1 int32 vectors of sh_spmv, sh_iterate and the apps; source in [0, 32 * words).
+ * sh_bits_from_column: bit `source` of B[i*words + source/32] := (v[i] != 0) for i < n, the other bits untouched.
+ * sh_bits_to_column:   v[i] := that bit as int32 0 / 1.   v >= n, B >= n*words elements.
+ * Both are asynchronous on the engine's stream. */
+int sh_bits_from_column(sh_engine *e, const sh_vec *v, int64_t n, int32_t words, int32_t source, sh_vec *B);
+int sh_bits_to_column(sh_engine *e, const sh_vec *B, int64_t n, int32_t words, int32_t source, sh_vec *v);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,11 @@ SIGNATURES = {
     "sh_spmm": (_int, [_vp, _int, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "sh_iterate_multi": (_int, [_vp, _int, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.c_double, _i32,
                                 C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_u64), C.POINTER(_u64)]),
+    "sh_bits_spmv": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "sh_bits_iterate": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                               C.POINTER(C.c_uint32), C.POINTER(_u64), C.POINTER(_u64)]),
+    "sh_bits_from_column": (_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp]),
+    "sh_bits_to_column": (_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp]),
 }
 
 _lib = None

@@ -1,19 +1,22 @@
 #!/usr/bin/env python3
 """Reads hipcc's -Rpass-analysis=kernel-resource-usage remarks and fails if a kernel of the tiled plan, or one of the
-multi-vector kernels (spmm_csr_kernel / spmm_long_fixup, multi.hip.h), uses scratch or spills VGPRs or SGPRs (see the
-asm-check target of the Makefile)."""
+multi-vector kernels (spmm_csr_kernel / spmm_long_fixup, multi.hip.h), or one of the packed-bit kernels (msbfs_csr_kernel /
+msbfs_long_fixup, msbfs.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi = [], 0, set()
+bad, seen, seen_multi, seen_bits = [], 0, set(), set()
 for blk in text.split("remark: Function Name: ")[1:]:
     name = blk.split()[0]
     multi = "spmm_csr" in name or "spmm_long" in name
-    if "spmv_tiled" not in name and not multi:
+    packed = "msbfs_csr" in name or "msbfs_long" in name
+    if "spmv_tiled" not in name and not multi and not packed:
         continue
     if multi:
         seen_multi.add(name)
+    elif packed:
+        seen_bits.add(name)
     else:
         seen += 1
     scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blk).group(1))
@@ -26,8 +29,9 @@ for blk in text.split("remark: Function Name: ")[1:]:
     # (a spilled SGPR lives in a lane of a VGPR the hand-scheduled loaders might otherwise count on, and costs
     # v_writelane / v_readlane traffic wherever it is used)
     # The multi-vector kernels run 256-thread workgroups, four per CU by their LDS (40 KB each): 16 waves per CU, four
-    # per SIMD, which 128 VGPRs per lane still allow -- the same bound.
-    if spill or sspill or vgprs > 128 or scratch:
+    # per SIMD, which 128 VGPRs per lane still allow -- the same bound.  The packed-bit kernels stage half as much (22 KB):
+    # seven workgroups per CU, 28 waves, seven per SIMD: 512 / 7 = 73 VGPRs would be the limit for that; they are held to 64.
+    if spill or sspill or vgprs > (64 if packed else 128) or scratch:
         bad.append((name, scratch, spill, vgprs, sspill))
 if not seen:
     sys.exit("no spmv_tiled kernels found in the resource-usage remarks")
@@ -35,7 +39,11 @@ if not seen:
 n_csr = sum("spmm_csr" in n for n in seen_multi)
 if n_csr != 16 or len(seen_multi) != 32:
     sys.exit(f"expected 16 spmm_csr_kernel and 16 spmm_long_fixup instantiations in the remarks, found {n_csr} and {len(seen_multi) - n_csr}")
+# four `words` x {plain, with level counts} of msbfs_csr_kernel, and as many fix-up kernels
+n_bits = sum("msbfs_csr" in n for n in seen_bits)
+if n_bits != 8 or len(seen_bits) != 16:
+    sys.exit(f"expected 8 msbfs_csr_kernel and 8 msbfs_long_fixup instantiations in the remarks, found {n_bits} and {len(seen_bits) - n_bits}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled and {len(seen_multi)} multi-vector kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector and {len(seen_bits)} packed-bit kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

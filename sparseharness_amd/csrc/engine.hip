@@ -9,6 +9,7 @@
 #include "kernels.hip.h"
 #include "bits.hip.h"
 #include "multi.hip.h"
+#include "msbfs.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -38,6 +39,7 @@ struct sh_engine {
   int32_t n_flags = 0;
   int32_t *h_flag = nullptr;    // pinned, 64 B: convergence flags of a batch of iterations, read back
   int32_t *d_mflags = nullptr, *h_mflags = nullptr;   // sh_iterate_multi: MULTI_FLAG_WORDS per-column flags of a batch (device / pinned copy)
+  uint32_t *d_bstate = nullptr, *h_bstate = nullptr;   // sh_bits_iterate: BITS_STATE_WORDS changed words and level counts of a batch (device / pinned copy)
   char name[256] = {0};
   int n_cus = 256;
   std::string err;
@@ -209,6 +211,8 @@ int sh_engine_destroy(sh_engine *e) {
   if (e->h_flag) (void)hipHostFree(e->h_flag);
   if (e->d_mflags) (void)hipFree(e->d_mflags);
   if (e->h_mflags) (void)hipHostFree(e->h_mflags);
+  if (e->d_bstate) (void)hipFree(e->d_bstate);
+  if (e->h_bstate) (void)hipHostFree(e->h_bstate);
   if (e->ev0) (void)hipEventDestroy(e->ev0);
   if (e->ev1) (void)hipEventDestroy(e->ev1);
   for (auto ev : e->ev_iter) if (ev) (void)hipEventDestroy(ev);
@@ -1497,6 +1501,249 @@ int sh_iterate_multi(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t widt
   *launches = it;
   if (total_ns)
     *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- (or,and) on packed bits (msbfs.hip.h) -------------------------------------------------------------------------
+constexpr int BITS_MAX_WORDS = 8;   // widest sh_bits_spmv: 256 sources
+static_assert(BITS_MAX_WORDS <= SPMM_MAX_WIDTH, "the long-row partials live in d_partial_multi");
+
+template <int W, bool COUNTS>
+static int launch_bits(sh_engine *e, const sh_csr *A, const sh_vec *X, const sh_vec *Y, uint32_t amask, uint32_t bmask,
+                       sh_vec *Out, BitsStep st) {
+  CsrDev dev{A->d_row_ptr, A->d_col, A->d_val, (int32_t)A->rows, (int32_t)A->cols};
+  const uint32_t *yp = bmask ? (const uint32_t *)Y->d : nullptr;
+  const int grid = A->n_stream + A->n_segs;
+  if (grid > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(msbfs_csr_kernel<W, COUNTS>), dim3(grid), dim3(BS), 0, e->stream, dev, (const uint32_t *)X->d, yp,
+                       amask, bmask, (uint32_t *)Out->d, A->d_blk_row, A->n_stream, A->d_segs, A->d_partial_multi, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (A->n_long > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(msbfs_long_fixup<W, COUNTS>), dim3((A->n_long * W + 63) / 64), dim3(64), 0, e->stream, A->d_long,
+                       A->n_long, A->d_partial_multi, yp, amask, bmask, (uint32_t *)Out->d, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  return SH_OK;
+}
+
+template <bool COUNTS>
+static int launch_bits_words(sh_engine *e, const sh_csr *A, int32_t words, const sh_vec *X, const sh_vec *Y, uint32_t amask,
+                             uint32_t bmask, sh_vec *Out, BitsStep st) {
+  switch (words) {
+  case 1: return launch_bits<1, COUNTS>(e, A, X, Y, amask, bmask, Out, st);
+  case 2: return launch_bits<2, COUNTS>(e, A, X, Y, amask, bmask, Out, st);
+  case 4: return launch_bits<4, COUNTS>(e, A, X, Y, amask, bmask, Out, st);
+  case 8: return launch_bits<8, COUNTS>(e, A, X, Y, amask, bmask, Out, st);
+  default: return fail(e, SH_EINVAL, "words %d: 1, 2, 4 or 8 words per vertex", (int)words);
+  }
+}
+
+static bool bits_words_ok(int32_t words) { return words == 1 || words == 2 || words == 4 || words == 8; }
+
+// What sh_bits_spmv and sh_bits_iterate ask of their operands (Y == NULL is legal when beta == 0).
+static int check_bits(sh_engine *e, const sh_csr *A, int32_t words, const sh_vec *X, const sh_vec *Y, const void *alpha,
+                      const void *beta, const sh_vec *Out, const char *who) {
+  if (!bits_words_ok(words))   // (by value first: refused without an engine too)
+    return fail(e, SH_EINVAL, "%s: words %d, must be 1, 2, 4 or 8", who, (int)words);
+  if (!e || !A || !X || !alpha || !beta || !Out)
+    return fail(e, SH_EINVAL, "%s: NULL argument", who);
+  if (!A->d_row_ptr || !A->d_blk_row)
+    return fail(e, SH_EINVAL, "%s: the matrix does not hold its CSR arrays on the device (it runs the tiled or the bit-blocked "
+                "plan); upload it with sh_plan_options::plan = 1 (SH_PLAN=stream)", who);
+  int32_t b;
+  memcpy(&b, beta, 4);
+  const bool use_y = OrAndI32::reads_y(b);
+  if (use_y && !Y)
+    return fail(e, SH_EINVAL, "%s: Y is NULL but the epilogue reads it (beta != 0)", who);
+  if (X->n < A->cols * words)
+    return fail(e, SH_ESHAPE, "%s: X has %lld elements, needs cols * words = %lld", who, (long long)X->n, (long long)(A->cols * words));
+  if (Out->n < A->rows * words)
+    return fail(e, SH_ESHAPE, "%s: Out has %lld elements, needs rows * words = %lld", who, (long long)Out->n, (long long)(A->rows * words));
+  if (use_y && Y->n < A->rows * words)
+    return fail(e, SH_ESHAPE, "%s: Y has %lld elements, needs rows * words = %lld", who, (long long)Y->n, (long long)(A->rows * words));
+  if (Out->d == X->d && A->rows > 0)
+    return fail(e, SH_EINVAL, "%s: Out must not alias X", who);
+  for (const sh_vec *v : {X, use_y ? Y : X, Out})
+    if ((uintptr_t)v->d % 16 != 0)
+      return fail(e, SH_EINVAL, "%s: vectors must be 16-byte aligned (a lane moves up to four words at a time)", who);
+  return SH_OK;
+}
+
+static void bits_masks(const void *alpha, const void *beta, uint32_t *amask, uint32_t *bmask) {
+  int32_t a, b;
+  memcpy(&a, alpha, 4);
+  memcpy(&b, beta, 4);
+  *amask = a != 0 ? ~0u : 0u;
+  *bmask = b != 0 ? ~0u : 0u;
+}
+
+extern "C" {
+
+int sh_bits_spmv(sh_engine *e, const sh_csr *A, int32_t words, const sh_vec *X, const sh_vec *Y, const void *alpha,
+                 const void *beta, sh_vec *Out, uint64_t *kernel_ns) {
+  int rc = check_bits(e, A, words, X, Y, alpha, beta, Out, "sh_bits_spmv");
+  if (rc)
+    return rc;
+  uint32_t amask, bmask;
+  bits_masks(alpha, beta, &amask, &bmask);
+  HIP_TRY(e, hipSetDevice(e->device));
+  if (kernel_ns)
+    HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  rc = launch_bits_words<false>(e, A, words, X, Y, amask, bmask, Out, BitsStep{nullptr, nullptr, nullptr, nullptr});
+  if (rc)
+    return rc;
+  if (kernel_ns) {
+    HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+    HIP_TRY(e, hipEventSynchronize(e->ev1));
+    float ms = 0.f;
+    HIP_TRY(e, hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    *kernel_ns = (uint64_t)((double)ms * 1e6);
+  }
+  return SH_OK;
+}
+
+int sh_bits_iterate(sh_engine *e, const sh_csr *A, int32_t words, sh_vec *X, const sh_vec *Y0, sh_vec *scratch,
+                    const void *alpha, const void *beta, int32_t max_iters, int32_t *launches,
+                    int32_t *iters_of_source, int32_t *converged_of_source, uint32_t *newly_set,
+                    uint64_t *ns_per_launch, uint64_t *total_ns) {
+  if (!bits_words_ok(words))
+    return fail(e, SH_EINVAL, "sh_bits_iterate: words %d, must be 1, 2, 4 or 8", (int)words);
+  if (!Y0 || !scratch || !launches || !iters_of_source || !converged_of_source)
+    return fail(e, SH_EINVAL, "sh_bits_iterate: NULL argument");
+  int rc = check_bits(e, A, words, X, Y0, alpha, beta, scratch, "sh_bits_iterate");
+  if (rc)
+    return rc;
+  if (A->rows != A->cols)
+    return fail(e, SH_ESHAPE, "sh_bits_iterate: matrix must be square (inc/common.h:49-52)");
+  if (Y0->n < A->rows * words)
+    return fail(e, SH_ESHAPE, "sh_bits_iterate: Y0 has %lld elements, needs rows * words = %lld", (long long)Y0->n, (long long)(A->rows * words));
+  if ((uintptr_t)Y0->d % 16 != 0)
+    return fail(e, SH_EINVAL, "sh_bits_iterate: vectors must be 16-byte aligned (a lane moves up to four words at a time)");
+  const int n_src = 32 * words;
+  *launches = 0;
+  for (int s = 0; s < n_src; s++) iters_of_source[s] = 0, converged_of_source[s] = 0;
+  if (total_ns)
+    *total_ns = 0;
+  if (max_iters <= 0)
+    return SH_OK;
+  if (newly_set)
+    memset(newly_set, 0, (size_t)max_iters * n_src * 4);
+  uint32_t amask, bmask;
+  bits_masks(alpha, beta, &amask, &bmask);
+  HIP_TRY(e, hipSetDevice(e->device));
+  // As sh_iterate_multi: launches are enqueued BITS_BATCH ahead of the host.  Slot k + 1 of the state holds the changed
+  // words of launch k of the batch, which launch k + 1 reads as its live mask; slot 0 holds those of the previous batch's
+  // last launch.  Behind the slots: 32 * BITS_MAX_WORDS level counts per launch of the batch.  A source's count = index
+  // of its first changed bit that stayed 0, plus one (the confirming launch included).
+  constexpr int BITS_BATCH = 8, SLOT = BITS_MAX_WORDS, CNT = 32 * BITS_MAX_WORDS, CNT0 = (BITS_BATCH + 1) * SLOT,
+                BITS_STATE_WORDS = CNT0 + BITS_BATCH * CNT;
+  if (!e->d_bstate)
+    HIP_TRY(e, hipMalloc((void **)&e->d_bstate, BITS_STATE_WORDS * 4));
+  if (!e->h_bstate)
+    HIP_TRY(e, hipHostMalloc((void **)&e->h_bstate, BITS_STATE_WORDS * 4, hipHostMallocDefault));
+  if (!e->ev_iter[0])
+    for (auto &ev : e->ev_iter) HIP_TRY(e, hipEventCreate(&ev));
+  sh_vec *in = X, *out = scratch;
+  const sh_vec *y = Y0;
+  int32_t it = 0, n_live = n_src;
+  uint64_t total = 0;
+  int last_slot = -1;   // slot of the latest launch that ran (-1: none yet, every source is live)
+  while (n_live > 0 && it < max_iters) {
+    const int nb = std::min<int32_t>(BITS_BATCH, max_iters - it);
+    if (last_slot > 0)
+      HIP_TRY(e, hipMemcpyAsync(e->d_bstate, e->d_bstate + last_slot * SLOT, SLOT * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(e, hipMemsetAsync(e->d_bstate + SLOT, 0, (BITS_STATE_WORDS - SLOT) * 4, e->stream));
+    HIP_TRY(e, hipEventRecord(e->ev_iter[0], e->stream));
+    for (int k = 0; k < nb; k++) {
+      const uint32_t *live = (k == 0 && last_slot < 0) ? nullptr : e->d_bstate + k * SLOT;
+      BitsStep st{e->d_bstate + (k + 1) * SLOT, (const uint32_t *)in->d, live, e->d_bstate + CNT0 + k * CNT};
+      rc = newly_set ? launch_bits_words<true>(e, A, words, in, y, amask, bmask, out, st)
+                     : launch_bits_words<false>(e, A, words, in, y, amask, bmask, out, st);
+      if (rc)
+        return rc;
+      HIP_TRY(e, hipEventRecord(e->ev_iter[k + 1], e->stream));
+      std::swap(in, out);   // std::swap(input, output), app/bfs.cpp as app/sssp.cpp:143
+      y = in;               // setGlobalArg(3, input_mem_ptr), :150
+    }
+    HIP_TRY(e, hipMemcpyAsync(e->h_bstate, e->d_bstate, (newly_set ? BITS_STATE_WORDS : CNT0) * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    int ran = 0;   // launches of this batch that did run: every one up to the first that left no source live
+    while (ran < nb && n_live > 0) {
+      const uint32_t *f = e->h_bstate + (ran + 1) * SLOT;
+      for (int s = 0; s < n_src; s++)
+        if (!converged_of_source[s] && ((f[s >> 5] >> (s & 31)) & 1u) == 0u) {
+          converged_of_source[s] = 1;
+          iters_of_source[s] = it + ran + 1;
+          n_live--;
+        }
+      if (newly_set)   // (the kernel's counts are word-major, 32 per word: source s at s)
+        memcpy(newly_set + (size_t)(it + ran) * n_src, e->h_bstate + CNT0 + ran * CNT, (size_t)n_src * 4);
+      ran++;
+    }
+    for (int k = 0; k < ran; k++) {
+      float ms = 0.f;
+      HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_iter[k], e->ev_iter[k + 1]));
+      const uint64_t ns = (uint64_t)((double)ms * 1e6);
+      if (ns_per_launch)
+        ns_per_launch[it + k] = ns;
+      total += ns;
+    }
+    // the gated launches behind the last one that ran wrote nothing: the result is what launch `ran` produced
+    if ((nb - ran) % 2) std::swap(in, out);
+    last_slot = ran;
+    it += ran;
+  }
+  for (int s = 0; s < n_src; s++)
+    if (!converged_of_source[s])
+      iters_of_source[s] = it;
+  if (in != X && A->rows > 0) {   // the final vector lives in `scratch`: hand it back in X
+    HIP_TRY(e, hipMemcpyAsync(X->d, in->d, (size_t)A->rows * words * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+  }
+  *launches = it;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+static int check_bits_column(sh_engine *e, const sh_vec *packed, const sh_vec *column, int64_t n, int32_t words, int32_t source,
+                             const char *who) {
+  if (!bits_words_ok(words))   // (by value first: refused without an engine too)
+    return fail(e, SH_EINVAL, "%s: words %d, must be 1, 2, 4 or 8", who, (int)words);
+  if (source < 0 || source >= 32 * words)
+    return fail(e, SH_EINVAL, "%s: source %d outside [0, 32 * words = %d)", who, (int)source, 32 * (int)words);
+  if (!e || !packed || !column)
+    return fail(e, SH_EINVAL, "%s: NULL argument", who);
+  if (n < 0)
+    return fail(e, SH_EINVAL, "%s: n is negative", who);
+  if (column->n < n || packed->n < n * words)
+    return fail(e, SH_ESHAPE, "%s: the column needs n = %lld elements, the packed vector n * words = %lld", who, (long long)n,
+                (long long)(n * words));
+  return SH_OK;
+}
+
+int sh_bits_from_column(sh_engine *e, const sh_vec *v, int64_t n, int32_t words, int32_t source, sh_vec *B) {
+  const int rc = check_bits_column(e, B, v, n, words, source, "sh_bits_from_column");
+  if (rc || n == 0)
+    return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipLaunchKernelGGL(msbfs_pack_column, dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, e->stream, (const uint32_t *)v->d, n, words,
+                     source, (uint32_t *)B->d);
+  HIP_TRY(e, hipGetLastError());
+  return SH_OK;
+}
+
+int sh_bits_to_column(sh_engine *e, const sh_vec *B, int64_t n, int32_t words, int32_t source, sh_vec *v) {
+  const int rc = check_bits_column(e, B, v, n, words, source, "sh_bits_to_column");
+  if (rc || n == 0)
+    return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  hipLaunchKernelGGL(msbfs_unpack_column, dim3((unsigned)((n + BS - 1) / BS)), dim3(BS), 0, e->stream, (const uint32_t *)B->d, n, words,
+                     source, (uint32_t *)v->d);
+  HIP_TRY(e, hipGetLastError());
   return SH_OK;
 }
 

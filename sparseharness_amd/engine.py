@@ -247,3 +247,32 @@ class Engine:
                                               _ptr(a), _ptr(b), delta, max_iters, C.byref(launches), iters, conv, per,
                                               C.byref(total)))
         return launches.value, list(iters[:width]), [bool(c) for c in conv[:width]], list(per[:launches.value]), total.value
+
+    # ---- (or,and) on packed bits: 32 * words sources, word w of vertex v at v * words + w, source s = bit s % 32 of word s // 32
+    def bits_spmv(self, A, X, Y, alpha, beta, Out, words, timed=False):
+        a, b = np.array([alpha], np.int32), np.array([beta], np.int32)
+        ns = C.c_uint64()
+        self._chk(abi.load().sh_bits_spmv(self.h, A.h, words, X.h, None if Y is None else Y.h, _ptr(a), _ptr(b), Out.h,
+                                          C.byref(ns) if timed else None))
+        return ns.value if timed else None
+
+    def bits_iterate(self, A, X, Y0, scratch, alpha, beta, words, max_iters=10000, counts=False):
+        """-> (launches, iters_of_source, converged_of_source, ns_per_launch, total_ns[, newly_set (launches, 32 * words)])"""
+        a, b = np.array([alpha], np.int32), np.array([beta], np.int32)
+        launches, total = C.c_int32(), C.c_uint64()
+        n_src = 32 * max(int(words), 1)   # (a `words` the engine refuses still gets buffers it could not overrun)
+        iters, conv = (C.c_int32 * n_src)(), (C.c_int32 * n_src)()
+        per = (C.c_uint64 * max(max_iters, 1))()
+        newly = np.zeros((max(max_iters, 0), n_src), np.uint32) if counts else None
+        self._chk(abi.load().sh_bits_iterate(self.h, A.h, words, X.h, None if Y0 is None else Y0.h, scratch.h, _ptr(a), _ptr(b),
+                                             max_iters, C.byref(launches), iters, conv,
+                                             newly.ctypes.data_as(C.POINTER(C.c_uint32)) if counts else None, per, C.byref(total)))
+        n_src = 32 * int(words)
+        res = (launches.value, list(iters[:n_src]), [bool(c) for c in conv[:n_src]], list(per[:launches.value]), total.value)
+        return res + (newly[:launches.value, :n_src].copy(),) if counts else res
+
+    def bits_from_column(self, v, n, words, source, B):
+        self._chk(abi.load().sh_bits_from_column(self.h, v.h, n, words, source, B.h))
+
+    def bits_to_column(self, B, n, words, source, v):
+        self._chk(abi.load().sh_bits_to_column(self.h, B.h, n, words, source, v.h))
