@@ -370,6 +370,64 @@ int sh_bits_iterate(sh_engine *e, const sh_csr *A, int32_t words, sh_vec *X, con
 int sh_bits_from_column(sh_engine *e, const sh_vec *v, int64_t n, int32_t words, int32_t source, sh_vec *B);
 int sh_bits_to_column(sh_engine *e, const sh_vec *B, int64_t n, int32_t words, int32_t source, sh_vec *v);
 
+/* ---- frontier-driven iteration: extends the do/while of HarnessSSSP::executeRun (app/sssp.cpp:97-176), its BFS twin
+ *      (app/bfs.cpp:94-174) and Harness::executeKernel (inc/harness.h:149-195).  The reference launches its kernel over
+ *      the whole matrix every time; it has no counterpart of the calls below.
+ *      sh_iterate's launches are dense: each reads the whole matrix, whatever the launch before changed.  From launch 1
+ *      on a launch computes x_{k+1}[r] from x_k[r] and x_k[col_j] over row r's entries, so a row none of whose inputs
+ *      changed between x_{k-1} and x_k keeps its word.  sh_iterate_frontier recomputes, from launch 2 on and while the
+ *      wavefront is thin, only
+ *        active_k = C_k  u  { r : row r has an entry with 0 <= col < cols and col in C_k },  C_k = rows whose bits changed,
+ *      found through the pattern of the transposed matrix and recomputed by a row gather on the CSR arrays, in place.
+ *      min / or / max are order-free, so every iterate, *iters and *converged equal sh_iterate's bit for bit, for any
+ *      alpha, beta, x0, y0 (promised for vectors without NaN / infinity; (min,+) needs delta > 0: an untouched row must
+ *      not fail |in - out| < delta).
+ *      Measured on an MI355X (DESIGN.md "Frontier-driven iteration", profiles/frontier_*.json), total device time as a
+ *      ratio to sh_iterate under the matrix' default plan, at dense_share = 0 (detection only) / the default / 1:
+ *        - 2048 x 2048 grid graph, BFS (4095 launches):   1.52 / 0.43 / 0.44    SSSP, weights 1..16 (4198):  1.89 / 1.57 / 2.27
+ *        - 170 998 rows, 0.96 M entries (23 / 27 launches of 17 us): 2.1 / 4.2 / 6.6 and 2.5 / 4.4 / 9.2
+ *        - R-MAT-23 (8 / 10 launches of 0.29 ms):           1.27 / 3.1 / 15.7 and 1.31 / 3.3 / 18.5
+ *        A sparse launch costs about 25 us at least (four small kernels); detection adds 30 to 90 us to a dense launch.
+ *        Rule: call it for runs of hundreds of launches or more on a matrix with bounded row and column lengths (meshes,
+ *        grids, road-like graphs) whose dense launch costs well above 30 us and in which a vertex changes a few times at
+ *        most (BFS, reachability, label propagation).  For power-law graphs, runs of a few dozen launches and small
+ *        matrices sh_iterate is faster; no dense_share serves both kinds, the default (0.02) is the grid's best.
+ *
+ * sh_frontier_create: A is square and was uploaded (under ANY plan) from the host arrays given here, which the call
+ * reads again.  The handle holds on the device: row_ptr / col_idx / val (borrowed from A when A keeps its CSR arrays --
+ * A must then outlive the handle -- copied otherwise), the pattern of the transpose (col_ptr[cols + 1], row_of[nnz];
+ * entries with col outside [0, cols) are left out), two worklists, a stamp word and a value word per row, two lists of
+ * pieces of long columns / rows.  The transpose is built on the device (column histogram, exclusive scan, scatter).
+ * sh_frontier_footprint: device bytes held =
+ *     (CSR arrays copied ? 4 * (rows + 1) + 8 * nnz : 0)  +  4 * (cols + 1) + 4 * nnz  +  16 * rows
+ *     + 8 * (nnz / 1024 + 1) + 8 * (nnz / 2048 + 1) + 512.
+ * sh_frontier_transpose (tests, tools): col_ptr receives cols + 1 words, row_of as many as col_ptr[cols]; either may be
+ * NULL.  The order of the rows inside one column is unspecified.
+ *
+ * sh_iterate_frontier: sh_iterate's contract for x / y0 / scratch / alpha / beta / delta / max_iters / iters / converged /
+ * ns_per_iter / total_ns, and the same result bit for bit.  f may serve any number of calls, one at a time.
+ * dense_share: a launch k >= 2 runs sparse when (entries of the transposed columns in C_k) <= dense_share * nnz, dense
+ *   otherwise (launches 0 and 1 are always dense).  0: every launch dense (sh_iterate plus the change detection);
+ *   >= 1: every launch from 2 on sparse; negative: the engine's default.
+ * mode_per_iter / changed_per_iter / active_per_iter (each may be NULL, capacity max_iters): per launch that ran, 0 dense /
+ *   1 sparse; |C| AFTER the launch (rows whose bits it changed); rows recomputed (= rows for a dense launch).
+ * The launches are enqueued ahead of the host as sh_iterate's are, up to 8 of ONE mode; the device closes the gate of
+ * the launches behind a change of mode (or the end of the loop), so the host joins in once per batch and per change.
+ * SH_EINVAL: SH_PLUS_TIMES_F32 (a recomputed row would have to reproduce the summation order of whichever plan ran the
+ * dense launches), delta <= 0 with SH_MIN_PLUS_F32, max_iters < 1, a handle made for another matrix.
+ * NOT covered: SH_PLUS_TIMES_F32, sh_iterate_multi / sh_bits_iterate, row pieces (sh_spmv_step_pieces), the multi-GPU
+ * driver and the C++ harness apps. */
+typedef struct sh_frontier sh_frontier;
+int sh_frontier_create(sh_engine *e, const sh_csr *A, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                       const void *val, sh_frontier **out);
+int sh_frontier_free(sh_engine *e, sh_frontier *f);
+int sh_frontier_footprint(const sh_frontier *f, uint64_t *device_bytes);
+int sh_frontier_transpose(sh_engine *e, const sh_frontier *f, int32_t *col_ptr, int32_t *row_of);
+int sh_iterate_frontier(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_frontier *f, sh_vec *x, const sh_vec *y0,
+                        sh_vec *scratch, const void *alpha, const void *beta, double delta, int32_t max_iters,
+                        double dense_share, int32_t *iters, int32_t *converged, int32_t *mode_per_iter,
+                        int64_t *changed_per_iter, int64_t *active_per_iter, uint64_t *ns_per_iter, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

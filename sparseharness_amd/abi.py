@@ -87,6 +87,13 @@ SIGNATURES = {
                                C.POINTER(C.c_uint32), C.POINTER(_u64), C.POINTER(_u64)]),
     "sh_bits_from_column": (_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp]),
     "sh_bits_to_column": (_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp]),
+    "sh_frontier_create": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _pp]),
+    "sh_frontier_free": (_int, [_vp, _vp]),
+    "sh_frontier_footprint": (_int, [_vp, C.POINTER(_u64)]),
+    "sh_frontier_transpose": (_int, [_vp, _vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "sh_iterate_frontier": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _i32, C.c_double,
+                                   C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64),
+                                   C.POINTER(_u64), C.POINTER(_u64)]),
 }
 
 _lib = None

@@ -1,19 +1,23 @@
 #!/usr/bin/env python3
 """Reads hipcc's -Rpass-analysis=kernel-resource-usage remarks and fails if a kernel of the tiled plan, or one of the
 multi-vector kernels (spmm_csr_kernel / spmm_long_fixup, multi.hip.h), or one of the packed-bit kernels (msbfs_csr_kernel /
-msbfs_long_fixup, msbfs.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+msbfs_long_fixup, msbfs.hip.h), or one of the frontier kernels (frontier_mark / frontier_pull / frontier_apply /
+frontier_detect, frontier.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi, seen_bits = [], 0, set(), set()
+bad, seen, seen_multi, seen_bits, seen_frontier = [], 0, set(), set(), set()
 for blk in text.split("remark: Function Name: ")[1:]:
     name = blk.split()[0]
     multi = "spmm_csr" in name or "spmm_long" in name
     packed = "msbfs_csr" in name or "msbfs_long" in name
-    if "spmv_tiled" not in name and not multi and not packed:
+    frontier = any(k in name for k in ("frontier_mark", "frontier_pull", "frontier_apply", "frontier_detect"))
+    if "spmv_tiled" not in name and not multi and not packed and not frontier:
         continue
-    if multi:
+    if frontier:
+        seen_frontier.add(name)
+    elif multi:
         seen_multi.add(name)
     elif packed:
         seen_bits.add(name)
@@ -43,7 +47,10 @@ if n_csr != 16 or len(seen_multi) != 32:
 n_bits = sum("msbfs_csr" in n for n in seen_bits)
 if n_bits != 8 or len(seen_bits) != 16:
     sys.exit(f"expected 8 msbfs_csr_kernel and 8 msbfs_long_fixup instantiations in the remarks, found {n_bits} and {len(seen_bits) - n_bits}")
+# frontier_mark, frontier_detect, and frontier_pull / frontier_apply for the three order-free semirings
+if len(seen_frontier) != 8:
+    sys.exit(f"expected 8 frontier kernels in the remarks, found {len(seen_frontier)}: {sorted(seen_frontier)}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled, {len(seen_multi)} multi-vector and {len(seen_bits)} packed-bit kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit and {len(seen_frontier)} frontier kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

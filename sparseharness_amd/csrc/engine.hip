@@ -10,6 +10,7 @@
 #include "bits.hip.h"
 #include "multi.hip.h"
 #include "msbfs.hip.h"
+#include "frontier.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -1753,3 +1754,274 @@ int sh_bits_to_column(sh_engine *e, const sh_vec *B, int64_t n, int32_t words, i
 #include "debug_tools.h"
 #endif
 
+
+// ---- frontier-driven iteration (frontier.hip.h) --------------------------------------------------------------------
+struct sh_frontier {
+  int64_t rows = 0, nnz = 0;
+  const sh_csr *A = nullptr;       // the matrix the handle was made for
+  bool borrowed = false;           // d_row_ptr / d_col / d_val are A's
+  int32_t *d_row_ptr = nullptr, *d_col = nullptr;
+  uint32_t *d_val = nullptr;
+  int32_t *d_col_ptr = nullptr, *d_row_of = nullptr;
+  uint32_t *d_clist = nullptr, *d_alist = nullptr, *d_stamp = nullptr, *d_side = nullptr;
+  FrPiece *d_cplist = nullptr, *d_rplist = nullptr;
+  FrontierCtl *d_ctl = nullptr;
+  FrontierRec *h_rec = nullptr;    // pinned: the records of a batch
+  uint32_t gen = 0;                // number of the latest sparse launch enqueued (what its stamps hold)
+  size_t bytes = 0;
+};
+// sh_iterate_frontier's dense_share < 0: see DESIGN.md "Frontier-driven iteration" (the sweep of tools/frontier_bench.py)
+static constexpr double FRONTIER_DENSE_SHARE = 0.02;
+static_assert(sizeof(FrontierCtl) <= FR_CTL_BYTES, "the control block is accounted as FR_CTL_BYTES (sh_frontier_footprint)");
+
+template <class SR>
+static int launch_sparse(sh_engine *e, sh_frontier *f, const sh_csr *A, sh_vec *cur, const void *alpha_p, const void *beta_p,
+                         double delta, int k, int p) {
+  using T = typename SR::T;
+  T alpha, beta;
+  memcpy(&alpha, alpha_p, 4);
+  memcpy(&beta, beta_p, 4);
+  if (++f->gen == 0) {   // the launch numbers wrapped: no stamp may look current
+    HIP_TRY(e, hipMemsetAsync(f->d_stamp, 0, (size_t)std::max<int64_t>(f->rows, 1) * 4, e->stream));
+    f->gen = 1;
+  }
+  const dim3 grid((unsigned)(e->n_cus * 4)), block(FR_BS);
+  const CsrDev dev{f->d_row_ptr, f->d_col, f->d_val, (int32_t)A->rows, (int32_t)A->cols};
+  hipLaunchKernelGGL(frontier_mark, grid, block, 0, e->stream, f->d_ctl, k, p, f->gen, (int32_t)A->rows, f->d_col_ptr, f->d_row_of,
+                     f->d_row_ptr, f->d_clist, f->d_cplist, f->d_stamp, f->d_alist, f->d_side, f->d_rplist, (uint32_t)SR::identity_bits);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(frontier_pull<SR>), grid, block, 0, e->stream, f->d_ctl, k, dev, (const uint32_t *)cur->d,
+                     f->d_alist, f->d_side, f->d_rplist);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(frontier_apply<SR>), grid, block, 0, e->stream, f->d_ctl, k, p ^ 1, (uint32_t *)cur->d, f->d_alist,
+                     f->d_side, f->d_col_ptr, f->d_clist, f->d_cplist, alpha, beta, SR::reads_y(beta) ? 1 : 0, delta);
+  HIP_TRY(e, hipGetLastError());
+  return SH_OK;
+}
+
+extern "C" {
+
+int sh_frontier_create(sh_engine *e, const sh_csr *A, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                       const void *val, sh_frontier **out) {
+  if (!e || !A || !row_ptr || !out || (nnz > 0 && (!col_idx || !val)))
+    return fail(e, SH_EINVAL, "sh_frontier_create: NULL argument");
+  *out = nullptr;
+  if (A->rows != A->cols)
+    return fail(e, SH_ESHAPE, "sh_frontier_create: matrix must be square");
+  if (nnz != A->nnz || row_ptr[0] != 0 || row_ptr[A->rows] != nnz)
+    return fail(e, SH_ESHAPE, "sh_frontier_create: the arrays hold %lld entries, the matrix %lld", (long long)nnz, (long long)A->nnz);
+  HIP_TRY(e, hipSetDevice(e->device));
+  sh_frontier *f = new (std::nothrow) sh_frontier();
+  if (!f)
+    return fail(e, SH_ENOMEM, "out of host memory");
+  const int64_t rows = A->rows, cols = A->cols;
+  f->rows = rows; f->nnz = nnz; f->A = A;
+  uint32_t *cnt = nullptr;   // column counts, then the scatter's cursors
+  auto cleanup = [&](int rc) { if (cnt) (void)hipFree(cnt); sh_frontier_free(e, f); return rc; };
+#define HIP_TRY_F(call)                                                         \
+  do {                                                                          \
+    hipError_t _r = (call);                                                     \
+    if (_r != hipSuccess)                                                       \
+      return cleanup(fail(e, _r == hipErrorOutOfMemory ? SH_ENOMEM : SH_EHIP,   \
+                          "%s failed: %s", #call, hipGetErrorString(_r)));      \
+  } while (0)
+  // (an array of `bytes` counts as that in the footprint; an empty one still gets a few bytes to point at)
+#define F_ARRAY(ptr, nbytes)                                                                   \
+  do {                                                                                         \
+    HIP_TRY_F(hipMalloc((void **)&(ptr), std::max<size_t>((size_t)(nbytes), 16)));             \
+    f->bytes += (size_t)(nbytes);                                                              \
+  } while (0)
+  f->borrowed = A->d_row_ptr && (nnz == 0 || (A->d_col && A->d_val));
+  if (f->borrowed) {
+    f->d_row_ptr = A->d_row_ptr; f->d_col = A->d_col; f->d_val = A->d_val;
+  } else {
+    F_ARRAY(f->d_row_ptr, (rows + 1) * 4);
+    F_ARRAY(f->d_col, nnz * 4);
+    F_ARRAY(f->d_val, nnz * 4);
+    HIP_TRY_F(hipMemcpyAsync(f->d_row_ptr, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    if (nnz > 0) {
+      HIP_TRY_F(hipMemcpyAsync(f->d_col, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+      HIP_TRY_F(hipMemcpyAsync(f->d_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    }
+  }
+  F_ARRAY(f->d_col_ptr, (cols + 1) * 4);
+  F_ARRAY(f->d_row_of, nnz * 4);
+  F_ARRAY(f->d_clist, rows * 4);
+  F_ARRAY(f->d_alist, rows * 4);
+  F_ARRAY(f->d_stamp, rows * 4);
+  F_ARRAY(f->d_side, rows * 4);
+  F_ARRAY(f->d_cplist, (nnz / 1024 + 1) * sizeof(FrPiece));   // sum of ceil(len / 2048) over columns longer than 2048 <= nnz / 1024
+  F_ARRAY(f->d_rplist, (nnz / 2048 + 1) * sizeof(FrPiece));   // the same for rows longer than 4096
+  F_ARRAY(f->d_ctl, FR_CTL_BYTES);
+  HIP_TRY_F(hipHostMalloc((void **)&f->h_rec, sizeof(FrontierRec) * FR_BATCH, hipHostMallocDefault));
+  HIP_TRY_F(hipMemsetAsync(f->d_stamp, 0, std::max<size_t>((size_t)rows * 4, 16), e->stream));
+  HIP_TRY_F(hipMemsetAsync(f->d_ctl, 0, FR_CTL_BYTES, e->stream));
+  // the pattern of the transpose: column histogram, exclusive scan, scatter through per-column cursors
+  HIP_TRY_F(hipMalloc((void **)&cnt, (size_t)(cols + 1) * 4));
+  HIP_TRY_F(hipMemsetAsync(cnt, 0, (size_t)(cols + 1) * 4, e->stream));
+  const dim3 egrid((unsigned)std::max<int64_t>(1, (nnz + FR_BS - 1) / FR_BS));
+  if (nnz > 0) {
+    hipLaunchKernelGGL(frontier_col_hist, egrid, dim3(FR_BS), 0, e->stream, f->d_col, nnz, (int32_t)cols, cnt);
+    HIP_TRY_F(hipGetLastError());
+  }
+  HIP_TRY_F(device_exclusive_sum_u32(e->stream, cnt, (uint32_t *)f->d_col_ptr, cols + 1));
+  HIP_TRY_F(hipMemcpyAsync(cnt, f->d_col_ptr, (size_t)(cols + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
+  if (nnz > 0) {
+    hipLaunchKernelGGL(frontier_scatter, egrid, dim3(FR_BS), 0, e->stream, f->d_row_ptr, f->d_col, nnz, (int32_t)rows, (int32_t)cols,
+                       cnt, f->d_row_of);
+    HIP_TRY_F(hipGetLastError());
+  }
+  HIP_TRY_F(hipStreamSynchronize(e->stream));   // the host arrays and the cursors are done with
+  (void)hipFree(cnt);
+  cnt = nullptr;
+#undef F_ARRAY
+#undef HIP_TRY_F
+  *out = f;
+  return SH_OK;
+}
+
+int sh_frontier_free(sh_engine *e, sh_frontier *f) {
+  if (!f)
+    return SH_OK;
+  if (e) {
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->stream);
+  }
+  if (!f->borrowed)
+    for (void *p : {(void *)f->d_row_ptr, (void *)f->d_col, (void *)f->d_val})
+      if (p) (void)hipFree(p);
+  for (void *p : {(void *)f->d_col_ptr, (void *)f->d_row_of, (void *)f->d_clist, (void *)f->d_alist, (void *)f->d_stamp,
+                  (void *)f->d_side, (void *)f->d_cplist, (void *)f->d_rplist, (void *)f->d_ctl})
+    if (p) (void)hipFree(p);
+  if (f->h_rec) (void)hipHostFree(f->h_rec);
+  delete f;
+  return SH_OK;
+}
+
+int sh_frontier_footprint(const sh_frontier *f, uint64_t *device_bytes) {
+  if (!f || !device_bytes)
+    return SH_EINVAL;
+  *device_bytes = (uint64_t)f->bytes;
+  return SH_OK;
+}
+
+int sh_frontier_transpose(sh_engine *e, const sh_frontier *f, int32_t *col_ptr, int32_t *row_of) {
+  if (!e || !f)
+    return fail(e, SH_EINVAL, "sh_frontier_transpose: NULL argument");
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  int32_t n = 0;
+  HIP_TRY(e, hipMemcpy(&n, f->d_col_ptr + f->rows, 4, hipMemcpyDeviceToHost));
+  if (col_ptr) HIP_TRY(e, hipMemcpy(col_ptr, f->d_col_ptr, (size_t)(f->rows + 1) * 4, hipMemcpyDeviceToHost));
+  if (row_of && n > 0) HIP_TRY(e, hipMemcpy(row_of, f->d_row_of, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return SH_OK;
+}
+
+int sh_iterate_frontier(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_frontier *f, sh_vec *x, const sh_vec *y0,
+                        sh_vec *scratch, const void *alpha, const void *beta, double delta, int32_t max_iters,
+                        double dense_share, int32_t *iters, int32_t *converged, int32_t *mode_per_iter,
+                        int64_t *changed_per_iter, int64_t *active_per_iter, uint64_t *ns_per_iter, uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (sr == SH_PLUS_TIMES_F32)
+    return fail(e, SH_EINVAL, "sh_iterate_frontier: SH_PLUS_TIMES_F32 is not served (a recomputed row would have to reproduce "
+                              "the summation order of the dense launches' plan): call sh_iterate");
+  if (sr != SH_MIN_PLUS_F32 && sr != SH_OR_AND_I32 && sr != SH_MAX_MIN_I32)
+    return fail(e, SH_EINVAL, "sh_iterate_frontier: unknown semiring %d", (int)sr);
+  if (max_iters < 1)
+    return fail(e, SH_EINVAL, "sh_iterate_frontier: max_iters = %d, must be at least 1", (int)max_iters);
+  if (sr == SH_MIN_PLUS_F32 && !(delta > 0.0))
+    return fail(e, SH_EINVAL, "sh_iterate_frontier: delta = %g, SH_MIN_PLUS_F32 needs delta > 0 (a row that is not recomputed "
+                              "must pass |in - out| < delta)", delta);
+  if (!e || !A || !f || !x || !y0 || !scratch || !alpha || !beta || !iters || !converged)
+    return fail(e, SH_EINVAL, "sh_iterate_frontier: NULL argument");
+  if (A->rows != A->cols)
+    return fail(e, SH_ESHAPE, "sh_iterate_frontier: matrix must be square (inc/common.h:49-52)");
+  if (f->rows != A->rows || f->nnz != A->nnz || (f->borrowed && f->A != A))
+    return fail(e, SH_EINVAL, "sh_iterate_frontier: the frontier handle was made for another matrix");
+  if (x->n < A->rows || scratch->n < A->rows || y0->n < A->rows)
+    return fail(e, SH_ESHAPE, "sh_iterate_frontier: vectors shorter than the matrix");
+  if (scratch->d == x->d && A->rows > 0)
+    return fail(e, SH_EINVAL, "sh_iterate_frontier: scratch must not alias x");
+  HIP_TRY(e, hipSetDevice(e->device));
+  if (!e->ev_iter[0])
+    for (auto &ev : e->ev_iter) HIP_TRY(e, hipEventCreate(&ev));
+  static_assert(FR_BATCH <= 8, "one event per launch of a batch, as sh_iterate");
+  if (dense_share < 0) dense_share = FRONTIER_DENSE_SHARE;
+  const bool never_sparse = dense_share == 0.0;
+  const uint32_t max_entries = dense_share >= 1.0 ? 0xFFFFFFFFu : (uint32_t)(dense_share * (double)A->nnz);
+  HIP_TRY(e, hipMemsetAsync(f->d_ctl, 0, FR_CTL_BYTES, e->stream));
+  const dim3 dgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((A->rows + FR_BS - 1) / FR_BS, (int64_t)e->n_cus * 8)));
+  sh_vec *in = x, *out = scratch;
+  const sh_vec *y = y0;
+  int32_t it = 0;
+  bool term = false, sparse = false;
+  uint64_t total = 0;
+  while (!term && it < max_iters) {
+    // A batch holds launches of ONE mode: which buffer a launch reads must be known when it is enqueued, and that
+    // depends on how many dense launches (which swap the buffers) ran before it.
+    const int nb = std::min<int32_t>(FR_BATCH, max_iters - it);
+    hipLaunchKernelGGL(frontier_begin, dim3(1), dim3(64), 0, e->stream, f->d_ctl);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(e->ev_iter[0], e->stream));
+    for (int k = 0; k < nb; k++) {
+      const int L = it + k, p = L & 1;
+      if (sparse) {
+        int rc;
+        switch (sr) {
+        case SH_MIN_PLUS_F32: rc = launch_sparse<MinPlusF32>(e, f, A, in, alpha, beta, delta, k, p); break;
+        case SH_OR_AND_I32: rc = launch_sparse<OrAndI32>(e, f, A, in, alpha, beta, delta, k, p); break;
+        default: rc = launch_sparse<MaxMinI32>(e, f, A, in, alpha, beta, delta, k, p); break;
+        }
+        if (rc)
+          return rc;
+      } else {
+        StepDev st{f->d_ctl->flag + k, (const uint32_t *)in->d, 0, delta, f->d_ctl->go + k};
+        int rc = dispatch(e, sr, A, in, y, alpha, beta, out, st);
+        if (rc)
+          return rc;
+        hipLaunchKernelGGL(frontier_detect, dgrid, dim3(FR_BS), 0, e->stream, f->d_ctl, k, p ^ 1, (const uint32_t *)in->d,
+                           (const uint32_t *)out->d, (int32_t)A->rows, f->d_col_ptr, f->d_clist, f->d_cplist);
+        HIP_TRY(e, hipGetLastError());
+        sh_vec *t = in; in = out; out = t;
+        y = in;
+      }
+      hipLaunchKernelGGL(frontier_decide, dim3(1), dim3(64), 0, e->stream, f->d_ctl, k, p, sparse ? 0 : 1, (int32_t)A->rows, max_entries,
+                         (!never_sparse && L + 1 >= 2) ? 1 : 0, sparse ? 1 : 0);
+      HIP_TRY(e, hipGetLastError());
+      HIP_TRY(e, hipEventRecord(e->ev_iter[k + 1], e->stream));
+    }
+    HIP_TRY(e, hipMemcpyAsync(f->h_rec, f->d_ctl->rec, sizeof(FrontierRec) * FR_BATCH, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    int ran = 0;
+    while (ran < nb && f->h_rec[ran].ran) ran++;
+    if (ran < 1)
+      return fail(e, SH_EHIP, "sh_iterate_frontier: the first launch of a batch did not report");
+    for (int k = 0; k < ran; k++) {
+      float ms = 0.f;
+      HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_iter[k], e->ev_iter[k + 1]));
+      const uint64_t ns = (uint64_t)((double)ms * 1e6);
+      if (ns_per_iter) ns_per_iter[it + k] = ns;
+      if (mode_per_iter) mode_per_iter[it + k] = sparse ? 1 : 0;
+      if (changed_per_iter) changed_per_iter[it + k] = (int64_t)f->h_rec[k].changed;
+      if (active_per_iter) active_per_iter[it + k] = (int64_t)f->h_rec[k].active;
+      total += ns;
+    }
+    // the gated launches behind the last one that ran wrote nothing; dense ones were enqueued with swapped buffers
+    if (!sparse && (nb - ran) % 2) { sh_vec *t = in; in = out; out = t; }
+    y = in;
+    term = f->h_rec[ran - 1].differs == 0;
+    sparse = f->h_rec[ran - 1].sparse_next != 0;
+    it += ran;
+  }
+  if (in != x) {
+    HIP_TRY(e, hipMemcpyAsync(x->d, in->d, A->rows * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+  }
+  *iters = it;
+  *converged = term ? 1 : 0;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"

@@ -288,6 +288,9 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
                           const int32_t *d_ci, const uint32_t *d_val, const sh_plan_options &opt, int n_cus, TiledHost &H,
                           TiledDevArrays &D, std::string &why);
 
+// Exclusive prefix sum of n words on the device (rocPRIM, plan_gpu.hip); in and out are different arrays.  Waits for the stream.
+hipError_t device_exclusive_sum_u32(hipStream_t stream, const uint32_t *in, uint32_t *out, int64_t n);
+
 // ---- the (or,and) semiring on bits (see bits.hip.h) -----------------------
 struct BitsHost {
   std::vector<BitsItem> items;

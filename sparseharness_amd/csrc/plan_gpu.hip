@@ -1018,6 +1018,18 @@ hip_failed:
 #undef CUB
 }
 
+// Exclusive prefix sum of n words on the device (sh_frontier_create: column counts -> col_ptr).
+hipError_t device_exclusive_sum_u32(hipStream_t stream, const uint32_t *in, uint32_t *out, int64_t n) {
+  if (n <= 0) return hipSuccess;
+  CubTemp tmp;
+  size_t bytes = 0;
+  hipError_t r = excl_sum((void *)nullptr, bytes, in, out, n, stream);
+  if (r == hipSuccess) r = tmp.reserve(bytes);
+  if (r == hipSuccess) r = excl_sum(tmp.p, bytes, in, out, n, stream);
+  if (r == hipSuccess) r = hipStreamSynchronize(stream);   // (the temporary storage dies here)
+  return r;
+}
+
 int build_bits_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *d_rp, const int32_t *d_ci,
                         const uint32_t *d_val, BitsHost &H, uint32_t **d_ent, std::string &why) {
   H.n_rr = (int32_t)std::max<int64_t>(1, (rows + BITS_BR - 1) / BITS_BR);

@@ -115,6 +115,34 @@ class CsrMatrix:
             self.h = None
 
 
+class Frontier:
+    """What the sparse launches of Engine.iterate_frontier need for one square matrix: its CSR arrays (borrowed from
+    the matrix when it keeps them, copied otherwise), the pattern of its transpose, worklists."""
+
+    def __init__(self, engine, handle, n):
+        self.engine, self.h, self.n = engine, handle, n
+
+    def transpose(self):
+        """(col_ptr[n + 1], row_of[col_ptr[n]]); the order of the rows inside one column is unspecified."""
+        lib = abi.load()
+        col_ptr = np.zeros(self.n + 1, np.int32)
+        self.engine._chk(lib.sh_frontier_transpose(self.engine.h, self.h, col_ptr.ctypes.data_as(C.POINTER(C.c_int32)), None))
+        row_of = np.zeros(max(int(col_ptr[-1]), 1), np.int32)
+        self.engine._chk(lib.sh_frontier_transpose(self.engine.h, self.h, None, row_of.ctypes.data_as(C.POINTER(C.c_int32))))
+        return col_ptr, row_of[:int(col_ptr[-1])]
+
+    def footprint(self):
+        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
+        b = C.c_uint64()
+        self.engine._chk(abi.load().sh_frontier_footprint(self.h, C.byref(b)))
+        return b.value
+
+    def free(self):
+        if self.h is not None:
+            abi.load().sh_frontier_free(self.engine.h, self.h)
+            self.h = None
+
+
 class Engine:
     """One HIP device + one stream (replaces Harness's OpenCL context/queue)."""
 
@@ -225,6 +253,32 @@ class Engine:
                                         delta, max_iters, None, C.byref(iters), C.byref(conv), per,
                                         C.byref(total)))
         return iters.value, bool(conv.value), list(per[:iters.value]), total.value
+
+    # ---- frontier-driven iteration: only the rows whose inputs changed are recomputed while the wavefront is thin
+    def frontier(self, A, row_ptr, col_idx, val):
+        """The handle Engine.iterate_frontier needs; the arrays are the ones A was uploaded from (A must outlive it)."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        val = np.ascontiguousarray(val)
+        assert val.dtype.itemsize == 4
+        h = C.c_void_p()
+        self._chk(abi.load().sh_frontier_create(self.h, A.h, int(row_ptr[-1]), _ptr(row_ptr), _ptr(col_idx), _ptr(val), C.byref(h)))
+        return Frontier(self, h, A.rows)
+
+    def iterate_frontier(self, semiring, A, F, x, y0, scratch, alpha, beta, delta=1e-4, max_iters=10000, dense_share=-1.0):
+        """-> (iters, converged, modes, changed, active, ns_per_iter, total_ns); per launch: 0 dense / 1 sparse, rows whose
+        bits it changed, rows it recomputed."""
+        dt = elem_dtype(semiring)
+        a, b = np.array([alpha], dt), np.array([beta], dt)
+        iters, conv, total = C.c_int32(), C.c_int32(), C.c_uint64()
+        cap = max(int(max_iters), 1)
+        per, modes = (C.c_uint64 * cap)(), (C.c_int32 * cap)()
+        changed, active = (C.c_int64 * cap)(), (C.c_int64 * cap)()
+        self._chk(abi.load().sh_iterate_frontier(self.h, semiring, A.h, F.h, x.h, y0.h, scratch.h, _ptr(a), _ptr(b), delta,
+                                                 max_iters, dense_share, C.byref(iters), C.byref(conv), modes, changed, active,
+                                                 per, C.byref(total)))
+        n = iters.value
+        return n, bool(conv.value), list(modes[:n]), list(changed[:n]), list(active[:n]), list(per[:n]), total.value
 
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
