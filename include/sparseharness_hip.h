@@ -428,6 +428,89 @@ int sh_iterate_frontier(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_fronti
                         double dense_share, int32_t *iters, int32_t *converged, int32_t *mode_per_iter,
                         int64_t *changed_per_iter, int64_t *active_per_iter, uint64_t *ns_per_iter, uint64_t *total_ns);
 
+/* ---- direction-optimising BFS with levels and parents: extends the BFS loop of HarnessBFS::executeRun
+ *      (app/bfs.cpp:94-174) and Harness::executeKernel (inc/harness.h:149-195).  The reference's BFS is an SpMV loop on
+ *      the (or,and) semiring whose answer is a 0/1 reachability vector; it has no counterpart of the calls below.
+ *      sh_bfs_levels is a BFS that is an algorithm of its own (Beamer, Asanovic, Patterson, SC 2012): it answers HOW FAR
+ *      every vertex is from the sources and, on request, THROUGH WHICH vertex it was reached.  In thin levels it goes
+ *      top-down over the out-edges of the frontier only; in fat levels bottom-up, where an unvisited row stops at its
+ *      first entry whose column is in the frontier -- the early exit that the semiring contract forbids to sh_spmv.
+ *
+ *      An EDGE c -> r exists when row r stores an entry with column c, 0 <= c < rows, and a value whose 32 bits are not
+ *      all zero: exactly the entries that can switch a row on under SH_OR_AND_I32.  The SOURCES are the v with x0[v] != 0.
+ *        level[v]  = 0 for a source, else k + 1 where launch k (from 0) of sh_iterate(SH_OR_AND_I32, alpha = 1, beta = 1,
+ *                    y0 = x0) is the first whose output has x[v] != 0; -1 if there is none (the BFS distance);
+ *        parent[v] = -1 for sources and unreached vertices, else the SMALLEST c with an edge c -> v and
+ *                    level[c] == level[v] - 1 (canonical: one extra row-parallel pass after the traversal, run only when
+ *                    `parent` is given; the traversal itself carries no parent atomics);
+ *        *depth = the largest level assigned, *reached = vertices with level >= 0, *complete = 1 when the frontier ran
+ *                    empty, 0 when max_levels steps were used up first (levels above max_levels stay -1).
+ *      Step L assigns level L + 1 from the vertices at level L; it runs while that frontier is not empty and
+ *      L < max_levels.  A complete search runs depth + 1 steps (the last finds nothing, as sh_iterate's confirming
+ *      launch), so sh_iterate's *iters == depth + 1; a search cut at max_levels == depth reports complete = 0.
+ *      The result does not depend on the direction any step ran in.
+ *
+ *      Measured on an MI355X (DESIGN.md "6e Direction-optimising BFS", profiles/bfs_levels_*.json), total device time at
+ *      the default shares as a ratio to sh_iterate(SH_OR_AND_I32) under the matrix' default plan / to sh_iterate_frontier at
+ *      its default share, without the parent pass, from vertex 0 and two random sources:
+ *        - R-MAT-23 (8.4 M rows, 134 M entries; 7-8 launches, 2.1-2.4 ms):   0.44-0.47 / 0.11-0.23; with parents 1.15-1.25
+ *        - power-law 10 M rows / 200 M entries (11 launches, 4.4 ms):        0.58-0.62 / 0.19;      with parents 1.36-1.40
+ *        - 2048 x 2048 grid graph (3087-4095 launches, 187-251 ms):          0.38-0.42 / 0.84-0.96; with parents the same
+ *        - 170 998 rows, 0.96 M entries (22-23 launches of 17 us, 0.4 ms):   1.54-1.62 / 0.34-0.37; with parents 1.60-1.68
+ *        The bottom-up steps looked at 5 to 24 % of the edges per step (R-MAT-23: 22 M of 134 M in its fattest level).  A step
+ *        costs 16 to 25 us at least (four dependent launches, two of them empty: all of the grid's 24-26 us per level, and why
+ *        the small matrix loses); a top-down step over a fat level is the expensive one (1.5 M edges: 0.9 ms), which is why
+ *        Beamer's 1/14 loses on the power-law matrix (2.3) and the default turns bottom-up at 0.5 % of the edges.  The parent
+ *        pass gathers level[] once per edge: 1.65 ms on R-MAT-23, 3.4 ms on the power-law matrix -- more than the search.
+ *        Rule: call it when you need levels or parents.  For reachability alone call it (without `parent`) on matrices whose
+ *        sh_iterate launch costs well above 25 us -- large power-law graphs and grids / meshes alike --; on small matrices
+ *        (a launch of under 25 us) sh_iterate stays faster.  No pair of shares makes the small matrix win.
+ *
+ * sh_bfs_graph_create: the handle is made from the host CSR arrays alone (no sh_csr: the search runs on a layout of its
+ * own, whatever plan the matrix was uploaded under).  The matrix is square (rows x rows); col_idx outside [0, rows) and
+ * stored zeros are legal and are no edges.  The handle holds on the device: the edge pattern by rows (in_ptr[rows + 1],
+ * in_col[edges], stored order of the survivors kept: 4 B per edge), its transpose (out_ptr[rows + 1], out_row[edges],
+ * order inside one list unspecified), two vertex queues, two frontier bitmaps (one bit per vertex), two lists of pieces
+ * of long out-lists, the pieces of long rows, a control block.  Built on the device (flag per entry, exclusive scan,
+ * compaction; column histogram, scan, scatter).  rows == 0 gives a valid handle.
+ * sh_bfs_graph_footprint: device bytes held, with W = (rows + 31) / 32 =
+ *     8 * (rows + 1) + 8 * edges  +  8 * rows  +  8 * W  +  16 * (edges / 1024 + 1)  +  8 * (edges / 2048 + 1)  +  18432.
+ * sh_bfs_graph_edges: the entries kept as edges.
+ *
+ * sh_bfs_levels: level, parent (may be NULL): int32 vectors of >= rows elements, written in full; x0 is only read; level
+ * and parent must not alias x0 or each other.  g may serve any number of calls, one at a time.
+ * max_levels >= 1.  The per-level arrays (each may be NULL) have capacity max_levels + 1 for size_per_level (entry 0 =
+ * the number of sources, entry L + 1 = vertices step L assigned) and max_levels for the others; one entry per step that
+ * ran, entries beyond are not written.
+ * mode_per_level[L]: 0 = step L ran top-down, 1 = bottom-up.  edges_per_level[L]: edges the step looked at -- top-down:
+ *   exactly the sum of the out-list lengths of its frontier; bottom-up: what the early exit left (informational: rows
+ *   above 32 edges are searched 64 edges at a time, and a whole group counts).
+ * ns_per_level / total_ns: device time (hipEvent) as elsewhere; total_ns also holds the set-up launch and the parent pass.
+ * The switching rule, with E = edges, n = rows, F_L = the vertices at level L, m_L = the sum of their out-list lengths:
+ *   step 0 is top-down unless m_0 > up_share * E; a step after a top-down step is bottom-up iff m_L > up_share * E; a
+ *   step after a bottom-up step is top-down iff |F_L| < down_share * n; otherwise the direction stays (all in double
+ *   arithmetic).  up_share >= 1: top-down throughout; up_share = down_share = 0: bottom-up throughout (unless m_0 = 0: sources without
+ *   out-edges, whose only step then runs top-down over nothing); a negative value:
+ *   the engine's default (0.005 and 0.01; Beamer's published 1/14 and 1/24 lose here: see the measurements).
+ * The launches are enqueued ahead of the host, 8 steps at first and up to 32 at a time: every step is enqueued as three
+ * launches (queue rebuild, top-down, bottom-up) that return at once unless the device-side control block says the step
+ * runs in their direction, plus one small launch that closes the step; the host joins in once per batch.
+ * SH_EINVAL: NULL arguments, rows < 0, max_levels < 1, a NaN share, aliasing.  SH_ESHAPE: row_ptr[0] != 0,
+ * row_ptr[rows] != nnz or a row_ptr that decreases, vectors shorter than rows.  All are reported before any device work.
+ * NOT covered: the other semirings, several independent sources per call (that is sh_bits_iterate), row pieces
+ * (sh_spmv_step_pieces), the multi-GPU driver and the C++ harness apps (their output is the reference's 0/1 vector).
+ */
+typedef struct sh_bfs_graph sh_bfs_graph;
+int sh_bfs_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_bfs_graph **out);
+int sh_bfs_graph_free(sh_engine *e, sh_bfs_graph *g);
+int sh_bfs_graph_footprint(const sh_bfs_graph *g, uint64_t *device_bytes);
+int sh_bfs_graph_edges(const sh_bfs_graph *g, int64_t *edges);
+int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level, sh_vec *parent, int32_t max_levels,
+                  double up_share, double down_share, int32_t *depth, int64_t *reached, int32_t *complete,
+                  int32_t *mode_per_level, int64_t *size_per_level, int64_t *edges_per_level, uint64_t *ns_per_level,
+                  uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,20 +2,25 @@
 """Reads hipcc's -Rpass-analysis=kernel-resource-usage remarks and fails if a kernel of the tiled plan, or one of the
 multi-vector kernels (spmm_csr_kernel / spmm_long_fixup, multi.hip.h), or one of the packed-bit kernels (msbfs_csr_kernel /
 msbfs_long_fixup, msbfs.hip.h), or one of the frontier kernels (frontier_mark / frontier_pull / frontier_apply /
-frontier_detect, frontier.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+frontier_detect, frontier.hip.h), or one of the BFS kernels (bfs_init / bfs_topdown / bfs_bottomup / bfs_queue_from_bitmap /
+bfs_decide / bfs_parents, bfs.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi, seen_bits, seen_frontier = [], 0, set(), set(), set()
+bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs = [], 0, set(), set(), set(), set()
+BFS_KERNELS = ("bfs_init", "bfs_topdown", "bfs_bottomup", "bfs_queue_from_bitmap", "bfs_decide", "bfs_parents")
 for blk in text.split("remark: Function Name: ")[1:]:
     name = blk.split()[0]
     multi = "spmm_csr" in name or "spmm_long" in name
     packed = "msbfs_csr" in name or "msbfs_long" in name
     frontier = any(k in name for k in ("frontier_mark", "frontier_pull", "frontier_apply", "frontier_detect"))
-    if "spmv_tiled" not in name and not multi and not packed and not frontier:
+    bfs = any(k in name for k in BFS_KERNELS)
+    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs:
         continue
-    if frontier:
+    if bfs:
+        seen_bfs.add(name)
+    elif frontier:
         seen_frontier.add(name)
     elif multi:
         seen_multi.add(name)
@@ -50,7 +55,10 @@ if n_bits != 8 or len(seen_bits) != 16:
 # frontier_mark, frontier_detect, and frontier_pull / frontier_apply for the three order-free semirings
 if len(seen_frontier) != 8:
     sys.exit(f"expected 8 frontier kernels in the remarks, found {len(seen_frontier)}: {sorted(seen_frontier)}")
+# the six kernels of sh_bfs_levels, under the limits of the frontier kernels
+if len(seen_bfs) != len(BFS_KERNELS):
+    sys.exit(f"expected {len(BFS_KERNELS)} BFS kernels in the remarks, found {len(seen_bfs)}: {sorted(seen_bfs)}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit and {len(seen_frontier)} frontier kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier and {len(seen_bfs)} BFS kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

@@ -11,6 +11,7 @@
 #include "multi.hip.h"
 #include "msbfs.hip.h"
 #include "frontier.hip.h"
+#include "bfs.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -2019,6 +2020,295 @@ int sh_iterate_frontier(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_fronti
   }
   *iters = it;
   *converged = term ? 1 : 0;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- direction-optimising BFS with levels and parents (bfs.hip.h) -----------------------------------------------------
+struct sh_bfs_graph {
+  int64_t rows = 0, nnz = 0, edges = 0;
+  int32_t words = 0;               // 32-bit words of one frontier bitmap
+  int32_t *d_in_ptr = nullptr, *d_in_col = nullptr, *d_out_ptr = nullptr, *d_out_row = nullptr;
+  uint32_t *d_queue[2] = {nullptr, nullptr}, *d_bm[2] = {nullptr, nullptr};
+  FrPiece *d_opieces[2] = {nullptr, nullptr};   // pieces of the long out-lists of the frontier in queue 0 / 1
+  FrPiece *d_rpieces = nullptr;                 // pieces of the rows above BFS_ROW_PIECE (static)
+  int32_t n_rpieces = 0;
+  BfsCtl *d_ctl = nullptr;         // BFS_CTL_BYTES, followed by the BfsParts
+  BfsPart *d_part = nullptr;
+  BfsCtl *h_ctl = nullptr;         // pinned: the control block as read back once per batch
+  hipEvent_t ev[BFS_BATCH + 1] = {};
+  size_t bytes = 0;
+};
+// sh_bfs_levels' up_share / down_share < 0: see DESIGN.md "6e Direction-optimising BFS" (the sweep of tools/bfs_levels_bench.py)
+static constexpr double BFS_UP_SHARE = 0.005, BFS_DOWN_SHARE = 0.01;
+static_assert(sizeof(BfsCtl) <= BFS_CTL_BYTES, "the control block is accounted as BFS_CTL_BYTES (sh_bfs_graph_footprint)");
+static_assert(sizeof(BfsPart) * BFS_MAX_BLOCKS == BFS_PART_BYTES, "one BfsPart per workgroup");
+
+extern "C" {
+
+int sh_bfs_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_bfs_graph **out) {
+  // what the scalars and the host arrays alone decide comes first: no device is needed to be told
+  if (out) *out = nullptr;
+  if (rows < 0 || rows > 0x7FFFFF00ll)
+    return fail(e, SH_EINVAL, "sh_bfs_graph_create: rows = %lld, must be in [0, 2^31 - 256]", (long long)rows);
+  if (nnz < 0 || nnz > 0x7FFFFF00ll)
+    return fail(e, SH_EINVAL, "sh_bfs_graph_create: nnz = %lld, must be in [0, 2^31 - 256]", (long long)nnz);
+  if (!row_ptr || !out || (nnz > 0 && (!col_idx || !val)))
+    return fail(e, SH_EINVAL, "sh_bfs_graph_create: NULL argument (row_ptr, out, or col_idx / val of a matrix with entries)");
+  if (row_ptr[0] != 0 || (int64_t)row_ptr[rows] != nnz)
+    return fail(e, SH_ESHAPE, "sh_bfs_graph_create: row_ptr[0] = %d and row_ptr[rows] = %d, must be 0 and nnz = %lld",
+                (int)row_ptr[0], (int)row_ptr[rows], (long long)nnz);
+  for (int64_t r = 0; r < rows; r++)   // (the build indexes by row_ptr on the device: it must stay inside the arrays)
+    if (row_ptr[r] > row_ptr[r + 1])
+      return fail(e, SH_ESHAPE, "sh_bfs_graph_create: row_ptr decreases at row %lld", (long long)r);
+  if (!e)
+    return fail(e, SH_EINVAL, "sh_bfs_graph_create: NULL argument (engine)");
+  HIP_TRY(e, hipSetDevice(e->device));
+  sh_bfs_graph *g = new (std::nothrow) sh_bfs_graph();
+  if (!g)
+    return fail(e, SH_ENOMEM, "out of host memory");
+  g->rows = rows; g->nnz = nnz;
+  g->words = (int32_t)((rows + 31) / 32);
+  // temporaries of the build: the CSR arrays as given, the edge flags and their scan, the scatter's cursors
+  int32_t *t_rp = nullptr, *t_ci = nullptr;
+  uint32_t *t_val = nullptr, *t_flag = nullptr, *t_pos = nullptr, *t_cnt = nullptr;
+  auto cleanup = [&](int rc) {
+    for (void *p : {(void *)t_rp, (void *)t_ci, (void *)t_val, (void *)t_flag, (void *)t_pos, (void *)t_cnt})
+      if (p) (void)hipFree(p);
+    t_rp = t_ci = nullptr; t_val = t_flag = t_pos = t_cnt = nullptr;
+    if (rc) sh_bfs_graph_free(e, g);
+    return rc;
+  };
+#define HIP_TRY_G(call)                                                         \
+  do {                                                                          \
+    hipError_t _r = (call);                                                     \
+    if (_r != hipSuccess)                                                       \
+      return cleanup(fail(e, _r == hipErrorOutOfMemory ? SH_ENOMEM : SH_EHIP,   \
+                          "%s failed: %s", #call, hipGetErrorString(_r)));      \
+  } while (0)
+  // (an array of `nbytes` counts as that in the footprint; an empty one still gets a few bytes to point at)
+#define G_ARRAY(ptr, nbytes)                                                                   \
+  do {                                                                                         \
+    HIP_TRY_G(hipMalloc((void **)&(ptr), std::max<size_t>((size_t)(nbytes), 16)));             \
+    g->bytes += (size_t)(nbytes);                                                              \
+  } while (0)
+  HIP_TRY_G(hipMalloc((void **)&t_rp, (size_t)(rows + 1) * 4));
+  HIP_TRY_G(hipMalloc((void **)&t_ci, std::max<size_t>((size_t)nnz * 4, 16)));
+  HIP_TRY_G(hipMalloc((void **)&t_val, std::max<size_t>((size_t)nnz * 4, 16)));
+  HIP_TRY_G(hipMalloc((void **)&t_flag, (size_t)(nnz + 1) * 4));
+  HIP_TRY_G(hipMalloc((void **)&t_pos, (size_t)(nnz + 1) * 4));
+  HIP_TRY_G(hipMalloc((void **)&t_cnt, (size_t)(rows + 1) * 4));
+  HIP_TRY_G(hipMemcpyAsync(t_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  if (nnz > 0) {
+    HIP_TRY_G(hipMemcpyAsync(t_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY_G(hipMemcpyAsync(t_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  // the entries that are edges: flag, exclusive scan, compaction (the stored order of the survivors is kept)
+  const dim3 blk(BFS_BS), ngrid((unsigned)((nnz + 1 + BFS_BS - 1) / BFS_BS)), rgrid((unsigned)((rows + 1 + BFS_BS - 1) / BFS_BS));
+  hipLaunchKernelGGL(bfs_edge_flag, ngrid, blk, 0, e->stream, t_ci, t_val, nnz, (int32_t)rows, t_flag);
+  HIP_TRY_G(hipGetLastError());
+  HIP_TRY_G(device_exclusive_sum_u32(e->stream, t_flag, t_pos, nnz + 1));
+  uint32_t n_edges = 0;
+  HIP_TRY_G(hipMemcpy(&n_edges, t_pos + nnz, 4, hipMemcpyDeviceToHost));
+  const int64_t E = (int64_t)n_edges;
+  g->edges = E;
+  G_ARRAY(g->d_in_ptr, (rows + 1) * 4);
+  G_ARRAY(g->d_in_col, E * 4);
+  G_ARRAY(g->d_out_ptr, (rows + 1) * 4);
+  G_ARRAY(g->d_out_row, E * 4);
+  for (int i = 0; i < 2; i++) {
+    G_ARRAY(g->d_queue[i], rows * 4);
+    G_ARRAY(g->d_bm[i], (int64_t)g->words * 4);
+    G_ARRAY(g->d_opieces[i], (E / 1024 + 1) * sizeof(FrPiece));   // sum of ceil(len / 2048) over out-lists longer than 2048 <= E / 1024
+  }
+  G_ARRAY(g->d_rpieces, (E / 2048 + 1) * sizeof(FrPiece));        // the same for rows longer than 4096
+  G_ARRAY(g->d_ctl, BFS_CTL_BYTES + BFS_PART_BYTES);
+  g->d_part = (BfsPart *)((char *)g->d_ctl + BFS_CTL_BYTES);
+  HIP_TRY_G(hipHostMalloc((void **)&g->h_ctl, sizeof(BfsCtl), hipHostMallocDefault));
+  for (auto &ev : g->ev) HIP_TRY_G(hipEventCreate(&ev));
+  HIP_TRY_G(hipMemsetAsync(g->d_ctl, 0, BFS_CTL_BYTES + BFS_PART_BYTES, e->stream));
+  if (nnz > 0) {
+    hipLaunchKernelGGL(bfs_edge_compact, ngrid, blk, 0, e->stream, t_ci, t_flag, t_pos, nnz, g->d_in_col);
+    HIP_TRY_G(hipGetLastError());
+  }
+  hipLaunchKernelGGL(bfs_row_starts, rgrid, blk, 0, e->stream, t_rp, t_pos, rows, g->d_in_ptr);
+  HIP_TRY_G(hipGetLastError());
+  // the static pieces of long rows (the cursor borrows the control block's first word, cleared again below)
+  if (rows > 0) {
+    hipLaunchKernelGGL(bfs_row_pieces, rgrid, blk, 0, e->stream, g->d_in_ptr, rows, (uint32_t *)g->d_ctl, g->d_rpieces);
+    HIP_TRY_G(hipGetLastError());
+  }
+  uint32_t n_rp = 0;
+  HIP_TRY_G(hipMemcpyAsync(&n_rp, g->d_ctl, 4, hipMemcpyDeviceToHost, e->stream));
+  // the pattern of the transpose: column histogram, exclusive scan, scatter through per-column cursors
+  HIP_TRY_G(hipMemsetAsync(t_cnt, 0, (size_t)(rows + 1) * 4, e->stream));
+  const dim3 egrid((unsigned)std::max<int64_t>(1, (E + FR_BS - 1) / FR_BS));
+  if (E > 0) {
+    hipLaunchKernelGGL(frontier_col_hist, egrid, dim3(FR_BS), 0, e->stream, g->d_in_col, E, (int32_t)rows, t_cnt);
+    HIP_TRY_G(hipGetLastError());
+  }
+  HIP_TRY_G(device_exclusive_sum_u32(e->stream, t_cnt, (uint32_t *)g->d_out_ptr, rows + 1));
+  HIP_TRY_G(hipMemcpyAsync(t_cnt, g->d_out_ptr, (size_t)(rows + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
+  if (E > 0) {
+    hipLaunchKernelGGL(frontier_scatter, egrid, dim3(FR_BS), 0, e->stream, g->d_in_ptr, g->d_in_col, E, (int32_t)rows, (int32_t)rows,
+                       t_cnt, g->d_out_row);
+    HIP_TRY_G(hipGetLastError());
+  }
+  HIP_TRY_G(hipMemsetAsync(g->d_ctl, 0, BFS_CTL_BYTES, e->stream));
+  HIP_TRY_G(hipStreamSynchronize(e->stream));   // the host arrays and the temporaries are done with
+  g->n_rpieces = (int32_t)n_rp;
+#undef G_ARRAY
+#undef HIP_TRY_G
+  *out = g;
+  return cleanup(SH_OK);
+}
+
+int sh_bfs_graph_free(sh_engine *e, sh_bfs_graph *g) {
+  if (!g)
+    return SH_OK;
+  if (e) {
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->stream);
+  }
+  for (void *p : {(void *)g->d_in_ptr, (void *)g->d_in_col, (void *)g->d_out_ptr, (void *)g->d_out_row, (void *)g->d_queue[0],
+                  (void *)g->d_queue[1], (void *)g->d_bm[0], (void *)g->d_bm[1], (void *)g->d_opieces[0], (void *)g->d_opieces[1],
+                  (void *)g->d_rpieces, (void *)g->d_ctl})
+    if (p) (void)hipFree(p);
+  if (g->h_ctl) (void)hipHostFree(g->h_ctl);
+  for (auto ev : g->ev)
+    if (ev) (void)hipEventDestroy(ev);
+  delete g;
+  return SH_OK;
+}
+
+int sh_bfs_graph_footprint(const sh_bfs_graph *g, uint64_t *device_bytes) {
+  if (!g || !device_bytes)
+    return SH_EINVAL;
+  *device_bytes = (uint64_t)g->bytes;
+  return SH_OK;
+}
+
+int sh_bfs_graph_edges(const sh_bfs_graph *g, int64_t *edges) {
+  if (!g || !edges)
+    return SH_EINVAL;
+  *edges = g->edges;
+  return SH_OK;
+}
+
+int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level, sh_vec *parent, int32_t max_levels,
+                  double up_share, double down_share, int32_t *depth, int64_t *reached, int32_t *complete,
+                  int32_t *mode_per_level, int64_t *size_per_level, int64_t *edges_per_level, uint64_t *ns_per_level,
+                  uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (max_levels < 1)
+    return fail(e, SH_EINVAL, "sh_bfs_levels: max_levels = %d, must be at least 1", (int)max_levels);
+  if (up_share != up_share || down_share != down_share)
+    return fail(e, SH_EINVAL, "sh_bfs_levels: %s is NaN", up_share != up_share ? "up_share" : "down_share");
+  if (!e || !g || !x0 || !level || !depth || !reached || !complete)
+    return fail(e, SH_EINVAL, "sh_bfs_levels: NULL argument (engine, graph, x0, level, depth, reached or complete)");
+  const int64_t rows = g->rows;
+  if (x0->n < rows || level->n < rows || (parent && parent->n < rows))
+    return fail(e, SH_ESHAPE, "sh_bfs_levels: %s is shorter than the graph's %lld rows",
+                x0->n < rows ? "x0" : level->n < rows ? "level" : "parent", (long long)rows);
+  if (rows > 0 && (level->d == x0->d || (parent && (parent->d == x0->d || parent->d == level->d))))
+    return fail(e, SH_EINVAL, "sh_bfs_levels: level and parent must not alias x0 or each other");
+  if (up_share < 0) up_share = BFS_UP_SHARE;
+  if (down_share < 0) down_share = BFS_DOWN_SHARE;
+  *depth = 0; *reached = 0; *complete = 1;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const double up_edges = up_share * (double)g->edges, down_rows = down_share * (double)rows;
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, BFS_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(BFS_BS);
+  const dim3 dgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)g->words + BFS_BS - 1) / BFS_BS, 256)));
+  auto ms_between = [&](hipEvent_t a, hipEvent_t b, uint64_t *ns) {
+    float ms = 0.f;
+    hipError_t r = hipEventElapsedTime(&ms, a, b);
+    *ns = (uint64_t)((double)ms * 1e6);
+    return r;
+  };
+  uint64_t total = 0, ns = 0;
+  // level from x0, the sources as queue 0 and bitmap 0, the direction of step 0
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, BFS_CTL_BYTES, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_bm[1], 0, (size_t)g->words * 4, e->stream));
+  hipLaunchKernelGGL(bfs_init, grid, block, 0, e->stream, g->d_ctl, (int32_t)rows, g->words, (const uint32_t *)x0->d, (int32_t *)level->d,
+                     g->d_out_ptr, g->d_queue[0], g->d_opieces[0], g->d_bm[0], g->d_part);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(bfs_decide, dim3(1), block, 0, e->stream, g->d_ctl, 0, -1, nblocks, g->d_part, g->d_bm[0], g->words, up_edges,
+                     down_rows);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  int32_t it = 0, batch = 8;
+  bool done = false;
+  int64_t n_reached = -1;
+  while (!done && it < max_levels) {
+    const int nb = std::min<int32_t>(batch, max_levels - it);
+    HIP_TRY(e, hipMemsetAsync((char *)g->d_ctl + offsetof(BfsCtl, rec), 0, sizeof(BfsRec) * BFS_BATCH, e->stream));
+    HIP_TRY(e, hipEventRecord(g->ev[0], e->stream));
+    for (int k = 0; k < nb; k++) {
+      // the three launches of a step: each returns at once unless the control block says the step runs in its direction
+      const int L = it + k, p = L & 1;
+      hipLaunchKernelGGL(bfs_queue_from_bitmap, grid, block, 0, e->stream, g->d_ctl, L, g->words, g->d_bm[p], g->d_out_ptr, g->d_queue[p],
+                         g->d_opieces[p]);
+      HIP_TRY(e, hipGetLastError());
+      hipLaunchKernelGGL(bfs_topdown, grid, block, 0, e->stream, g->d_ctl, L, (int32_t *)level->d, g->d_out_ptr, g->d_out_row, g->d_queue[p],
+                         g->d_opieces[p], g->d_queue[p ^ 1], g->d_opieces[p ^ 1], g->d_bm[p ^ 1], g->d_part);
+      HIP_TRY(e, hipGetLastError());
+      hipLaunchKernelGGL(bfs_bottomup, grid, block, 0, e->stream, g->d_ctl, L, (int32_t)rows, (int32_t *)level->d, g->d_in_ptr, g->d_in_col,
+                         g->d_bm[p], g->d_bm[p ^ 1], g->d_rpieces, g->n_rpieces, g->d_part);
+      HIP_TRY(e, hipGetLastError());
+      hipLaunchKernelGGL(bfs_decide, dgrid, block, 0, e->stream, g->d_ctl, k, L, nblocks, g->d_part, g->d_bm[p], g->words, up_edges,
+                         down_rows);
+      HIP_TRY(e, hipGetLastError());
+      HIP_TRY(e, hipEventRecord(g->ev[k + 1], e->stream));
+    }
+    HIP_TRY(e, hipMemcpyAsync(g->h_ctl, g->d_ctl, sizeof(BfsCtl), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (n_reached < 0) {   // (first batch: what bfs_init found)
+      n_reached = (int64_t)g->h_ctl->nsrc;
+      if (size_per_level) size_per_level[0] = n_reached;
+      HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+      total += ns;
+    }
+    int ran = 0;
+    while (ran < nb && g->h_ctl->rec[ran].ran) ran++;
+    for (int k = 0; k < ran; k++) {
+      const BfsRec &rc = g->h_ctl->rec[k];
+      HIP_TRY(e, ms_between(g->ev[k], g->ev[k + 1], &ns));
+      total += ns;
+      if (ns_per_level) ns_per_level[it + k] = ns;
+      if (mode_per_level) mode_per_level[it + k] = rc.mode;
+      if (size_per_level) size_per_level[it + k + 1] = (int64_t)rc.found;
+      if (edges_per_level) edges_per_level[it + k] = (int64_t)rc.edges;
+      n_reached += (int64_t)rc.found;
+      if (rc.found > 0) *depth = it + k + 1;
+    }
+    it += ran;
+    done = g->h_ctl->finished != 0;
+    if (!done && ran < nb)
+      return fail(e, SH_EHIP, "sh_bfs_levels: step %d of the search did not report", (int)it);
+    batch = std::min(batch * 2, BFS_BATCH);
+  }
+  if (parent) {
+    HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+    HIP_TRY(e, hipMemsetAsync(parent->d, 0xFF, (size_t)rows * 4, e->stream));
+    hipLaunchKernelGGL(bfs_parents, grid, block, 0, e->stream, (int32_t)rows, (const int32_t *)level->d, g->d_in_ptr, g->d_in_col,
+                       g->d_rpieces, g->n_rpieces, (int32_t *)parent->d);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+    total += ns;
+  }
+  *reached = n_reached;
+  *complete = done ? 1 : 0;
   if (total_ns)
     *total_ns = total;
   return SH_OK;

@@ -143,6 +143,33 @@ class Frontier:
             self.h = None
 
 
+class BfsGraph:
+    """What Engine.bfs_levels searches: the edge pattern of a square matrix by rows and its transpose, queues, bitmaps
+    (made from the host CSR arrays alone; needs no CsrMatrix)."""
+
+    def __init__(self, engine, handle, n):
+        self.engine, self.h, self.n = engine, handle, n
+
+    @property
+    def edges(self):
+        """Entries kept as edges (non-zero value bits, column inside the matrix)."""
+        k = C.c_int64()
+        self.engine._chk(abi.load().sh_bfs_graph_edges(self.h, C.byref(k)))
+        return k.value
+
+    @property
+    def footprint(self):
+        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
+        b = C.c_uint64()
+        self.engine._chk(abi.load().sh_bfs_graph_footprint(self.h, C.byref(b)))
+        return b.value
+
+    def free(self):
+        if self.h is not None:
+            abi.load().sh_bfs_graph_free(self.engine.h, self.h)
+            self.h = None
+
+
 class Engine:
     """One HIP device + one stream (replaces Harness's OpenCL context/queue)."""
 
@@ -279,6 +306,36 @@ class Engine:
                                                  per, C.byref(total)))
         n = iters.value
         return n, bool(conv.value), list(modes[:n]), list(changed[:n]), list(active[:n]), list(per[:n]), total.value
+
+    # ---- direction-optimising BFS: the level of every vertex and, on request, its canonical parent
+    def bfs_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.bfs_levels needs, from the CSR arrays of a square matrix."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        val = np.ascontiguousarray(val)
+        assert val.dtype.itemsize == 4
+        h = C.c_void_p()
+        self._chk(abi.load().sh_bfs_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
+                                                 C.byref(h)))
+        return BfsGraph(self, h, len(row_ptr) - 1)
+
+    def bfs_levels(self, G, x0, level, parent=None, max_levels=1 << 20, up_share=-1.0, down_share=-1.0):
+        """-> (depth, reached, complete, modes, sizes, edges, ns_per_level, total_ns); per step that ran: 0 top-down /
+        1 bottom-up, edges it looked at, device ns; sizes[l] = vertices at level l (one entry more than the steps)."""
+        depth, reached, complete, total = C.c_int32(), C.c_int64(), C.c_int32(), C.c_uint64()
+        cap = max(int(max_levels), 1)
+        modes, sizes = np.zeros(cap, np.int32), np.full(cap + 1, -1, np.int64)
+        edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
+        self._chk(abi.load().sh_bfs_levels(self.h, G.h, x0.h, level.h, None if parent is None else parent.h, max_levels,
+                                           up_share, down_share, C.byref(depth), C.byref(reached), C.byref(complete),
+                                           modes.ctypes.data_as(C.POINTER(C.c_int32)), sizes.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           edges.ctypes.data_as(C.POINTER(C.c_int64)), per.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           C.byref(total)))
+        n = int(np.count_nonzero(sizes >= 0)) - 1   # steps that ran (sizes holds one entry per step, plus the sources)
+        if n < 0:   # (a graph without rows: nothing ran and nothing was written)
+            n, sizes[0] = 0, 0
+        return (depth.value, reached.value, bool(complete.value), modes[:n].copy(), sizes[:n + 1].copy(), edges[:n].copy(),
+                per[:n].copy(), total.value)
 
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
