@@ -5,7 +5,9 @@ uploaded with plan=1: the multi-vector kernels run on the CSR-stream plan's arra
 Bounds.  Integer-valued (+,x) data and the three order-free semirings: bit for bit.  General floats: rows of at most 64
 entries drawn from [0.5, 1.5), every element within REL * max(1, |want|) of the gold sum -- with positive terms a
 sequential and a tree sum of n <= 64 floats each stay within (n-1) * 2^-24 relative of the exact sum, so the two
-differ by less than 7.6e-6 < REL whatever the order.
+differ by less than 7.6e-6 < REL whatever the order.  That is this file's general-float case only: (+,x) on mixed signs,
+wide dynamic range, rows through the wave sums, the long-row segments and their fix-up, the alpha / beta / Y epilogue and
+non-finite inputs is held to a derived float32 bound against float64 in tests/test_float_gpu.py (bound: tests/float_ref.py).
 """
 import numpy as np
 import pytest
