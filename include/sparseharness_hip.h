@@ -413,6 +413,12 @@ int sh_bits_to_column(sh_engine *e, const sh_vec *B, int64_t n, int32_t words, i
  *   1 sparse; |C| AFTER the launch (rows whose bits it changed); rows recomputed (= rows for a dense launch).
  * The launches are enqueued ahead of the host as sh_iterate's are, up to 8 of ONE mode; the device closes the gate of
  * the launches behind a change of mode (or the end of the loop), so the host joins in once per batch and per change.
+ * Outside the contract: a word of SH_MIN_PLUS_F32 that is Inf or NaN and STAYS so (alpha = Inf, say; with alpha finite a
+ *   launch replaces an Inf by a value <= FLT_MAX).  Its bits do not change, so it joins no changed list, while
+ *   |Inf - Inf| is NaN and fails sh_iterate's `|in - out| < delta` at every launch: sh_iterate runs to max_iters
+ *   unconverged; sh_iterate_frontier does the same while its launches are dense (dense_share = 0: always) and reports
+ *   converged at its first sparse launch, whose active set is empty -- launch 2 at the earliest.  The vector is the
+ *   same either way (tests/test_minplus_gpu.py pins both).
  * SH_EINVAL: SH_PLUS_TIMES_F32 (a recomputed row would have to reproduce the summation order of whichever plan ran the
  * dense launches), delta <= 0 with SH_MIN_PLUS_F32, max_iters < 1, a handle made for another matrix.
  * NOT covered: SH_PLUS_TIMES_F32, sh_iterate_multi / sh_bits_iterate, row pieces (sh_spmv_step_pieces), the multi-GPU
