@@ -517,6 +517,97 @@ int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level
                   int32_t *mode_per_level, int64_t *size_per_level, int64_t *edges_per_level, uint64_t *ns_per_level,
                   uint64_t *total_ns);
 
+/* ---- bucketed SSSP with distances and canonical predecessors: extends the SSSP loop of HarnessSSSP::executeRun
+ *      (app/sssp.cpp:97-176) and Harness::executeKernel (inc/harness.h:149-195).  The reference's SSSP is Bellman-Ford
+ *      as an SpMV loop on the (min,+) semiring: every launch reads the whole matrix, and a run takes as many launches as
+ *      the longest shortest path has edges; it has no counterpart of the calls below.  sh_sssp is an SSSP that is an
+ *      algorithm of its own: a bucketed, push-based label-correcting search (near-far: Davidson, Baxter, Garland, Owens,
+ *      IPDPS 2014; delta-stepping: Meyer, Sanders 2003) whose work is proportional to the edges it relaxes, and which
+ *      answers, on request, THROUGH WHICH vertex every distance was reached.
+ *
+ *      An EDGE c -> r of weight w = |a| exists when row r stores an entry with column c, 0 <= c < rows, and a value a
+ *      whose magnitude is finite.  A stored zero IS an edge, of weight 0 ((min,+) is unlike (or,and) here); an infinite
+ *      weight is no edge (under SH_MIN_PLUS_F32 it can never bring a word below FLT_MAX); NaN weights are outside the
+ *      contract, as for sh_iterate; parallel edges are legal.  The START is d0[v] = |x0[v]| (no NaN; an infinite start
+ *      counts as FLT_MAX, which is what sh_iterate's first launch makes of it): any non-negative vector is legal -- one
+ *      source at 0, several sources, sources with offsets; a vertex with d0 = FLT_MAX is not a source.
+ *        dist      = the greatest vector F <= d0 with F[r] <= fl32(F[c] + w) for every edge; equivalently the minimum over
+ *                    all paths of the path's length added up left to right in float32 from d0 of its first vertex
+ *                    (tests/minplus_ref.py gives the induction).  fl32 is monotone, so this vector is unique: ANY sequence
+ *                    of relaxations dist[r] = min(dist[r], fl32(dist[c] + w)) that starts at d0 and ends when no edge
+ *                    improves anything arrives at it, whatever the order, bucket width or queue contents.  It is
+ *                    therefore, bit for bit, what sh_iterate(SH_MIN_PLUS_F32, alpha = 0, beta = 0, y0 = x0) leaves when
+ *                    it runs with a delta so small that it stops only when nothing changes.
+ *        pred[v]   = -1 when bits(dist[v]) == bits(d0[v]) (the start value stands: v is a source, or unreached, or
+ *                    nothing beat its offset); otherwise the SMALLEST c with an edge c -> v and
+ *                    bits(fl32(dist[c] + w)) == bits(dist[v]) -- at a fixed point one exists.  Canonical, so comparable
+ *                    with ==; computed by one row-parallel pass after the search, and only when `pred` is given (the
+ *                    search itself carries no predecessor atomics).  pred is a FOREST whenever fl32(dist[c] + w) > dist[c]
+ *                    on every edge used; zero weights, or weights below half an ulp of the distance, can tie a vertex to
+ *                    one that is no nearer and close a cycle.
+ *        *reached  = vertices with dist < FLT_MAX.  *complete = 1 when the search ran out of work; 0 when max_rounds
+ *                    rounds were used up first: dist then satisfies fixed point <= dist <= d0 elementwise, every word is
+ *                    the rounded length of a real path, and pred is not written.
+ *        *rounds, *buckets (how often the threshold advanced) and *relaxed (edges looked at) are informational, as are
+ *                    the per-round arrays: the relaxations of one round race through atomic minima, so these counts may
+ *                    differ from run to run.  One statement holds for every complete run:
+ *                    *relaxed >= the sum of the out-degrees of the reached vertices.
+ *      delta is the bucket width: > 0 is used as given; +Inf means one bucket (a frontier push Bellman-Ford); <= 0 means
+ *      the engine's default, computed at handle creation as 32 * (mean weight) / (mean out-degree) = 32 * (sum of the
+ *      weights / edges) * (rows / edges) (1 if that is 0) and readable through sh_sssp_graph_delta; NaN gives SH_EINVAL.
+ *      The result does not depend on delta.
+ *
+ *      Measured on an MI355X (DESIGN.md "6f Bucketed SSSP", profiles/sssp_*.json): NOTHING YET.  tools/sssp_bench.py
+ *        (against sh_iterate(SH_MIN_PLUS_F32) under the matrix' default plan and sh_iterate_frontier at its default share,
+ *        on the 2048 x 2048 grid, the 170 998-row matrix, R-MAT-23 and the power-law 10 M / 200 M matrix) has not been run,
+ *        so there is no table, the factor 32 of the default width is Davidson et al.'s starting point and not the outcome
+ *        of a sweep, and profiles/sssp_*.json do not exist.  What is known from sh_bfs_levels, whose control this follows:
+ *        a round is four dependent launches and costs 16 to 25 us at least, so a matrix whose sh_iterate launch is cheaper
+ *        than that cannot win by rounds alone, and R-MAT-23 (10 launches of 0.3 ms) has 134 M atomic relaxations to pay for.
+ *        Rule: call it when you need predecessors, or a start vector's exact fixed point without choosing a delta.  For
+ *        distances alone sh_iterate stays the measured path until the bench has been run; the expected gain is on grids,
+ *        meshes and road-like graphs (thousands of dense launches), the expected loss on small matrices and fat power-law graphs.
+ *
+ * sh_sssp_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  The matrix is square (rows x rows);
+ * val holds float32 bit patterns; col_idx outside [0, rows) and infinite values are legal and are no edges.  The handle
+ * holds on the device: the out-edges by source vertex (out_ptr[rows + 1], out_row[edges], out_w[edges] = |a|, order inside
+ * one list unspecified), the in-edges by row (in_ptr[rows + 1], in_col[edges], in_w[edges], stored order of the survivors
+ * kept), one stamp word per vertex, two near lists and two far lists of `rows` entries (a vertex sits in a list at most
+ * once, so no list can overflow on any input), two lists of pieces of long out-lists, the pieces of long rows, a control
+ * block.  Built on the device (flag per entry, exclusive scan, compaction; column histogram, scan, scatter; a reduction
+ * for the mean weight).  rows == 0 gives a valid handle.  Freeing NULL is SH_OK.
+ * sh_sssp_graph_footprint: device bytes held =
+ *     8 * (rows + 1) + 16 * edges + 20 * rows + 16 * (edges / 1024 + 1) + 8 * (edges / 2048 + 1) + 22528.
+ * sh_sssp_graph_edges: the entries kept as edges.  sh_sssp_graph_delta: the default bucket width (0 for a graph without edges).
+ *
+ * sh_sssp: dist (float32) and pred (int32, may be NULL): vectors of >= rows elements, written in full (pred only by a
+ * complete run); x0 is only read; dist and pred must not alias x0 or each other.  g may serve any number of calls, one at
+ * a time.  max_rounds >= 1.  A ROUND relaxes the out-edges of every vertex of the near list; when the list ran empty the
+ * next round opens by moving the threshold to the end of the bucket that holds the smallest far distance (empty buckets
+ * cost no round) and carrying over what falls below it.  The per-round arrays (each may be NULL) have capacity max_rounds:
+ * size_per_round = vertices relaxed from, edges_per_round = edges looked at, ns_per_round / total_ns = device time
+ * (hipEvent) as elsewhere; total_ns also holds the set-up launch and the predecessor pass.
+ * The rounds are enqueued ahead of the host, 8 at first and up to 32 at a time: every round is four launches (the split
+ * in two phases, the relaxation, one small launch that closes the round) that return at once unless the device-side
+ * control block says they have work; the host reads the control block once per batch.  No kernel ever waits for another
+ * kernel's write.
+ * SH_EINVAL: NULL arguments, rows < 0, nnz < 0, max_rounds < 1, a NaN delta, aliasing.  SH_ESHAPE: row_ptr[0] != 0,
+ * row_ptr[rows] != nnz or a row_ptr that decreases, vectors shorter than rows.  All are reported before any device work.
+ * NOT covered: the other semirings, several independent start vectors per call (that is sh_iterate_multi), row pieces
+ * (sh_spmv_step_pieces), the multi-GPU driver and the C++ harness apps (their output stays the reference's vector).
+ */
+typedef struct sh_sssp_graph sh_sssp_graph;
+int sh_sssp_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                         const void *val, sh_sssp_graph **out);
+int sh_sssp_graph_free(sh_engine *e, sh_sssp_graph *g);
+int sh_sssp_graph_footprint(const sh_sssp_graph *g, uint64_t *device_bytes);
+int sh_sssp_graph_edges(const sh_sssp_graph *g, int64_t *edges);
+int sh_sssp_graph_delta(const sh_sssp_graph *g, double *delta);
+int sh_sssp(sh_engine *e, sh_sssp_graph *g, const sh_vec *x0, sh_vec *dist, sh_vec *pred, double delta,
+            int32_t max_rounds, int32_t *rounds, int32_t *buckets, int64_t *reached, int32_t *complete,
+            int64_t *relaxed, int64_t *size_per_round, int64_t *edges_per_round, uint64_t *ns_per_round,
+            uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,22 +3,27 @@
 multi-vector kernels (spmm_csr_kernel / spmm_long_fixup, multi.hip.h), or one of the packed-bit kernels (msbfs_csr_kernel /
 msbfs_long_fixup, msbfs.hip.h), or one of the frontier kernels (frontier_mark / frontier_pull / frontier_apply /
 frontier_detect, frontier.hip.h), or one of the BFS kernels (bfs_init / bfs_topdown / bfs_bottomup / bfs_queue_from_bitmap /
-bfs_decide / bfs_parents, bfs.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+bfs_decide / bfs_parents, bfs.hip.h), or one of the SSSP kernels (sssp_init / sssp_relax / sssp_split / sssp_decide /
+sssp_preds, sssp.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs = [], 0, set(), set(), set(), set()
+bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp = [], 0, set(), set(), set(), set(), set()
 BFS_KERNELS = ("bfs_init", "bfs_topdown", "bfs_bottomup", "bfs_queue_from_bitmap", "bfs_decide", "bfs_parents")
+SSSP_KERNELS = ("sssp_init", "sssp_relax", "sssp_split", "sssp_decide", "sssp_preds")
 for blk in text.split("remark: Function Name: ")[1:]:
     name = blk.split()[0]
     multi = "spmm_csr" in name or "spmm_long" in name
     packed = "msbfs_csr" in name or "msbfs_long" in name
     frontier = any(k in name for k in ("frontier_mark", "frontier_pull", "frontier_apply", "frontier_detect"))
     bfs = any(k in name for k in BFS_KERNELS)
-    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs:
+    sssp = any(k in name for k in SSSP_KERNELS)
+    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp:
         continue
-    if bfs:
+    if sssp:
+        seen_sssp.add(name)
+    elif bfs:
         seen_bfs.add(name)
     elif frontier:
         seen_frontier.add(name)
@@ -58,7 +63,10 @@ if len(seen_frontier) != 8:
 # the six kernels of sh_bfs_levels, under the limits of the frontier kernels
 if len(seen_bfs) != len(BFS_KERNELS):
     sys.exit(f"expected {len(BFS_KERNELS)} BFS kernels in the remarks, found {len(seen_bfs)}: {sorted(seen_bfs)}")
+# the five kernels of sh_sssp, under the limits of the BFS kernels
+if len(seen_sssp) != len(SSSP_KERNELS):
+    sys.exit(f"expected {len(SSSP_KERNELS)} SSSP kernels in the remarks, found {len(seen_sssp)}: {sorted(seen_sssp)}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier and {len(seen_bfs)} BFS kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS and {len(seen_sssp)} SSSP kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

@@ -12,6 +12,7 @@
 #include "msbfs.hip.h"
 #include "frontier.hip.h"
 #include "bfs.hip.h"
+#include "sssp.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -2308,6 +2309,314 @@ int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level
     total += ns;
   }
   *reached = n_reached;
+  *complete = done ? 1 : 0;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- bucketed SSSP with distances and canonical predecessors (sssp.hip.h) --------------------------------------------
+struct sh_sssp_graph {
+  int64_t rows = 0, nnz = 0, edges = 0;
+  double delta = 0.0;              // the default bucket width (0: no edges)
+  int32_t *d_in_ptr = nullptr, *d_in_col = nullptr, *d_out_ptr = nullptr, *d_out_row = nullptr;
+  uint32_t *d_in_w = nullptr, *d_out_w = nullptr;
+  uint32_t *d_stamp = nullptr, *d_near[2] = {nullptr, nullptr}, *d_far[2] = {nullptr, nullptr};
+  FrPiece *d_opieces[2] = {nullptr, nullptr};   // pieces of the long out-lists of near list 0 / 1
+  FrPiece *d_rpieces = nullptr;                 // pieces of the rows above SSSP_ROW_PIECE (static)
+  int32_t n_rpieces = 0;
+  SsspCtl *d_ctl = nullptr;        // SSSP_CTL_BYTES, followed by the BfsParts and the split's minima
+  BfsPart *d_part = nullptr;
+  uint32_t *d_pmin = nullptr;
+  SsspCtl *h_ctl = nullptr;        // pinned: the control block as read back once per batch
+  hipEvent_t ev[SSSP_BATCH + 1] = {};
+  size_t bytes = 0;
+};
+// The default bucket width is SSSP_DELTA_FACTOR * (mean weight) / (mean out-degree): Davidson et al.'s starting point.
+// tools/sssp_bench.py sweeps the factor; no sweep is on record yet (DESIGN.md "6f Bucketed SSSP").
+static constexpr double SSSP_DELTA_FACTOR = 32.0;
+static_assert(sizeof(SsspCtl) <= SSSP_CTL_BYTES, "the control block is accounted as SSSP_CTL_BYTES (sh_sssp_graph_footprint)");
+static_assert(sizeof(BfsPart) * SSSP_MAX_BLOCKS == SSSP_PART_BYTES, "one BfsPart per workgroup");
+
+extern "C" {
+
+int sh_sssp_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                         const void *val, sh_sssp_graph **out) {
+  // what the scalars and the host arrays alone decide comes first: no device is needed to be told
+  if (out) *out = nullptr;
+  if (rows < 0 || rows > 0x7FFFFF00ll)
+    return fail(e, SH_EINVAL, "sh_sssp_graph_create: rows = %lld, must be in [0, 2^31 - 256]", (long long)rows);
+  if (nnz < 0 || nnz > 0x7FFFFF00ll)
+    return fail(e, SH_EINVAL, "sh_sssp_graph_create: nnz = %lld, must be in [0, 2^31 - 256]", (long long)nnz);
+  if (!row_ptr || !out || (nnz > 0 && (!col_idx || !val)))
+    return fail(e, SH_EINVAL, "sh_sssp_graph_create: NULL argument (row_ptr, out, or col_idx / val of a matrix with entries)");
+  if (row_ptr[0] != 0 || (int64_t)row_ptr[rows] != nnz)
+    return fail(e, SH_ESHAPE, "sh_sssp_graph_create: row_ptr[0] = %d and row_ptr[rows] = %d, must be 0 and nnz = %lld",
+                (int)row_ptr[0], (int)row_ptr[rows], (long long)nnz);
+  for (int64_t r = 0; r < rows; r++)   // (the build indexes by row_ptr on the device: it must stay inside the arrays)
+    if (row_ptr[r] > row_ptr[r + 1])
+      return fail(e, SH_ESHAPE, "sh_sssp_graph_create: row_ptr decreases at row %lld", (long long)r);
+  if (!e)
+    return fail(e, SH_EINVAL, "sh_sssp_graph_create: NULL argument (engine)");
+  HIP_TRY(e, hipSetDevice(e->device));
+  sh_sssp_graph *g = new (std::nothrow) sh_sssp_graph();
+  if (!g)
+    return fail(e, SH_ENOMEM, "out of host memory");
+  g->rows = rows; g->nnz = nnz;
+  // temporaries of the build: the CSR arrays as given, the edge flags and their scan, the scatter's cursors, the weight sums
+  int32_t *t_rp = nullptr, *t_ci = nullptr;
+  uint32_t *t_val = nullptr, *t_flag = nullptr, *t_pos = nullptr, *t_cnt = nullptr;
+  double *t_sum = nullptr;
+  auto cleanup = [&](int rc) {
+    for (void *p : {(void *)t_rp, (void *)t_ci, (void *)t_val, (void *)t_flag, (void *)t_pos, (void *)t_cnt, (void *)t_sum})
+      if (p) (void)hipFree(p);
+    t_rp = t_ci = nullptr; t_val = t_flag = t_pos = t_cnt = nullptr; t_sum = nullptr;
+    if (rc) sh_sssp_graph_free(e, g);
+    return rc;
+  };
+#define HIP_TRY_G(call)                                                         \
+  do {                                                                          \
+    hipError_t _r = (call);                                                     \
+    if (_r != hipSuccess)                                                       \
+      return cleanup(fail(e, _r == hipErrorOutOfMemory ? SH_ENOMEM : SH_EHIP,   \
+                          "%s failed: %s", #call, hipGetErrorString(_r)));      \
+  } while (0)
+  // (an array of `nbytes` counts as that in the footprint; an empty one still gets a few bytes to point at)
+#define G_ARRAY(ptr, nbytes)                                                                   \
+  do {                                                                                         \
+    HIP_TRY_G(hipMalloc((void **)&(ptr), std::max<size_t>((size_t)(nbytes), 16)));             \
+    g->bytes += (size_t)(nbytes);                                                              \
+  } while (0)
+  constexpr int SUM_BLOCKS = 256;
+  HIP_TRY_G(hipMalloc((void **)&t_rp, (size_t)(rows + 1) * 4));
+  HIP_TRY_G(hipMalloc((void **)&t_ci, std::max<size_t>((size_t)nnz * 4, 16)));
+  HIP_TRY_G(hipMalloc((void **)&t_val, std::max<size_t>((size_t)nnz * 4, 16)));
+  HIP_TRY_G(hipMalloc((void **)&t_flag, (size_t)(nnz + 1) * 4));
+  HIP_TRY_G(hipMalloc((void **)&t_pos, (size_t)(nnz + 1) * 4));
+  HIP_TRY_G(hipMalloc((void **)&t_cnt, (size_t)(rows + 1) * 4));
+  HIP_TRY_G(hipMalloc((void **)&t_sum, SUM_BLOCKS * sizeof(double)));
+  HIP_TRY_G(hipMemcpyAsync(t_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  if (nnz > 0) {
+    HIP_TRY_G(hipMemcpyAsync(t_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY_G(hipMemcpyAsync(t_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  // the entries that are edges: flag, exclusive scan, compaction (the stored order of the survivors is kept)
+  const dim3 blk(SSSP_BS), ngrid((unsigned)((nnz + 1 + SSSP_BS - 1) / SSSP_BS)), rgrid((unsigned)((rows + 1 + SSSP_BS - 1) / SSSP_BS));
+  hipLaunchKernelGGL(sssp_edge_flag, ngrid, blk, 0, e->stream, t_ci, t_val, nnz, (int32_t)rows, t_flag);
+  HIP_TRY_G(hipGetLastError());
+  HIP_TRY_G(device_exclusive_sum_u32(e->stream, t_flag, t_pos, nnz + 1));
+  uint32_t n_edges = 0;
+  HIP_TRY_G(hipMemcpy(&n_edges, t_pos + nnz, 4, hipMemcpyDeviceToHost));
+  const int64_t E = (int64_t)n_edges;
+  g->edges = E;
+  G_ARRAY(g->d_in_ptr, (rows + 1) * 4);
+  G_ARRAY(g->d_in_col, E * 4);
+  G_ARRAY(g->d_in_w, E * 4);
+  G_ARRAY(g->d_out_ptr, (rows + 1) * 4);
+  G_ARRAY(g->d_out_row, E * 4);
+  G_ARRAY(g->d_out_w, E * 4);
+  G_ARRAY(g->d_stamp, rows * 4);
+  for (int i = 0; i < 2; i++) {
+    G_ARRAY(g->d_near[i], rows * 4);
+    G_ARRAY(g->d_far[i], rows * 4);
+    G_ARRAY(g->d_opieces[i], (E / 1024 + 1) * sizeof(FrPiece));   // sum of ceil(len / 2048) over out-lists longer than 2048 <= E / 1024
+  }
+  G_ARRAY(g->d_rpieces, (E / 2048 + 1) * sizeof(FrPiece));        // the same for rows longer than 4096
+  G_ARRAY(g->d_ctl, SSSP_CTL_BYTES + SSSP_PART_BYTES + SSSP_PMIN_BYTES);
+  g->d_part = (BfsPart *)((char *)g->d_ctl + SSSP_CTL_BYTES);
+  g->d_pmin = (uint32_t *)((char *)g->d_ctl + SSSP_CTL_BYTES + SSSP_PART_BYTES);
+  HIP_TRY_G(hipHostMalloc((void **)&g->h_ctl, sizeof(SsspCtl), hipHostMallocDefault));
+  for (auto &ev : g->ev) HIP_TRY_G(hipEventCreate(&ev));
+  HIP_TRY_G(hipMemsetAsync(g->d_ctl, 0, SSSP_CTL_BYTES + SSSP_PART_BYTES + SSSP_PMIN_BYTES, e->stream));
+  if (nnz > 0) {
+    hipLaunchKernelGGL(sssp_edge_compact, ngrid, blk, 0, e->stream, t_ci, t_val, t_flag, t_pos, nnz, g->d_in_col, g->d_in_w);
+    HIP_TRY_G(hipGetLastError());
+  }
+  hipLaunchKernelGGL(bfs_row_starts, rgrid, blk, 0, e->stream, t_rp, t_pos, rows, g->d_in_ptr);
+  HIP_TRY_G(hipGetLastError());
+  // the static pieces of long rows (the cursor borrows the control block's first word, cleared again below)
+  if (rows > 0) {
+    hipLaunchKernelGGL(bfs_row_pieces, rgrid, blk, 0, e->stream, g->d_in_ptr, rows, (uint32_t *)g->d_ctl, g->d_rpieces);
+    HIP_TRY_G(hipGetLastError());
+  }
+  uint32_t n_rp = 0;
+  HIP_TRY_G(hipMemcpyAsync(&n_rp, g->d_ctl, 4, hipMemcpyDeviceToHost, e->stream));
+  // the transpose with its weights: column histogram, exclusive scan, scatter through per-column cursors
+  HIP_TRY_G(hipMemsetAsync(t_cnt, 0, (size_t)(rows + 1) * 4, e->stream));
+  const dim3 egrid((unsigned)std::max<int64_t>(1, (E + FR_BS - 1) / FR_BS));
+  if (E > 0) {
+    hipLaunchKernelGGL(frontier_col_hist, egrid, dim3(FR_BS), 0, e->stream, g->d_in_col, E, (int32_t)rows, t_cnt);
+    HIP_TRY_G(hipGetLastError());
+  }
+  HIP_TRY_G(device_exclusive_sum_u32(e->stream, t_cnt, (uint32_t *)g->d_out_ptr, rows + 1));
+  HIP_TRY_G(hipMemcpyAsync(t_cnt, g->d_out_ptr, (size_t)(rows + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
+  double h_sum[SUM_BLOCKS] = {};
+  if (E > 0) {
+    hipLaunchKernelGGL(sssp_scatter, egrid, dim3(SSSP_BS), 0, e->stream, g->d_in_ptr, g->d_in_col, g->d_in_w, E, (int32_t)rows, t_cnt,
+                       g->d_out_row, g->d_out_w);
+    HIP_TRY_G(hipGetLastError());
+    // the mean weight, for the default bucket width
+    hipLaunchKernelGGL(sssp_weight_sum, dim3(SUM_BLOCKS), dim3(SSSP_BS), 0, e->stream, g->d_in_w, E, t_sum);
+    HIP_TRY_G(hipGetLastError());
+    HIP_TRY_G(hipMemcpyAsync(h_sum, t_sum, sizeof(h_sum), hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_TRY_G(hipMemsetAsync(g->d_ctl, 0, SSSP_CTL_BYTES, e->stream));
+  HIP_TRY_G(hipStreamSynchronize(e->stream));   // the host arrays and the temporaries are done with
+  g->n_rpieces = (int32_t)n_rp;
+  if (E > 0) {
+    double sum = 0.0;
+    for (double v : h_sum) sum += v;
+    // factor * (sum / E) / (E / rows); a graph whose weights are all zero has one bucket whatever the width: 1
+    const double d = SSSP_DELTA_FACTOR * (sum / (double)E) * ((double)rows / (double)E);
+    g->delta = (d > 0.0 && d < 1e300) ? d : 1.0;
+  }
+#undef G_ARRAY
+#undef HIP_TRY_G
+  *out = g;
+  return cleanup(SH_OK);
+}
+
+int sh_sssp_graph_free(sh_engine *e, sh_sssp_graph *g) {
+  if (!g)
+    return SH_OK;
+  if (e) {
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->stream);
+  }
+  for (void *p : {(void *)g->d_in_ptr, (void *)g->d_in_col, (void *)g->d_in_w, (void *)g->d_out_ptr, (void *)g->d_out_row,
+                  (void *)g->d_out_w, (void *)g->d_stamp, (void *)g->d_near[0], (void *)g->d_near[1], (void *)g->d_far[0],
+                  (void *)g->d_far[1], (void *)g->d_opieces[0], (void *)g->d_opieces[1], (void *)g->d_rpieces, (void *)g->d_ctl})
+    if (p) (void)hipFree(p);
+  if (g->h_ctl) (void)hipHostFree(g->h_ctl);
+  for (auto ev : g->ev)
+    if (ev) (void)hipEventDestroy(ev);
+  delete g;
+  return SH_OK;
+}
+
+int sh_sssp_graph_footprint(const sh_sssp_graph *g, uint64_t *device_bytes) {
+  if (!g || !device_bytes)
+    return SH_EINVAL;
+  *device_bytes = (uint64_t)g->bytes;
+  return SH_OK;
+}
+
+int sh_sssp_graph_edges(const sh_sssp_graph *g, int64_t *edges) {
+  if (!g || !edges)
+    return SH_EINVAL;
+  *edges = g->edges;
+  return SH_OK;
+}
+
+int sh_sssp_graph_delta(const sh_sssp_graph *g, double *delta) {
+  if (!g || !delta)
+    return SH_EINVAL;
+  *delta = g->delta;
+  return SH_OK;
+}
+
+int sh_sssp(sh_engine *e, sh_sssp_graph *g, const sh_vec *x0, sh_vec *dist, sh_vec *pred, double delta,
+            int32_t max_rounds, int32_t *rounds, int32_t *buckets, int64_t *reached, int32_t *complete,
+            int64_t *relaxed, int64_t *size_per_round, int64_t *edges_per_round, uint64_t *ns_per_round,
+            uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (max_rounds < 1)
+    return fail(e, SH_EINVAL, "sh_sssp: max_rounds = %d, must be at least 1", (int)max_rounds);
+  if (delta != delta)
+    return fail(e, SH_EINVAL, "sh_sssp: delta is NaN");
+  if (!e || !g || !x0 || !dist || !rounds || !buckets || !reached || !complete || !relaxed)
+    return fail(e, SH_EINVAL, "sh_sssp: NULL argument (engine, graph, x0, dist, rounds, buckets, reached, complete or relaxed)");
+  const int64_t rows = g->rows;
+  if (x0->n < rows || dist->n < rows || (pred && pred->n < rows))
+    return fail(e, SH_ESHAPE, "sh_sssp: %s is shorter than the graph's %lld rows",
+                x0->n < rows ? "x0" : dist->n < rows ? "dist" : "pred", (long long)rows);
+  if (rows > 0 && (dist->d == x0->d || (pred && (pred->d == x0->d || pred->d == dist->d))))
+    return fail(e, SH_EINVAL, "sh_sssp: dist and pred must not alias x0 or each other");
+  if (delta <= 0) delta = g->delta > 0 ? g->delta : 1.0;
+  *rounds = 0; *buckets = 0; *reached = 0; *complete = 1; *relaxed = 0;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, SSSP_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(SSSP_BS);
+  auto ms_between = [&](hipEvent_t a, hipEvent_t b, uint64_t *ns) {
+    float ms = 0.f;
+    hipError_t r = hipEventElapsedTime(&ms, a, b);
+    *ns = (uint64_t)((double)ms * 1e6);
+    return r;
+  };
+  uint32_t *d = (uint32_t *)dist->d;
+  uint64_t total = 0, ns = 0;
+  // dist and the stamps from x0, the sources as far list 0
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, SSSP_CTL_BYTES, e->stream));
+  hipLaunchKernelGGL(sssp_init, grid, block, 0, e->stream, g->d_ctl, (int32_t)rows, (const uint32_t *)x0->d, d, g->d_stamp, g->d_far[0]);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(sssp_decide, dim3(1), block, 0, e->stream, g->d_ctl, 0, -1, nblocks, g->d_part);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  int32_t it = 0, batch = 8;
+  bool done = false, first = true;
+  while (!done && it < max_rounds) {
+    const int nb = std::min<int32_t>(batch, max_rounds - it);
+    HIP_TRY(e, hipMemsetAsync((char *)g->d_ctl + offsetof(SsspCtl, rec), 0, sizeof(SsspRec) * SSSP_BATCH, e->stream));
+    HIP_TRY(e, hipEventRecord(g->ev[0], e->stream));
+    for (int k = 0; k < nb; k++) {
+      // the four launches of a round: each returns at once unless the control block says the round runs (with a split)
+      const int R = it + k, p = R & 1;
+      for (int phase = 0; phase < 2; phase++) {
+        hipLaunchKernelGGL(sssp_split, grid, block, 0, e->stream, g->d_ctl, R, phase, nblocks, delta, g->d_pmin, d, g->d_stamp,
+                           g->d_out_ptr, g->d_far[0], g->d_far[1], g->d_near[p], g->d_opieces[p]);
+        HIP_TRY(e, hipGetLastError());
+      }
+      hipLaunchKernelGGL(sssp_relax, grid, block, 0, e->stream, g->d_ctl, R, d, g->d_stamp, g->d_out_ptr, g->d_out_row, g->d_out_w,
+                         g->d_near[p], g->d_opieces[p], g->d_near[p ^ 1], g->d_opieces[p ^ 1], g->d_far[0], g->d_far[1], g->d_part);
+      HIP_TRY(e, hipGetLastError());
+      hipLaunchKernelGGL(sssp_decide, dim3(1), block, 0, e->stream, g->d_ctl, k, R, nblocks, g->d_part);
+      HIP_TRY(e, hipGetLastError());
+      HIP_TRY(e, hipEventRecord(g->ev[k + 1], e->stream));
+    }
+    HIP_TRY(e, hipMemcpyAsync(g->h_ctl, g->d_ctl, sizeof(SsspCtl), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (first) {
+      HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+      total += ns;
+      first = false;
+    }
+    int ran = 0;
+    while (ran < nb && g->h_ctl->rec[ran].ran) ran++;
+    for (int k = 0; k < ran; k++) {
+      const SsspRec &rc = g->h_ctl->rec[k];
+      HIP_TRY(e, ms_between(g->ev[k], g->ev[k + 1], &ns));
+      total += ns;
+      if (ns_per_round) ns_per_round[it + k] = ns;
+      if (size_per_round) size_per_round[it + k] = (int64_t)rc.size;
+      if (edges_per_round) edges_per_round[it + k] = (int64_t)rc.edges;
+    }
+    it += ran;
+    done = g->h_ctl->finished != 0;
+    if (!done && ran < nb)
+      return fail(e, SH_EHIP, "sh_sssp: round %d of the search did not report", (int)it);
+    batch = std::min(batch * 2, SSSP_BATCH);
+  }
+  if (pred && done) {
+    HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+    HIP_TRY(e, hipMemsetAsync(pred->d, 0xFF, (size_t)rows * 4, e->stream));
+    hipLaunchKernelGGL(sssp_preds, grid, block, 0, e->stream, (int32_t)rows, (const uint32_t *)x0->d, (const uint32_t *)d, g->d_in_ptr,
+                       g->d_in_col, g->d_in_w, g->d_rpieces, g->n_rpieces, (int32_t *)pred->d);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+    total += ns;
+  }
+  *rounds = it;
+  *buckets = (int32_t)g->h_ctl->buckets;
+  *reached = (int64_t)g->h_ctl->reached;
+  *relaxed = (int64_t)g->h_ctl->relaxed;
   *complete = done ? 1 : 0;
   if (total_ns)
     *total_ns = total;

@@ -170,6 +170,40 @@ class BfsGraph:
             self.h = None
 
 
+class SsspGraph:
+    """What Engine.sssp searches: the weighted out-edges of a square matrix by source vertex, its in-edges by row, work
+    lists (made from the host CSR arrays alone; needs no CsrMatrix)."""
+
+    def __init__(self, engine, handle, n):
+        self.engine, self.h, self.n = engine, handle, n
+
+    @property
+    def edges(self):
+        """Entries kept as edges (finite value, column inside the matrix; a stored zero is an edge of weight 0)."""
+        k = C.c_int64()
+        self.engine._chk(abi.load().sh_sssp_graph_edges(self.h, C.byref(k)))
+        return k.value
+
+    @property
+    def footprint(self):
+        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
+        b = C.c_uint64()
+        self.engine._chk(abi.load().sh_sssp_graph_footprint(self.h, C.byref(b)))
+        return b.value
+
+    @property
+    def delta(self):
+        """The default bucket width (0 for a graph without edges)."""
+        d = C.c_double()
+        self.engine._chk(abi.load().sh_sssp_graph_delta(self.h, C.byref(d)))
+        return d.value
+
+    def free(self):
+        if self.h is not None:
+            abi.load().sh_sssp_graph_free(self.engine.h, self.h)
+            self.h = None
+
+
 class Engine:
     """One HIP device + one stream (replaces Harness's OpenCL context/queue)."""
 
@@ -335,6 +369,33 @@ class Engine:
         if n < 0:   # (a graph without rows: nothing ran and nothing was written)
             n, sizes[0] = 0, 0
         return (depth.value, reached.value, bool(complete.value), modes[:n].copy(), sizes[:n + 1].copy(), edges[:n].copy(),
+                per[:n].copy(), total.value)
+
+    # ---- bucketed SSSP: the distance of every vertex and, on request, its canonical predecessor
+    def sssp_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.sssp needs, from the CSR arrays of a square matrix (val: float32 bit patterns)."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        val = np.ascontiguousarray(val)
+        assert val.dtype.itemsize == 4
+        h = C.c_void_p()
+        self._chk(abi.load().sh_sssp_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
+                                                  C.byref(h)))
+        return SsspGraph(self, h, len(row_ptr) - 1)
+
+    def sssp(self, G, x0, dist, pred=None, delta=-1.0, max_rounds=1 << 20):
+        """-> (rounds, buckets, reached, complete, relaxed, sizes, edges, ns_per_round, total_ns); per round that ran:
+        vertices relaxed from, edges looked at, device ns."""
+        rounds, buckets, reached, complete = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+        relaxed, total = C.c_int64(), C.c_uint64()
+        cap = max(int(max_rounds), 1)
+        sizes, edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
+        self._chk(abi.load().sh_sssp(self.h, G.h, x0.h, dist.h, None if pred is None else pred.h, delta, max_rounds,
+                                     C.byref(rounds), C.byref(buckets), C.byref(reached), C.byref(complete), C.byref(relaxed),
+                                     sizes.ctypes.data_as(C.POINTER(C.c_int64)), edges.ctypes.data_as(C.POINTER(C.c_int64)),
+                                     per.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)))
+        n = rounds.value
+        return (n, buckets.value, reached.value, bool(complete.value), relaxed.value, sizes[:n].copy(), edges[:n].copy(),
                 per[:n].copy(), total.value)
 
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
