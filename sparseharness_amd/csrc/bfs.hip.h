@@ -18,20 +18,19 @@
 // ever waits for another kernel's write: the gate words a kernel reads were written by a launch that ended before it.
 // bfs_parents is one row-parallel pass after the traversal (min over the row), so the traversal carries no parent atomics.
 //
-// Work distribution as in frontier.hip.h: fixed grids whose waves stride over a device-side length; short lists one
-// lane each, longer ones the whole wave, those above a piece size one wave per piece through a piece list.
+// Work distribution as worklist.hip.h describes it.  The handle is built by its kernels: wl_edge_flag<BfsKeep>,
+// wl_edge_compact, wl_row_starts, wl_row_pieces<BFS_ROW_PIECE>, wl_col_hist, wl_transpose_scatter.
 #pragma once
-#include "frontier.hip.h"
+#include "worklist.hip.h"
 
 namespace sh {
 
-constexpr int BFS_BS = 256;
 constexpr int BFS_SHORT = 8;            // out-lists (top-down) / rows (parent pass) up to this many edges: one lane each
 constexpr int BFS_BU_SHORT = 32;        // bottom-up: rows up to this many edges one lane each (the early exit makes a lane's walk short)
 constexpr int BFS_OUT_PIECE = 2048;     // out-lists above this are expanded in pieces of this many edges
 constexpr int BFS_ROW_PIECE = 4096;     // rows above this are searched in pieces of this many edges (a static list)
 constexpr int BFS_BATCH = 32;           // steps enqueued ahead of the host at most (the first batch holds 8)
-constexpr int BFS_MAX_BLOCKS = 1024;    // workgroups of a traversal launch at most: one BfsPart each
+constexpr int BFS_MAX_BLOCKS = 1024;    // workgroups of a traversal launch at most: one WlPart each
 constexpr int BFS_CTL_BYTES = 2048;     // device bytes set aside for BfsCtl
 constexpr int BFS_PART_BYTES = 16 * BFS_MAX_BLOCKS;
 
@@ -50,98 +49,35 @@ struct BfsCtl {
   uint32_t nsrc, fsize;             // number of sources; size of the frontier of `step`
   BfsRec rec[BFS_BATCH];
 };
-// Per workgroup of a traversal launch: its sums (no atomics on one address: thousands of waves adding to one word
-// retire about 6 ns apart, see frontier_detect).  init: a = out-list lengths of the sources.  top-down: a = edges looked
+// The WlPart of a workgroup of a traversal launch.  init: a = out-list lengths of the sources.  top-down: a = edges looked
 // at, b = out-list lengths of the vertices claimed.  bottom-up: a = rows that found a parent, b = edges looked at.
-struct BfsPart { uint32_t a, b, c, pad; };
 
-#define BFS_LANE ((int)(threadIdx.x & 63))
-#define BFS_WAVE ((int64_t)blockIdx.x * (BFS_BS / 64) + (threadIdx.x >> 6))
-#define BFS_WAVES ((int64_t)gridDim.x * (BFS_BS / 64))
+struct BfsKeep {   // wl_edge_flag: an entry is an edge when its value word is not zero (and its column is inside the matrix)
+  __device__ static bool value(uint32_t v) { return v != 0u; }
+};
 
 __device__ __forceinline__ bool bfs_bit(const uint32_t *__restrict__ bm, int32_t v) { return (bm[v >> 5] >> (v & 31)) & 1u; }
 __device__ __forceinline__ void bfs_or(uint32_t *p, uint32_t v) {
   (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// A place in a list for every lane that gets here together (any control flow: the ballot covers the active lanes, the
-// lowest of them adds for all and readfirstlane hands its answer round), as fr_claim does.
-__device__ __forceinline__ uint32_t bfs_append_here(uint32_t *cursor) {
-  const uint64_t here = __ballot(1);
-  const int lane = BFS_LANE;
-  uint32_t first = 0;
-  if (lane == __ffsll((unsigned long long)here) - 1) first = fr_add(cursor, (uint32_t)__popcll(here));
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)first) + (uint32_t)__popcll(here & ((1ull << lane) - 1ull));
-}
-// the pieces of a long out-list join piece list `pl`
-__device__ __forceinline__ void bfs_push_pieces(uint32_t *cursor, int32_t v, uint32_t len, FrPiece *__restrict__ pl) {
-  if (len > (uint32_t)BFS_OUT_PIECE) {
-    const uint32_t np = (len + BFS_OUT_PIECE - 1) / BFS_OUT_PIECE;
-    const uint32_t b = fr_add(cursor, np);
-    for (uint32_t j = 0; j < np; j++) pl[b + j] = FrPiece{(uint32_t)v, j * BFS_OUT_PIECE};
-  }
-}
-// The workgroup's sums -> its BfsPart (convergent control flow only).
-__device__ __forceinline__ void bfs_block_part(BfsPart *__restrict__ part, uint32_t a, uint32_t b) {
-  __shared__ uint32_t s_a[BFS_BS / 64], s_b[BFS_BS / 64];
-  a = fr_wave_sum(a);
-  b = fr_wave_sum(b);
-  if (BFS_LANE == 0) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t ta = 0, tb = 0;
-    for (int w = 0; w < BFS_BS / 64; w++) { ta += s_a[w]; tb += s_b[w]; }
-    part[blockIdx.x] = BfsPart{ta, tb, 0u, 0u};
-  }
-}
-
-// ---- building the handle (once): the entries that are edges, compacted in stored order; the static pieces of long rows
-// flag[j] = entry j is an edge (flag[nnz] = 0 closes the scan)
-__global__ __launch_bounds__(BFS_BS) void bfs_edge_flag(const int32_t *__restrict__ col_idx, const uint32_t *__restrict__ val,
-                                                        int64_t nnz, int32_t cols, uint32_t *__restrict__ flag) {
-  const int64_t j = (int64_t)blockIdx.x * BFS_BS + threadIdx.x;
-  if (j < nnz) flag[j] = (val[j] != 0u && (uint32_t)col_idx[j] < (uint32_t)cols) ? 1u : 0u;
-  else if (j == nnz) flag[j] = 0u;
-}
-// pos = exclusive scan of flag: edge j goes to in_col[pos[j]]
-__global__ __launch_bounds__(BFS_BS) void bfs_edge_compact(const int32_t *__restrict__ col_idx, const uint32_t *__restrict__ flag,
-                                                           const uint32_t *__restrict__ pos, int64_t nnz, int32_t *__restrict__ in_col) {
-  const int64_t j = (int64_t)blockIdx.x * BFS_BS + threadIdx.x;
-  if (j < nnz && flag[j]) in_col[pos[j]] = col_idx[j];
-}
-__global__ __launch_bounds__(BFS_BS) void bfs_row_starts(const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ pos,
-                                                         int64_t rows, int32_t *__restrict__ in_ptr) {
-  const int64_t r = (int64_t)blockIdx.x * BFS_BS + threadIdx.x;
-  if (r <= rows) in_ptr[r] = (int32_t)pos[row_ptr[r]];
-}
-__global__ __launch_bounds__(BFS_BS) void bfs_row_pieces(const int32_t *__restrict__ in_ptr, int64_t rows, uint32_t *cursor,
-                                                         FrPiece *__restrict__ rpieces) {
-  const int64_t r = (int64_t)blockIdx.x * BFS_BS + threadIdx.x;
-  if (r >= rows) return;
-  const uint32_t len = (uint32_t)(in_ptr[r + 1] - in_ptr[r]);
-  if (len > (uint32_t)BFS_ROW_PIECE) {
-    const uint32_t np = (len + BFS_ROW_PIECE - 1) / BFS_ROW_PIECE;
-    const uint32_t b = fr_add(cursor, np);
-    for (uint32_t j = 0; j < np; j++) rpieces[b + j] = FrPiece{(uint32_t)r, j * BFS_ROW_PIECE};
-  }
-}
 
 // ---- the search
 // level from x0; the sources into queue 0 and bitmap 0 (every word of bitmap 0 is written), their out-list lengths summed.
-__global__ __launch_bounds__(BFS_BS) void bfs_init(BfsCtl *ctl, int32_t rows, int32_t words, const uint32_t *__restrict__ x0,
+__global__ __launch_bounds__(WL_BS) void bfs_init(BfsCtl *ctl, int32_t rows, int32_t words, const uint32_t *__restrict__ x0,
                                                    int32_t *__restrict__ level, const int32_t *__restrict__ out_ptr,
-                                                   uint32_t *__restrict__ queue, FrPiece *__restrict__ pl, uint32_t *__restrict__ bm,
-                                                   BfsPart *__restrict__ part) {
-  const int lane = BFS_LANE;
+                                                   uint32_t *__restrict__ queue, WlPiece *__restrict__ pl, uint32_t *__restrict__ bm,
+                                                   WlPart *__restrict__ part) {
+  const int lane = wl_lane();
   uint32_t m = 0;
-  for (int64_t base = BFS_WAVE * 64; base < rows; base += BFS_WAVES * 64) {
+  for (int64_t base = wl_wave() * 64; base < rows; base += wl_waves() * 64) {
     const int64_t r = base + lane;
     const bool src = r < rows && x0[r] != 0u;
     if (r < rows) level[r] = src ? 0 : -1;
-    const uint32_t at = fr_wave_append(&ctl->qcount[0], src, lane);
+    const uint32_t at = wl_wave_append(&ctl->qcount[0], src, lane);
     if (src) {
       queue[at] = (uint32_t)r;
       const uint32_t len = (uint32_t)(out_ptr[r + 1] - out_ptr[r]);
-      bfs_push_pieces(&ctl->qpieces[0], (int32_t)r, len, pl);
+      wl_push_pieces<BFS_OUT_PIECE>(&ctl->qpieces[0], (uint32_t)r, len, pl);
       m += len;
     }
     const uint64_t sm = __ballot(src);
@@ -149,58 +85,36 @@ __global__ __launch_bounds__(BFS_BS) void bfs_init(BfsCtl *ctl, int32_t rows, in
     if (lane == 0 && w < words) bm[w] = (uint32_t)sm;
     if (lane == 32 && w + 1 < words) bm[w + 1] = (uint32_t)(sm >> 32);
   }
-  bfs_block_part(part, m, 0u);
+  wl_block_part(part, m, 0u);
 }
 
 // r was found unvisited by a top-down lane: the one that wins the compare-and-swap owns it
 __device__ __forceinline__ uint32_t bfs_visit(BfsCtl *ctl, int q, int32_t r, int32_t next_level, int32_t *level,
                                               const int32_t *__restrict__ out_ptr, uint32_t *__restrict__ queue,
-                                              FrPiece *__restrict__ pl, uint32_t *bm) {
+                                              WlPiece *__restrict__ pl, uint32_t *bm) {
   if (level[r] != -1) return 0;   // (a stale -1 only costs a compare-and-swap that fails; a level never returns to -1)
   int32_t expect = -1;
   if (!__hip_atomic_compare_exchange_strong(&level[r], &expect, next_level, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                             __HIP_MEMORY_SCOPE_AGENT))
     return 0;
-  queue[bfs_append_here(&ctl->qcount[q])] = (uint32_t)r;
+  queue[wl_append_here(&ctl->qcount[q])] = (uint32_t)r;
   bfs_or(&bm[r >> 5], 1u << (r & 31));
   const uint32_t len = (uint32_t)(out_ptr[r + 1] - out_ptr[r]);
-  bfs_push_pieces(&ctl->qpieces[q], r, len, pl);
+  wl_push_pieces<BFS_OUT_PIECE>(&ctl->qpieces[q], (uint32_t)r, len, pl);
   return len;
 }
 
-__global__ __launch_bounds__(BFS_BS) void bfs_topdown(BfsCtl *ctl, int L, int32_t *level, const int32_t *__restrict__ out_ptr,
+__global__ __launch_bounds__(WL_BS) void bfs_topdown(BfsCtl *ctl, int L, int32_t *level, const int32_t *__restrict__ out_ptr,
                                                       const int32_t *__restrict__ out_row, const uint32_t *__restrict__ queue,
-                                                      const FrPiece *__restrict__ pl, uint32_t *__restrict__ queue_next,
-                                                      FrPiece *__restrict__ pl_next, uint32_t *bm_next, BfsPart *__restrict__ part) {
+                                                      const WlPiece *__restrict__ pl, uint32_t *__restrict__ queue_next,
+                                                      WlPiece *__restrict__ pl_next, uint32_t *bm_next, WlPart *__restrict__ part) {
   if (ctl->step != L || ctl->mode != 0) return;
-  const int lane = BFS_LANE, p = L & 1, q = p ^ 1;
-  const int64_t n = ctl->qcount[p], np = ctl->qpieces[p];
-  uint32_t looked = 0, m_next = 0;
-#define BFS_VISIT(r) m_next += bfs_visit(ctl, q, (r), L + 1, level, out_ptr, queue_next, pl_next, bm_next)
-  for (int64_t base = BFS_WAVE * 64; base < n; base += BFS_WAVES * 64) {
-    const bool valid = base + lane < n;
-    const int32_t v = valid ? (int32_t)queue[base + lane] : 0;
-    const int32_t s = valid ? out_ptr[v] : 0;
-    const int32_t len = valid ? out_ptr[v + 1] - s : 0;
-    looked += (uint32_t)len;
-    if (len <= BFS_SHORT)
-      for (int32_t j = 0; j < len; j++) BFS_VISIT(out_row[s + j]);
-    uint64_t m = __ballot(len > BFS_SHORT && len <= BFS_OUT_PIECE);
-    while (m) {
-      const int src = __ffsll((unsigned long long)m) - 1;
-      m &= m - 1;
-      const int32_t sb = __shfl(s, src), lb = __shfl(len, src);
-      for (int32_t j = lane; j < lb; j += 64) BFS_VISIT(out_row[sb + j]);
-    }
-  }
-  for (int64_t i = BFS_WAVE; i < np; i += BFS_WAVES) {   // a hub's out-list: one wave per piece
-    const FrPiece pc = pl[i];
-    const int32_t s = out_ptr[pc.id] + (int32_t)pc.off;
-    const int32_t e = min(s + BFS_OUT_PIECE, out_ptr[pc.id + 1]);
-    for (int32_t j = s + lane; j < e; j += 64) BFS_VISIT(out_row[j]);
-  }
-#undef BFS_VISIT
-  bfs_block_part(part, looked, m_next);
+  const int p = L & 1, q = p ^ 1;
+  uint32_t m_next = 0;
+  const uint32_t looked = wl_expand<BFS_SHORT, BFS_OUT_PIECE>(
+      queue, ctl->qcount[p], pl, ctl->qpieces[p], out_ptr, [](int32_t, bool) { return 0u; },
+      [&](int32_t j, uint32_t) { m_next += bfs_visit(ctl, q, out_row[j], L + 1, level, out_ptr, queue_next, pl_next, bm_next); });
+  wl_block_part(part, looked, m_next);
 }
 
 // Does [s, e) of in_col hold a column of the frontier?  The whole wave looks, 64 edges at a time, and stops at the first
@@ -215,15 +129,15 @@ __device__ __forceinline__ bool bfs_wave_search(const int32_t *__restrict__ in_c
   return false;
 }
 
-__global__ __launch_bounds__(BFS_BS) void bfs_bottomup(BfsCtl *ctl, int L, int32_t rows, int32_t *level, const int32_t *__restrict__ in_ptr,
+__global__ __launch_bounds__(WL_BS) void bfs_bottomup(BfsCtl *ctl, int L, int32_t rows, int32_t *level, const int32_t *__restrict__ in_ptr,
                                                        const int32_t *__restrict__ in_col, const uint32_t *__restrict__ bm,
-                                                       uint32_t *bm_next, const FrPiece *__restrict__ rpieces, int32_t n_rpieces,
-                                                       BfsPart *__restrict__ part) {
+                                                       uint32_t *bm_next, const WlPiece *__restrict__ rpieces, int32_t n_rpieces,
+                                                       WlPart *__restrict__ part) {
   if (ctl->step != L || ctl->mode != 1) return;
-  const int lane = BFS_LANE;
+  const int lane = wl_lane();
   uint32_t found = 0, looked = 0;
   // 64 consecutive rows per wave step: level and in_ptr are read coalesced
-  for (int64_t base = BFS_WAVE * 64; base < rows; base += BFS_WAVES * 64) {
+  for (int64_t base = wl_wave() * 64; base < rows; base += wl_waves() * 64) {
     const int64_t r = base + lane;
     const bool open = r < rows && level[r] == -1;
     const int32_t s = open ? in_ptr[r] : 0;
@@ -253,8 +167,8 @@ __global__ __launch_bounds__(BFS_BS) void bfs_bottomup(BfsCtl *ctl, int L, int32
   // Rows above BFS_ROW_PIECE: one wave per piece.  A piece that comes late may find the row already claimed by another
   // piece and skips it; two pieces that both find a frontier column race for the row with a compare-and-swap -- both
   // would write the same level, but only one may count the row.
-  for (int64_t i = BFS_WAVE; i < n_rpieces; i += BFS_WAVES) {
-    const FrPiece pc = rpieces[i];
+  for (int64_t i = wl_wave(); i < n_rpieces; i += wl_waves()) {
+    const WlPiece pc = rpieces[i];
     const int32_t r = (int32_t)pc.id;
     if (level[r] != -1) continue;
     const int32_t s = in_ptr[r] + (int32_t)pc.off;
@@ -271,16 +185,16 @@ __global__ __launch_bounds__(BFS_BS) void bfs_bottomup(BfsCtl *ctl, int L, int32
       }
     }
   }
-  bfs_block_part(part, found, looked);
+  wl_block_part(part, found, looked);
 }
 
 // The frontier a bottom-up step left as a bitmap -> queue (and the pieces of its long out-lists), for a top-down step.
-__global__ __launch_bounds__(BFS_BS) void bfs_queue_from_bitmap(BfsCtl *ctl, int L, int32_t words, const uint32_t *__restrict__ bm,
+__global__ __launch_bounds__(WL_BS) void bfs_queue_from_bitmap(BfsCtl *ctl, int L, int32_t words, const uint32_t *__restrict__ bm,
                                                                 const int32_t *__restrict__ out_ptr, uint32_t *__restrict__ queue,
-                                                                FrPiece *__restrict__ pl) {
+                                                                WlPiece *__restrict__ pl) {
   if (ctl->step != L || ctl->mode != 0 || ctl->have_queue != 0) return;
-  const int lane = BFS_LANE, p = L & 1;
-  for (int64_t base = BFS_WAVE * 64; base < words; base += BFS_WAVES * 64) {
+  const int lane = wl_lane(), p = L & 1;
+  for (int64_t base = wl_wave() * 64; base < words; base += wl_waves() * 64) {
     uint32_t w = base + lane < words ? bm[base + lane] : 0u;
     const uint32_t cnt = (uint32_t)__popc(w);
     uint32_t incl = cnt;   // inclusive prefix sum over the wave
@@ -291,39 +205,33 @@ __global__ __launch_bounds__(BFS_BS) void bfs_queue_from_bitmap(BfsCtl *ctl, int
     const uint32_t total = (uint32_t)__shfl((int)incl, 63);
     if (total == 0) continue;
     uint32_t first = 0;
-    if (lane == 63) first = fr_add(&ctl->qcount[p], total);   // one add per 2048 vertices
+    if (lane == 63) first = wl_add(&ctl->qcount[p], total);   // one add per 2048 vertices
     uint32_t at = (uint32_t)__shfl((int)first, 63) + incl - cnt;
     while (w) {
       const int32_t v = (int32_t)((base + lane) * 32 + (__ffs((int)w) - 1));
       w &= w - 1;
       queue[at++] = (uint32_t)v;
-      bfs_push_pieces(&ctl->qpieces[p], v, (uint32_t)(out_ptr[v + 1] - out_ptr[v]), pl);
+      wl_push_pieces<BFS_OUT_PIECE>(&ctl->qpieces[p], (uint32_t)v, (uint32_t)(out_ptr[v + 1] - out_ptr[v]), pl);
     }
   }
 }
 
 // Closes step L (slot k of the batch); L = -1 closes bfs_init and chooses the direction of step 0.  Every workgroup
 // clears its share of the bitmap the step consumed, whether the step ran or not (after the end of the search nobody
-// reads a bitmap); workgroup 0 sums the BfsParts and its first lane applies the rule:
+// reads a bitmap); workgroup 0 sums the WlParts and its first lane applies the rule:
 //   after a top-down step (and for step 0): bottom-up iff m > up_edges (= up_share * edges);
 //   after a bottom-up step: top-down iff |F| < down_rows (= down_share * rows).
-__global__ __launch_bounds__(BFS_BS) void bfs_decide(BfsCtl *ctl, int k, int L, int nparts, const BfsPart *__restrict__ part,
+__global__ __launch_bounds__(WL_BS) void bfs_decide(BfsCtl *ctl, int k, int L, int nparts, const WlPart *__restrict__ part,
                                                      uint32_t *__restrict__ bm, int32_t words, double up_edges, double down_rows) {
   if (L >= 0)
-    for (int64_t i = (int64_t)blockIdx.x * BFS_BS + threadIdx.x; i < words; i += (int64_t)gridDim.x * BFS_BS) bm[i] = 0u;
+    for (int64_t i = (int64_t)blockIdx.x * WL_BS + threadIdx.x; i < words; i += (int64_t)gridDim.x * WL_BS) bm[i] = 0u;
   if (blockIdx.x != 0) return;
-  __shared__ uint32_t s_a[BFS_BS], s_b[BFS_BS];
   __shared__ int32_t s_go, s_mode;
   if (threadIdx.x == 0) { s_go = (L < 0 || ctl->step == L) ? 1 : 0; s_mode = ctl->mode; }
   __syncthreads();
   if (!s_go) return;
   uint32_t a = 0, b = 0;
-  for (int i = (int)threadIdx.x; i < nparts; i += BFS_BS) { a += part[i].a; b += part[i].b; }
-  s_a[threadIdx.x] = a; s_b[threadIdx.x] = b;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  a = 0; b = 0;
-  for (int i = 0; i < BFS_BS; i++) { a += s_a[i]; b += s_b[i]; }
+  if (!wl_sum_parts(part, nparts, &a, &b)) return;
   if (L < 0) {
     const uint32_t nsrc = ctl->qcount[0];
     ctl->nsrc = nsrc; ctl->fsize = nsrc;
@@ -346,57 +254,15 @@ __global__ __launch_bounds__(BFS_BS) void bfs_decide(BfsCtl *ctl, int k, int L, 
   ctl->step = L + 1;
 }
 
-// parent[r] = the smallest c with an edge c -> r and level[c] == level[r] - 1.  The host fills parent with -1 first;
-// pieces of long rows meet in parent[r] by an UNSIGNED atomic min, under which -1 (no candidate yet) is the largest word.
-__global__ __launch_bounds__(BFS_BS) void bfs_parents(int32_t rows, const int32_t *__restrict__ level, const int32_t *__restrict__ in_ptr,
-                                                      const int32_t *__restrict__ in_col, const FrPiece *__restrict__ rpieces,
-                                                      int32_t n_rpieces, int32_t *parent) {
-  const int lane = BFS_LANE;
-  for (int64_t base = BFS_WAVE * 64; base < rows; base += BFS_WAVES * 64) {
-    const int64_t r = base + lane;
-    const int32_t lv = r < rows ? level[r] : -1;
-    const int32_t s = lv > 0 ? in_ptr[r] : 0;
-    const int32_t len = lv > 0 ? in_ptr[r + 1] - s : 0;
-    uint32_t best = 0xFFFFFFFFu;
-    if (len <= BFS_SHORT)
-      for (int32_t j = 0; j < len; j++) {
-        const int32_t c = in_col[s + j];
-        if (level[c] == lv - 1) best = min(best, (uint32_t)c);
-      }
-    uint64_t m = __ballot(len > BFS_SHORT && len <= BFS_ROW_PIECE);
-    while (m) {
-      const int src = __ffsll((unsigned long long)m) - 1;
-      m &= m - 1;
-      const int32_t sb = __shfl(s, src), lb = __shfl(len, src), want = __shfl(lv, src) - 1;
-      uint32_t mine = 0xFFFFFFFFu;
-      for (int32_t j = lane; j < lb; j += 64) {
-        const int32_t c = in_col[sb + j];
-        if (level[c] == want) mine = min(mine, (uint32_t)c);
-      }
-      for (int o = 32; o > 0; o >>= 1) mine = min(mine, (uint32_t)__shfl_xor((int)mine, o));
-      if (lane == src) best = mine;
-    }
-    if (len > 0 && len <= BFS_ROW_PIECE) parent[r] = (int32_t)best;
-  }
-  for (int64_t i = BFS_WAVE; i < n_rpieces; i += BFS_WAVES) {
-    const FrPiece pc = rpieces[i];
-    const int32_t r = (int32_t)pc.id, want = level[r] - 1;
-    if (want < 0) continue;
-    const int32_t s = in_ptr[r] + (int32_t)pc.off;
-    const int32_t e = min(s + BFS_ROW_PIECE, in_ptr[r + 1]);
-    uint32_t mine = 0xFFFFFFFFu;
-    for (int32_t j = s + lane; j < e; j += 64) {
-      const int32_t c = in_col[j];
-      if (level[c] == want) mine = min(mine, (uint32_t)c);
-    }
-    for (int o = 32; o > 0; o >>= 1) mine = min(mine, (uint32_t)__shfl_xor((int)mine, o));
-    if (lane == 0 && mine != 0xFFFFFFFFu)
-      (void)__hip_atomic_fetch_min((uint32_t *)&parent[r], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+// parent[r] = the smallest c with an edge c -> r and level[c] == level[r] - 1 (wl_rows_min: the host fills parent with
+// -1 first).
+__global__ __launch_bounds__(WL_BS) void bfs_parents(int32_t rows, const int32_t *__restrict__ level, const int32_t *__restrict__ in_ptr,
+                                                     const int32_t *__restrict__ in_col, const WlPiece *__restrict__ rpieces,
+                                                     int32_t n_rpieces, int32_t *parent) {
+  wl_rows_min<BFS_SHORT, BFS_ROW_PIECE>(
+      rows, in_ptr, in_col, rpieces, n_rpieces, parent,
+      [&](int32_t r, uint32_t *want) { const int32_t lv = level[r]; *want = (uint32_t)(lv - 1); return lv > 0; },
+      [&](int32_t j, uint32_t want) { return level[in_col[j]] == (int32_t)want; });
 }
-
-#undef BFS_LANE
-#undef BFS_WAVE
-#undef BFS_WAVES
 
 } // namespace sh

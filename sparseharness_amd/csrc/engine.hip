@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -1757,6 +1758,231 @@ int sh_bits_to_column(sh_engine *e, const sh_vec *B, int64_t n, int32_t words, i
 #endif
 
 
+// ---- what the worklist handles share (worklist.hip.h) ----------------------------------------------------------------
+// Owner of device arrays: whatever it allocated is released with it.  A handle holds one for its arrays, and a create
+// function a second one for the temporaries of the build, which so go on every return path.
+struct DevArrays {
+  std::vector<void *> ptrs;
+  size_t bytes = 0;   // what a handle's footprint reports
+  DevArrays() = default;
+  DevArrays(const DevArrays &) = delete;
+  DevArrays &operator=(const DevArrays &) = delete;
+  ~DevArrays() {
+    for (void *p : ptrs) (void)hipFree(p);
+  }
+  // (an array of `nbytes` counts as that in the footprint; an empty one still gets a few bytes to point at)
+  template <class T>
+  hipError_t alloc(T **p, int64_t nbytes) {
+    void *q = nullptr;
+    const hipError_t r = hipMalloc(&q, std::max<size_t>((size_t)nbytes, 16));
+    if (r != hipSuccess) return r;
+    ptrs.push_back(q);
+    bytes += (size_t)nbytes;
+    *p = (T *)q;
+    return hipSuccess;
+  }
+};
+
+template <class H>
+static int free_handle(sh_engine *e, H *h) {
+  if (!h)
+    return SH_OK;
+  if (e) {
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->stream);
+  }
+  delete h;
+  return SH_OK;
+}
+
+static hipError_t ms_between(hipEvent_t a, hipEvent_t b, uint64_t *ns) {
+  float ms = 0.f;
+  const hipError_t r = hipEventElapsedTime(&ms, a, b);
+  *ns = (uint64_t)((double)ms * 1e6);
+  return r;
+}
+
+// The transpose of the pattern ptr / col with `n` entries (and of its weights when w != NULL): column histogram,
+// exclusive scan, scatter through per-column cursors.  Enqueued only: `tmp` lives until the stream has been synchronised.
+static int build_transpose(sh_engine *e, DevArrays &tmp, const int32_t *ptr, const int32_t *col, const uint32_t *w, int64_t n,
+                           int64_t rows, int64_t cols, int32_t *out_ptr, int32_t *out_row, uint32_t *out_w) {
+  uint32_t *cnt = nullptr;   // column counts, then the scatter's cursors
+  HIP_TRY(e, tmp.alloc(&cnt, (cols + 1) * 4));
+  HIP_TRY(e, hipMemsetAsync(cnt, 0, (size_t)(cols + 1) * 4, e->stream));
+  const dim3 grid((unsigned)std::max<int64_t>(1, (n + WL_BS - 1) / WL_BS)), blk(WL_BS);
+  if (n > 0) {
+    hipLaunchKernelGGL(wl_col_hist, grid, blk, 0, e->stream, col, n, (int32_t)cols, cnt);
+    HIP_TRY(e, hipGetLastError());
+  }
+  HIP_TRY(e, device_exclusive_sum_u32(e->stream, cnt, (uint32_t *)out_ptr, cols + 1));
+  HIP_TRY(e, hipMemcpyAsync(cnt, out_ptr, (size_t)(cols + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
+  if (n > 0) {
+    hipLaunchKernelGGL(wl_transpose_scatter, grid, blk, 0, e->stream, ptr, col, w, n, (int32_t)rows, (int32_t)cols, cnt, out_row, out_w);
+    HIP_TRY(e, hipGetLastError());
+  }
+  return SH_OK;
+}
+
+// What sh_bfs_graph and sh_sssp_graph share: the edges by row (in_*) and by source vertex (out_*), the static pieces of
+// the long rows, and what a batch of gated steps needs (run_batches).
+template <class Ctl>
+struct GraphHandle {
+  int64_t rows = 0, nnz = 0, edges = 0;
+  int32_t *d_in_ptr = nullptr, *d_in_col = nullptr, *d_out_ptr = nullptr, *d_out_row = nullptr;
+  uint32_t *d_in_w = nullptr, *d_out_w = nullptr;   // |a| of every edge (NULL in a handle without weights)
+  WlPiece *d_rpieces = nullptr;                     // pieces of the rows above the handle's row piece size (static)
+  int32_t n_rpieces = 0;
+  Ctl *d_ctl = nullptr;            // the control block, followed by the WlParts (and whatever else the handle puts there)
+  WlPart *d_part = nullptr;
+  Ctl *h_ctl = nullptr;            // pinned: the control block as read back once per batch
+  hipEvent_t ev[sizeof(Ctl::rec) / sizeof(Ctl::rec[0]) + 1] = {};
+  DevArrays dev;
+  ~GraphHandle() {
+    if (h_ctl) (void)hipHostFree(h_ctl);
+    for (auto v : ev)
+      if (v) (void)hipEventDestroy(v);
+  }
+};
+
+// What the scalars and the host arrays of fn = sh_bfs_graph_create / sh_sssp_graph_create alone decide: no device is
+// needed to be told.
+static int check_host_csr(sh_engine *e, const char *fn, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                          const void *val, const void *out) {
+  if (rows < 0 || rows > 0x7FFFFF00ll)
+    return fail(e, SH_EINVAL, "%s: rows = %lld, must be in [0, 2^31 - 256]", fn, (long long)rows);
+  if (nnz < 0 || nnz > 0x7FFFFF00ll)
+    return fail(e, SH_EINVAL, "%s: nnz = %lld, must be in [0, 2^31 - 256]", fn, (long long)nnz);
+  if (!row_ptr || !out || (nnz > 0 && (!col_idx || !val)))
+    return fail(e, SH_EINVAL, "%s: NULL argument (row_ptr, out, or col_idx / val of a matrix with entries)", fn);
+  if (row_ptr[0] != 0 || (int64_t)row_ptr[rows] != nnz)
+    return fail(e, SH_ESHAPE, "%s: row_ptr[0] = %d and row_ptr[rows] = %d, must be 0 and nnz = %lld", fn, (int)row_ptr[0],
+                (int)row_ptr[rows], (long long)nnz);
+  for (int64_t r = 0; r < rows; r++)   // (the build indexes by row_ptr on the device: it must stay inside the arrays)
+    if (row_ptr[r] > row_ptr[r + 1])
+      return fail(e, SH_ESHAPE, "%s: row_ptr decreases at row %lld", fn, (long long)r);
+  if (!e)
+    return fail(e, SH_EINVAL, "%s: NULL argument (engine)", fn);
+  return SH_OK;
+}
+
+// The edge lists of a graph handle from host CSR arrays: the entries that are edges (KEEP, see wl_edge_flag) by flag,
+// exclusive scan and compaction (the stored order of the survivors is kept), the static pieces of long rows, the
+// transpose; all with the weights |a| when `weights`.  ROW_PIECE: the handle's piece size for rows.  Returns with the
+// stream synchronised: the host arrays are done with.
+template <class KEEP, int ROW_PIECE, class Ctl>
+static int build_edge_lists(sh_engine *e, GraphHandle<Ctl> *g, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                            const void *val, bool weights) {
+  g->rows = rows; g->nnz = nnz;
+  // temporaries: the CSR arrays as given, the edge flags and their scan, the cursor of the row pieces
+  DevArrays tmp;
+  int32_t *t_rp = nullptr, *t_ci = nullptr;
+  uint32_t *t_val = nullptr, *t_flag = nullptr, *t_pos = nullptr, *t_cur = nullptr;
+  HIP_TRY(e, tmp.alloc(&t_rp, (rows + 1) * 4));
+  HIP_TRY(e, tmp.alloc(&t_ci, nnz * 4));
+  HIP_TRY(e, tmp.alloc(&t_val, nnz * 4));
+  HIP_TRY(e, tmp.alloc(&t_flag, (nnz + 1) * 4));
+  HIP_TRY(e, tmp.alloc(&t_pos, (nnz + 1) * 4));
+  HIP_TRY(e, tmp.alloc(&t_cur, 4));
+  HIP_TRY(e, hipMemcpyAsync(t_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  if (nnz > 0) {
+    HIP_TRY(e, hipMemcpyAsync(t_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(t_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  HIP_TRY(e, hipMemsetAsync(t_cur, 0, 4, e->stream));
+  const dim3 blk(WL_BS), ngrid((unsigned)((nnz + 1 + WL_BS - 1) / WL_BS)), rgrid((unsigned)((rows + 1 + WL_BS - 1) / WL_BS));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(wl_edge_flag<KEEP>), ngrid, blk, 0, e->stream, t_ci, t_val, nnz, (int32_t)rows, t_flag);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, device_exclusive_sum_u32(e->stream, t_flag, t_pos, nnz + 1));
+  uint32_t n_edges = 0;
+  HIP_TRY(e, hipMemcpy(&n_edges, t_pos + nnz, 4, hipMemcpyDeviceToHost));
+  const int64_t E = (int64_t)n_edges;
+  g->edges = E;
+  DevArrays &own = g->dev;
+  HIP_TRY(e, own.alloc(&g->d_in_ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_in_col, E * 4));
+  if (weights) HIP_TRY(e, own.alloc(&g->d_in_w, E * 4));
+  HIP_TRY(e, own.alloc(&g->d_out_ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_out_row, E * 4));
+  if (weights) HIP_TRY(e, own.alloc(&g->d_out_w, E * 4));
+  HIP_TRY(e, own.alloc(&g->d_rpieces, (E / (ROW_PIECE / 2) + 1) * sizeof(WlPiece)));   // see wl_push_pieces
+  if (nnz > 0) {
+    hipLaunchKernelGGL(wl_edge_compact, ngrid, blk, 0, e->stream, t_ci, t_val, t_flag, t_pos, nnz, g->d_in_col, g->d_in_w);
+    HIP_TRY(e, hipGetLastError());
+  }
+  hipLaunchKernelGGL(wl_row_starts, rgrid, blk, 0, e->stream, t_rp, t_pos, rows, g->d_in_ptr);
+  HIP_TRY(e, hipGetLastError());
+  if (rows > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(wl_row_pieces<ROW_PIECE>), rgrid, blk, 0, e->stream, g->d_in_ptr, rows, t_cur, g->d_rpieces);
+    HIP_TRY(e, hipGetLastError());
+  }
+  uint32_t n_rp = 0;
+  HIP_TRY(e, hipMemcpyAsync(&n_rp, t_cur, 4, hipMemcpyDeviceToHost, e->stream));
+  const int rc = build_transpose(e, tmp, g->d_in_ptr, g->d_in_col, g->d_in_w, E, rows, rows, g->d_out_ptr, g->d_out_row, g->d_out_w);
+  if (rc)
+    return rc;
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  g->n_rpieces = (int32_t)n_rp;
+  return SH_OK;
+}
+
+// The control block of a graph handle (`nbytes` of device memory, zeroed), its pinned copy and the events of a batch.
+template <class Ctl>
+static int open_control(sh_engine *e, GraphHandle<Ctl> *g, int64_t ctl_bytes, int64_t nbytes) {
+  HIP_TRY(e, g->dev.alloc(&g->d_ctl, nbytes));
+  g->d_part = (WlPart *)((char *)g->d_ctl + ctl_bytes);
+  HIP_TRY(e, hipHostMalloc((void **)&g->h_ctl, sizeof(Ctl), hipHostMallocDefault));
+  for (auto &ev : g->ev) HIP_TRY(e, hipEventCreate(&ev));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, (size_t)nbytes, e->stream));
+  return SH_OK;
+}
+
+// The loop of sh_bfs_levels and sh_sssp: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
+// enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
+// step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
+// `what`: "<function>: <step>" for the error of a step that did not report.
+template <class Ctl, class Enqueue, class Take>
+static int run_batches(sh_engine *e, const char *what, GraphHandle<Ctl> *g, int32_t cap, int32_t *steps, bool *finished, uint64_t *total,
+                       Enqueue enqueue, Take take) {
+  constexpr int32_t MAX_BATCH = sizeof(Ctl::rec) / sizeof(Ctl::rec[0]);
+  int32_t it = 0, batch = 8;
+  bool done = false;
+  uint64_t ns = 0;
+  while (!done && it < cap) {
+    const int nb = std::min<int32_t>(batch, cap - it);
+    HIP_TRY(e, hipMemsetAsync((char *)g->d_ctl + offsetof(Ctl, rec), 0, sizeof(Ctl::rec), e->stream));
+    HIP_TRY(e, hipEventRecord(g->ev[0], e->stream));
+    for (int k = 0; k < nb; k++) {
+      const int rc = enqueue(it + k, k);
+      if (rc)
+        return rc;
+      HIP_TRY(e, hipEventRecord(g->ev[k + 1], e->stream));
+    }
+    HIP_TRY(e, hipMemcpyAsync(g->h_ctl, g->d_ctl, sizeof(Ctl), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    if (batch == 8) {   // (the first batch)
+      HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+      *total += ns;
+    }
+    int ran = 0;
+    while (ran < nb && g->h_ctl->rec[ran].ran) ran++;
+    for (int k = 0; k < ran; k++) {
+      HIP_TRY(e, ms_between(g->ev[k], g->ev[k + 1], &ns));
+      *total += ns;
+      take(it + k, g->h_ctl->rec[k], ns);
+    }
+    it += ran;
+    done = g->h_ctl->finished != 0;
+    if (!done && ran < nb)
+      return fail(e, SH_EHIP, "%s %d of the search did not report", what, (int)it);
+    batch = std::min(batch * 2, MAX_BATCH);
+  }
+  *steps = it;
+  *finished = done;
+  return SH_OK;
+}
+
+
 // ---- frontier-driven iteration (frontier.hip.h) --------------------------------------------------------------------
 struct sh_frontier {
   int64_t rows = 0, nnz = 0;
@@ -1766,12 +1992,16 @@ struct sh_frontier {
   uint32_t *d_val = nullptr;
   int32_t *d_col_ptr = nullptr, *d_row_of = nullptr;
   uint32_t *d_clist = nullptr, *d_alist = nullptr, *d_stamp = nullptr, *d_side = nullptr;
-  FrPiece *d_cplist = nullptr, *d_rplist = nullptr;
+  WlPiece *d_cplist = nullptr, *d_rplist = nullptr;
   FrontierCtl *d_ctl = nullptr;
   FrontierRec *h_rec = nullptr;    // pinned: the records of a batch
   uint32_t gen = 0;                // number of the latest sparse launch enqueued (what its stamps hold)
-  size_t bytes = 0;
+  DevArrays dev;                   // the arrays that are the handle's own
+  ~sh_frontier() {
+    if (h_rec) (void)hipHostFree(h_rec);
+  }
 };
+
 // sh_iterate_frontier's dense_share < 0: see DESIGN.md "Frontier-driven iteration" (the sweep of tools/frontier_bench.py)
 static constexpr double FRONTIER_DENSE_SHARE = 0.02;
 static_assert(sizeof(FrontierCtl) <= FR_CTL_BYTES, "the control block is accounted as FR_CTL_BYTES (sh_frontier_footprint)");
@@ -1787,7 +2017,7 @@ static int launch_sparse(sh_engine *e, sh_frontier *f, const sh_csr *A, sh_vec *
     HIP_TRY(e, hipMemsetAsync(f->d_stamp, 0, (size_t)std::max<int64_t>(f->rows, 1) * 4, e->stream));
     f->gen = 1;
   }
-  const dim3 grid((unsigned)(e->n_cus * 4)), block(FR_BS);
+  const dim3 grid((unsigned)(e->n_cus * 4)), block(WL_BS);
   const CsrDev dev{f->d_row_ptr, f->d_col, f->d_val, (int32_t)A->rows, (int32_t)A->cols};
   hipLaunchKernelGGL(frontier_mark, grid, block, 0, e->stream, f->d_ctl, k, p, f->gen, (int32_t)A->rows, f->d_col_ptr, f->d_row_of,
                      f->d_row_ptr, f->d_clist, f->d_cplist, f->d_stamp, f->d_alist, f->d_side, f->d_rplist, (uint32_t)SR::identity_bits);
@@ -1813,97 +2043,51 @@ int sh_frontier_create(sh_engine *e, const sh_csr *A, int64_t nnz, const int32_t
   if (nnz != A->nnz || row_ptr[0] != 0 || row_ptr[A->rows] != nnz)
     return fail(e, SH_ESHAPE, "sh_frontier_create: the arrays hold %lld entries, the matrix %lld", (long long)nnz, (long long)A->nnz);
   HIP_TRY(e, hipSetDevice(e->device));
-  sh_frontier *f = new (std::nothrow) sh_frontier();
+  std::unique_ptr<sh_frontier> f(new (std::nothrow) sh_frontier());
   if (!f)
     return fail(e, SH_ENOMEM, "out of host memory");
   const int64_t rows = A->rows, cols = A->cols;
   f->rows = rows; f->nnz = nnz; f->A = A;
-  uint32_t *cnt = nullptr;   // column counts, then the scatter's cursors
-  auto cleanup = [&](int rc) { if (cnt) (void)hipFree(cnt); sh_frontier_free(e, f); return rc; };
-#define HIP_TRY_F(call)                                                         \
-  do {                                                                          \
-    hipError_t _r = (call);                                                     \
-    if (_r != hipSuccess)                                                       \
-      return cleanup(fail(e, _r == hipErrorOutOfMemory ? SH_ENOMEM : SH_EHIP,   \
-                          "%s failed: %s", #call, hipGetErrorString(_r)));      \
-  } while (0)
-  // (an array of `bytes` counts as that in the footprint; an empty one still gets a few bytes to point at)
-#define F_ARRAY(ptr, nbytes)                                                                   \
-  do {                                                                                         \
-    HIP_TRY_F(hipMalloc((void **)&(ptr), std::max<size_t>((size_t)(nbytes), 16)));             \
-    f->bytes += (size_t)(nbytes);                                                              \
-  } while (0)
+  DevArrays &own = f->dev, tmp;
   f->borrowed = A->d_row_ptr && (nnz == 0 || (A->d_col && A->d_val));
   if (f->borrowed) {
     f->d_row_ptr = A->d_row_ptr; f->d_col = A->d_col; f->d_val = A->d_val;
   } else {
-    F_ARRAY(f->d_row_ptr, (rows + 1) * 4);
-    F_ARRAY(f->d_col, nnz * 4);
-    F_ARRAY(f->d_val, nnz * 4);
-    HIP_TRY_F(hipMemcpyAsync(f->d_row_ptr, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, own.alloc(&f->d_row_ptr, (rows + 1) * 4));
+    HIP_TRY(e, own.alloc(&f->d_col, nnz * 4));
+    HIP_TRY(e, own.alloc(&f->d_val, nnz * 4));
+    HIP_TRY(e, hipMemcpyAsync(f->d_row_ptr, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
     if (nnz > 0) {
-      HIP_TRY_F(hipMemcpyAsync(f->d_col, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
-      HIP_TRY_F(hipMemcpyAsync(f->d_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(f->d_col, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(f->d_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
     }
   }
-  F_ARRAY(f->d_col_ptr, (cols + 1) * 4);
-  F_ARRAY(f->d_row_of, nnz * 4);
-  F_ARRAY(f->d_clist, rows * 4);
-  F_ARRAY(f->d_alist, rows * 4);
-  F_ARRAY(f->d_stamp, rows * 4);
-  F_ARRAY(f->d_side, rows * 4);
-  F_ARRAY(f->d_cplist, (nnz / 1024 + 1) * sizeof(FrPiece));   // sum of ceil(len / 2048) over columns longer than 2048 <= nnz / 1024
-  F_ARRAY(f->d_rplist, (nnz / 2048 + 1) * sizeof(FrPiece));   // the same for rows longer than 4096
-  F_ARRAY(f->d_ctl, FR_CTL_BYTES);
-  HIP_TRY_F(hipHostMalloc((void **)&f->h_rec, sizeof(FrontierRec) * FR_BATCH, hipHostMallocDefault));
-  HIP_TRY_F(hipMemsetAsync(f->d_stamp, 0, std::max<size_t>((size_t)rows * 4, 16), e->stream));
-  HIP_TRY_F(hipMemsetAsync(f->d_ctl, 0, FR_CTL_BYTES, e->stream));
-  // the pattern of the transpose: column histogram, exclusive scan, scatter through per-column cursors
-  HIP_TRY_F(hipMalloc((void **)&cnt, (size_t)(cols + 1) * 4));
-  HIP_TRY_F(hipMemsetAsync(cnt, 0, (size_t)(cols + 1) * 4, e->stream));
-  const dim3 egrid((unsigned)std::max<int64_t>(1, (nnz + FR_BS - 1) / FR_BS));
-  if (nnz > 0) {
-    hipLaunchKernelGGL(frontier_col_hist, egrid, dim3(FR_BS), 0, e->stream, f->d_col, nnz, (int32_t)cols, cnt);
-    HIP_TRY_F(hipGetLastError());
-  }
-  HIP_TRY_F(device_exclusive_sum_u32(e->stream, cnt, (uint32_t *)f->d_col_ptr, cols + 1));
-  HIP_TRY_F(hipMemcpyAsync(cnt, f->d_col_ptr, (size_t)(cols + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
-  if (nnz > 0) {
-    hipLaunchKernelGGL(frontier_scatter, egrid, dim3(FR_BS), 0, e->stream, f->d_row_ptr, f->d_col, nnz, (int32_t)rows, (int32_t)cols,
-                       cnt, f->d_row_of);
-    HIP_TRY_F(hipGetLastError());
-  }
-  HIP_TRY_F(hipStreamSynchronize(e->stream));   // the host arrays and the cursors are done with
-  (void)hipFree(cnt);
-  cnt = nullptr;
-#undef F_ARRAY
-#undef HIP_TRY_F
-  *out = f;
+  HIP_TRY(e, own.alloc(&f->d_col_ptr, (cols + 1) * 4));
+  HIP_TRY(e, own.alloc(&f->d_row_of, nnz * 4));
+  HIP_TRY(e, own.alloc(&f->d_clist, rows * 4));
+  HIP_TRY(e, own.alloc(&f->d_alist, rows * 4));
+  HIP_TRY(e, own.alloc(&f->d_stamp, rows * 4));
+  HIP_TRY(e, own.alloc(&f->d_side, rows * 4));
+  HIP_TRY(e, own.alloc(&f->d_cplist, (nnz / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: columns longer than 2048
+  HIP_TRY(e, own.alloc(&f->d_rplist, (nnz / 2048 + 1) * sizeof(WlPiece)));   // the same for rows longer than 4096
+  HIP_TRY(e, own.alloc(&f->d_ctl, FR_CTL_BYTES));
+  HIP_TRY(e, hipHostMalloc((void **)&f->h_rec, sizeof(FrontierRec) * FR_BATCH, hipHostMallocDefault));
+  HIP_TRY(e, hipMemsetAsync(f->d_stamp, 0, std::max<size_t>((size_t)rows * 4, 16), e->stream));
+  HIP_TRY(e, hipMemsetAsync(f->d_ctl, 0, FR_CTL_BYTES, e->stream));
+  const int rc = build_transpose(e, tmp, f->d_row_ptr, f->d_col, nullptr, nnz, rows, cols, f->d_col_ptr, f->d_row_of, nullptr);
+  if (rc)
+    return rc;
+  HIP_TRY(e, hipStreamSynchronize(e->stream));   // the host arrays and the cursors are done with
+  *out = f.release();
   return SH_OK;
 }
 
-int sh_frontier_free(sh_engine *e, sh_frontier *f) {
-  if (!f)
-    return SH_OK;
-  if (e) {
-    (void)hipSetDevice(e->device);
-    (void)hipStreamSynchronize(e->stream);
-  }
-  if (!f->borrowed)
-    for (void *p : {(void *)f->d_row_ptr, (void *)f->d_col, (void *)f->d_val})
-      if (p) (void)hipFree(p);
-  for (void *p : {(void *)f->d_col_ptr, (void *)f->d_row_of, (void *)f->d_clist, (void *)f->d_alist, (void *)f->d_stamp,
-                  (void *)f->d_side, (void *)f->d_cplist, (void *)f->d_rplist, (void *)f->d_ctl})
-    if (p) (void)hipFree(p);
-  if (f->h_rec) (void)hipHostFree(f->h_rec);
-  delete f;
-  return SH_OK;
-}
+int sh_frontier_free(sh_engine *e, sh_frontier *f) { return free_handle(e, f); }
 
 int sh_frontier_footprint(const sh_frontier *f, uint64_t *device_bytes) {
   if (!f || !device_bytes)
     return SH_EINVAL;
-  *device_bytes = (uint64_t)f->bytes;
+  *device_bytes = (uint64_t)f->dev.bytes;
   return SH_OK;
 }
 
@@ -1952,7 +2136,7 @@ int sh_iterate_frontier(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_fronti
   const bool never_sparse = dense_share == 0.0;
   const uint32_t max_entries = dense_share >= 1.0 ? 0xFFFFFFFFu : (uint32_t)(dense_share * (double)A->nnz);
   HIP_TRY(e, hipMemsetAsync(f->d_ctl, 0, FR_CTL_BYTES, e->stream));
-  const dim3 dgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((A->rows + FR_BS - 1) / FR_BS, (int64_t)e->n_cus * 8)));
+  const dim3 dgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((A->rows + WL_BS - 1) / WL_BS, (int64_t)e->n_cus * 8)));
   sh_vec *in = x, *out = scratch;
   const sh_vec *y = y0;
   int32_t it = 0;
@@ -1981,7 +2165,7 @@ int sh_iterate_frontier(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_fronti
         int rc = dispatch(e, sr, A, in, y, alpha, beta, out, st);
         if (rc)
           return rc;
-        hipLaunchKernelGGL(frontier_detect, dgrid, dim3(FR_BS), 0, e->stream, f->d_ctl, k, p ^ 1, (const uint32_t *)in->d,
+        hipLaunchKernelGGL(frontier_detect, dgrid, dim3(WL_BS), 0, e->stream, f->d_ctl, k, p ^ 1, (const uint32_t *)in->d,
                            (const uint32_t *)out->d, (int32_t)A->rows, f->d_col_ptr, f->d_clist, f->d_cplist);
         HIP_TRY(e, hipGetLastError());
         sh_vec *t = in; in = out; out = t;
@@ -2029,167 +2213,49 @@ int sh_iterate_frontier(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_fronti
 } // extern "C"
 
 // ---- direction-optimising BFS with levels and parents (bfs.hip.h) -----------------------------------------------------
-struct sh_bfs_graph {
-  int64_t rows = 0, nnz = 0, edges = 0;
+struct sh_bfs_graph : GraphHandle<BfsCtl> {   // d_ctl: BFS_CTL_BYTES, followed by the WlParts
   int32_t words = 0;               // 32-bit words of one frontier bitmap
-  int32_t *d_in_ptr = nullptr, *d_in_col = nullptr, *d_out_ptr = nullptr, *d_out_row = nullptr;
   uint32_t *d_queue[2] = {nullptr, nullptr}, *d_bm[2] = {nullptr, nullptr};
-  FrPiece *d_opieces[2] = {nullptr, nullptr};   // pieces of the long out-lists of the frontier in queue 0 / 1
-  FrPiece *d_rpieces = nullptr;                 // pieces of the rows above BFS_ROW_PIECE (static)
-  int32_t n_rpieces = 0;
-  BfsCtl *d_ctl = nullptr;         // BFS_CTL_BYTES, followed by the BfsParts
-  BfsPart *d_part = nullptr;
-  BfsCtl *h_ctl = nullptr;         // pinned: the control block as read back once per batch
-  hipEvent_t ev[BFS_BATCH + 1] = {};
-  size_t bytes = 0;
+  WlPiece *d_opieces[2] = {nullptr, nullptr};   // pieces of the long out-lists of the frontier in queue 0 / 1
 };
 // sh_bfs_levels' up_share / down_share < 0: see DESIGN.md "6e Direction-optimising BFS" (the sweep of tools/bfs_levels_bench.py)
 static constexpr double BFS_UP_SHARE = 0.005, BFS_DOWN_SHARE = 0.01;
 static_assert(sizeof(BfsCtl) <= BFS_CTL_BYTES, "the control block is accounted as BFS_CTL_BYTES (sh_bfs_graph_footprint)");
-static_assert(sizeof(BfsPart) * BFS_MAX_BLOCKS == BFS_PART_BYTES, "one BfsPart per workgroup");
+static_assert(sizeof(WlPart) * BFS_MAX_BLOCKS == BFS_PART_BYTES, "one WlPart per workgroup");
 
 extern "C" {
 
 int sh_bfs_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                         const void *val, sh_bfs_graph **out) {
-  // what the scalars and the host arrays alone decide comes first: no device is needed to be told
   if (out) *out = nullptr;
-  if (rows < 0 || rows > 0x7FFFFF00ll)
-    return fail(e, SH_EINVAL, "sh_bfs_graph_create: rows = %lld, must be in [0, 2^31 - 256]", (long long)rows);
-  if (nnz < 0 || nnz > 0x7FFFFF00ll)
-    return fail(e, SH_EINVAL, "sh_bfs_graph_create: nnz = %lld, must be in [0, 2^31 - 256]", (long long)nnz);
-  if (!row_ptr || !out || (nnz > 0 && (!col_idx || !val)))
-    return fail(e, SH_EINVAL, "sh_bfs_graph_create: NULL argument (row_ptr, out, or col_idx / val of a matrix with entries)");
-  if (row_ptr[0] != 0 || (int64_t)row_ptr[rows] != nnz)
-    return fail(e, SH_ESHAPE, "sh_bfs_graph_create: row_ptr[0] = %d and row_ptr[rows] = %d, must be 0 and nnz = %lld",
-                (int)row_ptr[0], (int)row_ptr[rows], (long long)nnz);
-  for (int64_t r = 0; r < rows; r++)   // (the build indexes by row_ptr on the device: it must stay inside the arrays)
-    if (row_ptr[r] > row_ptr[r + 1])
-      return fail(e, SH_ESHAPE, "sh_bfs_graph_create: row_ptr decreases at row %lld", (long long)r);
-  if (!e)
-    return fail(e, SH_EINVAL, "sh_bfs_graph_create: NULL argument (engine)");
+  int rc = check_host_csr(e, "sh_bfs_graph_create", rows, nnz, row_ptr, col_idx, val, out);
+  if (rc)
+    return rc;
   HIP_TRY(e, hipSetDevice(e->device));
-  sh_bfs_graph *g = new (std::nothrow) sh_bfs_graph();
+  std::unique_ptr<sh_bfs_graph> g(new (std::nothrow) sh_bfs_graph());
   if (!g)
     return fail(e, SH_ENOMEM, "out of host memory");
-  g->rows = rows; g->nnz = nnz;
   g->words = (int32_t)((rows + 31) / 32);
-  // temporaries of the build: the CSR arrays as given, the edge flags and their scan, the scatter's cursors
-  int32_t *t_rp = nullptr, *t_ci = nullptr;
-  uint32_t *t_val = nullptr, *t_flag = nullptr, *t_pos = nullptr, *t_cnt = nullptr;
-  auto cleanup = [&](int rc) {
-    for (void *p : {(void *)t_rp, (void *)t_ci, (void *)t_val, (void *)t_flag, (void *)t_pos, (void *)t_cnt})
-      if (p) (void)hipFree(p);
-    t_rp = t_ci = nullptr; t_val = t_flag = t_pos = t_cnt = nullptr;
-    if (rc) sh_bfs_graph_free(e, g);
+  if ((rc = build_edge_lists<BfsKeep, BFS_ROW_PIECE>(e, g.get(), rows, nnz, row_ptr, col_idx, val, false)))
     return rc;
-  };
-#define HIP_TRY_G(call)                                                         \
-  do {                                                                          \
-    hipError_t _r = (call);                                                     \
-    if (_r != hipSuccess)                                                       \
-      return cleanup(fail(e, _r == hipErrorOutOfMemory ? SH_ENOMEM : SH_EHIP,   \
-                          "%s failed: %s", #call, hipGetErrorString(_r)));      \
-  } while (0)
-  // (an array of `nbytes` counts as that in the footprint; an empty one still gets a few bytes to point at)
-#define G_ARRAY(ptr, nbytes)                                                                   \
-  do {                                                                                         \
-    HIP_TRY_G(hipMalloc((void **)&(ptr), std::max<size_t>((size_t)(nbytes), 16)));             \
-    g->bytes += (size_t)(nbytes);                                                              \
-  } while (0)
-  HIP_TRY_G(hipMalloc((void **)&t_rp, (size_t)(rows + 1) * 4));
-  HIP_TRY_G(hipMalloc((void **)&t_ci, std::max<size_t>((size_t)nnz * 4, 16)));
-  HIP_TRY_G(hipMalloc((void **)&t_val, std::max<size_t>((size_t)nnz * 4, 16)));
-  HIP_TRY_G(hipMalloc((void **)&t_flag, (size_t)(nnz + 1) * 4));
-  HIP_TRY_G(hipMalloc((void **)&t_pos, (size_t)(nnz + 1) * 4));
-  HIP_TRY_G(hipMalloc((void **)&t_cnt, (size_t)(rows + 1) * 4));
-  HIP_TRY_G(hipMemcpyAsync(t_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
-  if (nnz > 0) {
-    HIP_TRY_G(hipMemcpyAsync(t_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY_G(hipMemcpyAsync(t_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
-  }
-  // the entries that are edges: flag, exclusive scan, compaction (the stored order of the survivors is kept)
-  const dim3 blk(BFS_BS), ngrid((unsigned)((nnz + 1 + BFS_BS - 1) / BFS_BS)), rgrid((unsigned)((rows + 1 + BFS_BS - 1) / BFS_BS));
-  hipLaunchKernelGGL(bfs_edge_flag, ngrid, blk, 0, e->stream, t_ci, t_val, nnz, (int32_t)rows, t_flag);
-  HIP_TRY_G(hipGetLastError());
-  HIP_TRY_G(device_exclusive_sum_u32(e->stream, t_flag, t_pos, nnz + 1));
-  uint32_t n_edges = 0;
-  HIP_TRY_G(hipMemcpy(&n_edges, t_pos + nnz, 4, hipMemcpyDeviceToHost));
-  const int64_t E = (int64_t)n_edges;
-  g->edges = E;
-  G_ARRAY(g->d_in_ptr, (rows + 1) * 4);
-  G_ARRAY(g->d_in_col, E * 4);
-  G_ARRAY(g->d_out_ptr, (rows + 1) * 4);
-  G_ARRAY(g->d_out_row, E * 4);
   for (int i = 0; i < 2; i++) {
-    G_ARRAY(g->d_queue[i], rows * 4);
-    G_ARRAY(g->d_bm[i], (int64_t)g->words * 4);
-    G_ARRAY(g->d_opieces[i], (E / 1024 + 1) * sizeof(FrPiece));   // sum of ceil(len / 2048) over out-lists longer than 2048 <= E / 1024
+    HIP_TRY(e, g->dev.alloc(&g->d_queue[i], rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->d_bm[i], (int64_t)g->words * 4));
+    HIP_TRY(e, g->dev.alloc(&g->d_opieces[i], (g->edges / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: out-lists longer than 2048
   }
-  G_ARRAY(g->d_rpieces, (E / 2048 + 1) * sizeof(FrPiece));        // the same for rows longer than 4096
-  G_ARRAY(g->d_ctl, BFS_CTL_BYTES + BFS_PART_BYTES);
-  g->d_part = (BfsPart *)((char *)g->d_ctl + BFS_CTL_BYTES);
-  HIP_TRY_G(hipHostMalloc((void **)&g->h_ctl, sizeof(BfsCtl), hipHostMallocDefault));
-  for (auto &ev : g->ev) HIP_TRY_G(hipEventCreate(&ev));
-  HIP_TRY_G(hipMemsetAsync(g->d_ctl, 0, BFS_CTL_BYTES + BFS_PART_BYTES, e->stream));
-  if (nnz > 0) {
-    hipLaunchKernelGGL(bfs_edge_compact, ngrid, blk, 0, e->stream, t_ci, t_flag, t_pos, nnz, g->d_in_col);
-    HIP_TRY_G(hipGetLastError());
-  }
-  hipLaunchKernelGGL(bfs_row_starts, rgrid, blk, 0, e->stream, t_rp, t_pos, rows, g->d_in_ptr);
-  HIP_TRY_G(hipGetLastError());
-  // the static pieces of long rows (the cursor borrows the control block's first word, cleared again below)
-  if (rows > 0) {
-    hipLaunchKernelGGL(bfs_row_pieces, rgrid, blk, 0, e->stream, g->d_in_ptr, rows, (uint32_t *)g->d_ctl, g->d_rpieces);
-    HIP_TRY_G(hipGetLastError());
-  }
-  uint32_t n_rp = 0;
-  HIP_TRY_G(hipMemcpyAsync(&n_rp, g->d_ctl, 4, hipMemcpyDeviceToHost, e->stream));
-  // the pattern of the transpose: column histogram, exclusive scan, scatter through per-column cursors
-  HIP_TRY_G(hipMemsetAsync(t_cnt, 0, (size_t)(rows + 1) * 4, e->stream));
-  const dim3 egrid((unsigned)std::max<int64_t>(1, (E + FR_BS - 1) / FR_BS));
-  if (E > 0) {
-    hipLaunchKernelGGL(frontier_col_hist, egrid, dim3(FR_BS), 0, e->stream, g->d_in_col, E, (int32_t)rows, t_cnt);
-    HIP_TRY_G(hipGetLastError());
-  }
-  HIP_TRY_G(device_exclusive_sum_u32(e->stream, t_cnt, (uint32_t *)g->d_out_ptr, rows + 1));
-  HIP_TRY_G(hipMemcpyAsync(t_cnt, g->d_out_ptr, (size_t)(rows + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
-  if (E > 0) {
-    hipLaunchKernelGGL(frontier_scatter, egrid, dim3(FR_BS), 0, e->stream, g->d_in_ptr, g->d_in_col, E, (int32_t)rows, (int32_t)rows,
-                       t_cnt, g->d_out_row);
-    HIP_TRY_G(hipGetLastError());
-  }
-  HIP_TRY_G(hipMemsetAsync(g->d_ctl, 0, BFS_CTL_BYTES, e->stream));
-  HIP_TRY_G(hipStreamSynchronize(e->stream));   // the host arrays and the temporaries are done with
-  g->n_rpieces = (int32_t)n_rp;
-#undef G_ARRAY
-#undef HIP_TRY_G
-  *out = g;
-  return cleanup(SH_OK);
-}
-
-int sh_bfs_graph_free(sh_engine *e, sh_bfs_graph *g) {
-  if (!g)
-    return SH_OK;
-  if (e) {
-    (void)hipSetDevice(e->device);
-    (void)hipStreamSynchronize(e->stream);
-  }
-  for (void *p : {(void *)g->d_in_ptr, (void *)g->d_in_col, (void *)g->d_out_ptr, (void *)g->d_out_row, (void *)g->d_queue[0],
-                  (void *)g->d_queue[1], (void *)g->d_bm[0], (void *)g->d_bm[1], (void *)g->d_opieces[0], (void *)g->d_opieces[1],
-                  (void *)g->d_rpieces, (void *)g->d_ctl})
-    if (p) (void)hipFree(p);
-  if (g->h_ctl) (void)hipHostFree(g->h_ctl);
-  for (auto ev : g->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete g;
+  if ((rc = open_control(e, g.get(), BFS_CTL_BYTES, BFS_CTL_BYTES + BFS_PART_BYTES)))
+    return rc;
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  *out = g.release();
   return SH_OK;
 }
+
+int sh_bfs_graph_free(sh_engine *e, sh_bfs_graph *g) { return free_handle(e, g); }
 
 int sh_bfs_graph_footprint(const sh_bfs_graph *g, uint64_t *device_bytes) {
   if (!g || !device_bytes)
     return SH_EINVAL;
-  *device_bytes = (uint64_t)g->bytes;
+  *device_bytes = (uint64_t)g->dev.bytes;
   return SH_OK;
 }
 
@@ -2226,14 +2292,8 @@ int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level
   HIP_TRY(e, hipSetDevice(e->device));
   const double up_edges = up_share * (double)g->edges, down_rows = down_share * (double)rows;
   const int nblocks = std::max(1, std::min(e->n_cus * 4, BFS_MAX_BLOCKS));
-  const dim3 grid((unsigned)nblocks), block(BFS_BS);
-  const dim3 dgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)g->words + BFS_BS - 1) / BFS_BS, 256)));
-  auto ms_between = [&](hipEvent_t a, hipEvent_t b, uint64_t *ns) {
-    float ms = 0.f;
-    hipError_t r = hipEventElapsedTime(&ms, a, b);
-    *ns = (uint64_t)((double)ms * 1e6);
-    return r;
-  };
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
+  const dim3 dgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)g->words + WL_BS - 1) / WL_BS, 256)));
   uint64_t total = 0, ns = 0;
   // level from x0, the sources as queue 0 and bitmap 0, the direction of step 0
   HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
@@ -2246,57 +2306,39 @@ int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level
                      down_rows);
   HIP_TRY(e, hipGetLastError());
   HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
-  int32_t it = 0, batch = 8;
+  int32_t it = 0;
   bool done = false;
-  int64_t n_reached = -1;
-  while (!done && it < max_levels) {
-    const int nb = std::min<int32_t>(batch, max_levels - it);
-    HIP_TRY(e, hipMemsetAsync((char *)g->d_ctl + offsetof(BfsCtl, rec), 0, sizeof(BfsRec) * BFS_BATCH, e->stream));
-    HIP_TRY(e, hipEventRecord(g->ev[0], e->stream));
-    for (int k = 0; k < nb; k++) {
-      // the three launches of a step: each returns at once unless the control block says the step runs in its direction
-      const int L = it + k, p = L & 1;
-      hipLaunchKernelGGL(bfs_queue_from_bitmap, grid, block, 0, e->stream, g->d_ctl, L, g->words, g->d_bm[p], g->d_out_ptr, g->d_queue[p],
-                         g->d_opieces[p]);
-      HIP_TRY(e, hipGetLastError());
-      hipLaunchKernelGGL(bfs_topdown, grid, block, 0, e->stream, g->d_ctl, L, (int32_t *)level->d, g->d_out_ptr, g->d_out_row, g->d_queue[p],
-                         g->d_opieces[p], g->d_queue[p ^ 1], g->d_opieces[p ^ 1], g->d_bm[p ^ 1], g->d_part);
-      HIP_TRY(e, hipGetLastError());
-      hipLaunchKernelGGL(bfs_bottomup, grid, block, 0, e->stream, g->d_ctl, L, (int32_t)rows, (int32_t *)level->d, g->d_in_ptr, g->d_in_col,
-                         g->d_bm[p], g->d_bm[p ^ 1], g->d_rpieces, g->n_rpieces, g->d_part);
-      HIP_TRY(e, hipGetLastError());
-      hipLaunchKernelGGL(bfs_decide, dgrid, block, 0, e->stream, g->d_ctl, k, L, nblocks, g->d_part, g->d_bm[p], g->words, up_edges,
-                         down_rows);
-      HIP_TRY(e, hipGetLastError());
-      HIP_TRY(e, hipEventRecord(g->ev[k + 1], e->stream));
-    }
-    HIP_TRY(e, hipMemcpyAsync(g->h_ctl, g->d_ctl, sizeof(BfsCtl), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    if (n_reached < 0) {   // (first batch: what bfs_init found)
-      n_reached = (int64_t)g->h_ctl->nsrc;
-      if (size_per_level) size_per_level[0] = n_reached;
-      HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
-      total += ns;
-    }
-    int ran = 0;
-    while (ran < nb && g->h_ctl->rec[ran].ran) ran++;
-    for (int k = 0; k < ran; k++) {
-      const BfsRec &rc = g->h_ctl->rec[k];
-      HIP_TRY(e, ms_between(g->ev[k], g->ev[k + 1], &ns));
-      total += ns;
-      if (ns_per_level) ns_per_level[it + k] = ns;
-      if (mode_per_level) mode_per_level[it + k] = rc.mode;
-      if (size_per_level) size_per_level[it + k + 1] = (int64_t)rc.found;
-      if (edges_per_level) edges_per_level[it + k] = (int64_t)rc.edges;
-      n_reached += (int64_t)rc.found;
-      if (rc.found > 0) *depth = it + k + 1;
-    }
-    it += ran;
-    done = g->h_ctl->finished != 0;
-    if (!done && ran < nb)
-      return fail(e, SH_EHIP, "sh_bfs_levels: step %d of the search did not report", (int)it);
-    batch = std::min(batch * 2, BFS_BATCH);
-  }
+  int64_t n_found = 0;
+  // the three launches of a step: each returns at once unless the control block says the step runs in its direction
+  const auto enqueue = [&](int L, int k) {
+    const int p = L & 1;
+    hipLaunchKernelGGL(bfs_queue_from_bitmap, grid, block, 0, e->stream, g->d_ctl, L, g->words, g->d_bm[p], g->d_out_ptr, g->d_queue[p],
+                       g->d_opieces[p]);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(bfs_topdown, grid, block, 0, e->stream, g->d_ctl, L, (int32_t *)level->d, g->d_out_ptr, g->d_out_row, g->d_queue[p],
+                       g->d_opieces[p], g->d_queue[p ^ 1], g->d_opieces[p ^ 1], g->d_bm[p ^ 1], g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(bfs_bottomup, grid, block, 0, e->stream, g->d_ctl, L, (int32_t)rows, (int32_t *)level->d, g->d_in_ptr, g->d_in_col,
+                       g->d_bm[p], g->d_bm[p ^ 1], g->d_rpieces, g->n_rpieces, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(bfs_decide, dgrid, block, 0, e->stream, g->d_ctl, k, L, nblocks, g->d_part, g->d_bm[p], g->words, up_edges,
+                       down_rows);
+    HIP_TRY(e, hipGetLastError());
+    return (int)SH_OK;
+  };
+  const auto take = [&](int L, const BfsRec &rc, uint64_t step_ns) {
+    if (ns_per_level) ns_per_level[L] = step_ns;
+    if (mode_per_level) mode_per_level[L] = rc.mode;
+    if (size_per_level) size_per_level[L + 1] = (int64_t)rc.found;
+    if (edges_per_level) edges_per_level[L] = (int64_t)rc.edges;
+    n_found += (int64_t)rc.found;
+    if (rc.found > 0) *depth = L + 1;
+  };
+  const int rc = run_batches(e, "sh_bfs_levels: step", g, max_levels, &it, &done, &total, enqueue, take);
+  if (rc)
+    return rc;
+  // (what bfs_init found: h_ctl is fresh because max_levels >= 1 makes run_batches read at least one batch back)
+  if (size_per_level) size_per_level[0] = (int64_t)g->h_ctl->nsrc;
   if (parent) {
     HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
     HIP_TRY(e, hipMemsetAsync(parent->d, 0xFF, (size_t)rows * 4, e->stream));
@@ -2308,7 +2350,7 @@ int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level
     HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
     total += ns;
   }
-  *reached = n_reached;
+  *reached = (int64_t)g->h_ctl->nsrc + n_found;
   *complete = done ? 1 : 0;
   if (total_ns)
     *total_ns = total;
@@ -2318,153 +2360,53 @@ int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level
 } // extern "C"
 
 // ---- bucketed SSSP with distances and canonical predecessors (sssp.hip.h) --------------------------------------------
-struct sh_sssp_graph {
-  int64_t rows = 0, nnz = 0, edges = 0;
+struct sh_sssp_graph : GraphHandle<SsspCtl> {   // d_ctl: SSSP_CTL_BYTES, followed by the WlParts and the split's minima
   double delta = 0.0;              // the default bucket width (0: no edges)
-  int32_t *d_in_ptr = nullptr, *d_in_col = nullptr, *d_out_ptr = nullptr, *d_out_row = nullptr;
-  uint32_t *d_in_w = nullptr, *d_out_w = nullptr;
   uint32_t *d_stamp = nullptr, *d_near[2] = {nullptr, nullptr}, *d_far[2] = {nullptr, nullptr};
-  FrPiece *d_opieces[2] = {nullptr, nullptr};   // pieces of the long out-lists of near list 0 / 1
-  FrPiece *d_rpieces = nullptr;                 // pieces of the rows above SSSP_ROW_PIECE (static)
-  int32_t n_rpieces = 0;
-  SsspCtl *d_ctl = nullptr;        // SSSP_CTL_BYTES, followed by the BfsParts and the split's minima
-  BfsPart *d_part = nullptr;
+  WlPiece *d_opieces[2] = {nullptr, nullptr};   // pieces of the long out-lists of near list 0 / 1
   uint32_t *d_pmin = nullptr;
-  SsspCtl *h_ctl = nullptr;        // pinned: the control block as read back once per batch
-  hipEvent_t ev[SSSP_BATCH + 1] = {};
-  size_t bytes = 0;
 };
 // The default bucket width is SSSP_DELTA_FACTOR * (mean weight) / (mean out-degree): Davidson et al.'s starting point.
 // tools/sssp_bench.py sweeps the factor; no sweep is on record yet (DESIGN.md "6f Bucketed SSSP").
 static constexpr double SSSP_DELTA_FACTOR = 32.0;
 static_assert(sizeof(SsspCtl) <= SSSP_CTL_BYTES, "the control block is accounted as SSSP_CTL_BYTES (sh_sssp_graph_footprint)");
-static_assert(sizeof(BfsPart) * SSSP_MAX_BLOCKS == SSSP_PART_BYTES, "one BfsPart per workgroup");
+static_assert(sizeof(WlPart) * SSSP_MAX_BLOCKS == SSSP_PART_BYTES, "one WlPart per workgroup");
 
 extern "C" {
 
 int sh_sssp_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                          const void *val, sh_sssp_graph **out) {
-  // what the scalars and the host arrays alone decide comes first: no device is needed to be told
   if (out) *out = nullptr;
-  if (rows < 0 || rows > 0x7FFFFF00ll)
-    return fail(e, SH_EINVAL, "sh_sssp_graph_create: rows = %lld, must be in [0, 2^31 - 256]", (long long)rows);
-  if (nnz < 0 || nnz > 0x7FFFFF00ll)
-    return fail(e, SH_EINVAL, "sh_sssp_graph_create: nnz = %lld, must be in [0, 2^31 - 256]", (long long)nnz);
-  if (!row_ptr || !out || (nnz > 0 && (!col_idx || !val)))
-    return fail(e, SH_EINVAL, "sh_sssp_graph_create: NULL argument (row_ptr, out, or col_idx / val of a matrix with entries)");
-  if (row_ptr[0] != 0 || (int64_t)row_ptr[rows] != nnz)
-    return fail(e, SH_ESHAPE, "sh_sssp_graph_create: row_ptr[0] = %d and row_ptr[rows] = %d, must be 0 and nnz = %lld",
-                (int)row_ptr[0], (int)row_ptr[rows], (long long)nnz);
-  for (int64_t r = 0; r < rows; r++)   // (the build indexes by row_ptr on the device: it must stay inside the arrays)
-    if (row_ptr[r] > row_ptr[r + 1])
-      return fail(e, SH_ESHAPE, "sh_sssp_graph_create: row_ptr decreases at row %lld", (long long)r);
-  if (!e)
-    return fail(e, SH_EINVAL, "sh_sssp_graph_create: NULL argument (engine)");
+  int rc = check_host_csr(e, "sh_sssp_graph_create", rows, nnz, row_ptr, col_idx, val, out);
+  if (rc)
+    return rc;
   HIP_TRY(e, hipSetDevice(e->device));
-  sh_sssp_graph *g = new (std::nothrow) sh_sssp_graph();
+  std::unique_ptr<sh_sssp_graph> g(new (std::nothrow) sh_sssp_graph());
   if (!g)
     return fail(e, SH_ENOMEM, "out of host memory");
-  g->rows = rows; g->nnz = nnz;
-  // temporaries of the build: the CSR arrays as given, the edge flags and their scan, the scatter's cursors, the weight sums
-  int32_t *t_rp = nullptr, *t_ci = nullptr;
-  uint32_t *t_val = nullptr, *t_flag = nullptr, *t_pos = nullptr, *t_cnt = nullptr;
-  double *t_sum = nullptr;
-  auto cleanup = [&](int rc) {
-    for (void *p : {(void *)t_rp, (void *)t_ci, (void *)t_val, (void *)t_flag, (void *)t_pos, (void *)t_cnt, (void *)t_sum})
-      if (p) (void)hipFree(p);
-    t_rp = t_ci = nullptr; t_val = t_flag = t_pos = t_cnt = nullptr; t_sum = nullptr;
-    if (rc) sh_sssp_graph_free(e, g);
+  if ((rc = build_edge_lists<SsspKeep, SSSP_ROW_PIECE>(e, g.get(), rows, nnz, row_ptr, col_idx, val, true)))
     return rc;
-  };
-#define HIP_TRY_G(call)                                                         \
-  do {                                                                          \
-    hipError_t _r = (call);                                                     \
-    if (_r != hipSuccess)                                                       \
-      return cleanup(fail(e, _r == hipErrorOutOfMemory ? SH_ENOMEM : SH_EHIP,   \
-                          "%s failed: %s", #call, hipGetErrorString(_r)));      \
-  } while (0)
-  // (an array of `nbytes` counts as that in the footprint; an empty one still gets a few bytes to point at)
-#define G_ARRAY(ptr, nbytes)                                                                   \
-  do {                                                                                         \
-    HIP_TRY_G(hipMalloc((void **)&(ptr), std::max<size_t>((size_t)(nbytes), 16)));             \
-    g->bytes += (size_t)(nbytes);                                                              \
-  } while (0)
-  constexpr int SUM_BLOCKS = 256;
-  HIP_TRY_G(hipMalloc((void **)&t_rp, (size_t)(rows + 1) * 4));
-  HIP_TRY_G(hipMalloc((void **)&t_ci, std::max<size_t>((size_t)nnz * 4, 16)));
-  HIP_TRY_G(hipMalloc((void **)&t_val, std::max<size_t>((size_t)nnz * 4, 16)));
-  HIP_TRY_G(hipMalloc((void **)&t_flag, (size_t)(nnz + 1) * 4));
-  HIP_TRY_G(hipMalloc((void **)&t_pos, (size_t)(nnz + 1) * 4));
-  HIP_TRY_G(hipMalloc((void **)&t_cnt, (size_t)(rows + 1) * 4));
-  HIP_TRY_G(hipMalloc((void **)&t_sum, SUM_BLOCKS * sizeof(double)));
-  HIP_TRY_G(hipMemcpyAsync(t_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
-  if (nnz > 0) {
-    HIP_TRY_G(hipMemcpyAsync(t_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY_G(hipMemcpyAsync(t_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
-  }
-  // the entries that are edges: flag, exclusive scan, compaction (the stored order of the survivors is kept)
-  const dim3 blk(SSSP_BS), ngrid((unsigned)((nnz + 1 + SSSP_BS - 1) / SSSP_BS)), rgrid((unsigned)((rows + 1 + SSSP_BS - 1) / SSSP_BS));
-  hipLaunchKernelGGL(sssp_edge_flag, ngrid, blk, 0, e->stream, t_ci, t_val, nnz, (int32_t)rows, t_flag);
-  HIP_TRY_G(hipGetLastError());
-  HIP_TRY_G(device_exclusive_sum_u32(e->stream, t_flag, t_pos, nnz + 1));
-  uint32_t n_edges = 0;
-  HIP_TRY_G(hipMemcpy(&n_edges, t_pos + nnz, 4, hipMemcpyDeviceToHost));
-  const int64_t E = (int64_t)n_edges;
-  g->edges = E;
-  G_ARRAY(g->d_in_ptr, (rows + 1) * 4);
-  G_ARRAY(g->d_in_col, E * 4);
-  G_ARRAY(g->d_in_w, E * 4);
-  G_ARRAY(g->d_out_ptr, (rows + 1) * 4);
-  G_ARRAY(g->d_out_row, E * 4);
-  G_ARRAY(g->d_out_w, E * 4);
-  G_ARRAY(g->d_stamp, rows * 4);
+  const int64_t E = g->edges;
+  HIP_TRY(e, g->dev.alloc(&g->d_stamp, rows * 4));
   for (int i = 0; i < 2; i++) {
-    G_ARRAY(g->d_near[i], rows * 4);
-    G_ARRAY(g->d_far[i], rows * 4);
-    G_ARRAY(g->d_opieces[i], (E / 1024 + 1) * sizeof(FrPiece));   // sum of ceil(len / 2048) over out-lists longer than 2048 <= E / 1024
+    HIP_TRY(e, g->dev.alloc(&g->d_near[i], rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->d_far[i], rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->d_opieces[i], (E / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: out-lists longer than 2048
   }
-  G_ARRAY(g->d_rpieces, (E / 2048 + 1) * sizeof(FrPiece));        // the same for rows longer than 4096
-  G_ARRAY(g->d_ctl, SSSP_CTL_BYTES + SSSP_PART_BYTES + SSSP_PMIN_BYTES);
-  g->d_part = (BfsPart *)((char *)g->d_ctl + SSSP_CTL_BYTES);
+  if ((rc = open_control(e, g.get(), SSSP_CTL_BYTES, SSSP_CTL_BYTES + SSSP_PART_BYTES + SSSP_PMIN_BYTES)))
+    return rc;
   g->d_pmin = (uint32_t *)((char *)g->d_ctl + SSSP_CTL_BYTES + SSSP_PART_BYTES);
-  HIP_TRY_G(hipHostMalloc((void **)&g->h_ctl, sizeof(SsspCtl), hipHostMallocDefault));
-  for (auto &ev : g->ev) HIP_TRY_G(hipEventCreate(&ev));
-  HIP_TRY_G(hipMemsetAsync(g->d_ctl, 0, SSSP_CTL_BYTES + SSSP_PART_BYTES + SSSP_PMIN_BYTES, e->stream));
-  if (nnz > 0) {
-    hipLaunchKernelGGL(sssp_edge_compact, ngrid, blk, 0, e->stream, t_ci, t_val, t_flag, t_pos, nnz, g->d_in_col, g->d_in_w);
-    HIP_TRY_G(hipGetLastError());
-  }
-  hipLaunchKernelGGL(bfs_row_starts, rgrid, blk, 0, e->stream, t_rp, t_pos, rows, g->d_in_ptr);
-  HIP_TRY_G(hipGetLastError());
-  // the static pieces of long rows (the cursor borrows the control block's first word, cleared again below)
-  if (rows > 0) {
-    hipLaunchKernelGGL(bfs_row_pieces, rgrid, blk, 0, e->stream, g->d_in_ptr, rows, (uint32_t *)g->d_ctl, g->d_rpieces);
-    HIP_TRY_G(hipGetLastError());
-  }
-  uint32_t n_rp = 0;
-  HIP_TRY_G(hipMemcpyAsync(&n_rp, g->d_ctl, 4, hipMemcpyDeviceToHost, e->stream));
-  // the transpose with its weights: column histogram, exclusive scan, scatter through per-column cursors
-  HIP_TRY_G(hipMemsetAsync(t_cnt, 0, (size_t)(rows + 1) * 4, e->stream));
-  const dim3 egrid((unsigned)std::max<int64_t>(1, (E + FR_BS - 1) / FR_BS));
+  // the mean weight, for the default bucket width
+  constexpr int SUM_BLOCKS = 256;
+  DevArrays tmp;
+  double *t_sum = nullptr, h_sum[SUM_BLOCKS] = {};
+  HIP_TRY(e, tmp.alloc(&t_sum, SUM_BLOCKS * sizeof(double)));
   if (E > 0) {
-    hipLaunchKernelGGL(frontier_col_hist, egrid, dim3(FR_BS), 0, e->stream, g->d_in_col, E, (int32_t)rows, t_cnt);
-    HIP_TRY_G(hipGetLastError());
+    hipLaunchKernelGGL(sssp_weight_sum, dim3(SUM_BLOCKS), dim3(WL_BS), 0, e->stream, g->d_in_w, E, t_sum);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipMemcpyAsync(h_sum, t_sum, sizeof(h_sum), hipMemcpyDeviceToHost, e->stream));
   }
-  HIP_TRY_G(device_exclusive_sum_u32(e->stream, t_cnt, (uint32_t *)g->d_out_ptr, rows + 1));
-  HIP_TRY_G(hipMemcpyAsync(t_cnt, g->d_out_ptr, (size_t)(rows + 1) * 4, hipMemcpyDeviceToDevice, e->stream));
-  double h_sum[SUM_BLOCKS] = {};
-  if (E > 0) {
-    hipLaunchKernelGGL(sssp_scatter, egrid, dim3(SSSP_BS), 0, e->stream, g->d_in_ptr, g->d_in_col, g->d_in_w, E, (int32_t)rows, t_cnt,
-                       g->d_out_row, g->d_out_w);
-    HIP_TRY_G(hipGetLastError());
-    // the mean weight, for the default bucket width
-    hipLaunchKernelGGL(sssp_weight_sum, dim3(SUM_BLOCKS), dim3(SSSP_BS), 0, e->stream, g->d_in_w, E, t_sum);
-    HIP_TRY_G(hipGetLastError());
-    HIP_TRY_G(hipMemcpyAsync(h_sum, t_sum, sizeof(h_sum), hipMemcpyDeviceToHost, e->stream));
-  }
-  HIP_TRY_G(hipMemsetAsync(g->d_ctl, 0, SSSP_CTL_BYTES, e->stream));
-  HIP_TRY_G(hipStreamSynchronize(e->stream));   // the host arrays and the temporaries are done with
-  g->n_rpieces = (int32_t)n_rp;
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
   if (E > 0) {
     double sum = 0.0;
     for (double v : h_sum) sum += v;
@@ -2472,34 +2414,16 @@ int sh_sssp_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t 
     const double d = SSSP_DELTA_FACTOR * (sum / (double)E) * ((double)rows / (double)E);
     g->delta = (d > 0.0 && d < 1e300) ? d : 1.0;
   }
-#undef G_ARRAY
-#undef HIP_TRY_G
-  *out = g;
-  return cleanup(SH_OK);
-}
-
-int sh_sssp_graph_free(sh_engine *e, sh_sssp_graph *g) {
-  if (!g)
-    return SH_OK;
-  if (e) {
-    (void)hipSetDevice(e->device);
-    (void)hipStreamSynchronize(e->stream);
-  }
-  for (void *p : {(void *)g->d_in_ptr, (void *)g->d_in_col, (void *)g->d_in_w, (void *)g->d_out_ptr, (void *)g->d_out_row,
-                  (void *)g->d_out_w, (void *)g->d_stamp, (void *)g->d_near[0], (void *)g->d_near[1], (void *)g->d_far[0],
-                  (void *)g->d_far[1], (void *)g->d_opieces[0], (void *)g->d_opieces[1], (void *)g->d_rpieces, (void *)g->d_ctl})
-    if (p) (void)hipFree(p);
-  if (g->h_ctl) (void)hipHostFree(g->h_ctl);
-  for (auto ev : g->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete g;
+  *out = g.release();
   return SH_OK;
 }
+
+int sh_sssp_graph_free(sh_engine *e, sh_sssp_graph *g) { return free_handle(e, g); }
 
 int sh_sssp_graph_footprint(const sh_sssp_graph *g, uint64_t *device_bytes) {
   if (!g || !device_bytes)
     return SH_EINVAL;
-  *device_bytes = (uint64_t)g->bytes;
+  *device_bytes = (uint64_t)g->dev.bytes;
   return SH_OK;
 }
 
@@ -2541,13 +2465,7 @@ int sh_sssp(sh_engine *e, sh_sssp_graph *g, const sh_vec *x0, sh_vec *dist, sh_v
     return SH_OK;
   HIP_TRY(e, hipSetDevice(e->device));
   const int nblocks = std::max(1, std::min(e->n_cus * 4, SSSP_MAX_BLOCKS));
-  const dim3 grid((unsigned)nblocks), block(SSSP_BS);
-  auto ms_between = [&](hipEvent_t a, hipEvent_t b, uint64_t *ns) {
-    float ms = 0.f;
-    hipError_t r = hipEventElapsedTime(&ms, a, b);
-    *ns = (uint64_t)((double)ms * 1e6);
-    return r;
-  };
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
   uint32_t *d = (uint32_t *)dist->d;
   uint64_t total = 0, ns = 0;
   // dist and the stamps from x0, the sources as far list 0
@@ -2558,50 +2476,31 @@ int sh_sssp(sh_engine *e, sh_sssp_graph *g, const sh_vec *x0, sh_vec *dist, sh_v
   hipLaunchKernelGGL(sssp_decide, dim3(1), block, 0, e->stream, g->d_ctl, 0, -1, nblocks, g->d_part);
   HIP_TRY(e, hipGetLastError());
   HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
-  int32_t it = 0, batch = 8;
-  bool done = false, first = true;
-  while (!done && it < max_rounds) {
-    const int nb = std::min<int32_t>(batch, max_rounds - it);
-    HIP_TRY(e, hipMemsetAsync((char *)g->d_ctl + offsetof(SsspCtl, rec), 0, sizeof(SsspRec) * SSSP_BATCH, e->stream));
-    HIP_TRY(e, hipEventRecord(g->ev[0], e->stream));
-    for (int k = 0; k < nb; k++) {
-      // the four launches of a round: each returns at once unless the control block says the round runs (with a split)
-      const int R = it + k, p = R & 1;
-      for (int phase = 0; phase < 2; phase++) {
-        hipLaunchKernelGGL(sssp_split, grid, block, 0, e->stream, g->d_ctl, R, phase, nblocks, delta, g->d_pmin, d, g->d_stamp,
-                           g->d_out_ptr, g->d_far[0], g->d_far[1], g->d_near[p], g->d_opieces[p]);
-        HIP_TRY(e, hipGetLastError());
-      }
-      hipLaunchKernelGGL(sssp_relax, grid, block, 0, e->stream, g->d_ctl, R, d, g->d_stamp, g->d_out_ptr, g->d_out_row, g->d_out_w,
-                         g->d_near[p], g->d_opieces[p], g->d_near[p ^ 1], g->d_opieces[p ^ 1], g->d_far[0], g->d_far[1], g->d_part);
+  int32_t it = 0;
+  bool done = false;
+  // the four launches of a round: each returns at once unless the control block says the round runs (with a split)
+  const auto enqueue = [&](int R, int k) {
+    const int p = R & 1;
+    for (int phase = 0; phase < 2; phase++) {
+      hipLaunchKernelGGL(sssp_split, grid, block, 0, e->stream, g->d_ctl, R, phase, nblocks, delta, g->d_pmin, d, g->d_stamp,
+                         g->d_out_ptr, g->d_far[0], g->d_far[1], g->d_near[p], g->d_opieces[p]);
       HIP_TRY(e, hipGetLastError());
-      hipLaunchKernelGGL(sssp_decide, dim3(1), block, 0, e->stream, g->d_ctl, k, R, nblocks, g->d_part);
-      HIP_TRY(e, hipGetLastError());
-      HIP_TRY(e, hipEventRecord(g->ev[k + 1], e->stream));
     }
-    HIP_TRY(e, hipMemcpyAsync(g->h_ctl, g->d_ctl, sizeof(SsspCtl), hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    if (first) {
-      HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
-      total += ns;
-      first = false;
-    }
-    int ran = 0;
-    while (ran < nb && g->h_ctl->rec[ran].ran) ran++;
-    for (int k = 0; k < ran; k++) {
-      const SsspRec &rc = g->h_ctl->rec[k];
-      HIP_TRY(e, ms_between(g->ev[k], g->ev[k + 1], &ns));
-      total += ns;
-      if (ns_per_round) ns_per_round[it + k] = ns;
-      if (size_per_round) size_per_round[it + k] = (int64_t)rc.size;
-      if (edges_per_round) edges_per_round[it + k] = (int64_t)rc.edges;
-    }
-    it += ran;
-    done = g->h_ctl->finished != 0;
-    if (!done && ran < nb)
-      return fail(e, SH_EHIP, "sh_sssp: round %d of the search did not report", (int)it);
-    batch = std::min(batch * 2, SSSP_BATCH);
-  }
+    hipLaunchKernelGGL(sssp_relax, grid, block, 0, e->stream, g->d_ctl, R, d, g->d_stamp, g->d_out_ptr, g->d_out_row, g->d_out_w,
+                       g->d_near[p], g->d_opieces[p], g->d_near[p ^ 1], g->d_opieces[p ^ 1], g->d_far[0], g->d_far[1], g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(sssp_decide, dim3(1), block, 0, e->stream, g->d_ctl, k, R, nblocks, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    return (int)SH_OK;
+  };
+  const auto take = [&](int R, const SsspRec &rc, uint64_t round_ns) {
+    if (ns_per_round) ns_per_round[R] = round_ns;
+    if (size_per_round) size_per_round[R] = (int64_t)rc.size;
+    if (edges_per_round) edges_per_round[R] = (int64_t)rc.edges;
+  };
+  const int rc = run_batches(e, "sh_sssp: round", g, max_rounds, &it, &done, &total, enqueue, take);
+  if (rc)
+    return rc;
   if (pred && done) {
     HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
     HIP_TRY(e, hipMemsetAsync(pred->d, 0xFF, (size_t)rows * 4, e->stream));

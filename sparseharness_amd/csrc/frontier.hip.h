@@ -20,16 +20,14 @@
 // bits whatever kernel produced it.  That also makes integer atomics legal for rows cut over several waves: every
 // (min,+) partial is a non-negative float, whose order is that of its bit pattern as an unsigned word.
 //
-// Work distribution: every kernel runs a fixed grid whose waves stride over a device-side list length (the host does
-// not know it).  A wave takes 64 list entries at a time: rows / columns of up to FR_SHORT entries one lane each, longer
-// ones the whole wave one after the other, and those above FR_ROW_PIECE / FR_COL_PIECE entries are cut into pieces of
-// that size which go through a list of their own (built by whoever appended the row / column), one wave per piece.
+// Work distribution as worklist.hip.h describes it, with FR_SHORT and FR_COL_PIECE (mark) / FR_ROW_PIECE (pull).  The
+// transposed pattern is built once per handle by wl_col_hist / wl_transpose_scatter.
 #pragma once
 #include "kernels.hip.h"
+#include "worklist.hip.h"
 
 namespace sh {
 
-constexpr int FR_BS = 256;
 constexpr int FR_SHORT = 8;           // rows / columns up to this many entries: one lane each
 constexpr int FR_COL_PIECE = 2048;    // transposed columns above this are marked in pieces of this many entries
 constexpr int FR_ROW_PIECE = 4096;    // rows above the schedule's long-row threshold are pulled in pieces of this many entries
@@ -50,71 +48,20 @@ struct FrontierCtl {
   int32_t flag[FR_BATCH];         // SR::differs raised by launch k (what ends the loop)
   FrontierRec rec[FR_BATCH];
 };
-struct FrPiece { uint32_t id, off; };   // column (mark) or active-list slot (pull), first entry of the piece
+// (a WlPiece's id is a column for mark and an active-list slot for pull)
 
-#define FR_LANE ((int)(threadIdx.x & 63))
-#define FR_WAVE ((int64_t)blockIdx.x * (FR_BS / 64) + (threadIdx.x >> 6))
-#define FR_WAVES ((int64_t)gridDim.x * (FR_BS / 64))
-
-__device__ __forceinline__ uint32_t fr_add(uint32_t *p, uint32_t v) {
-  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// One atomic per wave for a list cursor: the first wanting lane adds the count, every wanting lane gets its place.
-// (Call from wave-uniform control flow only.)
-__device__ __forceinline__ uint32_t fr_wave_append(uint32_t *cursor, bool want, int lane) {
-  const uint64_t m = __ballot(want);
-  if (m == 0) return 0;
-  const int leader = __ffsll((unsigned long long)m) - 1;
-  uint32_t base = 0;
-  if (lane == leader) base = fr_add(cursor, (uint32_t)__popcll(m));
-  base = (uint32_t)__shfl((int)base, leader);
-  return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
-__device__ __forceinline__ uint32_t fr_wave_sum(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
 // a changed row joins the next changed list: its place, its transposed column's length, its pieces when the column is long
 __device__ __forceinline__ uint32_t fr_push_changed(FrontierCtl *ctl, int p, bool changed, int32_t r, int lane,
                                                     const int32_t *__restrict__ col_ptr, uint32_t *__restrict__ clist,
-                                                    FrPiece *__restrict__ cplist) {
-  const uint32_t at = fr_wave_append(&ctl->ccount[p], changed, lane);
+                                                    WlPiece *__restrict__ cplist) {
+  const uint32_t at = wl_wave_append(&ctl->ccount[p], changed, lane);
   uint32_t len = 0;
   if (changed) {
     clist[at] = (uint32_t)r;
     len = (uint32_t)(col_ptr[r + 1] - col_ptr[r]);
-    if (len > (uint32_t)FR_COL_PIECE) {
-      const uint32_t np = (len + FR_COL_PIECE - 1) / FR_COL_PIECE;
-      const uint32_t b = fr_add(&ctl->cpieces[p], np);
-      for (uint32_t j = 0; j < np; j++) cplist[b + j] = FrPiece{(uint32_t)r, j * FR_COL_PIECE};
-    }
+    wl_push_pieces<FR_COL_PIECE>(&ctl->cpieces[p], (uint32_t)r, len, cplist);
   }
   return len;
-}
-
-// ---- building the transposed pattern (once per handle): histogram, exclusive scan (rocPRIM, plan_gpu.hip), scatter
-__global__ __launch_bounds__(FR_BS) void frontier_col_hist(const int32_t *__restrict__ col_idx, int64_t nnz, int32_t cols,
-                                                           uint32_t *__restrict__ cnt) {
-  const int64_t j = (int64_t)blockIdx.x * FR_BS + threadIdx.x;
-  if (j < nnz) {
-    const int32_t c = col_idx[j];
-    if ((uint32_t)c < (uint32_t)cols) fr_add(&cnt[c], 1u);
-  }
-}
-// (the row of entry j by bisection of row_ptr: one-off work, and a hub row is spread over its entries' lanes)
-__global__ __launch_bounds__(FR_BS) void frontier_scatter(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
-                                                          int64_t nnz, int32_t rows, int32_t cols, uint32_t *__restrict__ cursor,
-                                                          int32_t *__restrict__ row_of) {
-  const int64_t j = (int64_t)blockIdx.x * FR_BS + threadIdx.x;
-  if (j >= nnz) return;
-  const int32_t c = col_idx[j];
-  if ((uint32_t)c >= (uint32_t)cols) return;
-  int32_t lo = 0, hi = rows;   // last r with row_ptr[r] <= j
-  while (hi - lo > 1) {
-    const int32_t mid = lo + (hi - lo) / 2;
-    if ((int64_t)row_ptr[mid] <= j) lo = mid; else hi = mid;
-  }
-  row_of[fr_add(&cursor[c], 1u)] = lo;
 }
 
 // ---- the loop
@@ -133,32 +80,32 @@ __global__ void frontier_begin(FrontierCtl *ctl) {
 // rows and reserves their places with ONE add on the list cursor, then it reads the run again (out of L2) and writes
 // them.  (One add per wave and 64 rows was measured first: adds on one address retire about 6 ns apart, which made this
 // kernel cost 20 us on 171 K rows and 650 us on 8.4 M, twice the dense launch it follows.)
-__global__ __launch_bounds__(FR_BS) void frontier_detect(FrontierCtl *ctl, int k, int p, const uint32_t *__restrict__ in,
+__global__ __launch_bounds__(WL_BS) void frontier_detect(FrontierCtl *ctl, int k, int p, const uint32_t *__restrict__ in,
                                                          const uint32_t *__restrict__ out, int32_t rows,
                                                          const int32_t *__restrict__ col_ptr, uint32_t *__restrict__ clist,
-                                                         FrPiece *__restrict__ cplist) {
+                                                         WlPiece *__restrict__ cplist) {
   if (ctl->go[k] == 0) return;
-  __shared__ uint32_t s_cnt[FR_BS / 64], s_base;
-  const int lane = FR_LANE, wave = (int)(threadIdx.x >> 6);
-  const int64_t per = (((int64_t)rows + gridDim.x - 1) / gridDim.x + FR_BS - 1) / FR_BS * FR_BS;   // rows per workgroup
+  __shared__ uint32_t s_cnt[WL_BS / 64], s_base;
+  const int lane = wl_lane(), wave = (int)(threadIdx.x >> 6);
+  const int64_t per = (((int64_t)rows + gridDim.x - 1) / gridDim.x + WL_BS - 1) / WL_BS * WL_BS;   // rows per workgroup
   const int64_t r0 = (int64_t)blockIdx.x * per, r1 = min(r0 + per, (int64_t)rows);
   uint32_t mine = 0;   // changed rows of this wave
-  for (int64_t base = r0 + wave * 64; base < r1; base += FR_BS) {
+  for (int64_t base = r0 + wave * 64; base < r1; base += WL_BS) {
     const int64_t r = base + lane;
     mine += (uint32_t)__popcll(__ballot(r < r1 && in[r] != out[r]));
   }
   if (lane == 0) s_cnt[wave] = mine;
   __syncthreads();
   uint32_t total = 0, before = 0;
-  for (int w = 0; w < FR_BS / 64; w++) {
+  for (int w = 0; w < WL_BS / 64; w++) {
     if (w < wave) before += s_cnt[w];
     total += s_cnt[w];
   }
   if (total == 0) return;   // (uniform over the workgroup)
-  if (threadIdx.x == 0) s_base = fr_add(&ctl->ccount[p], total);
+  if (threadIdx.x == 0) s_base = wl_add(&ctl->ccount[p], total);
   __syncthreads();
   uint32_t at = s_base + before, entries = 0;
-  for (int64_t base = r0 + wave * 64; base < r1; base += FR_BS) {
+  for (int64_t base = r0 + wave * 64; base < r1; base += WL_BS) {
     const int64_t r = base + lane;
     const bool changed = r < r1 && in[r] != out[r];
     const uint64_t m = __ballot(changed);
@@ -166,73 +113,38 @@ __global__ __launch_bounds__(FR_BS) void frontier_detect(FrontierCtl *ctl, int k
       clist[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)r;
       const uint32_t len = (uint32_t)(col_ptr[r + 1] - col_ptr[r]);
       entries += len;
-      if (len > (uint32_t)FR_COL_PIECE) {
-        const uint32_t np = (len + FR_COL_PIECE - 1) / FR_COL_PIECE;
-        const uint32_t b = fr_add(&ctl->cpieces[p], np);
-        for (uint32_t j = 0; j < np; j++) cplist[b + j] = FrPiece{(uint32_t)r, j * FR_COL_PIECE};
-      }
+      wl_push_pieces<FR_COL_PIECE>(&ctl->cpieces[p], (uint32_t)r, len, cplist);
     }
     at += (uint32_t)__popcll(m);
   }
-  entries = fr_wave_sum(entries);
-  if (lane == 0 && entries) fr_add(&ctl->centries[p], entries);
+  entries = wl_wave_sum(entries);
+  if (lane == 0 && entries) wl_add(&ctl->centries[p], entries);
 }
 
 // A lane claims row r for the launch whose number is `gen`: whoever sees an older stamp appends the row.
 __device__ __forceinline__ void fr_claim(FrontierCtl *ctl, int32_t r, uint32_t gen, const int32_t *__restrict__ row_ptr,
                                          uint32_t *__restrict__ stamp, uint32_t *__restrict__ alist, uint32_t *__restrict__ side,
-                                         FrPiece *__restrict__ rplist, uint32_t identity_bits) {
+                                         WlPiece *__restrict__ rplist, uint32_t identity_bits) {
   if (__hip_atomic_exchange(&stamp[r], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gen) return;
-  // one add per wave for the lanes that get here together (any control flow: the ballot covers the active lanes, the
-  // lowest of them adds and readfirstlane hands its answer round); one add per lane serialises on the one address
-  const uint64_t here = __ballot(1);
-  const int lane = (int)(threadIdx.x & 63);
-  uint32_t first = 0;
-  if (lane == __ffsll((unsigned long long)here) - 1) first = fr_add(&ctl->acount, (uint32_t)__popcll(here));
-  const uint32_t i = (uint32_t)__builtin_amdgcn_readfirstlane((int)first) + (uint32_t)__popcll(here & ((1ull << lane) - 1ull));
+  const uint32_t i = wl_append_here(&ctl->acount);
   alist[i] = (uint32_t)r;
   const uint32_t len = (uint32_t)(row_ptr[r + 1] - row_ptr[r]);
-  if (len > (uint32_t)FR_ROW_PIECE) {   // pulled in pieces that meet in side[i] by integer atomics: start from the identity
-    side[i] = identity_bits;
-    const uint32_t np = (len + FR_ROW_PIECE - 1) / FR_ROW_PIECE;
-    const uint32_t b = fr_add(&ctl->rpieces, np);
-    for (uint32_t j = 0; j < np; j++) rplist[b + j] = FrPiece{i, j * FR_ROW_PIECE};
-  }
+  if (len > (uint32_t)FR_ROW_PIECE) side[i] = identity_bits;   // pulled in pieces that meet in side[i] by integer atomics: start from the identity
+  wl_push_pieces<FR_ROW_PIECE>(&ctl->rpieces, i, len, rplist);
 }
 
-__global__ __launch_bounds__(FR_BS) void frontier_mark(FrontierCtl *ctl, int k, int p, uint32_t gen, int32_t rows,
+__global__ __launch_bounds__(WL_BS) void frontier_mark(FrontierCtl *ctl, int k, int p, uint32_t gen, int32_t rows,
                                                        const int32_t *__restrict__ col_ptr, const int32_t *__restrict__ row_of,
                                                        const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ clist,
-                                                       const FrPiece *__restrict__ cplist, uint32_t *__restrict__ stamp,
+                                                       const WlPiece *__restrict__ cplist, uint32_t *__restrict__ stamp,
                                                        uint32_t *__restrict__ alist, uint32_t *__restrict__ side,
-                                                       FrPiece *__restrict__ rplist, uint32_t identity_bits) {
+                                                       WlPiece *__restrict__ rplist, uint32_t identity_bits) {
   if (ctl->go[k] == 0) return;
-  const int lane = FR_LANE;
-  const int64_t n = ctl->ccount[p], np = ctl->cpieces[p];
-  for (int64_t base = FR_WAVE * 64; base < n; base += FR_WAVES * 64) {
-    const bool valid = base + lane < n;
-    const int32_t c = valid ? (int32_t)clist[base + lane] : 0;
-    const int32_t s = valid ? col_ptr[c] : 0;
-    const int32_t len = valid ? col_ptr[c + 1] - s : 0;
-    if (valid) {
-      if (c < rows) fr_claim(ctl, c, gen, row_ptr, stamp, alist, side, rplist, identity_bits);   // rows of C_k themselves
-      if (len <= FR_SHORT)
-        for (int32_t j = 0; j < len; j++) fr_claim(ctl, row_of[s + j], gen, row_ptr, stamp, alist, side, rplist, identity_bits);
-    }
-    uint64_t m = __ballot(len > FR_SHORT && len <= FR_COL_PIECE);
-    while (m) {
-      const int src = __ffsll((unsigned long long)m) - 1;
-      m &= m - 1;
-      const int32_t sb = __shfl(s, src), lb = __shfl(len, src);
-      for (int32_t j = lane; j < lb; j += 64) fr_claim(ctl, row_of[sb + j], gen, row_ptr, stamp, alist, side, rplist, identity_bits);
-    }
-  }
-  for (int64_t q = FR_WAVE; q < np; q += FR_WAVES) {   // a hub column: one wave per piece
-    const FrPiece pc = cplist[q];
-    const int32_t s = col_ptr[pc.id] + (int32_t)pc.off;
-    const int32_t e = min(s + FR_COL_PIECE, col_ptr[pc.id + 1]);
-    for (int32_t j = s + lane; j < e; j += 64) fr_claim(ctl, row_of[j], gen, row_ptr, stamp, alist, side, rplist, identity_bits);
-  }
+  const auto claim = [&](int32_t r) { fr_claim(ctl, r, gen, row_ptr, stamp, alist, side, rplist, identity_bits); };
+  (void)wl_expand<FR_SHORT, FR_COL_PIECE>(
+      clist, ctl->ccount[p], cplist, ctl->cpieces[p], col_ptr,
+      [&](int32_t c, bool listed) { if (listed && c < rows) claim(c); return 0u; },   // the rows of C_k themselves
+      [&](int32_t j, uint32_t) { claim(row_of[j]); });
 }
 
 template <class SR>
@@ -251,14 +163,14 @@ __device__ __forceinline__ typename SR::T fr_entries(const CsrDev &A, const uint
 
 // side[i] = the reduction over the entries of active row i (before the epilogue)
 template <class SR>
-__global__ __launch_bounds__(FR_BS) void frontier_pull(FrontierCtl *ctl, int k, CsrDev A, const uint32_t *__restrict__ x,
+__global__ __launch_bounds__(WL_BS) void frontier_pull(FrontierCtl *ctl, int k, CsrDev A, const uint32_t *__restrict__ x,
                                                        const uint32_t *__restrict__ alist, uint32_t *__restrict__ side,
-                                                       const FrPiece *__restrict__ rplist) {
+                                                       const WlPiece *__restrict__ rplist) {
   using T = typename SR::T;
   if (ctl->go[k] == 0) return;
-  const int lane = FR_LANE;
+  const int lane = wl_lane();
   const int64_t n = ctl->acount, np = ctl->rpieces;
-  for (int64_t base = FR_WAVE * 64; base < n; base += FR_WAVES * 64) {
+  for (int64_t base = wl_wave() * 64; base < n; base += wl_waves() * 64) {
     const bool valid = base + lane < n;
     const int32_t r = valid ? (int32_t)alist[base + lane] : 0;
     const int32_t s = valid ? A.row_ptr[r] : 0;
@@ -275,8 +187,8 @@ __global__ __launch_bounds__(FR_BS) void frontier_pull(FrontierCtl *ctl, int k, 
     }
     if (valid && len <= FR_ROW_PIECE) side[base + lane] = to_bits<T>(mine);
   }
-  for (int64_t q = FR_WAVE; q < np; q += FR_WAVES) {
-    const FrPiece pc = rplist[q];
+  for (int64_t q = wl_wave(); q < np; q += wl_waves()) {
+    const WlPiece pc = rplist[q];
     const int32_t r = (int32_t)alist[pc.id];
     const int32_t s = A.row_ptr[r] + (int32_t)pc.off;
     const int32_t e = min(s + FR_ROW_PIECE, A.row_ptr[r + 1]);
@@ -294,18 +206,18 @@ __global__ __launch_bounds__(FR_BS) void frontier_pull(FrontierCtl *ctl, int k, 
 
 // Epilogue with y = x[r], in place: only words that differ are written (p: the changed list this launch PRODUCES).
 template <class SR>
-__global__ __launch_bounds__(FR_BS) void frontier_apply(FrontierCtl *ctl, int k, int p, uint32_t *__restrict__ x,
+__global__ __launch_bounds__(WL_BS) void frontier_apply(FrontierCtl *ctl, int k, int p, uint32_t *__restrict__ x,
                                                         const uint32_t *__restrict__ alist, const uint32_t *__restrict__ side,
                                                         const int32_t *__restrict__ col_ptr, uint32_t *__restrict__ clist,
-                                                        FrPiece *__restrict__ cplist, typename SR::T alpha, typename SR::T beta,
+                                                        WlPiece *__restrict__ cplist, typename SR::T alpha, typename SR::T beta,
                                                         int use_y, double delta) {
   using T = typename SR::T;
   if (ctl->go[k] == 0) return;
-  const int lane = FR_LANE;
+  const int lane = wl_lane();
   const int64_t n = ctl->acount;
   uint32_t entries = 0;
   bool differs = false;
-  for (int64_t base = FR_WAVE * 64; base < n; base += FR_WAVES * 64) {
+  for (int64_t base = wl_wave() * 64; base < n; base += wl_waves() * 64) {
     const bool valid = base + lane < n;
     int32_t r = 0;
     bool changed = false;
@@ -320,8 +232,8 @@ __global__ __launch_bounds__(FR_BS) void frontier_apply(FrontierCtl *ctl, int k,
     }
     entries += fr_push_changed(ctl, p, changed, r, lane, col_ptr, clist, cplist);
   }
-  entries = fr_wave_sum(entries);
-  if (lane == 0 && entries) fr_add(&ctl->centries[p], entries);
+  entries = wl_wave_sum(entries);
+  if (lane == 0 && entries) wl_add(&ctl->centries[p], entries);
   if (differs) ctl->flag[k] = 1;   // benign race: every writer stores 1
 }
 
@@ -337,9 +249,5 @@ __global__ void frontier_decide(FrontierCtl *ctl, int k, int p, int dense, int32
   ctl->ccount[p] = 0; ctl->centries[p] = 0; ctl->cpieces[p] = 0;
   ctl->acount = 0; ctl->rpieces = 0;
 }
-
-#undef FR_LANE
-#undef FR_WAVE
-#undef FR_WAVES
 
 } // namespace sh

@@ -1,0 +1,244 @@
+// worklist.hip.h -- what the worklist algorithms share (frontier.hip.h, bfs.hip.h, sssp.hip.h): list cursors, the cutting
+// of long lists into pieces, per-workgroup sums, the two traversal skeletons and the kernels that build a graph handle.
+//
+// Work distribution: every kernel runs a fixed grid whose waves stride over a device-side list length (the host does
+// not know it).  A wave takes 64 list entries at a time: lists of up to SHORT entries one lane each, longer ones the
+// whole wave one after the other, and those above PIECE entries are cut into pieces of that size which go through a
+// list of their own (built by whoever appended the entry: wl_push_pieces), one wave per piece.  wl_expand is that
+// traversal for a push along the lists of a worklist's entries, wl_rows_min for a pass over all rows that looks for the
+// smallest matching in-neighbour.  The loops whose bodies do not fit either (a reduction in a semiring type, an early
+// exit, a two-pass reservation, a prefix scan, a list split) stay with their kernels and use the helpers only: a
+// skeleton wide enough to serve them would branch on its caller.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace sh {
+
+constexpr int WL_BS = 256;   // threads of a workgroup of every worklist kernel
+
+struct WlPiece { uint32_t id, off; };   // whose list (a vertex, a row, or a slot of a list of rows), first entry of the piece
+// Per workgroup of a traversal launch: its sums (no atomics on one address: thousands of waves adding to one word
+// retire about 6 ns apart, see frontier_detect).
+struct WlPart { uint32_t a, b, c, pad; };
+
+__device__ __forceinline__ int wl_lane() { return (int)(threadIdx.x & 63); }
+__device__ __forceinline__ int64_t wl_wave() { return (int64_t)blockIdx.x * (WL_BS / 64) + (threadIdx.x >> 6); }
+__device__ __forceinline__ int64_t wl_waves() { return (int64_t)gridDim.x * (WL_BS / 64); }
+
+__device__ __forceinline__ uint32_t wl_add(uint32_t *p, uint32_t v) {
+  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// One atomic per wave for a list cursor: the first wanting lane adds the count, every wanting lane gets its place.
+// (Call from wave-uniform control flow only.)
+__device__ __forceinline__ uint32_t wl_wave_append(uint32_t *cursor, bool want, int lane) {
+  const uint64_t m = __ballot(want);
+  if (m == 0) return 0;
+  const int leader = __ffsll((unsigned long long)m) - 1;
+  uint32_t base = 0;
+  if (lane == leader) base = wl_add(cursor, (uint32_t)__popcll(m));
+  base = (uint32_t)__shfl((int)base, leader);
+  return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+// A place in a list for every lane that gets here together (any control flow: the ballot covers the active lanes, the
+// lowest of them adds for all and readfirstlane hands its answer round); one add per lane serialises on the one address.
+__device__ __forceinline__ uint32_t wl_append_here(uint32_t *cursor) {
+  const uint64_t here = __ballot(1);
+  const int lane = wl_lane();
+  uint32_t first = 0;
+  if (lane == __ffsll((unsigned long long)here) - 1) first = wl_add(cursor, (uint32_t)__popcll(here));
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)first) + (uint32_t)__popcll(here & ((1ull << lane) - 1ull));
+}
+__device__ __forceinline__ uint32_t wl_wave_sum(uint32_t v) {
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+  return v;
+}
+__device__ __forceinline__ uint32_t wl_wave_min(uint32_t v) {
+  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+  return v;
+}
+// The pieces of a list of `len` entries join piece list `list` (nothing when it is no longer than PIECE).  A piece list
+// over lists that hold E entries in all needs E / (PIECE / 2) + 1 places: sum of ceil(len / PIECE) over len > PIECE.
+template <int PIECE>
+__device__ __forceinline__ void wl_push_pieces(uint32_t *cursor, uint32_t id, uint32_t len, WlPiece *__restrict__ list) {
+  if (len > (uint32_t)PIECE) {
+    const uint32_t np = (len + PIECE - 1) / PIECE;
+    const uint32_t b = wl_add(cursor, np);
+    for (uint32_t j = 0; j < np; j++) list[b + j] = WlPiece{id, j * PIECE};
+  }
+}
+// The workgroup's sums -> its WlPart (convergent control flow only).
+__device__ __forceinline__ void wl_block_part(WlPart *__restrict__ part, uint32_t a, uint32_t b) {
+  __shared__ uint32_t s_a[WL_BS / 64], s_b[WL_BS / 64];
+  a = wl_wave_sum(a);
+  b = wl_wave_sum(b);
+  if (wl_lane() == 0) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t ta = 0, tb = 0;
+    for (int w = 0; w < WL_BS / 64; w++) { ta += s_a[w]; tb += s_b[w]; }
+    part[blockIdx.x] = WlPart{ta, tb, 0u, 0u};
+  }
+}
+// The sums of a launch's WlParts, by one workgroup (convergent control flow only): thread 0 gets them, and only for it
+// the answer is true.
+__device__ __forceinline__ bool wl_sum_parts(const WlPart *__restrict__ part, int nparts, uint32_t *a, uint32_t *b) {
+  __shared__ uint32_t s_a[WL_BS], s_b[WL_BS];
+  uint32_t ta = 0, tb = 0;
+  for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) { ta += part[i].a; tb += part[i].b; }
+  s_a[threadIdx.x] = ta; s_b[threadIdx.x] = tb;
+  __syncthreads();
+  if (threadIdx.x != 0) return false;
+  ta = 0; tb = 0;
+  for (int i = 0; i < WL_BS; i++) { ta += s_a[i]; tb += s_b[i]; }
+  *a = ta; *b = tb;
+  return true;
+}
+
+// The push traversal: for every v of list[0, n) the entries [ptr[v], ptr[v + 1]), lists above PIECE entries through
+// pieces[0, np) instead.  visit(v, true) runs once per valid list entry and returns a 32-bit word that the skeleton
+// carries to the lanes that walk v's list; a piece reads it again as visit(v, false), which must do nothing else.
+// edge(j, carried) runs once per entry j.  -> the lane's sum of list lengths.
+template <int SHORT, int PIECE, class Visit, class Edge>
+__device__ __forceinline__ uint32_t wl_expand(const uint32_t *__restrict__ list, int64_t n, const WlPiece *__restrict__ pieces,
+                                              int64_t np, const int32_t *__restrict__ ptr, Visit visit, Edge edge) {
+  const int lane = wl_lane();
+  uint32_t looked = 0;
+  for (int64_t base = wl_wave() * 64; base < n; base += wl_waves() * 64) {
+    const bool valid = base + lane < n;
+    const int32_t v = valid ? (int32_t)list[base + lane] : 0;
+    const int32_t s = valid ? ptr[v] : 0;
+    const int32_t len = valid ? ptr[v + 1] - s : 0;
+    const uint32_t w = valid ? visit(v, true) : 0u;
+    looked += (uint32_t)len;
+    if (len <= SHORT)
+      for (int32_t j = 0; j < len; j++) edge(s + j, w);
+    uint64_t m = __ballot(len > SHORT && len <= PIECE);
+    while (m) {
+      const int src = __ffsll((unsigned long long)m) - 1;
+      m &= m - 1;
+      const int32_t sb = __shfl(s, src), lb = __shfl(len, src);
+      const uint32_t wb = (uint32_t)__shfl((int)w, src);
+      for (int32_t j = lane; j < lb; j += 64) edge(sb + j, wb);
+    }
+  }
+  for (int64_t q = wl_wave(); q < np; q += wl_waves()) {   // a hub's list: one wave per piece
+    const WlPiece pc = pieces[q];
+    const int32_t s = ptr[pc.id] + (int32_t)pc.off;
+    const int32_t e = min(s + PIECE, ptr[pc.id + 1]);
+    const uint32_t w = visit((int32_t)pc.id, false);
+    for (int32_t j = s + lane; j < e; j += 64) edge(j, w);
+  }
+  return looked;
+}
+
+// The row pass: out[r] = the smallest in_col[j] over the entries j of row r with hit(j, want), for every row with
+// open(r, &want) (whether row r takes part, and its wanted word).  The host fills `out` with -1 first; pieces of rows
+// above PIECE entries (rpieces: a static list) meet in out[r] by an UNSIGNED atomic min, under which -1 (no candidate
+// yet) is the largest word.
+template <int SHORT, int PIECE, class Open, class Hit>
+__device__ __forceinline__ void wl_rows_min(int32_t rows, const int32_t *__restrict__ in_ptr, const int32_t *__restrict__ in_col,
+                                            const WlPiece *__restrict__ rpieces, int32_t n_rpieces, int32_t *out, Open open, Hit hit) {
+  const int lane = wl_lane();
+  for (int64_t base = wl_wave() * 64; base < rows; base += wl_waves() * 64) {
+    const int64_t r = base + lane;
+    uint32_t want = 0;
+    const bool on = r < rows && open((int32_t)r, &want);
+    const int32_t s = on ? in_ptr[r] : 0;
+    const int32_t len = on ? in_ptr[r + 1] - s : 0;
+    uint32_t best = 0xFFFFFFFFu;
+    if (len <= SHORT)
+      for (int32_t j = s; j < s + len; j++)
+        if (hit(j, want)) best = min(best, (uint32_t)in_col[j]);
+    uint64_t m = __ballot(len > SHORT && len <= PIECE);
+    while (m) {
+      const int src = __ffsll((unsigned long long)m) - 1;
+      m &= m - 1;
+      const int32_t sb = __shfl(s, src), lb = __shfl(len, src);
+      const uint32_t wb = (uint32_t)__shfl((int)want, src);
+      uint32_t mine = 0xFFFFFFFFu;
+      for (int32_t j = sb + lane; j < sb + lb; j += 64)
+        if (hit(j, wb)) mine = min(mine, (uint32_t)in_col[j]);
+      mine = wl_wave_min(mine);
+      if (lane == src) best = mine;
+    }
+    if (len > 0 && len <= PIECE) out[r] = (int32_t)best;
+  }
+  for (int64_t i = wl_wave(); i < n_rpieces; i += wl_waves()) {
+    const WlPiece pc = rpieces[i];
+    const int32_t r = (int32_t)pc.id;
+    uint32_t want = 0;
+    if (!open(r, &want)) continue;
+    const int32_t s = in_ptr[r] + (int32_t)pc.off;
+    const int32_t e = min(s + PIECE, in_ptr[r + 1]);
+    uint32_t mine = 0xFFFFFFFFu;
+    for (int32_t j = s + lane; j < e; j += 64)
+      if (hit(j, want)) mine = min(mine, (uint32_t)in_col[j]);
+    mine = wl_wave_min(mine);
+    if (lane == 0 && mine != 0xFFFFFFFFu)
+      (void)__hip_atomic_fetch_min((uint32_t *)&out[r], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ---- building a handle (once): the entries that are edges, compacted in stored order; the static pieces of long rows;
+// the transpose (column histogram, exclusive scan by rocPRIM in plan_gpu.hip, scatter through per-column cursors)
+// flag[j] = entry j is an edge: KEEP::value(its value word) and a column inside the matrix (flag[nnz] = 0 closes the scan)
+template <class KEEP>
+__global__ __launch_bounds__(WL_BS) void wl_edge_flag(const int32_t *__restrict__ col_idx, const uint32_t *__restrict__ val,
+                                                      int64_t nnz, int32_t cols, uint32_t *__restrict__ flag) {
+  const int64_t j = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (j < nnz) flag[j] = (KEEP::value(val[j]) && (uint32_t)col_idx[j] < (uint32_t)cols) ? 1u : 0u;
+  else if (j == nnz) flag[j] = 0u;
+}
+// pos = exclusive scan of flag: edge j goes to in_col[pos[j]] and, where weights are kept (in_w != NULL), its |a| to in_w[pos[j]]
+__global__ __launch_bounds__(WL_BS) void wl_edge_compact(const int32_t *__restrict__ col_idx, const uint32_t *__restrict__ val,
+                                                         const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                                                         int64_t nnz, int32_t *__restrict__ in_col, uint32_t *__restrict__ in_w) {
+  const int64_t j = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (j < nnz && flag[j]) {
+    in_col[pos[j]] = col_idx[j];
+    if (in_w) in_w[pos[j]] = val[j] & 0x7FFFFFFFu;
+  }
+}
+__global__ __launch_bounds__(WL_BS) void wl_row_starts(const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ pos,
+                                                       int64_t rows, int32_t *__restrict__ in_ptr) {
+  const int64_t r = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (r <= rows) in_ptr[r] = (int32_t)pos[row_ptr[r]];
+}
+template <int PIECE>
+__global__ __launch_bounds__(WL_BS) void wl_row_pieces(const int32_t *__restrict__ in_ptr, int64_t rows, uint32_t *cursor,
+                                                       WlPiece *__restrict__ rpieces) {
+  const int64_t r = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (r < rows) wl_push_pieces<PIECE>(cursor, (uint32_t)r, (uint32_t)(in_ptr[r + 1] - in_ptr[r]), rpieces);
+}
+__global__ __launch_bounds__(WL_BS) void wl_col_hist(const int32_t *__restrict__ col_idx, int64_t nnz, int32_t cols,
+                                                     uint32_t *__restrict__ cnt) {
+  const int64_t j = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (j < nnz) {
+    const int32_t c = col_idx[j];
+    if ((uint32_t)c < (uint32_t)cols) wl_add(&cnt[c], 1u);
+  }
+}
+// Entry j of row r goes to the list of its column, with its weight where there are weights (w != NULL).  (The row of
+// entry j by bisection of row_ptr: one-off work, and a hub row is spread over its entries' lanes.  The column is
+// checked: sh_frontier_create passes arrays that are not compacted.)
+__global__ __launch_bounds__(WL_BS) void wl_transpose_scatter(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
+                                                              const uint32_t *__restrict__ w, int64_t nnz, int32_t rows, int32_t cols,
+                                                              uint32_t *__restrict__ cursor, int32_t *__restrict__ row_of,
+                                                              uint32_t *__restrict__ out_w) {
+  const int64_t j = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (j >= nnz) return;
+  const int32_t c = col_idx[j];
+  if ((uint32_t)c >= (uint32_t)cols) return;
+  int32_t lo = 0, hi = rows;   // last r with row_ptr[r] <= j
+  while (hi - lo > 1) {
+    const int32_t mid = lo + (hi - lo) / 2;
+    if ((int64_t)row_ptr[mid] <= j) lo = mid; else hi = mid;
+  }
+  const uint32_t at = wl_add(&cursor[c], 1u);
+  row_of[at] = lo;
+  if (w) out_w[at] = w[j];
+}
+
+} // namespace sh

@@ -13,6 +13,7 @@ assertion on two changes applies to every other matrix.
 import numpy as np
 import pytest
 
+import graph_patterns as P
 from conftest import MATRICES, mtx
 from oracle import oracle as O
 from sparseharness_amd import hostlib as H
@@ -31,34 +32,12 @@ def eng():
     e.close()
 
 
-def rows_of_entries(rp):
-    return np.repeat(np.arange(len(rp) - 1, dtype=np.int32), np.diff(rp))
+rows_of_entries = P.rows_of_entries
 
 
-def ragged_square(seed=77, n=3001, long_len=20_001):
-    """As ragged_square of tests/test_frontier_gpu.py: empty rows, short and medium rows, ONE row of 20 001 entries, ONE
-    column of 20 001 entries (spread over all rows), column indices outside [0, n) on both sides, a third of the values 0."""
-    rng = np.random.default_rng(seed)
-    hub = 7
-    deg = rng.integers(0, 12, n)
-    deg[rng.random(n) < 0.3] = 0
-    deg[rng.integers(0, n, 40)] = rng.integers(17, 300, 40)
-    deg[n // 3] = long_len
-    deg[0] = 3
-    deg[n - 1] = 5
-    extra = np.full(n, long_len // n, np.int64)   # entries of the hub column per row
-    extra[: long_len - extra.sum()] += 1
-    extra[rng.random(n) < 0.2] = 0                # (some rows stay empty) ...
-    extra[n // 2] += long_len - extra.sum()       # ... and one row makes the count up
-    tot = deg + extra
-    rp = np.concatenate([[0], np.cumsum(tot)]).astype(np.int32)
-    ci = rng.integers(0, n, rp[-1]).astype(np.int32)
-    ci[ci == hub] = hub + 1
-    oob = rng.random(rp[-1]) < 0.03
-    ci[oob] = np.where(rng.random(oob.sum()) < 0.5, -1 - rng.integers(0, 5, oob.sum()), n + rng.integers(0, 1000, oob.sum()))
-    for r in range(n):                            # the hub entries sit at the end of each row
-        ci[rp[r + 1] - extra[r]: rp[r + 1]] = hub
-    assert (ci == hub).sum() == long_len and tot[n // 3] >= long_len and (tot == 0).any()
+def ragged_square():
+    """P.ragged_pattern with small integer values, a third of them 0."""
+    rng, rp, ci = P.ragged_pattern()
     va = rng.integers(0, 3, rp[-1]).astype(np.int32)   # a third of the stored values are 0
     return rp, ci, va
 
@@ -92,6 +71,9 @@ def matrix(name):
         elif name == "rmat17":   # long rows and long out-lists in both kernels
             rp, ci, va = H.rmat(17, seed=40)
             va = va.astype(np.int32)
+        elif name == "edges":    # list lengths on the kernels' thresholds, all values 1
+            rp, ci = P.edges_pattern()
+            va = np.ones(len(ci), np.int32)
         else:
             rows, cols, _, rp, ci, va = H.mm_load(mtx(name), elem_is_int=True)
             assert rows == cols
@@ -248,12 +230,21 @@ def source_vector(n, sources):
 
 
 # ------------------------------------------------------------------ 1. every matrix, every way of choosing directions
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + ["edges"])
 def test_levels_and_parents_in_every_direction(eng, name):
     n, rp, ci, va = matrix(name)
-    x0 = source_vector(n, [0])
-    b = oracle_bfs(n, rp, ci, va, x0)
+    if name == "edges":
+        P.assert_edge_lengths(rp, ci)
     G = eng.bfs_graph(rp, ci, va)
+    for source in P.sources(name):
+        levels_and_parents_in_every_direction(eng, name, G, source)
+    G.free()
+
+
+def levels_and_parents_in_every_direction(eng, name, G, source):
+    n, rp, ci, va = matrix(name)
+    x0 = source_vector(n, [source])
+    b = oracle_bfs(n, rp, ci, va, x0)
     assert G.edges == b.E
     up, down, n_changes = pair_with_two_changes(b)
     if b.steps >= 3:
@@ -272,7 +263,6 @@ def test_levels_and_parents_in_every_direction(eng, name):
         assert b.depth == 498
     if name == "rmat17":
         assert b.indeg.max() > 32 and b.outdeg.max() > 2048
-    G.free()
 
 
 # ------------------------------------------------------------------ 2. against the entry points that exist

@@ -4,6 +4,8 @@ definition computed in numpy, inputs that are not monotone, reuse of a handle, t
 import numpy as np
 import pytest
 
+import graph_patterns as P
+import minplus_ref as M
 from conftest import MATRICES, mtx
 from oracle import oracle as O
 from sparseharness_amd import hostlib as H
@@ -26,8 +28,7 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def rows_of_entries(rp):
-    return np.repeat(np.arange(len(rp) - 1, dtype=np.int32), np.diff(rp))
+rows_of_entries = P.rows_of_entries
 
 
 def scc_values(rp, ci):
@@ -36,31 +37,9 @@ def scc_values(rp, ci):
     return np.where(ci == r, np.int32(O.INT_MIN), r).astype(np.int32)
 
 
-def ragged_square(seed=77, n=3001, long_len=20_001):
-    """Like ragged_csr of tests/test_bits_gpu.py, but square: empty rows, short and medium rows, ONE row of 20 001
-    entries (above the long-row threshold), ONE column of 20 001 entries (spread over all rows, several per row), column
-    indices outside [0, n) on both sides, stored zeros."""
-    rng = np.random.default_rng(seed)
-    hub = 7
-    deg = rng.integers(0, 12, n)
-    deg[rng.random(n) < 0.3] = 0
-    deg[rng.integers(0, n, 40)] = rng.integers(17, 300, 40)
-    deg[n // 3] = long_len
-    deg[0] = 3
-    deg[n - 1] = 5
-    extra = np.full(n, long_len // n, np.int64)   # entries of the hub column per row
-    extra[: long_len - extra.sum()] += 1
-    extra[rng.random(n) < 0.2] = 0                # (some rows stay empty) ...
-    extra[n // 2] += long_len - extra.sum()       # ... and one row makes the count up
-    tot = deg + extra
-    rp = np.concatenate([[0], np.cumsum(tot)]).astype(np.int32)
-    ci = rng.integers(0, n, rp[-1]).astype(np.int32)
-    ci[ci == hub] = hub + 1
-    oob = rng.random(rp[-1]) < 0.03
-    ci[oob] = np.where(rng.random(oob.sum()) < 0.5, -1 - rng.integers(0, 5, oob.sum()), n + rng.integers(0, 1000, oob.sum()))
-    for r in range(n):                            # the hub entries sit at the end of each row
-        ci[rp[r + 1] - extra[r]: rp[r + 1]] = hub
-    assert (ci == hub).sum() == long_len and tot[n // 3] >= long_len and (tot == 0).any()
+def ragged_square():
+    """P.ragged_pattern with small integer values, a third of them stored zeros."""
+    rng, rp, ci = P.ragged_pattern()
     va = rng.integers(0, 3, rp[-1]).astype(np.int32)   # a third of the stored values are 0
     return rp, ci, va
 
@@ -90,6 +69,9 @@ def matrix(name):
             rp, ci, va = ragged_square()
         elif name == "grid":
             rp, ci, va = grid_graph()
+        elif name == "edges":   # list lengths on the kernels' thresholds; ones (real weights for (min,+): see case)
+            rp, ci = P.edges_pattern()
+            va = np.ones(len(ci), np.int32)
         else:
             rows, cols, _, rp, ci, va = H.mm_load(mtx(name), elem_is_int=True)
             assert rows == cols
@@ -97,12 +79,15 @@ def matrix(name):
     return _cache[name]
 
 
-def case(sr, name):
-    """(n, rp, ci, values, x0, y0, alpha, beta) of the app that runs `sr`, on matrix `name`."""
+def case(sr, name, source=0):
+    """(n, rp, ci, values, x0, y0, alpha, beta) of the app that runs `sr`, on matrix `name`, started from `source`."""
     n, rp, ci, va = matrix(name)
     x0 = O.initial_vector(sr, n)
+    if sr != O.MAX_MIN_I32:     # (the SCC labels have no source)
+        x0 = np.roll(x0, source)
     if sr == O.MIN_PLUS_F32:    # SSSP (app/sssp.cpp)
-        return n, rp, ci, va.astype(np.float32), x0, x0, 0.0, 0.0
+        vals = M.real_weights(np.random.default_rng(78), len(ci)) if name == "edges" else va.astype(np.float32)
+        return n, rp, ci, vals, x0, x0, 0.0, 0.0
     if sr == O.OR_AND_I32:      # BFS that keeps what it has reached
         return n, rp, ci, va, x0, x0, 1, 1
     return n, rp, ci, scc_values(rp, ci), x0, np.full(n, O.INT_MIN, np.int32), O.INT_MAX, O.INT_MIN   # SCC labels (app/scc.cpp)
@@ -129,7 +114,7 @@ def run_dense(eng, sr, A, x0, y0, a, b, delta=1e-4, cap=2000):
 
 
 # ------------------------------------------------------------------ 1. the transposed pattern
-@pytest.mark.parametrize("name", MATRICES + ["ragged"])
+@pytest.mark.parametrize("name", MATRICES + ["ragged", "edges"])
 @pytest.mark.parametrize("plan", [1, 2])
 def test_transpose(eng, name, plan):
     n, rp, ci, va = matrix(name)
@@ -147,6 +132,8 @@ def test_transpose(eng, name, plan):
     np.testing.assert_array_equal(got, rows[order])   # (rows ascend inside a column of a stable sort of the CSR walk)
     if name == "ragged":
         assert np.diff(col_ptr).max() == 20_001 and np.diff(rp).max() >= 20_001
+    if name == "edges":
+        P.assert_edge_lengths(rp, ci)
     F.free()
     A.free()
 
@@ -159,10 +146,17 @@ def uploads(sr):
     return ups
 
 
-@pytest.mark.parametrize("name", MATRICES + ["ragged", "grid"])
+@pytest.mark.parametrize("name", MATRICES + ["ragged", "grid", "edges"])
 @pytest.mark.parametrize("sr", SEMIRINGS)
 def test_equals_iterate_and_oracle(eng, sr, name):
-    n, rp, ci, vals, x0, y0, a, b = case(sr, name)
+    if name == "edges":
+        P.assert_edge_lengths(*matrix(name)[1:3])
+    for source in P.sources(name) if sr != O.MAX_MIN_I32 else (0,):
+        equals_iterate_and_oracle(eng, sr, name, source)
+
+
+def equals_iterate_and_oracle(eng, sr, name, source):
+    n, rp, ci, vals, x0, y0, a, b = case(sr, name, source)
     want, w_it, w_conv = O.iterate(sr, rp, ci, vals, x0, y0, a, b, 1e-4, 2000)
     if name == "grid" and sr != O.MAX_MIN_I32:   # (the SCC labels of a grid settle in two launches)
         assert w_conv and w_it > 400   # the wavefront crosses 498 edges
@@ -174,8 +168,8 @@ def test_equals_iterate_and_oracle(eng, sr, name):
         np.testing.assert_array_equal(bits(d_got), bits(want))
         for share in SHARES:
             got, (it, conv, modes, changed, active, per, total) = run_frontier(eng, sr, A, F, x0, y0, a, b, share)
-            assert (it, conv) == (w_it, w_conv), f"{up} dense_share {share}: {it} launches, converged {conv}"
-            np.testing.assert_array_equal(bits(got), bits(want), err_msg=f"{up} dense_share {share}")
+            assert (it, conv) == (w_it, w_conv), f"{up} dense_share {share} source {source}: {it} launches, converged {conv}"
+            np.testing.assert_array_equal(bits(got), bits(want), err_msg=f"{up} dense_share {share} source {source}")
             assert len(modes) == len(per) == it and total == sum(per)
             if share == 0.0:
                 assert not any(modes) and all(k == n for k in active)

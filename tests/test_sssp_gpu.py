@@ -9,6 +9,7 @@ Every comparison is exact (== on uint32 / int32 arrays): the fixed point is uniq
 import numpy as np
 import pytest
 
+import graph_patterns as P
 import minplus_ref as M
 import sssp_ref as S
 from conftest import MATRICES, mtx
@@ -29,31 +30,9 @@ def eng():
     e.close()
 
 
-def ragged_square(seed=77, n=3001, long_len=20_001):
-    """The pattern of ragged_square of tests/test_bfs_levels_gpu.py: empty rows, short and medium rows, ONE row of 20 001
-    entries, ONE column of 20 001 entries (spread over all rows), column indices outside [0, n) on both sides.  Values:
-    real weights of mixed sign, a third of them zero, a few +-Inf."""
-    rng = np.random.default_rng(seed)
-    hub = 7
-    deg = rng.integers(0, 12, n)
-    deg[rng.random(n) < 0.3] = 0
-    deg[rng.integers(0, n, 40)] = rng.integers(17, 300, 40)
-    deg[n // 3] = long_len
-    deg[0] = 3
-    deg[n - 1] = 5
-    extra = np.full(n, long_len // n, np.int64)   # entries of the hub column per row
-    extra[: long_len - extra.sum()] += 1
-    extra[rng.random(n) < 0.2] = 0                # (some rows stay empty) ...
-    extra[n // 2] += long_len - extra.sum()       # ... and one row makes the count up
-    tot = deg + extra
-    rp = np.concatenate([[0], np.cumsum(tot)]).astype(np.int32)
-    ci = rng.integers(0, n, rp[-1]).astype(np.int32)
-    ci[ci == hub] = hub + 1
-    oob = rng.random(rp[-1]) < 0.03
-    ci[oob] = np.where(rng.random(oob.sum()) < 0.5, -1 - rng.integers(0, 5, oob.sum()), n + rng.integers(0, 1000, oob.sum()))
-    for r in range(n):                            # the hub entries sit at the end of each row
-        ci[rp[r + 1] - extra[r]: rp[r + 1]] = hub
-    assert (ci == hub).sum() == long_len and tot[n // 3] >= long_len and (tot == 0).any()
+def ragged_square():
+    """P.ragged_pattern with real weights of mixed sign, a third of them zero, a few +-Inf."""
+    rng, rp, ci = P.ragged_pattern()
     va = M.real_weights(rng, int(rp[-1]))
     va[rng.random(len(va)) < 1.0 / 3.0] = 0.0
     va[rng.choice(len(va), 40, replace=False)] = np.where(rng.random(40) < 0.5, np.inf, -np.inf).astype(np.float32)
@@ -92,6 +71,9 @@ def matrix(name):
         elif name == "rmat17":   # long rows and long out-lists
             rp, ci, _ = H.rmat(17, seed=40)
             va = M.real_weights(np.random.default_rng(41), len(ci))
+        elif name == "edges":    # list lengths on the kernels' thresholds
+            rp, ci = P.edges_pattern()
+            va = M.real_weights(np.random.default_rng(78), len(ci))
         else:
             rows, cols, _, rp, ci, va = H.mm_load(mtx(name))
             assert rows == cols
@@ -160,14 +142,23 @@ def iterate_arm(eng, name, x0):
 
 
 # ------------------------------------------------------------------ 1. every matrix, every bucket width
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + ["edges"])
 def test_dist_and_pred_under_every_bucket_width(eng, name):
     n, rp, ci, va = matrix(name)
-    x0 = M.start_vector(n, 0)
+    if name == "edges":
+        P.assert_edge_lengths(rp, ci)
+    G = eng.sssp_graph(rp, ci, va)
+    for source in P.sources(name):
+        dist_and_pred_under_every_bucket_width(eng, name, G, source)
+    G.free()
+
+
+def dist_and_pred_under_every_bucket_width(eng, name, G, source):
+    n, rp, ci, va = matrix(name)
+    x0 = M.start_vector(n, source)
     want_dist, want_pred, _, _ = reference(name, x0)
     it_dist, iters = iterate_arm(eng, name, x0)
     np.testing.assert_array_equal(M.bits(it_dist), M.bits(want_dist), err_msg=f"{name}: sh_iterate against the reference")
-    G = eng.sssp_graph(rp, ci, va)
     c, r, w = S.edges_of(n, rp, ci, va)
     assert G.edges == len(c)
     for delta in widths(name):
@@ -188,7 +179,6 @@ def test_dist_and_pred_under_every_bucket_width(eng, name):
         assert iters > 300
     if name == "rmat17":
         assert np.bincount(c, minlength=n).max() > 2048
-    G.free()
 
 
 # ------------------------------------------------------------------ 2. starts of every kind
