@@ -5,11 +5,12 @@
 // Tools / CPU tests only (never in the product build): build the tiled plan on the host and execute BOTH phases
 // on the host, entry by entry, through exactly the tables the kernels read (fold flags, obase, gdest, gblk / ptab,
 // pslot, lrp) with the kernels' indexing.  A test that compares the result with a plain CSR product thereby
-// checks the layout without a GPU.  semiring: 0 = (+,x) float, 2 = (or,and) int32.  stats[0..7]: stream entries,
+// checks the layout without a GPU.  semiring: 0 = (+,x) float, 2 = (or,and) int32, 3 = (max,min) int32.  stats[0..7]: stream entries,
 // light entries, products, bins, chunks, heavy rows, P words never written but read (must be 0), tiles.
 namespace {
 struct HPlusTimes { using T = float; static T identity() { return 0.0f; } static T mul(T x, T a) { return x * a; } static T add(T a, T b) { return a + b; } };
 struct HOrAnd { using T = int32_t; static T identity() { return 0; } static T mul(T x, T a) { return (x != 0) && (a != 0); } static T add(T a, T b) { return (a != 0) || (b != 0); } };
+struct HMaxMin { using T = int32_t; static T identity() { return INT32_MIN; } static T mul(T x, T a) { return x < a ? x : a; } static T add(T a, T b) { return a > b ? a : b; } };
 template <class T> T hbits(uint32_t u) { T v; memcpy(&v, &u, 4); return v; }
 template <class T> uint32_t tobits(T v) { uint32_t u; memcpy(&u, &v, 4); return u; }
 
@@ -177,6 +178,7 @@ extern "C" int sh_debug_emulate_plan(int64_t rows, int64_t cols, int64_t nnz, co
   if (!build_tiled_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, 256, H)) return -1;
   if (semiring == 0) return emulate<HPlusTimes>(H, rows, cols, (const uint32_t *)x, (uint32_t *)y, stats);
   if (semiring == 2) return emulate<HOrAnd>(H, rows, cols, (const uint32_t *)x, (uint32_t *)y, stats);
+  if (semiring == 3) return emulate<HMaxMin>(H, rows, cols, (const uint32_t *)x, (uint32_t *)y, stats);
   return -2;
 }
 // Builds the tiled layout of one matrix twice -- host builder and device builder -- and compares every array.

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import int_ref as I
 from sparseharness_amd import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,13 +36,17 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def emulate(lib, rows, cols, rp, ci, va, sem, **options):
+def emulate(lib, rows, cols, rp, ci, va, sem, x=None, **options):
+    """`x`: the input vector (32-bit words); without one, 1 + c % 7 for (+,x) and every third column set for the others."""
     opt = abi.sh_plan_options()
     lib.sh_plan_options_default(C.byref(opt))
     opt.plan = 2
     for k, v in options.items():
         setattr(opt, k, v)
-    x = (1 + np.arange(cols) % 7).astype(np.float32) if sem == 0 else (np.arange(cols) % 3 == 0).astype(np.int32)
+    if x is None:
+        x = (1 + np.arange(cols) % 7).astype(np.float32) if sem == 0 else (np.arange(cols) % 3 == 0).astype(np.int32)
+    x = np.ascontiguousarray(x)
+    assert x.dtype.itemsize == 4 and len(x) == cols
     y = np.zeros(rows, np.float32 if sem == 0 else np.int32)
     st = np.zeros(8, np.int64)
     rc = lib.sh_debug_emulate_plan(rows, cols, len(ci), _p(rp), _p(ci), _p(va), C.byref(opt), sem, _p(x), _p(y), _p(st))
@@ -102,6 +107,41 @@ def test_emulated_plan_equals_csr_product(emu, shape):
             np.testing.assert_array_equal(y, exact(rows, cols, rp, ci, vals, x, sem), err_msg=str((sem, options, st)))
             if options.get("fold") == 0:
                 assert st["products"] >= st["light"]                  # one product per light entry (+ padding)
+
+
+INT_OPTIONS = [dict(fold=f, value_coding=vc) for f in (0, 1) for vc in (0, 8, -1)]
+
+
+@pytest.mark.parametrize("sem", [I.OR_AND, I.MAX_MIN])
+@pytest.mark.parametrize("shape", range(len(SHAPES)))
+def test_emulated_plan_on_arbitrary_words(emu, shape, sem):
+    """The integer semirings on arbitrary 32-bit words (tests/int_ref.py: INT_MIN = -0.0, NaN patterns, subnormals,
+    2^24 + 1, halves of a word) through padding entries, folded pairs, heavy strips and partial slots, with identity
+    INT_MIN for (max,min): raw values, a 16-word and a 255-word set (four-bit and one-byte codes), and for (max,min) a case
+    in which every value and every x is negative, so that a 0 leaking from a padding entry would win the max."""
+    rows, cols, avg, heavy, kw = SHAPES[shape]
+    rng = np.random.default_rng(500 + 10 * shape + sem)
+    rp, ci, _ = random_matrix(rng, rows, cols, avg, heavy, **kw)
+    nnz = len(ci)
+    draw = I.truth_words if sem == I.OR_AND else I.words
+    cases = [("raw", draw(rng, nnz), draw(rng, cols))]
+    for distinct in (16, 255):
+        pool = I.value_pool(rng, distinct)
+        cases.append((f"{distinct} words", pool[rng.integers(0, distinct, nnz)], draw(rng, cols)))
+    if sem == I.MAX_MIN:
+        cases.append(("all negative", I.negative_words(rng, nnz), I.negative_words(rng, cols)))
+        cases.append(("all negative, 16 words", (I.bits(cases[1][1]) | np.uint32(0x80000000)).view(np.int32), I.negative_words(rng, cols)))
+    alpha, beta = (1, 0) if sem == I.OR_AND else (I.INT_MAX, I.INT_MIN)     # the row results themselves
+    for what, vals, x in cases:
+        vals = np.ascontiguousarray(vals, np.int32)
+        want = I.kernel(sem, rp, ci, vals, x, None, alpha, beta, cols)
+        if what.startswith("all negative") and nnz:
+            assert (vals < 0).all() and (x < 0).all() and (want < 0).all()
+        for options in INT_OPTIONS:
+            rc, y, st, _ = emulate(emu, rows, cols, rp, ci, vals, sem, x=x, **options)
+            assert rc == 0, (rc, what, options, st)
+            assert st["poison_reads"] == 0, (what, options, st)
+            np.testing.assert_array_equal(I.bits(y), I.bits(want), err_msg=str((sem, what, options, st)))
 
 
 @pytest.mark.parametrize("distinct", [300, 4095, 4096, 6000])
