@@ -608,6 +608,105 @@ int sh_sssp(sh_engine *e, sh_sssp_graph *g, const sh_vec *x0, sh_vec *dist, sh_v
             int64_t *relaxed, int64_t *size_per_round, int64_t *edges_per_round, uint64_t *ns_per_round,
             uint64_t *total_ns);
 
+/* ---- strongly connected components by trim, pivot and colouring: extends the SCC loop of HarnessSCC::executeRun
+ *      (app/scc.cpp:96-176) and Harness::executeKernel (inc/harness.h:149-195).  The reference's SCC app is an SpMV loop
+ *      on the (max,min) semiring; on scc_normalise'd input it leaves a label vector that is NOT the partition into
+ *      strongly connected components, and the reference has no counterpart of the calls below.  sh_scc computes that
+ *      partition: trimming (Fleischer, Hendrickson, Pinar 2000), one forward-backward round from a pivot, then
+ *      colouring rounds (Orzan 2004), scheduled as in Slota, Rajamanickam, Madduri (IPDPS 2014).
+ *
+ *      The edge rule is that of sh_bfs_levels: an EDGE c -> r exists when row r stores an entry with column c,
+ *      0 <= c < rows, and a value whose 32 bits are not all zero.  Self-loops and parallel edges are legal and change nothing.
+ *        comp[v]   = the largest u such that v reaches u and u reaches v (v itself counts): canonical, so comparable
+ *                    with ==.  It is -1 only where an incomplete run (*complete == 0: max_steps used up) had not settled
+ *                    v; every word that is not -1 is final and right.
+ *        *components = the number of v with comp[v] == v; *settled = the number of v with comp[v] >= 0; *trimmed = the
+ *                    vertices settled by trim rounds.
+ *      The result does not depend on trim, pivot, the schedule or the run.
+ *
+ *      A STEP is one sweep over a work list: a trim sweep, a propagation sweep or a claim sweep (and, once per round that
+ *      is no trim round, the sweep that seeds its colours; once per pivot round, the sweep that writes its label).  A
+ *      ROUND is a maximal run of steps of one kind that settles vertices; kind_per_round is 0 (trim), 1 (pivot) or
+ *      2 (colouring).  The schedule is fixed, so kind_per_round and size_per_round are the same in every run.  LIVE means
+ *      not settled; edges count only between live vertices, and self-loops never count.
+ *        1. If trim != 0, a TRIM ROUND: repeatedly settle every live vertex with no live in-neighbour or no live
+ *           out-neighbour as its own component (comp[v] = v), until none is left.  The set it removes is unique (a
+ *           closure).  A trim round that settles nothing is not recorded.
+ *        2. If live vertices remain and pivot != 0, a PIVOT ROUND, at most once per call: p = the live vertex with the
+ *           largest (stored in-list length) x (stored out-list length) as uint64, ties to the largest index; mark what p
+ *           reaches through live vertices; from p claim backwards along in-lists inside the marked set.  The claimed set
+ *           is p's component and gets the largest index in it as its label.
+ *        3. Otherwise a COLOURING ROUND: every live v starts with colour v; colours propagate forwards along live edges by
+ *           atomic max until nothing changes (colour[u] is then the largest live index that reaches u); the roots are
+ *           the v with colour[v] == v; from all roots at once, claim backwards along in-lists any live c whose colour
+ *           equals that of the claimed vertex it has an edge to.  The claimed vertices get their colour as label.
+ *        4. After every pivot or colouring round go to 1.  Stop when no vertex is live.
+ *      Why that is right: a path between two vertices of one component stays inside it, so removing whole components
+ *      leaves the others intact in the live subgraph.  A root v is the largest index of its component (every member
+ *      reaches v).  c is claimed iff c reaches v (the claim) and v reaches c (the colour), and every vertex on a path inside
+ *      v's component has colour v.  Every colouring round settles at least the component of the largest live index.
+ *      Worst cases: a descending chain of k components takes k colouring rounds (and a propagation sweep per hop in each:
+ *      the directed path n - 1 -> ... -> 0 without trim takes n rounds and about n * n / 4 sweeps); a directed path takes
+ *      rows / 2 trim sweeps.  max_steps bounds the call.
+ *
+ *      Measured on an MI355X (DESIGN.md "6g Strongly connected components", profiles/scc_grid2048.json, scc_scircuit.json, scc_rmat23.json;
+ *        tools/scc_bench.py, one process per matrix, arms alternating, 5 rounds, device time in us as median (min-max);
+ *        Tarjan = wall time of hostlib.scc_labels, two BFS = two sh_bfs_levels calls from the pivot on the matrix and on
+ *        its transpose):
+ *        - 2048 x 2048 grid (4 194 304 rows, 16 769 024 edges): trim + pivot 255 608 us (241 168-271 066), 8190 steps = 3.66 of Tarjan's 69 869 (66 127-71 147);
+ *          pivot round 255 502 = 1.30 of two BFS 196 965 (196 492-200 049); trim + colouring 1 531 543 = 21.92 of Tarjan
+ *        - 170 998-row matrix (scircuit stand-in) (170 998 rows, 958 936 edges): trim + pivot 2 296 us (2 180-2 315), 36 steps = 0.12 of Tarjan's 19 602 (14 995-31 996);
+ *          pivot round 2 167 = 2.37 of two BFS 914 (849-930); trim + colouring 4 843 = 0.25 of Tarjan
+ *        - R-MAT-23 (8 388 608 rows, 134 217 728 edges): trim + pivot 34 608 us (34 577-34 676), 19 steps = 0.010 of Tarjan's 3 442 346 (3 369 227-3 467 730);
+ *          pivot round 28 693 = 22.09 of two BFS 1 299 (1 294-1 311); trim + colouring 48 855 = 0.014 of Tarjan
+ *        A step with next to nothing to do costs 29-33 us (medians of three runs over 20 699 steps; single runs 23.5-40.2):
+ *        eight launches, seven of them empty, against 16 to 25 us of a sh_bfs_levels step.  The power-law 10 M / 200 M
+ *        matrix has no run on record.
+ *        Rule: call it, with trim and pivot on (the defaults), on graphs of small diameter: R-MAT-23 is settled 100
+ *        times faster than by the host Tarjan, the 170 998-row matrix 8 times.  Never turn pivot off when a giant
+ *        component is expected (the colouring round costs 1.5 to 6 times the pivot round).  Do NOT call it on high-diameter
+ *        graphs -- grids, meshes, road networks: about 31 us per hop of the diameter, twice over; the 2048 x 2048 grid
+ *        LOSES to the host Tarjan by 3.7 and by 22 without the pivot round -- nor on long chains of components.  The pivot
+ *        round itself loses to the two-BFS yardstick everywhere, by 22 on R-MAT-23 (it pushes along every edge with
+ *        atomics where the BFS goes bottom-up): for one vertex' reach alone call sh_bfs_levels.  In a trim sweep a list
+ *        longer than 32 entries is searched by one wave without pieces: a hub whose neighbours are all settled costs that
+ *        wave a walk of the whole list.  The power-law matrix is unmeasured.
+ *
+ * sh_scc_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  The matrix is square (rows x rows);
+ * col_idx outside [0, rows) and stored zeros are legal and are no edges.  The handle holds on the device: the edge pattern
+ * by rows and its transpose as sh_bfs_graph does, one colour and one stamp word per vertex, two work lists and the trim's
+ * candidate list of `rows` entries (a vertex enters a list at most once per sweep, so no list can overflow on any input),
+ * two lists of pieces of long out-lists and two of long in-lists, the pieces of long rows, a control block.
+ * rows == 0 gives a valid handle.  Freeing NULL is SH_OK.
+ * sh_scc_graph_footprint: device bytes held =
+ *     8 * (rows + 1) + 8 * edges + 20 * rows + 32 * (edges / 1024 + 1) + 8 * (edges / 2048 + 1) + 34816.
+ * sh_scc_graph_edges: the entries kept as edges.
+ *
+ * sh_scc: comp: an int32 vector of >= rows elements, written in full.  g may serve any number of calls, one at a time.
+ * max_steps >= 1.  The per-round arrays (each may be NULL) have capacity max_steps; one entry per recorded round:
+ * size_per_round = vertices the round settled; steps_per_round, edges_per_round (edges looked at), ns_per_round and
+ * total_ns are informational (the sweeps race, so their number may differ from run to run); ns_per_round / total_ns are
+ * device time (hipEvent) as elsewhere, total_ns also holds the set-up launch and the trim rounds that settled nothing.
+ * The steps are enqueued ahead of the host, 8 at first and up to 32 at a time: every step is a fixed set of eight launches
+ * (trim in two phases, pivot choice, seed, propagation, claim, label, one small launch that closes the step) that return
+ * at once unless the device-side control block gives them work; the host reads the control block once per batch.
+ * No kernel ever waits for another kernel's write.
+ * SH_EINVAL: NULL arguments, rows < 0, nnz < 0, max_steps < 1.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a
+ * row_ptr that decreases, comp shorter than rows.  All are reported before any device work.
+ * NOT covered: the other semirings, row pieces (sh_spmv_step_pieces), the multi-GPU driver, the C++ harness apps
+ * (scc_harness keeps the reference's vector), weakly connected components, a serial tail for long chains.
+ */
+typedef struct sh_scc_graph sh_scc_graph;
+int sh_scc_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_scc_graph **out);
+int sh_scc_graph_free(sh_engine *e, sh_scc_graph *g);
+int sh_scc_graph_footprint(const sh_scc_graph *g, uint64_t *device_bytes);
+int sh_scc_graph_edges(const sh_scc_graph *g, int64_t *edges);
+int sh_scc(sh_engine *e, sh_scc_graph *g, sh_vec *comp, int32_t trim, int32_t pivot, int32_t max_steps,
+           int64_t *components, int64_t *settled, int64_t *trimmed, int32_t *rounds, int32_t *steps, int32_t *complete,
+           int32_t *kind_per_round, int64_t *size_per_round, int32_t *steps_per_round, int64_t *edges_per_round,
+           uint64_t *ns_per_round, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,13 @@ SIGNATURES = {
     "sh_sssp_graph_delta": (_int, [_vp, C.POINTER(C.c_double)]),
     "sh_sssp": (_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64),
                        C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "sh_scc_graph_create": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _pp]),
+    "sh_scc_graph_free": (_int, [_vp, _vp]),
+    "sh_scc_graph_footprint": (_int, [_vp, C.POINTER(_u64)]),
+    "sh_scc_graph_edges": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_scc": (_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32),
+                      C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64),
+                      C.POINTER(_u64), C.POINTER(_u64)]),
 }
 
 _lib = None

@@ -13,6 +13,7 @@
 #include "frontier.hip.h"
 #include "bfs.hip.h"
 #include "sssp.hip.h"
+#include "scc.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -1823,7 +1824,7 @@ static int build_transpose(sh_engine *e, DevArrays &tmp, const int32_t *ptr, con
   return SH_OK;
 }
 
-// What sh_bfs_graph and sh_sssp_graph share: the edges by row (in_*) and by source vertex (out_*), the static pieces of
+// What sh_bfs_graph, sh_sssp_graph and sh_scc_graph share: the edges by row (in_*) and by source vertex (out_*), the static pieces of
 // the long rows, and what a batch of gated steps needs (run_batches).
 template <class Ctl>
 struct GraphHandle {
@@ -1844,7 +1845,7 @@ struct GraphHandle {
   }
 };
 
-// What the scalars and the host arrays of fn = sh_bfs_graph_create / sh_sssp_graph_create alone decide: no device is
+// What the scalars and the host arrays of fn = sh_bfs_graph_create / sh_sssp_graph_create / sh_scc_graph_create alone decide: no device is
 // needed to be told.
 static int check_host_csr(sh_engine *e, const char *fn, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                           const void *val, const void *out) {
@@ -1936,7 +1937,7 @@ static int open_control(sh_engine *e, GraphHandle<Ctl> *g, int64_t ctl_bytes, in
   return SH_OK;
 }
 
-// The loop of sh_bfs_levels and sh_sssp: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// The loop of sh_bfs_levels, sh_sssp and sh_scc: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
 // next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
 // enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
 // step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
@@ -2516,6 +2517,153 @@ int sh_sssp(sh_engine *e, sh_sssp_graph *g, const sh_vec *x0, sh_vec *dist, sh_v
   *buckets = (int32_t)g->h_ctl->buckets;
   *reached = (int64_t)g->h_ctl->reached;
   *relaxed = (int64_t)g->h_ctl->relaxed;
+  *complete = done ? 1 : 0;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- strongly connected components by trim, pivot and colouring (scc.hip.h) ------------------------------------------
+struct sh_scc_graph : GraphHandle<SccCtl> {   // d_ctl: SCC_CTL_BYTES, followed by the WlParts and the pivot candidates
+  uint32_t *d_colour = nullptr, *d_stamp = nullptr, *d_list[2] = {nullptr, nullptr}, *d_cand = nullptr;
+  WlPiece *d_opieces[2] = {nullptr, nullptr}, *d_ipieces[2] = {nullptr, nullptr};   // pieces of the long out- / in-lists of list 0 / 1
+  SccPick *d_pick = nullptr;
+};
+static_assert(sizeof(SccCtl) <= SCC_CTL_BYTES, "the control block is accounted as SCC_CTL_BYTES (sh_scc_graph_footprint)");
+static_assert(sizeof(WlPart) * SCC_MAX_BLOCKS == SCC_PART_BYTES, "one WlPart per workgroup");
+static_assert(sizeof(SccPick) * SCC_MAX_BLOCKS == SCC_PICK_BYTES, "one SccPick per workgroup");
+
+extern "C" {
+
+int sh_scc_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_scc_graph **out) {
+  if (out) *out = nullptr;
+  int rc = check_host_csr(e, "sh_scc_graph_create", rows, nnz, row_ptr, col_idx, val, out);
+  if (rc)
+    return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  std::unique_ptr<sh_scc_graph> g(new (std::nothrow) sh_scc_graph());
+  if (!g)
+    return fail(e, SH_ENOMEM, "out of host memory");
+  if ((rc = build_edge_lists<BfsKeep, SCC_ROW_PIECE>(e, g.get(), rows, nnz, row_ptr, col_idx, val, false)))
+    return rc;
+  const int64_t E = g->edges;
+  HIP_TRY(e, g->dev.alloc(&g->d_colour, rows * 4));
+  HIP_TRY(e, g->dev.alloc(&g->d_stamp, rows * 4));
+  HIP_TRY(e, g->dev.alloc(&g->d_cand, rows * 4));
+  for (int i = 0; i < 2; i++) {
+    HIP_TRY(e, g->dev.alloc(&g->d_list[i], rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->d_opieces[i], (E / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: lists longer than 2048
+    HIP_TRY(e, g->dev.alloc(&g->d_ipieces[i], (E / 1024 + 1) * sizeof(WlPiece)));
+  }
+  if ((rc = open_control(e, g.get(), SCC_CTL_BYTES, SCC_CTL_BYTES + SCC_PART_BYTES + SCC_PICK_BYTES)))
+    return rc;
+  g->d_pick = (SccPick *)((char *)g->d_ctl + SCC_CTL_BYTES + SCC_PART_BYTES);
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  *out = g.release();
+  return SH_OK;
+}
+
+int sh_scc_graph_free(sh_engine *e, sh_scc_graph *g) { return free_handle(e, g); }
+
+int sh_scc_graph_footprint(const sh_scc_graph *g, uint64_t *device_bytes) {
+  if (!g || !device_bytes)
+    return SH_EINVAL;
+  *device_bytes = (uint64_t)g->dev.bytes;
+  return SH_OK;
+}
+
+int sh_scc_graph_edges(const sh_scc_graph *g, int64_t *edges) {
+  if (!g || !edges)
+    return SH_EINVAL;
+  *edges = g->edges;
+  return SH_OK;
+}
+
+int sh_scc(sh_engine *e, sh_scc_graph *g, sh_vec *comp, int32_t trim, int32_t pivot, int32_t max_steps,
+           int64_t *components, int64_t *settled, int64_t *trimmed, int32_t *rounds, int32_t *steps, int32_t *complete,
+           int32_t *kind_per_round, int64_t *size_per_round, int32_t *steps_per_round, int64_t *edges_per_round,
+           uint64_t *ns_per_round, uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (max_steps < 1)
+    return fail(e, SH_EINVAL, "sh_scc: max_steps = %d, must be at least 1", (int)max_steps);
+  if (!e || !g || !comp || !components || !settled || !trimmed || !rounds || !steps || !complete)
+    return fail(e, SH_EINVAL, "sh_scc: NULL argument (engine, graph, comp, components, settled, trimmed, rounds, steps or complete)");
+  const int64_t rows = g->rows;
+  if (comp->n < rows)
+    return fail(e, SH_ESHAPE, "sh_scc: comp is shorter than the graph's %lld rows", (long long)rows);
+  *components = 0; *settled = 0; *trimmed = 0; *rounds = 0; *steps = 0; *complete = 1;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, SCC_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
+  const SccGraph G{(int32_t)rows, g->d_in_ptr, g->d_in_col, g->d_out_ptr, g->d_out_row};
+  const SccLists L{g->d_list[0], g->d_list[1], g->d_cand, g->d_opieces[0], g->d_opieces[1], g->d_ipieces[0], g->d_ipieces[1]};
+  int32_t *c = (int32_t *)comp->d;
+  uint64_t total = 0;
+  // every vertex live, the stamps cleared, the first phase chosen
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, SCC_CTL_BYTES, e->stream));
+  hipLaunchKernelGGL(scc_init, grid, block, 0, e->stream, (int32_t)rows, c, g->d_stamp);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(scc_decide, dim3(1), block, 0, e->stream, g->d_ctl, 0, -1, nblocks, g->d_part, (int32_t)rows, trim != 0 ? 1 : 0,
+                     pivot != 0 ? 1 : 0);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  int32_t it = 0, n_rounds = 0;
+  bool done = false;
+  // the eight launches of a step: each returns at once unless the control block says the step is in its phase
+  const auto enqueue = [&](int s, int k) {
+    for (int phase = 0; phase < 2; phase++) {
+      hipLaunchKernelGGL(scc_trim, grid, block, 0, e->stream, g->d_ctl, s, phase, G, L, c, g->d_stamp, g->d_part);
+      HIP_TRY(e, hipGetLastError());
+    }
+    hipLaunchKernelGGL(scc_pick, grid, block, 0, e->stream, g->d_ctl, s, G, c, g->d_pick);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(scc_seed, grid, block, 0, e->stream, g->d_ctl, s, nblocks, G, L, c, g->d_colour, g->d_pick);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(scc_propagate, grid, block, 0, e->stream, g->d_ctl, s, G, L, c, g->d_colour, g->d_stamp, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(scc_claim, grid, block, 0, e->stream, g->d_ctl, s, G, L, c, g->d_colour, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(scc_label, grid, block, 0, e->stream, g->d_ctl, s, (int32_t)rows, c, g->d_colour, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(scc_decide, dim3(1), block, 0, e->stream, g->d_ctl, k, s, nblocks, g->d_part, (int32_t)rows, 0, 0);
+    HIP_TRY(e, hipGetLastError());
+    return (int)SH_OK;
+  };
+  // the steps of one round add up; a round that settled nothing (a trim round that found nothing to trim) is not recorded
+  struct { int32_t id = -1, kind = 0, steps = 0; int64_t size = 0, edges = 0; uint64_t ns = 0; } cur;
+  const auto flush = [&]() {
+    if (cur.id >= 0 && cur.size > 0) {
+      if (kind_per_round) kind_per_round[n_rounds] = cur.kind;
+      if (size_per_round) size_per_round[n_rounds] = cur.size;
+      if (steps_per_round) steps_per_round[n_rounds] = cur.steps;
+      if (edges_per_round) edges_per_round[n_rounds] = cur.edges;
+      if (ns_per_round) ns_per_round[n_rounds] = cur.ns;
+      n_rounds++;
+    }
+  };
+  const auto take = [&](int, const SccRec &rc, uint64_t step_ns) {
+    if (rc.round != cur.id) {
+      flush();
+      cur.id = rc.round; cur.kind = rc.kind; cur.steps = 0; cur.size = 0; cur.edges = 0; cur.ns = 0;
+    }
+    cur.steps++; cur.size += (int64_t)rc.settled; cur.edges += (int64_t)rc.edges; cur.ns += step_ns;
+  };
+  const int rc = run_batches(e, "sh_scc: step", g, max_steps, &it, &done, &total, enqueue, take);
+  if (rc)
+    return rc;
+  flush();
+  *components = (int64_t)g->h_ctl->components;
+  *settled = (int64_t)g->h_ctl->settled;
+  *trimmed = (int64_t)g->h_ctl->trimmed;
+  *rounds = n_rounds;
+  *steps = it;
   *complete = done ? 1 : 0;
   if (total_ns)
     *total_ns = total;

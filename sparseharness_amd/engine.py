@@ -204,6 +204,33 @@ class SsspGraph:
             self.h = None
 
 
+class SccGraph:
+    """What Engine.scc searches: the edge pattern of a square matrix by rows and its transpose, colours, work lists
+    (made from the host CSR arrays alone; needs no CsrMatrix)."""
+
+    def __init__(self, engine, handle, n):
+        self.engine, self.h, self.n = engine, handle, n
+
+    @property
+    def edges(self):
+        """Entries kept as edges (non-zero value bits, column inside the matrix)."""
+        k = C.c_int64()
+        self.engine._chk(abi.load().sh_scc_graph_edges(self.h, C.byref(k)))
+        return k.value
+
+    @property
+    def footprint(self):
+        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
+        b = C.c_uint64()
+        self.engine._chk(abi.load().sh_scc_graph_footprint(self.h, C.byref(b)))
+        return b.value
+
+    def free(self):
+        if self.h is not None:
+            abi.load().sh_scc_graph_free(self.engine.h, self.h)
+            self.h = None
+
+
 class Engine:
     """One HIP device + one stream (replaces Harness's OpenCL context/queue)."""
 
@@ -397,6 +424,35 @@ class Engine:
         n = rounds.value
         return (n, buckets.value, reached.value, bool(complete.value), relaxed.value, sizes[:n].copy(), edges[:n].copy(),
                 per[:n].copy(), total.value)
+
+    # ---- strongly connected components: comp[v] = the largest vertex index of v's component
+    def scc_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.scc needs, from the CSR arrays of a square matrix."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        val = np.ascontiguousarray(val)
+        assert val.dtype.itemsize == 4
+        h = C.c_void_p()
+        self._chk(abi.load().sh_scc_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
+                                                 C.byref(h)))
+        return SccGraph(self, h, len(row_ptr) - 1)
+
+    def scc(self, G, comp, trim=True, pivot=True, max_steps=1 << 20):
+        """-> (components, settled, trimmed, rounds, steps, complete, kinds, sizes, steps_per, edges, ns, total_ns); per
+        round: 0 trim / 1 pivot / 2 colouring, vertices it settled, its steps, edges it looked at, device ns."""
+        components, settled, trimmed = C.c_int64(), C.c_int64(), C.c_int64()
+        rounds, steps, complete, total = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+        cap = max(int(max_steps), 1)
+        kinds, sizes, steps_per = np.zeros(cap, np.int32), np.zeros(cap, np.int64), np.zeros(cap, np.int32)
+        edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        self._chk(abi.load().sh_scc(self.h, G.h, comp.h, int(bool(trim)), int(bool(pivot)), max_steps, C.byref(components),
+                                    C.byref(settled), C.byref(trimmed), C.byref(rounds), C.byref(steps), C.byref(complete),
+                                    kinds.ctypes.data_as(i32p), sizes.ctypes.data_as(i64p), steps_per.ctypes.data_as(i32p),
+                                    edges.ctypes.data_as(i64p), per.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)))
+        n = rounds.value
+        return (components.value, settled.value, trimmed.value, n, steps.value, bool(complete.value), kinds[:n].copy(),
+                sizes[:n].copy(), steps_per[:n].copy(), edges[:n].copy(), per[:n].copy(), total.value)
 
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):

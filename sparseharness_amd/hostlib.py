@@ -1,6 +1,7 @@
 """ctypes face of libsparseharness_host.so (no HIP): the product's MatrixMarket
-loader (host/src/sparse_matrix.cpp) and the seeded synthetic generators
-(host/src/synth.cpp) that define the benchmark configs of BASELINE.json."""
+loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
+(host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
+host gold of sh_scc (host/src/scc_labels.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -42,6 +43,8 @@ def load():
         _lib.sh_synth_rmat.restype = C.c_int
         _lib.sh_synth_rmat.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.sh_scc_labels.restype = C.c_int
+        _lib.sh_scc_labels.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.sh_mm_load.restype = C.c_int
         _lib.sh_mm_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]
         _lib.sh_mm_load_ex.restype = C.c_int
@@ -83,6 +86,21 @@ def rmat(scale, edge_factor=16, a=0.57, b=0.19, c=0.19, seed=SEED_RMAT, permute=
 def scircuit_like(seed=SEED_SCIRCUIT):
     """Stand-in of SuiteSparse scircuit's shape (config 2): 170 998 rows, 958 936 entries, max row 353."""
     return powerlaw(170_998, 958_936, dmax=353, seed=seed)
+
+
+def scc_labels(row_ptr, col_idx, val):
+    """label[v] = the largest vertex index of v's strongly connected component (Engine.scc's comp), by a single-threaded
+    Tarjan on the host.  Entry (r, c) is the edge c -> r when 0 <= c < rows and its 32 value bits are not all zero."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    val = np.ascontiguousarray(val)
+    assert val.dtype.itemsize == 4 and len(val) == len(col_idx)
+    n = len(row_ptr) - 1
+    label = np.empty(n, np.int32)
+    rc = load().sh_scc_labels(n, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), _p(label))
+    if rc:
+        raise RuntimeError(f"sh_scc_labels failed: {rc}")
+    return label
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
