@@ -694,7 +694,8 @@ int sh_sssp(sh_engine *e, sh_sssp_graph *g, const sh_vec *x0, sh_vec *dist, sh_v
  * SH_EINVAL: NULL arguments, rows < 0, nnz < 0, max_steps < 1.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a
  * row_ptr that decreases, comp shorter than rows.  All are reported before any device work.
  * NOT covered: the other semirings, row pieces (sh_spmv_step_pieces), the multi-GPU driver, the C++ harness apps
- * (scc_harness keeps the reference's vector), weakly connected components, a serial tail for long chains.
+ * (scc_harness keeps the reference's vector), a serial tail for long chains.  (What hangs together regardless of direction, the weakly connected
+ * components, is sh_wcc's: below and DESIGN.md 6h.)
  */
 typedef struct sh_scc_graph sh_scc_graph;
 int sh_scc_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
@@ -705,6 +706,107 @@ int sh_scc_graph_edges(const sh_scc_graph *g, int64_t *edges);
 int sh_scc(sh_engine *e, sh_scc_graph *g, sh_vec *comp, int32_t trim, int32_t pivot, int32_t max_steps,
            int64_t *components, int64_t *settled, int64_t *trimmed, int32_t *rounds, int32_t *steps, int32_t *complete,
            int32_t *kind_per_round, int64_t *size_per_round, int32_t *steps_per_round, int64_t *edges_per_round,
+           uint64_t *ns_per_round, uint64_t *total_ns);
+
+/* ---- weakly connected components by hooking roots and pointer jumping: extends the SCC loop of HarnessSCC::executeRun
+ *      (app/scc.cpp:96-176) and Harness::executeKernel (inc/harness.h:149-195); the reference has no counterpart of the
+ *      calls below.  sh_wcc answers which vertices hang together at all: hooking and pointer jumping (Shiloach, Vishkin
+ *      1982) with neighbour sampling and a skip of the largest tree (Sutton, Ben-Nun, Barak, "Afforest", IPDPS 2018).  It
+ *      is the first search here that does not pay per hop of the diameter.
+ *
+ *      The edge rule is that of sh_bfs_levels / sh_scc: row r storing column c with 0 <= c < rows and a value whose 32
+ *      bits are not all zero is an EDGE.  Here its direction is ignored.  Self-loops, parallel edges, stored zeros and
+ *      columns outside the matrix are legal and change nothing.
+ *        comp[v]     = the largest vertex index of v's weak component (the convention of sh_scc): canonical, so
+ *                      comparable with ==.  On a pattern that holds c -> r whenever it holds r -> c, sh_wcc's comp equals
+ *                      sh_scc's.  After an incomplete run (*complete == 0: max_rounds used up) comp is -1 EVERYWHERE,
+ *                      because a half-built forest is not a partition; the handle is still good for another call.
+ *        *components = the number of v with comp[v] == v; *skipped = the number of vertices whose lists the full rounds
+ *                      did not walk (0 when sample == 0).
+ *      The result does not depend on sample, the schedule or the run.
+ *
+ *      State: one parent word p[v] per vertex, p[v] >= v always, so there are no cycles and a root (p[r] == r) is the
+ *      largest index of its tree.  A HOOK is a compare-and-swap on a root: p[lo] goes from lo to hi, lo < hi; a JUMP is
+ *      p[v] = p[p[v]].  So trees only ever merge, never split; no pointer of a non-root is ever raised by an atomic max.
+ *      A ROUND is one fixed set of launches; kind_per_round is 0 (a sampling round) or 1 (a full round).
+ *        1. p[v] = v.
+ *        2. SAMPLING ROUNDS j = 0 .. sample - 1: every vertex hooks along the j-th stored edge of its row, if it has one;
+ *           then up to 6 jumping launches over all rows (at most 8 jumps per vertex each), each of which returns at once
+ *           unless the one before it changed a pointer.
+ *        3. PICK AND COMPACT, only if sample > 0, in front of the first full round: L = the most frequent parent among the
+ *           1024 vertices v = i * rows / 1024, ties to the larger index (deterministic for a given forest; a sample, so it
+ *           may pick any tree, and the result never depends on which).  S = { v : p[v] == L } is fixed here, once.  The
+ *           vertices outside S are compacted into one work list, their long in-lists and long out-lists into two piece
+ *           lists.  With sample == 0, S is empty and the list is every vertex.
+ *        4. FULL ROUNDS: for every entry of the in-lists AND of the out-lists of the work list's vertices, hook the two
+ *           ends (an edge with one end in S is stored in the row of either end and only the other end walks; edges inside
+ *           S are never looked at); then the jumping launches, over all rows.  A hook climbs from the smaller of the two
+ *           ancestors it holds, and retries after a failed compare-and-swap, at most 8 times in all; an entry it could
+ *           not settle is left to the next round and counted, so the run cannot end over it.
+ *        5. Stop after a full round that found both ends of every walked entry under one parent, hooked nothing and
+ *           jumped nothing.  comp[v] = p[v].
+ *      Why that is right: pointers never leave a component.  The last round wrote nothing, so what it saw is one state:
+ *      every tree a star, every walked edge with both ends under one root.  S sits in one tree.  So a component is one
+ *      star, and its root is its largest index.
+ *      Worst cases: the number of rounds grows with log(rows) while the lanes' races are won at random, not with the
+ *      diameter (a path of 65 536 vertices: 2 to 9 rounds).  Hooking on roots only needs many rounds when ONE root is
+ *      wanted by many larger ones and the smallest keeps winning: a vertex of smallest index whose k neighbours hook in
+ *      ascending order settles 8 of them per round, k / 8 rounds (not seen in a run: which lane wins is arbitrary, and
+ *      the wanted set then about halves per try).  Every tree of larger index that joins a star re-roots it: all its
+ *      members jump again.  A round's jumping launches halve every depth six times at least; what is left is jumped in
+ *      the next round.  Every round costs its ten launches, the empty ones included.  max_rounds bounds the call.
+ *
+ *      Measured on an MI355X (DESIGN.md "6h Weakly connected components", profiles/wcc_scircuit.json; tools/wcc_bench.py,
+ *        one process per matrix, arms alternating, 5 rounds, device time in us as median (min-max); union-find = wall
+ *        time of hostlib.wcc_labels; sh_scc with trim and pivot on the matrix plus its transpose):
+ *        - 170 998-row matrix (scircuit stand-in) (170 998 rows, 958 936 edges, one component): sample 0: 303 us
+ *          (286-345), 2 rounds; sample 1: 326 (320-328), 3 rounds; sample 2: 218 (208-248), 4 rounds, 170 969 vertices
+ *          skipped, 272 987 entries looked at instead of 3 835 744 = 0.053 of the union-find's 4 135 (4 008-4 152);
+ *          sample 4: 266 (254-269), 6 rounds.  On the symmetric pattern (1 917 872 edges): sh_wcc sample 2 207
+ *          (186-234) = 0.096 of sh_scc's 2 161 (2 116-2 164, 18 steps).
+ *        - the 2048 x 2048 grid and R-MAT-23 have no run on record: unmeasured.
+ *        From the tests (single runs): a path of 65 536 vertices 2-9 rounds, 87-420 us; the 128 x 128 grid 2-3 rounds.
+ *        A round with next to nothing to do costs about 25 us (ten launches).
+ *        Rule: for what hangs together regardless of direction call sh_wcc, not sh_scc on a symmetrised pattern: on the
+ *        one matrix measured it is 10 times faster on the same input and takes half the device memory.  Keep the
+ *        default sample = 2: it is the fastest of 0, 1, 2, 4 there (one sampled neighbour leaves the largest tree too
+ *        small to skip, four cost two more rounds than they save).  A call is at least sample + 1 rounds of about 25 us each, whatever
+ *        the graph.  Whether the grid wins against the host
+ *        union-find and what the skip saves on R-MAT-23 is not known: both are unmeasured.
+ *
+ * sh_wcc_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  The matrix is square (rows x rows).
+ * The handle holds on the device: the edge pattern by rows and its transpose as sh_bfs_graph does, one parent word per
+ * vertex, one work list of `rows` entries (a vertex enters it at most once per call, so it cannot overflow on any input),
+ * one list of pieces of long in-lists and one of long out-lists, the pieces of long rows, a control block.
+ * rows == 0 gives a valid handle.  Freeing NULL is SH_OK.
+ * sh_wcc_graph_footprint: device bytes held =
+ *     8 * (rows + 1) + 8 * edges + 8 * rows + 16 * (edges / 1024 + 1) + 8 * (edges / 2048 + 1) + 34816.
+ * sh_wcc_graph_edges: the entries kept as edges.
+ *
+ * sh_wcc: comp: an int32 vector of >= rows elements, written in full.  g may serve any number of calls, one at a time.
+ * sample >= 0: the number of stored neighbours per vertex that the sampling rounds look at (the Python binding's default
+ * is 2).  max_rounds >= 1.  The per-round arrays (each may be NULL) have capacity max_rounds, one entry per round:
+ * hooks_per_round (compare-and-swaps won), jumps_per_round (pointers changed), edges_per_round (entries looked at),
+ * ns_per_round, total_ns and *rounds itself are informational: the lanes race, so they may differ from run to run.
+ * ns_per_round / total_ns are device time (hipEvent) as elsewhere; total_ns also holds the set-up and the labelling launch.
+ * The rounds are enqueued ahead of the host, 8 at first and up to 32 at a time: every round is a fixed set of ten launches
+ * (sampling hooks, pick and compaction, the full walk, six jumping launches, one small launch that closes the round) that
+ * return at once unless the device-side control block gives them work; the host reads the control block once per batch.
+ * No kernel ever waits for another kernel's write, and no lane spins on a word until another lane writes it.
+ * SH_EINVAL: NULL arguments, rows < 0, nnz < 0, sample < 0, max_rounds < 1.  SH_ESHAPE: row_ptr[0] != 0,
+ * row_ptr[rows] != nnz or a row_ptr that decreases, comp shorter than rows.  All are reported before any device work.
+ * NOT covered: the multi-GPU driver, row pieces (sh_spmv_step_pieces), the C++ harness apps, component sizes or a
+ * histogram, incremental updates.
+ */
+typedef struct sh_wcc_graph sh_wcc_graph;
+int sh_wcc_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_wcc_graph **out);
+int sh_wcc_graph_free(sh_engine *e, sh_wcc_graph *g);
+int sh_wcc_graph_footprint(const sh_wcc_graph *g, uint64_t *device_bytes);
+int sh_wcc_graph_edges(const sh_wcc_graph *g, int64_t *edges);
+int sh_wcc(sh_engine *e, sh_wcc_graph *g, sh_vec *comp, int32_t sample, int32_t max_rounds,
+           int64_t *components, int64_t *skipped, int32_t *rounds, int32_t *complete,
+           int32_t *kind_per_round, int64_t *hooks_per_round, int64_t *jumps_per_round, int64_t *edges_per_round,
            uint64_t *ns_per_round, uint64_t *total_ns);
 
 #ifdef __cplusplus

@@ -14,6 +14,7 @@
 #include "bfs.hip.h"
 #include "sssp.hip.h"
 #include "scc.hip.h"
+#include "wcc.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -1824,7 +1825,7 @@ static int build_transpose(sh_engine *e, DevArrays &tmp, const int32_t *ptr, con
   return SH_OK;
 }
 
-// What sh_bfs_graph, sh_sssp_graph and sh_scc_graph share: the edges by row (in_*) and by source vertex (out_*), the static pieces of
+// What sh_bfs_graph, sh_sssp_graph, sh_scc_graph and sh_wcc_graph share: the edges by row (in_*) and by source vertex (out_*), the static pieces of
 // the long rows, and what a batch of gated steps needs (run_batches).
 template <class Ctl>
 struct GraphHandle {
@@ -1845,7 +1846,7 @@ struct GraphHandle {
   }
 };
 
-// What the scalars and the host arrays of fn = sh_bfs_graph_create / sh_sssp_graph_create / sh_scc_graph_create alone decide: no device is
+// What the scalars and the host arrays of fn = sh_bfs_graph_create / sh_sssp_graph_create / sh_scc_graph_create / sh_wcc_graph_create alone decide: no device is
 // needed to be told.
 static int check_host_csr(sh_engine *e, const char *fn, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                           const void *val, const void *out) {
@@ -1937,7 +1938,7 @@ static int open_control(sh_engine *e, GraphHandle<Ctl> *g, int64_t ctl_bytes, in
   return SH_OK;
 }
 
-// The loop of sh_bfs_levels, sh_sssp and sh_scc: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// The loop of sh_bfs_levels, sh_sssp, sh_scc and sh_wcc: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
 // next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
 // enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
 // step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
@@ -2664,6 +2665,137 @@ int sh_scc(sh_engine *e, sh_scc_graph *g, sh_vec *comp, int32_t trim, int32_t pi
   *trimmed = (int64_t)g->h_ctl->trimmed;
   *rounds = n_rounds;
   *steps = it;
+  *complete = done ? 1 : 0;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- weakly connected components by hooking roots and pointer jumping (wcc.hip.h) ------------------------------------
+struct sh_wcc_graph : GraphHandle<WccCtl> {   // d_ctl: WCC_CTL_BYTES, followed by the WlParts of the walk and those of the jumps
+  uint32_t *d_parent = nullptr, *d_list = nullptr;
+  WlPiece *d_ipieces = nullptr, *d_opieces = nullptr;   // pieces of the long in- / out-lists of the work list's vertices
+  WlPart *d_jpart = nullptr;
+};
+static_assert(sizeof(WccCtl) <= WCC_CTL_BYTES, "the control block is accounted as WCC_CTL_BYTES (sh_wcc_graph_footprint)");
+static_assert(sizeof(WlPart) * WCC_MAX_BLOCKS == WCC_PART_BYTES, "one WlPart per workgroup");
+
+extern "C" {
+
+int sh_wcc_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_wcc_graph **out) {
+  if (out) *out = nullptr;
+  int rc = check_host_csr(e, "sh_wcc_graph_create", rows, nnz, row_ptr, col_idx, val, out);
+  if (rc)
+    return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  std::unique_ptr<sh_wcc_graph> g(new (std::nothrow) sh_wcc_graph());
+  if (!g)
+    return fail(e, SH_ENOMEM, "out of host memory");
+  if ((rc = build_edge_lists<BfsKeep, WCC_ROW_PIECE>(e, g.get(), rows, nnz, row_ptr, col_idx, val, false)))
+    return rc;
+  const int64_t E = g->edges;
+  HIP_TRY(e, g->dev.alloc(&g->d_parent, rows * 4));
+  HIP_TRY(e, g->dev.alloc(&g->d_list, rows * 4));   // a vertex joins the work list at most once per call (wcc_compact)
+  HIP_TRY(e, g->dev.alloc(&g->d_ipieces, (E / (WCC_PIECE / 2) + 1) * sizeof(WlPiece)));   // see wl_push_pieces
+  HIP_TRY(e, g->dev.alloc(&g->d_opieces, (E / (WCC_PIECE / 2) + 1) * sizeof(WlPiece)));
+  if ((rc = open_control(e, g.get(), WCC_CTL_BYTES, WCC_CTL_BYTES + 2 * WCC_PART_BYTES)))
+    return rc;
+  g->d_jpart = (WlPart *)((char *)g->d_ctl + WCC_CTL_BYTES + WCC_PART_BYTES);
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  *out = g.release();
+  return SH_OK;
+}
+
+int sh_wcc_graph_free(sh_engine *e, sh_wcc_graph *g) { return free_handle(e, g); }
+
+int sh_wcc_graph_footprint(const sh_wcc_graph *g, uint64_t *device_bytes) {
+  if (!g || !device_bytes)
+    return SH_EINVAL;
+  *device_bytes = (uint64_t)g->dev.bytes;
+  return SH_OK;
+}
+
+int sh_wcc_graph_edges(const sh_wcc_graph *g, int64_t *edges) {
+  if (!g || !edges)
+    return SH_EINVAL;
+  *edges = g->edges;
+  return SH_OK;
+}
+
+int sh_wcc(sh_engine *e, sh_wcc_graph *g, sh_vec *comp, int32_t sample, int32_t max_rounds,
+           int64_t *components, int64_t *skipped, int32_t *rounds, int32_t *complete,
+           int32_t *kind_per_round, int64_t *hooks_per_round, int64_t *jumps_per_round, int64_t *edges_per_round,
+           uint64_t *ns_per_round, uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (sample < 0)
+    return fail(e, SH_EINVAL, "sh_wcc: sample = %d, must not be negative", (int)sample);
+  if (max_rounds < 1)
+    return fail(e, SH_EINVAL, "sh_wcc: max_rounds = %d, must be at least 1", (int)max_rounds);
+  if (!e || !g || !comp || !components || !skipped || !rounds || !complete)
+    return fail(e, SH_EINVAL, "sh_wcc: NULL argument (engine, graph, comp, components, skipped, rounds or complete)");
+  const int64_t rows = g->rows;
+  if (comp->n < rows)
+    return fail(e, SH_ESHAPE, "sh_wcc: comp is shorter than the graph's %lld rows", (long long)rows);
+  *components = 0; *skipped = 0; *rounds = 0; *complete = 1;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, WCC_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
+  const WccGraph G{(int32_t)rows, g->d_in_ptr, g->d_in_col, g->d_out_ptr, g->d_out_row};
+  uint32_t *p = g->d_parent;
+  uint64_t total = 0, ns = 0;
+  // every vertex a tree of its own
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, WCC_CTL_BYTES, e->stream));
+  hipLaunchKernelGGL(wcc_init, grid, block, 0, e->stream, g->d_ctl, (int32_t)rows, sample, p);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  int32_t it = 0;
+  bool done = false;
+  // the launches of a round: each returns at once unless the control block says the round is its kind (and, for a
+  // jumping launch after the first, unless the one before it changed a pointer)
+  const auto enqueue = [&](int s, int k) {
+    hipLaunchKernelGGL(wcc_sample, grid, block, 0, e->stream, g->d_ctl, s, G, p, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(wcc_compact, grid, block, 0, e->stream, g->d_ctl, s, G, p, g->d_list, g->d_ipieces, g->d_opieces);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(wcc_full, grid, block, 0, e->stream, g->d_ctl, s, G, p, g->d_list, g->d_ipieces, g->d_opieces, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    for (int i = 0; i < WCC_SWEEPS; i++) {
+      hipLaunchKernelGGL(wcc_jump, grid, block, 0, e->stream, g->d_ctl, s, i, (int32_t)rows, p, g->d_jpart);
+      HIP_TRY(e, hipGetLastError());
+    }
+    hipLaunchKernelGGL(wcc_decide, dim3(1), block, 0, e->stream, g->d_ctl, k, s, nblocks, g->d_part, g->d_jpart);
+    HIP_TRY(e, hipGetLastError());
+    return (int)SH_OK;
+  };
+  const auto take = [&](int s, const WccRec &rc, uint64_t round_ns) {
+    if (kind_per_round) kind_per_round[s] = rc.kind;
+    if (hooks_per_round) hooks_per_round[s] = (int64_t)rc.hooks;
+    if (jumps_per_round) jumps_per_round[s] = (int64_t)rc.jumps;
+    if (edges_per_round) edges_per_round[s] = (int64_t)rc.edges;
+    if (ns_per_round) ns_per_round[s] = round_ns;
+  };
+  const int rc = run_batches(e, "sh_wcc: round", g, max_rounds, &it, &done, &total, enqueue, take);
+  if (rc)
+    return rc;
+  // the labels (or -1 everywhere) and the number of roots
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  hipLaunchKernelGGL(wcc_label, grid, block, 0, e->stream, g->d_ctl, (int32_t)rows, done ? 1 : 0, p, (int32_t *)comp->d);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(g->h_ctl, g->d_ctl, sizeof(WccCtl), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+  total += ns;
+  *components = (int64_t)g->h_ctl->components;
+  *skipped = (int64_t)g->h_ctl->skipped;
+  *rounds = it;
   *complete = done ? 1 : 0;
   if (total_ns)
     *total_ns = total;

@@ -231,6 +231,33 @@ class SccGraph:
             self.h = None
 
 
+class WccGraph:
+    """What Engine.wcc searches: the edge pattern of a square matrix by rows and its transpose, a parent word per vertex,
+    a work list (made from the host CSR arrays alone; needs no CsrMatrix)."""
+
+    def __init__(self, engine, handle, n):
+        self.engine, self.h, self.n = engine, handle, n
+
+    @property
+    def edges(self):
+        """Entries kept as edges (non-zero value bits, column inside the matrix)."""
+        k = C.c_int64()
+        self.engine._chk(abi.load().sh_wcc_graph_edges(self.h, C.byref(k)))
+        return k.value
+
+    @property
+    def footprint(self):
+        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
+        b = C.c_uint64()
+        self.engine._chk(abi.load().sh_wcc_graph_footprint(self.h, C.byref(b)))
+        return b.value
+
+    def free(self):
+        if self.h is not None:
+            abi.load().sh_wcc_graph_free(self.engine.h, self.h)
+            self.h = None
+
+
 class Engine:
     """One HIP device + one stream (replaces Harness's OpenCL context/queue)."""
 
@@ -453,6 +480,35 @@ class Engine:
         n = rounds.value
         return (components.value, settled.value, trimmed.value, n, steps.value, bool(complete.value), kinds[:n].copy(),
                 sizes[:n].copy(), steps_per[:n].copy(), edges[:n].copy(), per[:n].copy(), total.value)
+
+    # ---- weakly connected components: comp[v] = the largest vertex index of v's weak component
+    def wcc_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.wcc needs, from the CSR arrays of a square matrix."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        val = np.ascontiguousarray(val)
+        assert val.dtype.itemsize == 4
+        h = C.c_void_p()
+        self._chk(abi.load().sh_wcc_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
+                                                 C.byref(h)))
+        return WccGraph(self, h, len(row_ptr) - 1)
+
+    def wcc(self, G, comp, sample=2, max_rounds=1 << 20):
+        """-> (components, skipped, rounds, complete, kinds, hooks, jumps, edges, ns, total_ns); per round: 0 sampling /
+        1 full, compare-and-swaps won, pointers changed, entries looked at, device ns."""
+        components, skipped = C.c_int64(), C.c_int64()
+        rounds, complete, total = C.c_int32(), C.c_int32(), C.c_uint64()
+        cap = max(int(max_rounds), 1)
+        kinds, hooks, jumps = np.zeros(cap, np.int32), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+        edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
+        i64p = C.POINTER(C.c_int64)
+        self._chk(abi.load().sh_wcc(self.h, G.h, comp.h, sample, max_rounds, C.byref(components), C.byref(skipped),
+                                    C.byref(rounds), C.byref(complete), kinds.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    hooks.ctypes.data_as(i64p), jumps.ctypes.data_as(i64p), edges.ctypes.data_as(i64p),
+                                    per.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)))
+        n = rounds.value
+        return (components.value, skipped.value, n, bool(complete.value), kinds[:n].copy(), hooks[:n].copy(), jumps[:n].copy(),
+                edges[:n].copy(), per[:n].copy(), total.value)
 
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):

@@ -21,6 +21,12 @@ int sh_synth_rmat(int scale, int edge_factor, double a, double b, double c, uint
 int sh_scc_labels(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                   int32_t *label);
 
+/* The weakly connected components of a square CSR pattern (union-find, single-threaded): the gold for sh_wcc.  Entry
+ * (r, c) joins r and c when 0 <= c < rows and its 32 value bits are not all zero; label[v] (rows words) becomes the
+ * largest vertex index of v's component.  Return 0, -1 bad argument. */
+int sh_wcc_labels(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                  int32_t *label);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

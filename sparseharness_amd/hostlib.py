@@ -1,7 +1,7 @@
 """ctypes face of libsparseharness_host.so (no HIP): the product's MatrixMarket
 loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
-host gold of sh_scc (host/src/scc_labels.cpp)."""
+host golds of sh_scc (host/src/scc_labels.cpp) and sh_wcc (host/src/wcc_labels.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -45,6 +45,8 @@ def load():
                                        C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.sh_scc_labels.restype = C.c_int
         _lib.sh_scc_labels.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.sh_wcc_labels.restype = C.c_int
+        _lib.sh_wcc_labels.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.sh_mm_load.restype = C.c_int
         _lib.sh_mm_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]
         _lib.sh_mm_load_ex.restype = C.c_int
@@ -100,6 +102,21 @@ def scc_labels(row_ptr, col_idx, val):
     rc = load().sh_scc_labels(n, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), _p(label))
     if rc:
         raise RuntimeError(f"sh_scc_labels failed: {rc}")
+    return label
+
+
+def wcc_labels(row_ptr, col_idx, val):
+    """label[v] = the largest vertex index of v's weakly connected component (Engine.wcc's comp), by a single-threaded
+    union-find on the host.  Entry (r, c) joins r and c when 0 <= c < rows and its 32 value bits are not all zero."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    val = np.ascontiguousarray(val)
+    assert val.dtype.itemsize == 4 and len(val) == len(col_idx)
+    n = len(row_ptr) - 1
+    label = np.empty(n, np.int32)
+    rc = load().sh_wcc_labels(n, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), _p(label))
+    if rc:
+        raise RuntimeError(f"sh_wcc_labels failed: {rc}")
     return label
 
 
