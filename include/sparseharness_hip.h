@@ -809,6 +809,92 @@ int sh_wcc(sh_engine *e, sh_wcc_graph *g, sh_vec *comp, int32_t sample, int32_t 
            int32_t *kind_per_round, int64_t *hooks_per_round, int64_t *jumps_per_round, int64_t *edges_per_round,
            uint64_t *ns_per_round, uint64_t *total_ns);
 
+/* ---- exact triangle counts, per vertex and in total, by intersecting forward lists: extends the graph handles made from
+ *      the CSR arrays alone (sh_bfs_graph_create ... sh_wcc_graph_create above), which extend the loop of
+ *      HarnessSCC::executeRun (app/scc.cpp:96-176) and Harness::executeKernel (inc/harness.h:149-195); the reference
+ *      has no counterpart of the calls below.  In semiring words the total is the sum of (L . L) o L on (+,x), L the
+ *      oriented pattern; the mask makes the product an intersection of two sorted lists, not another SpMV.
+ *
+ *      The edge rule is that of sh_bfs_levels / sh_scc / sh_wcc: row r storing column c with 0 <= c < rows and a value
+ *      whose 32 bits are not all zero is an entry that counts.  The graph is the SIMPLE UNDIRECTED graph under those
+ *      entries: {u, v} with u != v is one edge if either row stores the other, once or many times.  Self-loops, parallel
+ *      entries, stored zeros and columns outside the matrix are legal and change nothing.  M = the number of such edges.
+ *        tri[v]      = the number of triangles {v, a, b} of that graph, an unsigned 64-bit count, written in full.
+ *        deg[v]      = the degree of v in that graph (int32).  The local clustering coefficient is then
+ *                      2 * tri / (deg * (deg - 1)), one line for the caller; there is no call for it.
+ *        *triangles  = the number of triangles = (the sum of tri[v]) / 3.
+ *      The result does not depend on order, the schedule or the run: counts are integers and integer addition is
+ *      associative, so every comparison is ==.
+ *
+ *      order = 0 orients every edge from the smaller index to the larger; order = 1 (the Python binding's default) from
+ *      the smaller (deg, index) pair to the larger.  N+(v), the forward list of v, holds the ends of the edges that leave
+ *      v, strictly ascending by index.  Under order = 1 every forward list holds at most sqrt(2M) entries: the
+ *      out-neighbours of v all have degree >= deg(v) >= |N+(v)|, so the degrees of those |N+(v)| vertices alone add up to
+ *      at least |N+(v)|^2, and all degrees add up to 2M.  Both orders give the same tri.
+ *      Schedule: a fixed number of launches, no host loop.  Every triangle has one lowest vertex a and one middle vertex
+ *      b in the orientation's order; it is found once, at the forward edge a -> b, as an element c of both N+(a) and
+ *      N+(b).  The work item is a source vertex a with its whole forward list, in one of three classes by its length n:
+ *      n <= 8: one lane (every other c of N+(a) is bisected into N+(b) in memory); 8 < n <= 512: one wave (N+(a) staged
+ *      in LDS once, every N+(b) streamed with coalesced loads, each entry bisected into the staged list); n > 512: one
+ *      workgroup, N+(a) staged in chunks of at most 2048 entries, every N+(b) of the whole list streamed against each
+ *      chunk.  A list of any length goes through the chunks: there is no further path for longer lists.
+ *      Per found c one 64-bit add to tri[c]; the hits of an edge a -> b are counted across the wave and added once to
+ *      tri[b], those of all of a's edges once to tri[a]; totals go per workgroup into partial sums that a last small launch
+ *      adds up.  With tri == NULL the adds to tri are not compiled in.
+ *      Why that is right: the order is total, so a triangle's vertices are a < b < c in one way; its edges are then b in
+ *      N+(a), c in N+(a), c in N+(b) and in no other list; the count at edge x -> y sees z in both N+(x) and N+(y), which
+ *      needs x < y < z: the edge a -> b alone, and c stands once in either list.  No kernel ever waits for another
+ *      kernel's write, and every loop is bounded by a list length.
+ *      Worst cases: under order = 0 a hub of smallest index has its whole row as its forward list (one workgroup walks
+ *      it, against every neighbour's list, once per chunk of 2048).  A dense clique costs its n^3 / 6 hits under either
+ *      order, each an atomic add when tri is wanted.  A wave takes the b of its list one after the other: forward lists
+ *      of a few entries leave most of its lanes idle.
+ *
+ *      Measured on an MI355X (DESIGN.md "6i Triangle counting"; tools/tri_bench.py, one process per matrix, arms
+ *        alternating, 5 rounds, device time against the wall time of hostlib.triangle_counts): no run is on record.
+ *        The 170 998-row matrix (scircuit stand-in), R-MAT-18 and the 2048 x 2048 grid are all unmeasured, and so is
+ *        the time of K_2400 in the tests.
+ *        Rule: the numbers support no rule yet.  By construction order = 1 bounds every forward list by sqrt(2M) and
+ *        order = 0 does not; pass tri == NULL when only the total is wanted.  Whether a call beats the host's forward
+ *        algorithm, and by how much order = 1 beats order = 0, is unmeasured.
+ *
+ * sh_tri_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  The matrix is square (rows x rows).
+ * order: 0 or 1, see above.  The handle holds on the device: fwd_ptr[rows + 1], fwd_col[M], deg[rows] and a control block
+ * (with the workgroups' partial sums); nothing else, and no transpose.  rows == 0 gives a valid handle.  Freeing NULL is
+ * SH_OK.  The build runs on the device, once: the entries that count and are no self-loops become 64-bit keys
+ * (min << bits | max, bits = those of rows - 1), a radix sort over 2 * bits bits, the first key of every run is an edge,
+ * deg is a histogram over both ends, the oriented keys (src << bits | dst) are sorted again and the row starts taken
+ * from them.  While it runs the build needs 4 * (rows + 1) + 16 * nnz + 8 bytes for the arrays as given, their flags and
+ * scan, 16 bytes per surviving entry for the keys and the sorted keys, and the sort's own scratch (rocPRIM: about one
+ * more copy of the keys); all of it is released before the call returns.  nnz is bounded as for the other handles.
+ * sh_tri_graph_footprint: device bytes held =
+ *     4 * (rows + 1) + 4 * rows + 4 * edges + 33024.
+ * sh_tri_graph_edges: M.  sh_tri_graph_max_forward: the length of the longest forward list.
+ *
+ * sh_tri: tri: NULL, or a vector of >= 2 * rows four-byte elements, 8-byte aligned, read as `rows` little-endian uint64
+ * (as the `words` per vertex of sh_bits_*: all elements are still 4 bytes); 2 * rows elements are overwritten, no more.
+ * With tri == NULL the call gives the total only and does not pay for the per-vertex adds.  deg: NULL, or an int32 vector
+ * of >= rows elements.  A per-vertex count above 2^32 needs a vertex in more than 4.29e9 triangles; no test reaches that:
+ * the high word of tri[v] is untested beyond being zero.  *triangles above 2^31 is tested (K_2400).
+ * *probes (may be NULL) is informational: the list entries the count looked at, each time it looked (the entries of N+(a)
+ * once, every streamed entry of an N+(b) once, every entry a bisection compared with).  *total_ns (may be NULL) is device
+ * time (hipEvent) as elsewhere.  g may serve any number of calls, one at a time.
+ * SH_EINVAL: NULL arguments (engine, graph, triangles, out, the arrays), rows < 0, nnz < 0, an order other than 0 or 1, a
+ * tri that is not 8-byte aligned.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases, tri
+ * shorter than 2 * rows, deg shorter than rows.  All are reported before any device work, with the buffers untouched.
+ * NOT covered: per-edge support and k-truss, the multi-GPU driver, row pieces (sh_spmv_step_pieces), the C++ harness
+ * apps, incremental updates.
+ */
+typedef struct sh_tri_graph sh_tri_graph;
+int sh_tri_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, int32_t order, sh_tri_graph **out);
+int sh_tri_graph_free(sh_engine *e, sh_tri_graph *g);
+int sh_tri_graph_footprint(const sh_tri_graph *g, uint64_t *device_bytes);
+int sh_tri_graph_edges(const sh_tri_graph *g, int64_t *edges);            /* M */
+int sh_tri_graph_max_forward(const sh_tri_graph *g, int64_t *entries);    /* the longest forward list */
+int sh_tri(sh_engine *e, sh_tri_graph *g, sh_vec *tri, sh_vec *deg,
+           uint64_t *triangles, uint64_t *probes, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,12 @@ SIGNATURES = {
     "sh_wcc_graph_edges": (_int, [_vp, C.POINTER(_i64)]),
     "sh_wcc": (_int, [_vp, _vp, _vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32),
                       C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "sh_tri_graph_create": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _pp]),
+    "sh_tri_graph_free": (_int, [_vp, _vp]),
+    "sh_tri_graph_footprint": (_int, [_vp, C.POINTER(_u64)]),
+    "sh_tri_graph_edges": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_tri_graph_max_forward": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_tri": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
 }
 
 _lib = None

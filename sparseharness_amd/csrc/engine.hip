@@ -15,6 +15,7 @@
 #include "sssp.hip.h"
 #include "scc.hip.h"
 #include "wcc.hip.h"
+#include "tri.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -2799,6 +2800,185 @@ int sh_wcc(sh_engine *e, sh_wcc_graph *g, sh_vec *comp, int32_t sample, int32_t 
   *complete = done ? 1 : 0;
   if (total_ns)
     *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- triangle counts by intersecting forward lists (tri.hip.h) -------------------------------------------------------
+struct sh_tri_graph {   // d_ctl: TRI_CTL_BYTES, followed by the TriParts of tri_count_light and those of tri_count_heavy
+  int64_t rows = 0, nnz = 0, edges = 0, max_forward = 0;
+  int32_t *d_fwd_ptr = nullptr, *d_fwd_col = nullptr;
+  uint32_t *d_deg = nullptr;
+  TriCtl *d_ctl = nullptr;
+  TriPart *d_part = nullptr;
+  DevArrays dev;
+};
+static_assert(sizeof(TriCtl) <= TRI_CTL_BYTES, "the control block is accounted as TRI_CTL_BYTES (sh_tri_graph_footprint)");
+static_assert(sizeof(TriPart) * TRI_MAX_BLOCKS == TRI_PART_BYTES, "one TriPart per workgroup");
+
+// The forward lists of a triangle handle from host CSR arrays: the entries that count and are no self-loops as sorted
+// keys, the first key of every run (the edges of the simple graph), the degrees, the oriented keys sorted again.
+// Returns with the stream synchronised: the host arrays are done with.
+static int build_forward_lists(sh_engine *e, sh_tri_graph *g, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                               const void *val, int32_t order) {
+  g->rows = rows; g->nnz = nnz;
+  DevArrays &own = g->dev;
+  HIP_TRY(e, own.alloc(&g->d_fwd_ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_deg, rows * 4));
+  HIP_TRY(e, own.alloc(&g->d_ctl, TRI_CTL_BYTES + 2 * TRI_PART_BYTES));
+  g->d_part = (TriPart *)((char *)g->d_ctl + TRI_CTL_BYTES);
+  HIP_TRY(e, hipMemsetAsync(g->d_fwd_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_deg, 0, (size_t)std::max<int64_t>(rows, 1) * 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, TRI_CTL_BYTES + 2 * TRI_PART_BYTES, e->stream));
+  // temporaries: the CSR arrays as given, flags and their scan (twice), the keys and the sorted keys (twice)
+  DevArrays tmp;
+  int32_t *t_rp = nullptr, *t_ci = nullptr;
+  uint32_t *t_val = nullptr, *t_flag = nullptr, *t_pos = nullptr;
+  uint64_t *t_key = nullptr, *t_sorted = nullptr;
+  int64_t S = 0, M = 0;   // surviving entries, edges of the simple graph
+  const int bits = 32 - __builtin_clz((unsigned)std::max<int64_t>(rows - 1, 1));   // of the largest index (rows <= 2^31 - 256)
+  const dim3 blk(WL_BS);
+  const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
+  if (rows > 0 && nnz > 0) {
+    HIP_TRY(e, tmp.alloc(&t_rp, (rows + 1) * 4));
+    HIP_TRY(e, tmp.alloc(&t_ci, nnz * 4));
+    HIP_TRY(e, tmp.alloc(&t_val, nnz * 4));
+    HIP_TRY(e, tmp.alloc(&t_flag, (nnz + 1) * 4));
+    HIP_TRY(e, tmp.alloc(&t_pos, (nnz + 1) * 4));
+    HIP_TRY(e, hipMemcpyAsync(t_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(t_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(t_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(wl_und_flag<BfsKeep>), grid_for(nnz + 1), blk, 0, e->stream, t_rp, t_ci, t_val, nnz, (int32_t)rows, t_flag);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_exclusive_sum_u32(e->stream, t_flag, t_pos, nnz + 1));
+    uint32_t n = 0;
+    HIP_TRY(e, hipMemcpy(&n, t_pos + nnz, 4, hipMemcpyDeviceToHost));
+    S = (int64_t)n;
+  }
+  if (S > 0) {
+    HIP_TRY(e, tmp.alloc(&t_key, S * 8));
+    HIP_TRY(e, tmp.alloc(&t_sorted, S * 8));
+    hipLaunchKernelGGL(wl_und_keys, grid_for(nnz), blk, 0, e->stream, t_rp, t_ci, t_flag, t_pos, nnz, (int32_t)rows, bits, t_key);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_keys_u64(e->stream, t_key, t_sorted, S, 2 * bits));
+    // (t_flag and t_pos hold nnz + 1 >= S + 1 words: they serve the run heads and their scan)
+    hipLaunchKernelGGL(wl_run_heads, grid_for(S + 1), blk, 0, e->stream, t_sorted, S, t_flag);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_exclusive_sum_u32(e->stream, t_flag, t_pos, S + 1));
+    uint32_t n = 0;
+    HIP_TRY(e, hipMemcpy(&n, t_pos + S, 4, hipMemcpyDeviceToHost));
+    M = (int64_t)n;
+  }
+  g->edges = M;
+  HIP_TRY(e, own.alloc(&g->d_fwd_col, M * 4));
+  if (M > 0) {
+    hipLaunchKernelGGL(wl_und_degrees, grid_for(S), blk, 0, e->stream, t_sorted, t_flag, S, bits, g->d_deg);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(wl_orient, grid_for(S), blk, 0, e->stream, t_sorted, t_flag, t_pos, S, bits, order, g->d_deg, t_key);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_keys_u64(e->stream, t_key, t_sorted, M, 2 * bits));
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(M, rows + 1)), blk, 0, e->stream, t_sorted, M, rows, bits, g->d_fwd_ptr, g->d_fwd_col);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(wl_max_len, dim3((unsigned)std::max(1, std::min(e->n_cus * 4, TRI_MAX_BLOCKS))), blk, 0, e->stream, g->d_fwd_ptr, rows,
+                       &g->d_ctl->max_forward);
+    HIP_TRY(e, hipGetLastError());
+  }
+  uint32_t longest = 0;
+  HIP_TRY(e, hipMemcpyAsync(&longest, &g->d_ctl->max_forward, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  g->max_forward = (int64_t)longest;
+  return SH_OK;
+}
+
+template <bool PER_VERTEX>
+static void launch_tri(sh_engine *e, sh_tri_graph *g, dim3 grid, uint64_t *tri) {
+  const dim3 block(WL_BS);
+  const TriGraph G{(int32_t)g->rows, g->d_fwd_ptr, g->d_fwd_col};
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(tri_count_light<PER_VERTEX>), grid, block, 0, e->stream, G, tri, g->d_part);
+  if (g->max_forward > TRI_WAVE)   // (a fact of the handle, known since it was built: not a host loop)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(tri_count_heavy<PER_VERTEX>), grid, block, 0, e->stream, G, tri, g->d_part + TRI_MAX_BLOCKS);
+}
+
+extern "C" {
+
+int sh_tri_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, int32_t order, sh_tri_graph **out) {
+  if (out) *out = nullptr;
+  if (order != 0 && order != 1)
+    return fail(e, SH_EINVAL, "sh_tri_graph_create: order = %d, must be 0 (by index) or 1 (by degree, then index)", (int)order);
+  int rc = check_host_csr(e, "sh_tri_graph_create", rows, nnz, row_ptr, col_idx, val, out);
+  if (rc)
+    return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  std::unique_ptr<sh_tri_graph> g(new (std::nothrow) sh_tri_graph());
+  if (!g)
+    return fail(e, SH_ENOMEM, "out of host memory");
+  if ((rc = build_forward_lists(e, g.get(), rows, nnz, row_ptr, col_idx, val, order)))
+    return rc;
+  *out = g.release();
+  return SH_OK;
+}
+
+int sh_tri_graph_free(sh_engine *e, sh_tri_graph *g) { return free_handle(e, g); }
+
+int sh_tri_graph_footprint(const sh_tri_graph *g, uint64_t *device_bytes) {
+  if (!g || !device_bytes)
+    return SH_EINVAL;
+  *device_bytes = (uint64_t)g->dev.bytes;
+  return SH_OK;
+}
+
+int sh_tri_graph_edges(const sh_tri_graph *g, int64_t *edges) {
+  if (!g || !edges)
+    return SH_EINVAL;
+  *edges = g->edges;
+  return SH_OK;
+}
+
+int sh_tri_graph_max_forward(const sh_tri_graph *g, int64_t *entries) {
+  if (!g || !entries)
+    return SH_EINVAL;
+  *entries = g->max_forward;
+  return SH_OK;
+}
+
+int sh_tri(sh_engine *e, sh_tri_graph *g, sh_vec *tri, sh_vec *deg, uint64_t *triangles, uint64_t *probes, uint64_t *total_ns) {
+  if (!e || !g || !triangles)
+    return fail(e, SH_EINVAL, "sh_tri: NULL argument (engine, graph or triangles)");
+  const int64_t rows = g->rows;
+  if (tri && tri->n < 2 * rows)
+    return fail(e, SH_ESHAPE, "sh_tri: tri holds fewer than 2 elements for each of the graph's %lld rows", (long long)rows);
+  if (deg && deg->n < rows)
+    return fail(e, SH_ESHAPE, "sh_tri: deg is shorter than the graph's %lld rows", (long long)rows);
+  if (tri && ((uintptr_t)tri->d & 7u))
+    return fail(e, SH_EINVAL, "sh_tri: tri is not aligned to 8 bytes");
+  *triangles = 0;
+  if (probes) *probes = 0;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const dim3 grid((unsigned)std::max(1, std::min(e->n_cus * 4, TRI_MAX_BLOCKS)));
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  // (the TriParts of a launch that does not run stay zero)
+  HIP_TRY(e, hipMemsetAsync(g->d_part, 0, 2 * TRI_PART_BYTES, e->stream));
+  if (tri) HIP_TRY(e, hipMemsetAsync(tri->d, 0, (size_t)rows * 8, e->stream));
+  if (deg) HIP_TRY(e, hipMemcpyAsync(deg->d, g->d_deg, (size_t)rows * 4, hipMemcpyDeviceToDevice, e->stream));
+  if (tri) launch_tri<true>(e, g, grid, (uint64_t *)tri->d);
+  else launch_tri<false>(e, g, grid, nullptr);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(tri_finish, dim3(1), dim3(WL_BS), 0, e->stream, g->d_ctl, 2 * TRI_MAX_BLOCKS, g->d_part);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  TriCtl got;
+  HIP_TRY(e, hipMemcpyAsync(&got, g->d_ctl, sizeof(TriCtl), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  uint64_t ns = 0;
+  HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+  *triangles = got.triangles;
+  if (probes) *probes = got.probes;
+  if (total_ns) *total_ns = ns;
   return SH_OK;
 }
 

@@ -290,6 +290,9 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
 
 // Exclusive prefix sum of n words on the device (rocPRIM, plan_gpu.hip); in and out are different arrays.  Waits for the stream.
 hipError_t device_exclusive_sum_u32(hipStream_t stream, const uint32_t *in, uint32_t *out, int64_t n);
+// n 64-bit keys sorted ascending by their bits [0, bits) (rocPRIM radix sort, plan_gpu.hip); in and out are different arrays.
+// Waits for the stream.
+hipError_t device_sort_keys_u64(hipStream_t stream, const uint64_t *in, uint64_t *out, int64_t n, int bits);
 
 // ---- the (or,and) semiring on bits (see bits.hip.h) -----------------------
 struct BitsHost {

@@ -1030,6 +1030,19 @@ hipError_t device_exclusive_sum_u32(hipStream_t stream, const uint32_t *in, uint
   return r;
 }
 
+// n 64-bit keys by their bits [0, bits), ascending (sh_tri_graph_create: the edge keys, twice).  in and out are different
+// arrays; `in` is left as it was.  Waits for the stream.
+hipError_t device_sort_keys_u64(hipStream_t stream, const uint64_t *in, uint64_t *out, int64_t n, int bits) {
+  if (n <= 0) return hipSuccess;
+  CubTemp tmp;
+  size_t bytes = 0;
+  hipError_t r = rocprim::radix_sort_keys((void *)nullptr, bytes, in, out, (size_t)n, 0u, (unsigned)bits, stream);
+  if (r == hipSuccess) r = tmp.reserve(bytes);
+  if (r == hipSuccess) r = rocprim::radix_sort_keys(tmp.p, bytes, in, out, (size_t)n, 0u, (unsigned)bits, stream);
+  if (r == hipSuccess) r = hipStreamSynchronize(stream);   // (the temporary storage dies here)
+  return r;
+}
+
 int build_bits_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *d_rp, const int32_t *d_ci,
                         const uint32_t *d_val, BitsHost &H, uint32_t **d_ent, std::string &why) {
   H.n_rr = (int32_t)std::max<int64_t>(1, (rows + BITS_BR - 1) / BITS_BR);

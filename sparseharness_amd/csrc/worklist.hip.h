@@ -241,4 +241,88 @@ __global__ __launch_bounds__(WL_BS) void wl_transpose_scatter(const int32_t *__r
   if (w) out_w[at] = w[j];
 }
 
+// ---- building the handle of sh_tri (once): the simple undirected graph under the entries, oriented, every forward
+// list strictly ascending.  An edge {u, v} is one 64-bit key (first << bits | second), `bits` = the bits of rows - 1, so
+// that a radix sort looks at 2 * bits bits only (the sorts and scans are rocPRIM's, in plan_gpu.hip).
+// The row of entry j: the last r with row_ptr[r] <= j (one-off work, as in wl_transpose_scatter).
+__device__ __forceinline__ int32_t wl_row_of(const int32_t *__restrict__ row_ptr, int32_t rows, int64_t j) {
+  int32_t lo = 0, hi = rows;
+  while (hi - lo > 1) {
+    const int32_t mid = lo + (hi - lo) / 2;
+    if ((int64_t)row_ptr[mid] <= j) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// flag[j] = entry j counts (wl_edge_flag's rule) and is no self-loop (flag[nnz] = 0 closes the scan)
+template <class KEEP>
+__global__ __launch_bounds__(WL_BS) void wl_und_flag(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
+                                                     const uint32_t *__restrict__ val, int64_t nnz, int32_t rows,
+                                                     uint32_t *__restrict__ flag) {
+  const int64_t j = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (j < nnz) {
+    const int32_t c = col_idx[j];
+    flag[j] = (KEEP::value(val[j]) && (uint32_t)c < (uint32_t)rows && c != wl_row_of(row_ptr, rows, j)) ? 1u : 0u;
+  } else if (j == nnz) flag[j] = 0u;
+}
+// pos = exclusive scan of flag: survivor j -> key[pos[j]] = (min(r, c) << bits | max(r, c))
+__global__ __launch_bounds__(WL_BS) void wl_und_keys(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col_idx,
+                                                     const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                                                     int64_t nnz, int32_t rows, int bits, uint64_t *__restrict__ key) {
+  const int64_t j = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (j < nnz && flag[j]) {
+    const uint32_t r = (uint32_t)wl_row_of(row_ptr, rows, j), c = (uint32_t)col_idx[j];
+    key[pos[j]] = ((uint64_t)min(r, c) << bits) | (uint64_t)max(r, c);
+  }
+}
+// head[i] = sorted key i is the first of its run: one per edge of the simple graph (head[n] = 0 closes the scan)
+__global__ __launch_bounds__(WL_BS) void wl_run_heads(const uint64_t *__restrict__ key, int64_t n, uint32_t *__restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (i < n) head[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
+  else if (i == n) head[i] = 0u;
+}
+// deg as a histogram over both ends of every edge (deg zeroed by the host)
+__global__ __launch_bounds__(WL_BS) void wl_und_degrees(const uint64_t *__restrict__ key, const uint32_t *__restrict__ head, int64_t n,
+                                                        int bits, uint32_t *__restrict__ deg) {
+  const int64_t i = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (i < n && head[i]) {
+    wl_add(&deg[key[i] >> bits], 1u);
+    wl_add(&deg[key[i] & ((1ull << bits) - 1ull)], 1u);
+  }
+}
+// Edge i of the simple graph (pos = exclusive scan of head) -> okey[pos[i]] = (src << bits | dst).  order 0: from the
+// smaller index to the larger; order 1: from the smaller (deg, index) pair to the larger.
+__global__ __launch_bounds__(WL_BS) void wl_orient(const uint64_t *__restrict__ key, const uint32_t *__restrict__ head,
+                                                   const uint32_t *__restrict__ pos, int64_t n, int bits, int32_t order,
+                                                   const uint32_t *__restrict__ deg, uint64_t *__restrict__ okey) {
+  const int64_t i = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (i < n && head[i]) {
+    const uint64_t u = key[i] >> bits, v = key[i] & ((1ull << bits) - 1ull);   // u < v
+    const bool swap = order == 1 && deg[v] < deg[u];                           // (equal degrees: the smaller index first)
+    okey[pos[i]] = swap ? ((v << bits) | u) : ((u << bits) | v);
+  }
+}
+// From the sorted oriented keys: fwd_col, and fwd_ptr[r] = the first key of a source >= r (r in [0, rows]; a bisection
+// over m keys per row)
+__global__ __launch_bounds__(WL_BS) void wl_forward_lists(const uint64_t *__restrict__ okey, int64_t m, int64_t rows, int bits,
+                                                          int32_t *__restrict__ fwd_ptr, int32_t *__restrict__ fwd_col) {
+  const int64_t i = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (i < m) fwd_col[i] = (int32_t)(okey[i] & ((1ull << bits) - 1ull));
+  if (i <= rows) {
+    int64_t lo = 0, hi = m;   // the first key with (key >> bits) >= i
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if ((int64_t)(okey[mid] >> bits) < i) lo = mid + 1; else hi = mid;
+    }
+    fwd_ptr[i] = (int32_t)lo;
+  }
+}
+// *out = the longest list of ptr (a fixed grid: one atomic per wave of it; *out zeroed by the host)
+__global__ __launch_bounds__(WL_BS) void wl_max_len(const int32_t *__restrict__ ptr, int64_t rows, uint32_t *out) {
+  uint32_t best = 0;
+  for (int64_t r = (int64_t)blockIdx.x * WL_BS + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WL_BS)
+    best = max(best, (uint32_t)(ptr[r + 1] - ptr[r]));
+  for (int o = 32; o > 0; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o));
+  if (wl_lane() == 0 && best) (void)__hip_atomic_fetch_max(out, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 } // namespace sh

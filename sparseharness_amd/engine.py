@@ -258,6 +258,40 @@ class WccGraph:
             self.h = None
 
 
+class TriGraph:
+    """What Engine.triangles counts in: the simple undirected graph under the entries of a square matrix, oriented, as
+    ascending forward lists, with its degrees (made from the host CSR arrays alone; needs no CsrMatrix)."""
+
+    def __init__(self, engine, handle, n):
+        self.engine, self.h, self.n = engine, handle, n
+
+    @property
+    def edges(self):
+        """M: the edges of the simple undirected graph."""
+        k = C.c_int64()
+        self.engine._chk(abi.load().sh_tri_graph_edges(self.h, C.byref(k)))
+        return k.value
+
+    @property
+    def max_forward(self):
+        """The length of the longest forward list."""
+        k = C.c_int64()
+        self.engine._chk(abi.load().sh_tri_graph_max_forward(self.h, C.byref(k)))
+        return k.value
+
+    @property
+    def footprint(self):
+        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
+        b = C.c_uint64()
+        self.engine._chk(abi.load().sh_tri_graph_footprint(self.h, C.byref(b)))
+        return b.value
+
+    def free(self):
+        if self.h is not None:
+            abi.load().sh_tri_graph_free(self.engine.h, self.h)
+            self.h = None
+
+
 class Engine:
     """One HIP device + one stream (replaces Harness's OpenCL context/queue)."""
 
@@ -509,6 +543,27 @@ class Engine:
         n = rounds.value
         return (components.value, skipped.value, n, bool(complete.value), kinds[:n].copy(), hooks[:n].copy(), jumps[:n].copy(),
                 edges[:n].copy(), per[:n].copy(), total.value)
+
+    # ---- triangle counts: tri[v] = the triangles through v (uint64, two 4-byte elements per vertex), deg[v] = its degree
+    def tri_graph(self, row_ptr, col_idx, val, order=1):
+        """The handle Engine.triangles needs, from the CSR arrays of a square matrix.  order 0: edges run from the
+        smaller index to the larger; 1: from the smaller (degree, index) to the larger."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        val = np.ascontiguousarray(val)
+        assert val.dtype.itemsize == 4
+        h = C.c_void_p()
+        self._chk(abi.load().sh_tri_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
+                                                 order, C.byref(h)))
+        return TriGraph(self, h, len(row_ptr) - 1)
+
+    def triangles(self, G, tri=None, deg=None):
+        """-> (triangles, probes, total_ns).  tri: None or a vector of >= 2 * rows 4-byte elements (rows uint64 counts);
+        deg: None or an int32 vector of >= rows elements."""
+        count, probes, total = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(abi.load().sh_tri(self.h, G.h, None if tri is None else tri.h, None if deg is None else deg.h,
+                                    C.byref(count), C.byref(probes), C.byref(total)))
+        return count.value, probes.value, total.value
 
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):

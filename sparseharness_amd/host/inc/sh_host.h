@@ -27,6 +27,13 @@ int sh_scc_labels(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32
 int sh_wcc_labels(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                   int32_t *label);
 
+/* Exact triangle counts of the simple undirected graph under a square CSR pattern (clean, degree-orient, sort,
+ * merge-intersect; single-threaded): the gold for sh_tri.  Entry (r, c) counts when 0 <= c < rows, c != r and its 32
+ * value bits are not all zero, in either direction, once.  tri[v] (rows 64-bit words) becomes the number of triangles
+ * through v, deg[v] (rows words) its degree.  Return 0, -1 bad argument. */
+int sh_triangle_counts(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                       uint64_t *tri, int32_t *deg);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

@@ -1,7 +1,8 @@
 """ctypes face of libsparseharness_host.so (no HIP): the product's MatrixMarket
 loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
-host golds of sh_scc (host/src/scc_labels.cpp) and sh_wcc (host/src/wcc_labels.cpp)."""
+host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp) and sh_tri
+(host/src/triangle_counts.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -47,6 +48,8 @@ def load():
         _lib.sh_scc_labels.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.sh_wcc_labels.restype = C.c_int
         _lib.sh_wcc_labels.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.sh_triangle_counts.restype = C.c_int
+        _lib.sh_triangle_counts.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.sh_mm_load.restype = C.c_int
         _lib.sh_mm_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]
         _lib.sh_mm_load_ex.restype = C.c_int
@@ -118,6 +121,22 @@ def wcc_labels(row_ptr, col_idx, val):
     if rc:
         raise RuntimeError(f"sh_wcc_labels failed: {rc}")
     return label
+
+
+def triangle_counts(row_ptr, col_idx, val):
+    """-> (tri, deg): tri[v] (uint64) = the triangles through v of the simple undirected graph under the entries,
+    deg[v] (int32) = its degree there (Engine.triangles' tri and deg), by a single-threaded forward algorithm on the
+    host.  Entry (r, c) counts when 0 <= c < rows, c != r and its 32 value bits are not all zero."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    val = np.ascontiguousarray(val)
+    assert val.dtype.itemsize == 4 and len(val) == len(col_idx)
+    n = len(row_ptr) - 1
+    tri, deg = np.empty(n, np.uint64), np.empty(n, np.int32)
+    rc = load().sh_triangle_counts(n, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), _p(tri), _p(deg))
+    if rc:
+        raise RuntimeError(f"sh_triangle_counts failed: {rc}")
+    return tri, deg
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
