@@ -895,6 +895,118 @@ int sh_tri_graph_max_forward(const sh_tri_graph *g, int64_t *entries);    /* the
 int sh_tri(sh_engine *e, sh_tri_graph *g, sh_vec *tri, sh_vec *deg,
            uint64_t *triangles, uint64_t *probes, uint64_t *total_ns);
 
+/* ---- core numbers (k-core decomposition) and the degeneracy, by parallel peeling: extends the graph handles made from
+ *      the CSR arrays alone (sh_bfs_graph_create ... sh_tri_graph_create above), which extend the loop of
+ *      HarnessSCC::executeRun (app/scc.cpp:96-176) and Harness::executeKernel (inc/harness.h:149-195); the reference
+ *      has no counterpart of the calls below.
+ *
+ *      The edge rule is word for word sh_tri's: row r storing column c with 0 <= c < rows and a value whose 32 bits are
+ *      not all zero is an entry that counts.  The graph is the SIMPLE UNDIRECTED graph under those entries: {u, v} with
+ *      u != v is one edge if either row stores the other, once or many times.  Self-loops, parallel entries, stored
+ *      zeros, columns outside the matrix and direction are legal and change nothing.  M = the number of such edges.
+ *        core[v]      = the core number of v: the largest k such that v lies in a subgraph whose vertices all have at
+ *                       least k neighbours in it (int32, written in full).
+ *        deg[v]       = the degree of v in that graph (int32), as sh_tri's.
+ *        *degeneracy  = max core[v]; 0 for a graph without edges or rows.
+ *        *levels      = the number of distinct values in core.
+ *        *rounds      = the number of peel rounds run.
+ *        *complete    = 1 if every vertex was settled within max_rounds; if 0, core holds -1 for the vertices not yet
+ *                       settled and the settled ones are right (and *degeneracy, *levels speak of the settled ones).
+ *      core, deg, *degeneracy and *levels do not depend on chase, the schedule or the run: a graph has one vector of core
+ *      numbers and they are integers, so every comparison is ==.
+ *
+ *      Schedule (csrc/core.hip.h).  cur[v] is the remaining degree of v, core[v] = -1 until v is settled.  The call walks
+ *      the levels k upwards and runs rounds inside a level; a round is one fixed set of four launches enqueued ahead of
+ *      the host in batches (8, 16, 32, 32, ...), each of which returns at once unless the control block on the device
+ *      gives it work; the host learns k, the list sizes and the end only from one readback per batch.  When the work
+ *      list is empty and vertices remain, the round opens a level: one pass over all vertices takes the smallest cur
+ *      among the unsettled (a minimum per workgroup, not one word hit by every wave), that minimum becomes k -- empty
+ *      levels are skipped, not walked -- and a second pass puts every unsettled v with cur[v] <= k on the work list.
+ *      The peel then walks the lists of the work list's vertices -- up to 8 entries one lane, up to 2048 one wave,
+ *      longer ones in pieces of 2048, one wave per piece -- settles v with core[v] = k and gives every entry u with
+ *      cur[u] > k one atomic decrement.  The one lane that sees the old value k + 1 owns u and appends it to the next
+ *      round's list; a lane that sees an old value <= k restores it with one add.  There is no compare-and-swap and no
+ *      retry.  A last small launch sums the workgroups' counts, takes the settled from the remaining, swaps the lists,
+ *      records the round and finishes when nothing remains.
+ *      chase > 0: a lane that owns a u whose list has at most 8 entries keeps it in hand (at most one; any other goes to
+ *      the next list), and after its own walk settles u and walks u's list the same way, at most `chase` times in a
+ *      row; what it still holds then goes to the next list.  The loop is bounded by chase * 8 entries per lane.  It keeps
+ *      a chain from costing one round per vertex: a path of n vertices takes about n / (2 (chase + 1)) rounds instead
+ *      of n / 2.
+ *      What is deterministic: with chase == 0 a round's set is exactly the vertices whose remaining degree fell to <= k
+ *      in the round before (in an opening round: those whose remaining degree is the smallest), so *rounds, k_per_round,
+ *      size_per_round and edges_per_round are deterministic too.  With chase > 0 these records are informational -- who
+ *      owns, and so who is chased, depends on the schedule -- and *rounds is never larger than with chase == 0.
+ *      Why that is right: peeling is monotone -- removing more only lowers remaining degrees further.  A level ends when
+ *      no unsettled vertex has cur <= k; the set settled in it is the closure of "delete a vertex of remaining degree
+ *      <= k", the same in whatever order and grouping, so every level starts from one state and core[v] is the level v
+ *      fell in.  If a chasing run has settled a superset A of what the run with chase == 0 has settled (B) after as many
+ *      rounds, a vertex of remaining degree <= k after B's deletions has it after A's too, so it is settled in A or on A's
+ *      list: one round later A still contains B.  The decrement: once the word of u has gone from k + 1 to k, it is k
+ *      minus the decrements that have not restored yet and never exceeds k again, so the owner is unique, and every
+ *      reader only compares with `> k`, so a transient value below k answers like k (csrc/core.hip.h has the steps).
+ *      Every vertex is settled once; no kernel ever waits for another kernel's write; every loop is bounded by a list
+ *      length, `rows` or chase * 8.
+ *      Worst cases: the number of rounds is the depth of the peeling, not the diameter -- a path or a grid needs rounds
+ *      in proportion to its side (the 128 x 128 grid: 127 rounds, one level; chasing shortens chains of short lists
+ *      only).  Every non-empty level costs two passes over all vertices.  A hub's list is walked once, in pieces, when
+ *      the hub is settled.
+ *
+ *      Measured on an MI355X (DESIGN.md "6j k-core decomposition"; tools/core_bench.py, one process per matrix, arms
+ *        chase = 0 / 4 / 16 / 64 alternating, 5 rounds, device time against the wall time of hostlib.core_numbers):
+ *        the 2048 x 2048 grid (4 194 304 rows, 8 384 512 edges, degeneracy 2, one level; host gold 652 ms), median
+ *        (min-max) in ms and rounds: chase 0: 47.8 (47.7-48.1), 2047; 4: 58.4 (58.3-58.5), 1194; 16: 119.7 (119.1-119.8),
+ *        1082; 64: 314.4 (314.0-314.7), 1039.  R-MAT-18 (262 144 rows, 3 805 085 edges, degeneracy 374, 138 levels, largest
+ *        degree 25 104; host gold 312 ms): chase 0: 45.57 (45.49-45.61), 451; 4: 45.49 (45.42-45.52), 442; 16: 45.41
+ *        (45.37-45.43), 442; 64: 45.47 (45.46-45.52), 442.  The handle is built in 0.06 s on either.  A round of four
+ *        launches costs about 23 us however small its list is.  On the grid chasing saves rounds and loses time: its
+ *        front is no chain, and a launch lasts as long as its longest chase.  On R-MAT-18 1137 vertices are chased at all.
+ *        Rule: the binding's default is chase = 0, the fastest arm on the grid and no slower than any on R-MAT-18.  Pass
+ *        chase > 0 only for a graph that hangs long chains of degree-2 vertices off its cores (a path of 4096: 2048
+ *        rounds with chase 0, at most 2048 / (chase + 1) + 2 with it); the time of such a run is unmeasured.
+ *
+ * sh_core_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  The matrix is square (rows x rows).
+ * The handle holds on the device: adj_ptr[rows + 1] and adj_col[2M] (every list strictly ascending; no transpose: the
+ * lists are symmetric), deg[rows], cur[rows], two work lists of `rows` entries (a vertex enters a list at most once per
+ * call: they cannot overflow), two piece lists of 2M / 1024 + 1 places, and a control block with the workgroups' counts.
+ * rows == 0 gives a valid handle.  Freeing NULL is SH_OK.  The build runs on the device, once, and shares its first half
+ * with sh_tri_graph_create: the entries that count and are no self-loops become 64-bit keys (min << bits | max, bits =
+ * those of rows - 1), a radix sort over 2 * bits bits, the first key of every run is an edge, deg is a histogram over
+ * both ends; then every edge is written both ways (u << bits | v and v << bits | u), the 2M keys are sorted and the row
+ * starts taken from them.  While it runs the build needs 4 * (rows + 1) + 16 * nnz + 8 bytes for the arrays as given,
+ * their flags and scan, 16 bytes per surviving entry for the keys and the sorted keys, 32 bytes per edge for the keys
+ * both ways and their sorted copy, and the sort's own scratch (rocPRIM: about one more copy of the keys); all of it is
+ * released before the call returns.  nnz is bounded as for the other handles, and 2M by 2^31 - 256.
+ * sh_core_graph_footprint: device bytes held =
+ *     4 * (rows + 1) + 8 * edges + 16 * rows + 16 * (2 * edges / 1024 + 1) + 34816.
+ * sh_core_graph_edges: M.  sh_core_graph_max_degree: the largest degree (the length of the longest list).
+ *
+ * sh_core: core: an int32 vector of >= rows elements; `rows` elements are overwritten, no more.  deg: NULL, or an int32
+ * vector of >= rows elements.  chase >= 0 (the Python binding's default: see the rule above).  max_rounds >= 1 bounds the
+ * rounds; rows + 1 can never cut a run short (the Python binding's default).  The per-round arrays (capacity max_rounds;
+ * each may be NULL): k_per_round the k being peeled, size_per_round the vertices taken from the round's work list,
+ * chased_per_round the vertices settled inside the launch without passing through a list, edges_per_round the list
+ * entries looked at, ns_per_round device time; size + chased over all rounds of a complete run is `rows`.  *total_ns
+ * (may be NULL) is device time (hipEvent) as elsewhere.  g may serve any number of calls, one at a time; every call
+ * starts from cur = deg.
+ * SH_EINVAL: NULL arguments (engine, graph, core, degeneracy, levels, rounds, complete, out, the arrays), rows < 0,
+ * nnz < 0, chase < 0, max_rounds < 1.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases, core
+ * or deg shorter than rows.  All are reported before any device work, with the buffers untouched.
+ * NOT covered: the removal order / degeneracy ordering as an output, k-truss, the multi-GPU driver, row pieces
+ * (sh_spmv_step_pieces), the C++ harness apps, incremental updates.
+ */
+typedef struct sh_core_graph sh_core_graph;
+int sh_core_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                         const void *val, sh_core_graph **out);
+int sh_core_graph_free(sh_engine *e, sh_core_graph *g);
+int sh_core_graph_footprint(const sh_core_graph *g, uint64_t *device_bytes);
+int sh_core_graph_edges(const sh_core_graph *g, int64_t *edges);          /* M */
+int sh_core_graph_max_degree(const sh_core_graph *g, int64_t *entries);
+int sh_core(sh_engine *e, sh_core_graph *g, sh_vec *core, sh_vec *deg, int32_t chase, int32_t max_rounds,
+            int32_t *degeneracy, int32_t *levels, int32_t *rounds, int32_t *complete,
+            int32_t *k_per_round, int64_t *size_per_round, int64_t *chased_per_round, int64_t *edges_per_round,
+            uint64_t *ns_per_round, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,13 @@ SIGNATURES = {
     "sh_tri_graph_edges": (_int, [_vp, C.POINTER(_i64)]),
     "sh_tri_graph_max_forward": (_int, [_vp, C.POINTER(_i64)]),
     "sh_tri": (_int, [_vp, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "sh_core_graph_create": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _pp]),
+    "sh_core_graph_free": (_int, [_vp, _vp]),
+    "sh_core_graph_footprint": (_int, [_vp, C.POINTER(_u64)]),
+    "sh_core_graph_edges": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_core_graph_max_degree": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_core": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                       C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_u64), C.POINTER(_u64)]),
 }
 
 _lib = None

@@ -7,16 +7,18 @@ bfs_decide / bfs_parents, bfs.hip.h), or one of the SSSP kernels (sssp_init / ss
 sssp_preds, sssp.hip.h), or one of the SCC kernels (scc_init / scc_trim / scc_pick / scc_seed / scc_propagate / scc_claim /
 scc_label / scc_decide, scc.hip.h), or one of the WCC kernels (wcc_init / wcc_sample / wcc_compact / wcc_full / wcc_jump /
 wcc_decide / wcc_label, wcc.hip.h), or one of the triangle kernels (tri_count_light / tri_count_heavy, each with and without
-per-vertex counts, and tri_finish, tri.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+per-vertex counts, and tri_finish, tri.hip.h), or one of the core-number kernels (core_init / core_min / core_open / core_peel /
+core_close, core.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri = [], 0, set(), set(), set(), set(), set(), set(), set(), set()
+bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set()
 BFS_KERNELS = ("bfs_init", "bfs_topdown", "bfs_bottomup", "bfs_queue_from_bitmap", "bfs_decide", "bfs_parents")
 SSSP_KERNELS = ("sssp_init", "sssp_relax", "sssp_split", "sssp_decide", "sssp_preds")
 SCC_KERNELS = ("scc_init", "scc_trim", "scc_pick", "scc_seed", "scc_propagate", "scc_claim", "scc_label", "scc_decide")
 TRI_KERNELS = ("tri_count_light", "tri_count_heavy", "tri_finish")
+CORE_KERNELS = ("core_init", "core_min", "core_open", "core_peel", "core_close")
 WCC_KERNELS = ("wcc_init", "wcc_sample", "wcc_compact", "wcc_full", "wcc_jump", "wcc_decide", "wcc_label")
 for blk in text.split("remark: Function Name: ")[1:]:
     name = blk.split()[0]
@@ -28,9 +30,12 @@ for blk in text.split("remark: Function Name: ")[1:]:
     scc = any(k in name for k in SCC_KERNELS)
     wcc = any(k in name for k in WCC_KERNELS)
     tri = any(k in name for k in TRI_KERNELS)
-    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri:
+    core = any(k in name for k in CORE_KERNELS)
+    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core:
         continue
-    if tri:
+    if core:
+        seen_core.add(name)
+    elif tri:
         seen_tri.add(name)
     elif wcc:
         seen_wcc.add(name)
@@ -90,7 +95,10 @@ if len(seen_wcc) != len(WCC_KERNELS):
 # the two counting kernels of sh_tri with and without per-vertex counts and tri_finish, under the limits of the BFS kernels
 if len(seen_tri) != 5:
     sys.exit(f"expected 5 triangle kernels in the remarks, found {len(seen_tri)}: {sorted(seen_tri)}")
+# the five kernels of sh_core, under the limits of the BFS kernels
+if len(seen_core) != len(CORE_KERNELS):
+    sys.exit(f"expected {len(CORE_KERNELS)} core-number kernels in the remarks, found {len(seen_core)}: {sorted(seen_core)}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC and {len(seen_tri)} triangle kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle and {len(seen_core)} core-number kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

@@ -16,6 +16,7 @@
 #include "scc.hip.h"
 #include "wcc.hip.h"
 #include "tri.hip.h"
+#include "core.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -1827,7 +1828,7 @@ static int build_transpose(sh_engine *e, DevArrays &tmp, const int32_t *ptr, con
 }
 
 // What sh_bfs_graph, sh_sssp_graph, sh_scc_graph and sh_wcc_graph share: the edges by row (in_*) and by source vertex (out_*), the static pieces of
-// the long rows, and what a batch of gated steps needs (run_batches).
+// the long rows, and what a batch of gated steps needs (run_batches).  sh_core_graph keeps its symmetric lists in in_* alone.
 template <class Ctl>
 struct GraphHandle {
   int64_t rows = 0, nnz = 0, edges = 0;
@@ -1847,7 +1848,7 @@ struct GraphHandle {
   }
 };
 
-// What the scalars and the host arrays of fn = sh_bfs_graph_create / sh_sssp_graph_create / sh_scc_graph_create / sh_wcc_graph_create alone decide: no device is
+// What the scalars and the host arrays of fn = sh_bfs_graph_create / ... / sh_tri_graph_create / sh_core_graph_create alone decide: no device is
 // needed to be told.
 static int check_host_csr(sh_engine *e, const char *fn, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                           const void *val, const void *out) {
@@ -1939,7 +1940,7 @@ static int open_control(sh_engine *e, GraphHandle<Ctl> *g, int64_t ctl_bytes, in
   return SH_OK;
 }
 
-// The loop of sh_bfs_levels, sh_sssp, sh_scc and sh_wcc: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc and sh_core: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
 // next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
 // enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
 // step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
@@ -2817,27 +2818,24 @@ struct sh_tri_graph {   // d_ctl: TRI_CTL_BYTES, followed by the TriParts of tri
 static_assert(sizeof(TriCtl) <= TRI_CTL_BYTES, "the control block is accounted as TRI_CTL_BYTES (sh_tri_graph_footprint)");
 static_assert(sizeof(TriPart) * TRI_MAX_BLOCKS == TRI_PART_BYTES, "one TriPart per workgroup");
 
-// The forward lists of a triangle handle from host CSR arrays: the entries that count and are no self-loops as sorted
-// keys, the first key of every run (the edges of the simple graph), the degrees, the oriented keys sorted again.
-// Returns with the stream synchronised: the host arrays are done with.
-static int build_forward_lists(sh_engine *e, sh_tri_graph *g, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
-                               const void *val, int32_t order) {
-  g->rows = rows; g->nnz = nnz;
-  DevArrays &own = g->dev;
-  HIP_TRY(e, own.alloc(&g->d_fwd_ptr, (rows + 1) * 4));
-  HIP_TRY(e, own.alloc(&g->d_deg, rows * 4));
-  HIP_TRY(e, own.alloc(&g->d_ctl, TRI_CTL_BYTES + 2 * TRI_PART_BYTES));
-  g->d_part = (TriPart *)((char *)g->d_ctl + TRI_CTL_BYTES);
-  HIP_TRY(e, hipMemsetAsync(g->d_fwd_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
-  HIP_TRY(e, hipMemsetAsync(g->d_deg, 0, (size_t)std::max<int64_t>(rows, 1) * 4, e->stream));
-  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, TRI_CTL_BYTES + 2 * TRI_PART_BYTES, e->stream));
-  // temporaries: the CSR arrays as given, flags and their scan (twice), the keys and the sorted keys (twice)
-  DevArrays tmp;
+// What the builds of sh_tri_graph and sh_core_graph share: the edges of the simple undirected graph under host CSR arrays.
+// The entries that count and are no self-loops become keys (min << bits | max), sorted; the first key of every run is an
+// edge; deg (zeroed by the caller) is the histogram over both ends.  Leaves in `tmp`: sorted[S] with head[S + 1] and its
+// exclusive scan pos[S + 1] (edge i of the M stands at the key with head = 1 and pos = i), and key[S] free for reuse.
+struct UndEdges {
+  int64_t S = 0, M = 0;   // surviving entries, edges of the simple graph
+  int bits = 1;           // of the largest index
+  uint64_t *key = nullptr, *sorted = nullptr;
+  uint32_t *head = nullptr, *pos = nullptr;
+};
+static int build_und_edges(sh_engine *e, DevArrays &tmp, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                           const void *val, uint32_t *deg, UndEdges *u) {
+  // temporaries: the CSR arrays as given, flags and their scan (twice), the keys and the sorted keys
   int32_t *t_rp = nullptr, *t_ci = nullptr;
   uint32_t *t_val = nullptr, *t_flag = nullptr, *t_pos = nullptr;
   uint64_t *t_key = nullptr, *t_sorted = nullptr;
-  int64_t S = 0, M = 0;   // surviving entries, edges of the simple graph
-  const int bits = 32 - __builtin_clz((unsigned)std::max<int64_t>(rows - 1, 1));   // of the largest index (rows <= 2^31 - 256)
+  int64_t S = 0, M = 0;
+  const int bits = 32 - __builtin_clz((unsigned)std::max<int64_t>(rows - 1, 1));   // (rows <= 2^31 - 256)
   const dim3 blk(WL_BS);
   const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
   if (rows > 0 && nnz > 0) {
@@ -2870,15 +2868,42 @@ static int build_forward_lists(sh_engine *e, sh_tri_graph *g, int64_t rows, int6
     HIP_TRY(e, hipMemcpy(&n, t_pos + S, 4, hipMemcpyDeviceToHost));
     M = (int64_t)n;
   }
+  if (M > 0) {
+    hipLaunchKernelGGL(wl_und_degrees, grid_for(S), blk, 0, e->stream, t_sorted, t_flag, S, bits, deg);
+    HIP_TRY(e, hipGetLastError());
+  }
+  *u = UndEdges{S, M, bits, t_key, t_sorted, t_flag, t_pos};
+  return SH_OK;
+}
+
+// The forward lists of a triangle handle from host CSR arrays: the edges of the simple graph and the degrees
+// (build_und_edges), the oriented keys sorted again.  Returns with the stream synchronised: the host arrays are done with.
+static int build_forward_lists(sh_engine *e, sh_tri_graph *g, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                               const void *val, int32_t order) {
+  g->rows = rows; g->nnz = nnz;
+  DevArrays &own = g->dev;
+  HIP_TRY(e, own.alloc(&g->d_fwd_ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_deg, rows * 4));
+  HIP_TRY(e, own.alloc(&g->d_ctl, TRI_CTL_BYTES + 2 * TRI_PART_BYTES));
+  g->d_part = (TriPart *)((char *)g->d_ctl + TRI_CTL_BYTES);
+  HIP_TRY(e, hipMemsetAsync(g->d_fwd_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_deg, 0, (size_t)std::max<int64_t>(rows, 1) * 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, TRI_CTL_BYTES + 2 * TRI_PART_BYTES, e->stream));
+  DevArrays tmp;
+  UndEdges u;
+  const int rc = build_und_edges(e, tmp, rows, nnz, row_ptr, col_idx, val, g->d_deg, &u);
+  if (rc)
+    return rc;
+  const int64_t S = u.S, M = u.M;
+  const dim3 blk(WL_BS);
+  const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
   g->edges = M;
   HIP_TRY(e, own.alloc(&g->d_fwd_col, M * 4));
   if (M > 0) {
-    hipLaunchKernelGGL(wl_und_degrees, grid_for(S), blk, 0, e->stream, t_sorted, t_flag, S, bits, g->d_deg);
+    hipLaunchKernelGGL(wl_orient, grid_for(S), blk, 0, e->stream, u.sorted, u.head, u.pos, S, u.bits, order, g->d_deg, u.key);
     HIP_TRY(e, hipGetLastError());
-    hipLaunchKernelGGL(wl_orient, grid_for(S), blk, 0, e->stream, t_sorted, t_flag, t_pos, S, bits, order, g->d_deg, t_key);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, device_sort_keys_u64(e->stream, t_key, t_sorted, M, 2 * bits));
-    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(M, rows + 1)), blk, 0, e->stream, t_sorted, M, rows, bits, g->d_fwd_ptr, g->d_fwd_col);
+    HIP_TRY(e, device_sort_keys_u64(e->stream, u.key, u.sorted, M, 2 * u.bits));
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(M, rows + 1)), blk, 0, e->stream, u.sorted, M, rows, u.bits, g->d_fwd_ptr, g->d_fwd_col);
     HIP_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(wl_max_len, dim3((unsigned)std::max(1, std::min(e->n_cus * 4, TRI_MAX_BLOCKS))), blk, 0, e->stream, g->d_fwd_ptr, rows,
                        &g->d_ctl->max_forward);
@@ -2979,6 +3004,188 @@ int sh_tri(sh_engine *e, sh_tri_graph *g, sh_vec *tri, sh_vec *deg, uint64_t *tr
   *triangles = got.triangles;
   if (probes) *probes = got.probes;
   if (total_ns) *total_ns = ns;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- core numbers by parallel peeling (core.hip.h) -------------------------------------------------------------------
+// The GraphHandle base serves run_batches (control block, pinned copy, events).  Of its edge arrays the symmetric lists
+// use d_in_ptr / d_in_col alone (adj_ptr / adj_col): a list is its own transpose, so d_out_* and the static row pieces
+// stay NULL and take no memory.  d_ctl: CORE_CTL_BYTES, followed by the WlParts of core_peel and those of core_min.
+struct sh_core_graph : GraphHandle<CoreCtl> {
+  int64_t max_degree = 0;
+  uint32_t *d_deg = nullptr;
+  int32_t *d_cur = nullptr;
+  CoreLists lists = {};
+  WlPart *d_mins = nullptr;
+};
+static_assert(sizeof(CoreCtl) <= CORE_CTL_BYTES, "the control block is accounted as CORE_CTL_BYTES (sh_core_graph_footprint)");
+static_assert(sizeof(WlPart) * CORE_MAX_BLOCKS == CORE_PART_BYTES, "one WlPart per workgroup");
+static_assert(sizeof(CoreCtl::rec) / sizeof(CoreRec) == CORE_BATCH, "one record per round of a batch");
+
+// The symmetric lists of a core handle from host CSR arrays: the edges of the simple graph and the degrees
+// (build_und_edges), every edge as two keys (src << bits | dst), sorted, the row starts taken from them.  Returns with
+// the stream synchronised: the host arrays are done with.
+static int build_symmetric_lists(sh_engine *e, sh_core_graph *g, int64_t rows, int64_t nnz, const int32_t *row_ptr,
+                                 const int32_t *col_idx, const void *val) {
+  g->rows = rows; g->nnz = nnz;
+  DevArrays &own = g->dev;
+  HIP_TRY(e, own.alloc(&g->d_in_ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_deg, rows * 4));
+  HIP_TRY(e, own.alloc(&g->d_cur, rows * 4));
+  HIP_TRY(e, hipMemsetAsync(g->d_in_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_deg, 0, (size_t)std::max<int64_t>(rows, 1) * 4, e->stream));
+  DevArrays tmp;
+  UndEdges u;
+  const int rc = build_und_edges(e, tmp, rows, nnz, row_ptr, col_idx, val, g->d_deg, &u);
+  if (rc)
+    return rc;
+  const int64_t S = u.S, M = u.M, E = 2 * M;
+  if (E > 0x7FFFFF00ll)
+    return fail(e, SH_EINVAL, "sh_core_graph_create: the lists hold %lld entries (twice the %lld edges), must be at most 2^31 - 256",
+                (long long)E, (long long)M);
+  g->edges = M;
+  HIP_TRY(e, own.alloc(&g->d_in_col, E * 4));
+  for (int i = 0; i < 2; i++) {
+    HIP_TRY(e, own.alloc(&g->lists.list[i], rows * 4));   // a vertex joins a work list at most once per call (core.hip.h, invariant 1)
+    HIP_TRY(e, own.alloc(&g->lists.pieces[i], (E / (CORE_PIECE / 2) + 1) * sizeof(WlPiece)));   // see wl_push_pieces
+  }
+  uint32_t *t_longest = nullptr;
+  HIP_TRY(e, tmp.alloc(&t_longest, 4));
+  HIP_TRY(e, hipMemsetAsync(t_longest, 0, 4, e->stream));
+  if (M > 0) {
+    const dim3 blk(WL_BS);
+    const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
+    uint64_t *t_key = nullptr, *t_sorted = nullptr;
+    HIP_TRY(e, tmp.alloc(&t_key, E * 8));
+    HIP_TRY(e, tmp.alloc(&t_sorted, E * 8));
+    hipLaunchKernelGGL(wl_both_ways, grid_for(S), blk, 0, e->stream, u.sorted, u.head, u.pos, S, u.bits, t_key);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_keys_u64(e->stream, t_key, t_sorted, E, 2 * u.bits));
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(E, rows + 1)), blk, 0, e->stream, t_sorted, E, rows, u.bits, g->d_in_ptr, g->d_in_col);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(wl_max_len, dim3((unsigned)std::max(1, std::min(e->n_cus * 4, CORE_MAX_BLOCKS))), blk, 0, e->stream, g->d_in_ptr, rows,
+                       t_longest);
+    HIP_TRY(e, hipGetLastError());
+  }
+  uint32_t longest = 0;
+  HIP_TRY(e, hipMemcpyAsync(&longest, t_longest, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  g->max_degree = (int64_t)longest;
+  return SH_OK;
+}
+
+extern "C" {
+
+int sh_core_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                         const void *val, sh_core_graph **out) {
+  if (out) *out = nullptr;
+  int rc = check_host_csr(e, "sh_core_graph_create", rows, nnz, row_ptr, col_idx, val, out);
+  if (rc)
+    return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  std::unique_ptr<sh_core_graph> g(new (std::nothrow) sh_core_graph());
+  if (!g)
+    return fail(e, SH_ENOMEM, "out of host memory");
+  if ((rc = build_symmetric_lists(e, g.get(), rows, nnz, row_ptr, col_idx, val)))
+    return rc;
+  if ((rc = open_control(e, g.get(), CORE_CTL_BYTES, CORE_CTL_BYTES + 2 * CORE_PART_BYTES)))
+    return rc;
+  g->d_mins = (WlPart *)((char *)g->d_ctl + CORE_CTL_BYTES + CORE_PART_BYTES);
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  *out = g.release();
+  return SH_OK;
+}
+
+int sh_core_graph_free(sh_engine *e, sh_core_graph *g) { return free_handle(e, g); }
+
+int sh_core_graph_footprint(const sh_core_graph *g, uint64_t *device_bytes) {
+  if (!g || !device_bytes)
+    return SH_EINVAL;
+  *device_bytes = (uint64_t)g->dev.bytes;
+  return SH_OK;
+}
+
+int sh_core_graph_edges(const sh_core_graph *g, int64_t *edges) {
+  if (!g || !edges)
+    return SH_EINVAL;
+  *edges = g->edges;
+  return SH_OK;
+}
+
+int sh_core_graph_max_degree(const sh_core_graph *g, int64_t *entries) {
+  if (!g || !entries)
+    return SH_EINVAL;
+  *entries = g->max_degree;
+  return SH_OK;
+}
+
+int sh_core(sh_engine *e, sh_core_graph *g, sh_vec *core, sh_vec *deg, int32_t chase, int32_t max_rounds,
+            int32_t *degeneracy, int32_t *levels, int32_t *rounds, int32_t *complete,
+            int32_t *k_per_round, int64_t *size_per_round, int64_t *chased_per_round, int64_t *edges_per_round,
+            uint64_t *ns_per_round, uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (chase < 0)
+    return fail(e, SH_EINVAL, "sh_core: chase = %d, must not be negative", (int)chase);
+  if (max_rounds < 1)
+    return fail(e, SH_EINVAL, "sh_core: max_rounds = %d, must be at least 1", (int)max_rounds);
+  if (!e || !g || !core || !degeneracy || !levels || !rounds || !complete)
+    return fail(e, SH_EINVAL, "sh_core: NULL argument (engine, graph, core, degeneracy, levels, rounds or complete)");
+  const int64_t rows = g->rows;
+  if (core->n < rows)
+    return fail(e, SH_ESHAPE, "sh_core: core is shorter than the graph's %lld rows", (long long)rows);
+  if (deg && deg->n < rows)
+    return fail(e, SH_ESHAPE, "sh_core: deg is shorter than the graph's %lld rows", (long long)rows);
+  *degeneracy = 0; *levels = 0; *rounds = 0; *complete = 1;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, CORE_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
+  const CoreGraph G{(int32_t)rows, g->d_in_ptr, g->d_in_col};
+  int32_t *c = (int32_t *)core->d;
+  uint64_t total = 0;
+  // every vertex unsettled, its remaining degree its degree
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, CORE_CTL_BYTES, e->stream));
+  if (deg) HIP_TRY(e, hipMemcpyAsync(deg->d, g->d_deg, (size_t)rows * 4, hipMemcpyDeviceToDevice, e->stream));
+  hipLaunchKernelGGL(core_init, grid, block, 0, e->stream, g->d_ctl, (int32_t)rows, chase, g->d_deg, g->d_cur, c);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  int32_t it = 0;
+  bool done = false;
+  // the launches of a round: each returns at once unless the control block says the round is its turn (and, for the
+  // two passes that open a level, unless the work list is empty)
+  const auto enqueue = [&](int s, int k) {
+    hipLaunchKernelGGL(core_min, grid, block, 0, e->stream, g->d_ctl, s, (int32_t)rows, g->d_cur, c, g->d_mins);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(core_open, grid, block, 0, e->stream, g->d_ctl, s, G, g->d_cur, c, g->d_mins, g->lists);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(core_peel, grid, block, 0, e->stream, g->d_ctl, s, G, g->d_cur, c, g->lists, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(core_close, dim3(1), block, 0, e->stream, g->d_ctl, k, s, nblocks, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    return (int)SH_OK;
+  };
+  const auto take = [&](int s, const CoreRec &rc, uint64_t round_ns) {
+    if (k_per_round) k_per_round[s] = rc.k;
+    if (size_per_round) size_per_round[s] = (int64_t)rc.size;
+    if (chased_per_round) chased_per_round[s] = (int64_t)rc.chased;
+    if (edges_per_round) edges_per_round[s] = (int64_t)rc.edges;
+    if (ns_per_round) ns_per_round[s] = round_ns;
+  };
+  const int rc = run_batches(e, "sh_core: round", g, max_rounds, &it, &done, &total, enqueue, take);
+  if (rc)
+    return rc;
+  // (the control block as the last batch's readback left it in h_ctl: levels and the latest of them)
+  *degeneracy = g->h_ctl->degeneracy;
+  *levels = g->h_ctl->levels;
+  *rounds = it;
+  *complete = done ? 1 : 0;
+  if (total_ns)
+    *total_ns = total;
   return SH_OK;
 }
 

@@ -1,4 +1,4 @@
-// worklist.hip.h -- what the worklist algorithms share (frontier.hip.h, bfs.hip.h, sssp.hip.h): list cursors, the cutting
+// worklist.hip.h -- what the worklist algorithms share (frontier.hip.h, bfs.hip.h, sssp.hip.h, ..., core.hip.h): list cursors, the cutting
 // of long lists into pieces, per-workgroup sums, the two traversal skeletons and the kernels that build a graph handle.
 //
 // Work distribution: every kernel runs a fixed grid whose waves stride over a device-side list length (the host does
@@ -299,6 +299,18 @@ __global__ __launch_bounds__(WL_BS) void wl_orient(const uint64_t *__restrict__ 
     const uint64_t u = key[i] >> bits, v = key[i] & ((1ull << bits) - 1ull);   // u < v
     const bool swap = order == 1 && deg[v] < deg[u];                           // (equal degrees: the smaller index first)
     okey[pos[i]] = swap ? ((v << bits) | u) : ((u << bits) | v);
+  }
+}
+// Edge i of the simple graph (pos = exclusive scan of head), both ways, for the symmetric lists of sh_core_graph:
+// okey[2 * pos[i]] = (u << bits | v) and okey[2 * pos[i] + 1] = (v << bits | u)
+__global__ __launch_bounds__(WL_BS) void wl_both_ways(const uint64_t *__restrict__ key, const uint32_t *__restrict__ head,
+                                                      const uint32_t *__restrict__ pos, int64_t n, int bits,
+                                                      uint64_t *__restrict__ okey) {
+  const int64_t i = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (i < n && head[i]) {
+    const uint64_t u = key[i] >> bits, v = key[i] & ((1ull << bits) - 1ull);
+    okey[2 * (int64_t)pos[i]] = (u << bits) | v;
+    okey[2 * (int64_t)pos[i] + 1] = (v << bits) | u;
   }
 }
 // From the sorted oriented keys: fwd_col, and fwd_ptr[r] = the first key of a source >= r (r in [0, rows]; a bisection

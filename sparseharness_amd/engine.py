@@ -292,6 +292,41 @@ class TriGraph:
             self.h = None
 
 
+class CoreGraph:
+    """What Engine.core_numbers peels: the simple undirected graph under the entries of a square matrix as symmetric
+    ascending lists, with its degrees, the remaining degrees of a call and two work lists (made from the host CSR
+    arrays alone; needs no CsrMatrix)."""
+
+    def __init__(self, engine, handle, n):
+        self.engine, self.h, self.n = engine, handle, n
+
+    @property
+    def edges(self):
+        """M: the edges of the simple undirected graph."""
+        k = C.c_int64()
+        self.engine._chk(abi.load().sh_core_graph_edges(self.h, C.byref(k)))
+        return k.value
+
+    @property
+    def max_degree(self):
+        """The largest degree (the length of the longest list)."""
+        k = C.c_int64()
+        self.engine._chk(abi.load().sh_core_graph_max_degree(self.h, C.byref(k)))
+        return k.value
+
+    @property
+    def footprint(self):
+        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
+        b = C.c_uint64()
+        self.engine._chk(abi.load().sh_core_graph_footprint(self.h, C.byref(b)))
+        return b.value
+
+    def free(self):
+        if self.h is not None:
+            abi.load().sh_core_graph_free(self.engine.h, self.h)
+            self.h = None
+
+
 class Engine:
     """One HIP device + one stream (replaces Harness's OpenCL context/queue)."""
 
@@ -564,6 +599,41 @@ class Engine:
         self._chk(abi.load().sh_tri(self.h, G.h, None if tri is None else tri.h, None if deg is None else deg.h,
                                     C.byref(count), C.byref(probes), C.byref(total)))
         return count.value, probes.value, total.value
+
+    # ---- core numbers: core[v] = the largest k such that v lies in a subgraph of minimum degree k
+    def core_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.core_numbers needs, from the CSR arrays of a square matrix."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        col_idx = np.ascontiguousarray(col_idx, np.int32)
+        val = np.ascontiguousarray(val)
+        assert val.dtype.itemsize == 4
+        h = C.c_void_p()
+        self._chk(abi.load().sh_core_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
+                                                  C.byref(h)))
+        return CoreGraph(self, h, len(row_ptr) - 1)
+
+    # chase = 0: the fastest arm of tools/core_bench.py on the 2048 x 2048 grid and no slower than any on R-MAT-18
+    # (DESIGN.md 6j); chasing pays for chains of degree-2 vertices only
+    def core_numbers(self, G, core, deg=None, chase=0, max_rounds=None):
+        """-> (degeneracy, levels, rounds, complete, ks, sizes, chased, edges, ns, total_ns); per round: the level k being
+        peeled, vertices taken from the work list, vertices settled inside the launch, list entries looked at, device ns.
+        core: an int32 vector of >= rows elements; deg: None or one more.  max_rounds = None: rows + 1, which cannot cut
+        a run short."""
+        if max_rounds is None:
+            max_rounds = G.n + 1
+        degeneracy, levels, rounds, complete, total = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+        cap = max(int(max_rounds), 1)
+        ks, sizes, chased = np.zeros(cap, np.int32), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
+        edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
+        i64p = C.POINTER(C.c_int64)
+        self._chk(abi.load().sh_core(self.h, G.h, core.h, None if deg is None else deg.h, chase, max_rounds,
+                                     C.byref(degeneracy), C.byref(levels), C.byref(rounds), C.byref(complete),
+                                     ks.ctypes.data_as(C.POINTER(C.c_int32)), sizes.ctypes.data_as(i64p),
+                                     chased.ctypes.data_as(i64p), edges.ctypes.data_as(i64p),
+                                     per.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)))
+        n = rounds.value
+        return (degeneracy.value, levels.value, n, bool(complete.value), ks[:n].copy(), sizes[:n].copy(), chased[:n].copy(),
+                edges[:n].copy(), per[:n].copy(), total.value)
 
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):

@@ -34,6 +34,14 @@ int sh_wcc_labels(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32
 int sh_triangle_counts(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                        uint64_t *tri, int32_t *deg);
 
+/* The core numbers of the simple undirected graph under a square CSR pattern (clean, then the bucket algorithm of
+ * Batagelj and Zaversnik; single-threaded, O(rows + edges) after the clean-up's sort): the gold for sh_core.  Entry (r, c)
+ * counts when 0 <= c < rows, c != r and its 32 value bits are not all zero, in either direction, once.  core[v] (rows
+ * words) becomes the largest k such that v lies in a subgraph whose vertices all have at least k neighbours in it, deg[v]
+ * (rows words) its degree, *edges (may be NULL) the number of edges.  Return 0, -1 bad argument. */
+int sh_core_numbers(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                    int32_t *core, int32_t *deg, int64_t *edges);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

@@ -1,8 +1,8 @@
 """ctypes face of libsparseharness_host.so (no HIP): the product's MatrixMarket
 loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
-host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp) and sh_tri
-(host/src/triangle_counts.cpp)."""
+host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp), sh_tri
+(host/src/triangle_counts.cpp) and sh_core (host/src/core_numbers.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -50,6 +50,9 @@ def load():
         _lib.sh_wcc_labels.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.sh_triangle_counts.restype = C.c_int
         _lib.sh_triangle_counts.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.sh_core_numbers.restype = C.c_int
+        _lib.sh_core_numbers.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int64)]
         _lib.sh_mm_load.restype = C.c_int
         _lib.sh_mm_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]
         _lib.sh_mm_load_ex.restype = C.c_int
@@ -137,6 +140,23 @@ def triangle_counts(row_ptr, col_idx, val):
     if rc:
         raise RuntimeError(f"sh_triangle_counts failed: {rc}")
     return tri, deg
+
+
+def core_numbers(row_ptr, col_idx, val):
+    """-> (core, deg, M): core[v] (int32) = the core number of v in the simple undirected graph under the entries,
+    deg[v] (int32) = its degree there (Engine.core_numbers' core and deg), M = the number of edges, by the single-threaded
+    bucket algorithm of Batagelj and Zaversnik on the host.  Entry (r, c) counts when 0 <= c < rows, c != r and its 32
+    value bits are not all zero."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    val = np.ascontiguousarray(val)
+    assert val.dtype.itemsize == 4 and len(val) == len(col_idx)
+    n = len(row_ptr) - 1
+    core, deg, m = np.empty(n, np.int32), np.empty(n, np.int32), C.c_int64()
+    rc = load().sh_core_numbers(n, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), _p(core), _p(deg), C.byref(m))
+    if rc:
+        raise RuntimeError(f"sh_core_numbers failed: {rc}")
+    return core, deg, m.value
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2

@@ -1,0 +1,302 @@
+"""sh_core on the GPU: core, deg, the number of edges, degeneracy and levels against tests/core_ref.py (pinned by
+tests/test_core_ref.py), against closed forms and against the host gold, for chase in (0, 1, 16); with chase == 0 the
+records of every round as well.
+
+Every comparison is exact (==): core numbers are integers and a graph has one vector of them, whatever the lanes race
+on.  The shapes are the smallest at which the kernels can still go wrong: lists on both sides of the classes' limits
+(one lane up to 8 entries, one wave up to 2048, pieces beyond), one hub of 70 001 entries (35 pieces), more rounds
+than a batch holds (the grid, the path, R-MAT).
+The caps on the round counts with chase > 0 are the reference's counts with chase == 0, which tests/test_core_ref.py
+asserts."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import core_ref as R
+import tri_ref as T
+import wcc_ref as W
+from sparseharness_amd import abi
+from sparseharness_amd import hostlib as H
+from sparseharness_amd.engine import Engine, EngineError
+
+pytestmark = pytest.mark.gpu
+
+CHASES = (0, 1, 16)
+_cache, _want = {}, {}
+
+
+def _loops():
+    n = 1000
+    return n, np.arange(n + 1, dtype=np.int32), np.arange(n, dtype=np.int32), np.ones(n, np.float32)
+
+
+MAKERS = {
+    "no-rows": lambda: (0, np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32)),
+    "empty": lambda: (5, np.zeros(6, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32)),
+    "loops": _loops,
+    "pattern": T.pattern,
+    "noise": lambda: T.with_noise(*T.pattern()),
+    "upper": lambda: T.upper_only(*T.pattern()),
+    "lower": lambda: T.lower_only(*T.pattern()),
+    "K9": lambda: T.complete(9),
+    "K300": lambda: T.complete(300),
+    "K300,200": lambda: T.bipartite(300, 200),
+    "path": lambda: W.path(4096),
+    "tree": R.tree,
+    "cycle": lambda: R.cycle(1000),
+    "grid": lambda: W.grid(128),
+    "tgrid": lambda: T.triangulated_grid(128),
+    "friendship": lambda: T.friendship(500),
+    "star": lambda: R.star(3000),
+    "cliques": R.cliques,
+    "isolated": R.isolated,
+    "limits": lambda: R.class_limits()[:4],
+    "hub": R.big_hub,
+    "hub+K9": lambda: R.big_hub(clique=9),
+    "rmat12": lambda: (1 << 12,) + H.rmat(12, seed=40),
+    "rmat15": lambda: (1 << 15,) + H.rmat(15, seed=40),
+}
+TRIVIAL = ("no-rows", "empty", "loops")
+PATTERNS = tuple(k for k in MAKERS if k not in TRIVIAL)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = Engine(0)
+    yield e
+    e.close()
+
+
+def matrix(name):
+    if name not in _cache:
+        n, rp, ci, va = MAKERS[name]()
+        _cache[name] = (n, rp, ci, np.ascontiguousarray(va))
+    return _cache[name]
+
+
+def want(name):
+    """The reference's answer and records, computed once per pattern and left unchanged."""
+    if name not in _want:
+        r = R.peel(*matrix(name))
+        for v in r.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+        _want[name] = r
+    return _want[name]
+
+
+def header_footprint(n, edges):
+    """The formula of include/sparseharness_hip.h (tests/test_core_abi.py asserts that the header states it)."""
+    return 4 * (n + 1) + 8 * edges + 16 * n + 16 * ((2 * edges) // 1024 + 1) + 34816
+
+
+def run(eng, mat, chase, with_deg=True, max_rounds=None, G=None):
+    """-> dict of one call's outputs (on a handle of its own unless G is given)."""
+    n = mat[0]
+    own = G is None
+    if own:
+        G = eng.core_graph(*mat[1:])
+    cv = eng.alloc(max(n, 1))
+    dv = eng.alloc(max(n, 1)) if with_deg else None
+    try:
+        cv.upload(np.full(max(n, 1), 7, np.int32))
+        degeneracy, levels, rounds, complete, ks, sizes, chased, edges, ns, total = eng.core_numbers(G, cv, dv, chase=chase,
+                                                                                                     max_rounds=max_rounds)
+        return dict(core=cv.download(np.int32, n) if n else np.zeros(0, np.int32),
+                    deg=dv.download(np.int32, n) if (with_deg and n) else np.zeros(0, np.int32),
+                    degeneracy=degeneracy, levels=levels, rounds=rounds, complete=complete, k=ks, size=sizes, chased=chased,
+                    edges=edges, M=G.edges, max_degree=G.max_degree, footprint=G.footprint)
+    finally:
+        cv.free()
+        if dv is not None:
+            dv.free()
+        if own:
+            G.free()
+
+
+def check(eng, name, chase, mat=None):
+    w = want(name)
+    mat = matrix(name) if mat is None else mat
+    n = mat[0]
+    got = run(eng, mat, chase)
+    assert np.array_equal(got["core"], w["core"]) and np.array_equal(got["deg"], w["deg"])
+    assert got["M"] == w["M"] and got["degeneracy"] == w["degeneracy"] and got["levels"] == w["levels"]
+    assert got["complete"] is True
+    assert got["max_degree"] == (int(w["deg"].max()) if n else 0)
+    assert got["footprint"] == header_footprint(n, w["M"])
+    assert int(got["size"].sum() + got["chased"].sum()) == n
+    if chase == 0:
+        assert got["rounds"] == w["rounds"] and (got["chased"] == 0).all()
+        for f in ("k", "size", "edges"):
+            assert np.array_equal(got[f], w[f]), f
+    else:
+        assert got["rounds"] <= w["rounds"]
+    return got
+
+
+# ---- 1. trivial inputs
+@pytest.mark.parametrize("chase", CHASES)
+@pytest.mark.parametrize("name", TRIVIAL)
+def test_nothing_to_peel(eng, name, chase):
+    got = check(eng, name, chase)
+    assert (got["core"] == 0).all() and got["degeneracy"] == 0 and got["M"] == 0 and got["rounds"] <= 1
+    assert got["levels"] == (0 if name == "no-rows" else 1)
+
+
+# ---- 2. every pattern
+@pytest.mark.parametrize("chase", CHASES)
+@pytest.mark.parametrize("name", PATTERNS)
+def test_patterns(eng, name, chase):
+    check(eng, name, chase)
+
+
+@pytest.mark.parametrize("chase", CHASES)
+def test_noise_and_storage_forms_change_nothing(eng, chase):
+    for form in ("noise", "upper", "lower"):
+        check(eng, "pattern", chase, mat=matrix(form))
+
+
+def test_closed_forms(eng):
+    core = lambda name: run(eng, matrix(name), 0)["core"]   # noqa: E731
+    assert (core("K9") == 8).all() and (core("K300") == 299).all()
+    assert (core("path") == 1).all() and (core("tree") == 1).all() and (core("star") == 1).all()
+    assert (core("cycle") == 2).all() and (core("grid") == 2).all() and (core("friendship") == 2).all()
+    assert (core("K300,200") == 200).all()
+    got = run(eng, matrix("cliques"), 0)
+    assert got["levels"] == 39 and got["degeneracy"] == 39 and got["rounds"] == 39
+    iso = core("isolated")
+    assert (iso[:100] == 2).all() and (iso[100:] == 0).all()
+
+
+# ---- 3. chasing shortens chains
+@pytest.mark.parametrize("chase", [1, 4, 16, 64])
+def test_path_takes_fewer_rounds_with_chase(eng, chase):
+    assert want("path")["rounds"] == 2048
+    got = check(eng, "path", chase)
+    assert got["rounds"] <= 2048 / (chase + 1) + 2
+    assert int(got["chased"].sum()) > 0
+
+
+# ---- 4. class limits
+@pytest.mark.parametrize("chase", CHASES)
+def test_class_limits(eng, chase):
+    n, rp, ci, va, hubs = R.class_limits()
+    got = check(eng, "limits", chase)
+    assert tuple(got["deg"][hubs].tolist()) == (8, 9, 2048, 2049, 4097)
+    assert (got["core"][hubs] == 2).all()
+    for h, d in zip(hubs.tolist(), R.HUB_DEGREES):   # the hub's walk reached its first and its last entry
+        assert got["core"][h + 1] == 2 and got["core"][h + 6 + d - 2] == 2 and (got["core"][h + 2:h + 6] == 3).all()
+
+
+@pytest.mark.parametrize("chase", CHASES)
+def test_hub_of_70001_leaves(eng, chase):
+    got = check(eng, "hub", chase)
+    assert (got["core"] == 1).all() and got["max_degree"] == 70_001
+    got = check(eng, "hub+K9", chase)
+    assert got["core"][0] == 8 and (got["core"][1:70_002] == 1).all() and (got["core"][70_002:] == 8).all()
+
+
+# ---- 5. the decrement race: every vertex is hit by hundreds of lanes in one round
+@pytest.mark.parametrize("name", ["K300", "K300,200"])
+def test_decrement_race_gives_one_answer(eng, name):
+    w = want(name)
+    assert w["rounds"] == (1 if name == "K300" else 2)
+    first = check(eng, name, 0)
+    second = check(eng, name, 0)
+    third = check(eng, name, 0)
+    for other in (second, third):
+        for f in ("core", "deg", "k", "size", "edges"):
+            assert np.array_equal(first[f], other[f])
+
+
+# ---- 6. max_rounds cuts a run short; the handle serves the next call
+def test_cut_short_and_reuse(eng):
+    mat = matrix("grid")
+    n = mat[0]
+    full = want("grid")
+    part = R.peel(*mat, max_rounds=10)
+    G = eng.core_graph(*mat[1:])
+    try:
+        got = run(eng, mat, 0, max_rounds=10, G=G)
+        assert got["complete"] is False and got["rounds"] == 10
+        assert np.array_equal(got["core"], part["core"]) and (got["core"][part["core"] < 0] == -1).all()
+        assert np.array_equal(got["size"], full["size"][:10]) and np.array_equal(got["k"], full["k"][:10])
+        again = run(eng, mat, 0, G=G)
+        assert again["complete"] is True and again["rounds"] == full["rounds"]
+        assert np.array_equal(again["core"], full["core"]) and np.array_equal(again["deg"], full["deg"])
+        assert int(again["size"].sum()) == n
+    finally:
+        G.free()
+
+
+# ---- 7. two handles, calls alternated
+def test_two_handles_interleaved(eng):
+    a, b = matrix("rmat12"), matrix("pattern")
+    Ga, Gb = eng.core_graph(*a[1:]), eng.core_graph(*b[1:])
+    try:
+        for chase in (0, 16, 0):
+            ga = run(eng, a, chase, G=Ga)
+            gb = run(eng, b, chase, G=Gb)
+            for got, name in ((ga, "rmat12"), (gb, "pattern")):
+                w = want(name)
+                assert np.array_equal(got["core"], w["core"]) and np.array_equal(got["deg"], w["deg"])
+                assert got["complete"] is True and got["degeneracy"] == w["degeneracy"] and got["levels"] == w["levels"]
+                if chase == 0:
+                    assert got["rounds"] == w["rounds"] and np.array_equal(got["size"], w["size"])
+    finally:
+        Ga.free()
+        Gb.free()
+
+
+# ---- 8. the call's face
+def test_optional_outputs_through_the_abi(eng):
+    """deg == NULL and every per-round array NULL; vectors longer than rows keep their tail; short ones are refused
+    with the buffers untouched."""
+    n, rp, ci, va = matrix("rmat12")
+    w = want("rmat12")
+    lib = abi.load()
+    G = eng.core_graph(rp, ci, va)
+    spare = 5
+    cv, dv, short = eng.alloc(n + spare), eng.alloc(n + spare), eng.alloc(n - 1)
+    try:
+        cv.upload(np.full(n + spare, 7, np.int32))
+        d, lv, rd, cp = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        rc = lib.sh_core(eng.h, G.h, cv.h, None, 0, n + 1, C.byref(d), C.byref(lv), C.byref(rd), C.byref(cp),
+                         None, None, None, None, None, None)
+        assert rc == abi.SH_OK
+        assert (d.value, lv.value, rd.value, cp.value) == (w["degeneracy"], w["levels"], w["rounds"], 1)
+        c = cv.download(np.int32)
+        assert np.array_equal(c[:n], w["core"]) and (c[n:] == 7).all()
+        dv.upload(np.full(n + spare, 7, np.int32))
+        eng.core_numbers(G, cv, dv)
+        dd = dv.download(np.int32)
+        assert np.array_equal(dd[:n], w["deg"]) and (dd[n:] == 7).all()
+        short.upload(np.full(n - 1, 7, np.int32))
+        cv.upload(np.full(n + spare, 7, np.int32))
+        dv.upload(np.full(n + spare, 7, np.int32))
+        for bad_c, bad_d in ((short, dv), (cv, short)):
+            with pytest.raises(EngineError) as err:
+                eng.core_numbers(G, bad_c, bad_d)
+            assert err.value.code == abi.SH_ESHAPE
+        for bad in (dict(chase=-1), dict(max_rounds=0)):
+            with pytest.raises(EngineError) as err:
+                eng.core_numbers(G, cv, dv, **bad)
+            assert err.value.code == abi.SH_EINVAL
+        for v in (short, cv, dv):
+            assert (v.download(np.int32) == 7).all()             # the buffers are untouched
+    finally:
+        for v in (cv, dv, short):
+            v.free()
+        G.free()
+
+
+# ---- 9. against the host gold
+@pytest.mark.parametrize("name", ["rmat15", "tgrid"])
+def test_against_the_host_gold(eng, name):
+    n, rp, ci, va = matrix(name)
+    core, deg, edges = H.core_numbers(rp, ci, va)
+    for chase in (0, 16):
+        got = run(eng, matrix(name), chase)
+        assert np.array_equal(got["core"], core) and np.array_equal(got["deg"], deg) and got["M"] == edges
+        assert got["degeneracy"] == int(core.max()) and got["levels"] == len(np.unique(core))
