@@ -1799,6 +1799,10 @@ static int free_handle(sh_engine *e, H *h) {
   return SH_OK;
 }
 
+// What every sh_*_footprint / _edges / _max_forward / _max_degree / _delta accessor is: SH_EINVAL for a NULL handle or
+// out pointer (no message is set: there is no engine to hold one), else the value.
+#define HANDLE_GET(h, out, value) ((h) && (out) ? (*(out) = (value), (int)SH_OK) : (int)SH_EINVAL)
+
 static hipError_t ms_between(hipEvent_t a, hipEvent_t b, uint64_t *ns) {
   float ms = 0.f;
   const hipError_t r = hipEventElapsedTime(&ms, a, b);
@@ -1829,9 +1833,14 @@ static int build_transpose(sh_engine *e, DevArrays &tmp, const int32_t *ptr, con
 
 // What sh_bfs_graph, sh_sssp_graph, sh_scc_graph and sh_wcc_graph share: the edges by row (in_*) and by source vertex (out_*), the static pieces of
 // the long rows, and what a batch of gated steps needs (run_batches).  sh_core_graph keeps its symmetric lists in in_* alone.
-template <class Ctl>
-struct GraphHandle {
+// What every sh_*_graph has: the shape it was made from, the edges it kept, and the device arrays it owns.
+struct GraphBase {
   int64_t rows = 0, nnz = 0, edges = 0;
+  DevArrays dev;   // (released after whatever a derived handle's destructor lets go of)
+};
+
+template <class Ctl>
+struct GraphHandle : GraphBase {
   int32_t *d_in_ptr = nullptr, *d_in_col = nullptr, *d_out_ptr = nullptr, *d_out_row = nullptr;
   uint32_t *d_in_w = nullptr, *d_out_w = nullptr;   // |a| of every edge (NULL in a handle without weights)
   WlPiece *d_rpieces = nullptr;                     // pieces of the rows above the handle's row piece size (static)
@@ -1840,7 +1849,6 @@ struct GraphHandle {
   WlPart *d_part = nullptr;
   Ctl *h_ctl = nullptr;            // pinned: the control block as read back once per batch
   hipEvent_t ev[sizeof(Ctl::rec) / sizeof(Ctl::rec[0]) + 1] = {};
-  DevArrays dev;
   ~GraphHandle() {
     if (h_ctl) (void)hipHostFree(h_ctl);
     for (auto v : ev)
@@ -1937,6 +1945,28 @@ static int open_control(sh_engine *e, GraphHandle<Ctl> *g, int64_t ctl_bytes, in
   HIP_TRY(e, hipHostMalloc((void **)&g->h_ctl, sizeof(Ctl), hipHostMallocDefault));
   for (auto &ev : g->ev) HIP_TRY(e, hipEventCreate(&ev));
   HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, (size_t)nbytes, e->stream));
+  return SH_OK;
+}
+
+// What fn = sh_bfs_graph_create / ... / sh_core_graph_create share: *out is cleared, the host arrays are checked
+// (check_host_csr), the handle is made, build(g) fills it, and once the stream has drained the handle is the caller's.
+// On any error the handle and what it allocated so far are released and *out stays NULL.  (A build that has to wait for
+// the stream itself, as sh_sssp_graph's for its weight sum and sh_tri_graph's for its longest list, leaves it idle.)
+template <class H, class Build>
+static int create_graph_handle(sh_engine *e, const char *fn, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                               const void *val, H **out, Build build) {
+  if (out) *out = nullptr;
+  int rc = check_host_csr(e, fn, rows, nnz, row_ptr, col_idx, val, out);
+  if (rc)
+    return rc;
+  HIP_TRY(e, hipSetDevice(e->device));
+  std::unique_ptr<H> g(new (std::nothrow) H());
+  if (!g)
+    return fail(e, SH_ENOMEM, "out of host memory");
+  if ((rc = build(g.get())))
+    return rc;
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  *out = g.release();
   return SH_OK;
 }
 
@@ -2088,12 +2118,7 @@ int sh_frontier_create(sh_engine *e, const sh_csr *A, int64_t nnz, const int32_t
 
 int sh_frontier_free(sh_engine *e, sh_frontier *f) { return free_handle(e, f); }
 
-int sh_frontier_footprint(const sh_frontier *f, uint64_t *device_bytes) {
-  if (!f || !device_bytes)
-    return SH_EINVAL;
-  *device_bytes = (uint64_t)f->dev.bytes;
-  return SH_OK;
-}
+int sh_frontier_footprint(const sh_frontier *f, uint64_t *device_bytes) { return HANDLE_GET(f, device_bytes, (uint64_t)f->dev.bytes); }
 
 int sh_frontier_transpose(sh_engine *e, const sh_frontier *f, int32_t *col_ptr, int32_t *row_of) {
   if (!e || !f)
@@ -2231,44 +2256,25 @@ extern "C" {
 
 int sh_bfs_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                         const void *val, sh_bfs_graph **out) {
-  if (out) *out = nullptr;
-  int rc = check_host_csr(e, "sh_bfs_graph_create", rows, nnz, row_ptr, col_idx, val, out);
-  if (rc)
-    return rc;
-  HIP_TRY(e, hipSetDevice(e->device));
-  std::unique_ptr<sh_bfs_graph> g(new (std::nothrow) sh_bfs_graph());
-  if (!g)
-    return fail(e, SH_ENOMEM, "out of host memory");
-  g->words = (int32_t)((rows + 31) / 32);
-  if ((rc = build_edge_lists<BfsKeep, BFS_ROW_PIECE>(e, g.get(), rows, nnz, row_ptr, col_idx, val, false)))
-    return rc;
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(e, g->dev.alloc(&g->d_queue[i], rows * 4));
-    HIP_TRY(e, g->dev.alloc(&g->d_bm[i], (int64_t)g->words * 4));
-    HIP_TRY(e, g->dev.alloc(&g->d_opieces[i], (g->edges / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: out-lists longer than 2048
-  }
-  if ((rc = open_control(e, g.get(), BFS_CTL_BYTES, BFS_CTL_BYTES + BFS_PART_BYTES)))
-    return rc;
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  *out = g.release();
-  return SH_OK;
+  return create_graph_handle<sh_bfs_graph>(e, "sh_bfs_graph_create", rows, nnz, row_ptr, col_idx, val, out, [&](sh_bfs_graph *g) -> int {
+    int rc;
+    g->words = (int32_t)((rows + 31) / 32);
+    if ((rc = build_edge_lists<BfsKeep, BFS_ROW_PIECE>(e, g, rows, nnz, row_ptr, col_idx, val, false)))
+      return rc;
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(e, g->dev.alloc(&g->d_queue[i], rows * 4));
+      HIP_TRY(e, g->dev.alloc(&g->d_bm[i], (int64_t)g->words * 4));
+      HIP_TRY(e, g->dev.alloc(&g->d_opieces[i], (g->edges / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: out-lists longer than 2048
+    }
+    return open_control(e, g, BFS_CTL_BYTES, BFS_CTL_BYTES + BFS_PART_BYTES);
+  });
 }
 
 int sh_bfs_graph_free(sh_engine *e, sh_bfs_graph *g) { return free_handle(e, g); }
 
-int sh_bfs_graph_footprint(const sh_bfs_graph *g, uint64_t *device_bytes) {
-  if (!g || !device_bytes)
-    return SH_EINVAL;
-  *device_bytes = (uint64_t)g->dev.bytes;
-  return SH_OK;
-}
+int sh_bfs_graph_footprint(const sh_bfs_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
 
-int sh_bfs_graph_edges(const sh_bfs_graph *g, int64_t *edges) {
-  if (!g || !edges)
-    return SH_EINVAL;
-  *edges = g->edges;
-  return SH_OK;
-}
+int sh_bfs_graph_edges(const sh_bfs_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
 
 int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level, sh_vec *parent, int32_t max_levels,
                   double up_share, double down_share, int32_t *depth, int64_t *reached, int32_t *complete,
@@ -2380,70 +2386,49 @@ extern "C" {
 
 int sh_sssp_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                          const void *val, sh_sssp_graph **out) {
-  if (out) *out = nullptr;
-  int rc = check_host_csr(e, "sh_sssp_graph_create", rows, nnz, row_ptr, col_idx, val, out);
-  if (rc)
-    return rc;
-  HIP_TRY(e, hipSetDevice(e->device));
-  std::unique_ptr<sh_sssp_graph> g(new (std::nothrow) sh_sssp_graph());
-  if (!g)
-    return fail(e, SH_ENOMEM, "out of host memory");
-  if ((rc = build_edge_lists<SsspKeep, SSSP_ROW_PIECE>(e, g.get(), rows, nnz, row_ptr, col_idx, val, true)))
-    return rc;
-  const int64_t E = g->edges;
-  HIP_TRY(e, g->dev.alloc(&g->d_stamp, rows * 4));
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(e, g->dev.alloc(&g->d_near[i], rows * 4));
-    HIP_TRY(e, g->dev.alloc(&g->d_far[i], rows * 4));
-    HIP_TRY(e, g->dev.alloc(&g->d_opieces[i], (E / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: out-lists longer than 2048
-  }
-  if ((rc = open_control(e, g.get(), SSSP_CTL_BYTES, SSSP_CTL_BYTES + SSSP_PART_BYTES + SSSP_PMIN_BYTES)))
-    return rc;
-  g->d_pmin = (uint32_t *)((char *)g->d_ctl + SSSP_CTL_BYTES + SSSP_PART_BYTES);
-  // the mean weight, for the default bucket width
-  constexpr int SUM_BLOCKS = 256;
-  DevArrays tmp;
-  double *t_sum = nullptr, h_sum[SUM_BLOCKS] = {};
-  HIP_TRY(e, tmp.alloc(&t_sum, SUM_BLOCKS * sizeof(double)));
-  if (E > 0) {
-    hipLaunchKernelGGL(sssp_weight_sum, dim3(SUM_BLOCKS), dim3(WL_BS), 0, e->stream, g->d_in_w, E, t_sum);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipMemcpyAsync(h_sum, t_sum, sizeof(h_sum), hipMemcpyDeviceToHost, e->stream));
-  }
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  if (E > 0) {
-    double sum = 0.0;
-    for (double v : h_sum) sum += v;
-    // factor * (sum / E) / (E / rows); a graph whose weights are all zero has one bucket whatever the width: 1
-    const double d = SSSP_DELTA_FACTOR * (sum / (double)E) * ((double)rows / (double)E);
-    g->delta = (d > 0.0 && d < 1e300) ? d : 1.0;
-  }
-  *out = g.release();
-  return SH_OK;
+  return create_graph_handle<sh_sssp_graph>(e, "sh_sssp_graph_create", rows, nnz, row_ptr, col_idx, val, out, [&](sh_sssp_graph *g) -> int {
+    int rc;
+    if ((rc = build_edge_lists<SsspKeep, SSSP_ROW_PIECE>(e, g, rows, nnz, row_ptr, col_idx, val, true)))
+      return rc;
+    const int64_t E = g->edges;
+    HIP_TRY(e, g->dev.alloc(&g->d_stamp, rows * 4));
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(e, g->dev.alloc(&g->d_near[i], rows * 4));
+      HIP_TRY(e, g->dev.alloc(&g->d_far[i], rows * 4));
+      HIP_TRY(e, g->dev.alloc(&g->d_opieces[i], (E / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: out-lists longer than 2048
+    }
+    if ((rc = open_control(e, g, SSSP_CTL_BYTES, SSSP_CTL_BYTES + SSSP_PART_BYTES + SSSP_PMIN_BYTES)))
+      return rc;
+    g->d_pmin = (uint32_t *)((char *)g->d_ctl + SSSP_CTL_BYTES + SSSP_PART_BYTES);
+    // the mean weight, for the default bucket width
+    constexpr int SUM_BLOCKS = 256;
+    DevArrays tmp;
+    double *t_sum = nullptr, h_sum[SUM_BLOCKS] = {};
+    HIP_TRY(e, tmp.alloc(&t_sum, SUM_BLOCKS * sizeof(double)));
+    if (E > 0) {
+      hipLaunchKernelGGL(sssp_weight_sum, dim3(SUM_BLOCKS), dim3(WL_BS), 0, e->stream, g->d_in_w, E, t_sum);
+      HIP_TRY(e, hipGetLastError());
+      HIP_TRY(e, hipMemcpyAsync(h_sum, t_sum, sizeof(h_sum), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // (h_sum and t_sum end with this scope: the sums must have landed)
+    if (E > 0) {
+      double sum = 0.0;
+      for (double v : h_sum) sum += v;
+      // factor * (sum / E) / (E / rows); a graph whose weights are all zero has one bucket whatever the width: 1
+      const double d = SSSP_DELTA_FACTOR * (sum / (double)E) * ((double)rows / (double)E);
+      g->delta = (d > 0.0 && d < 1e300) ? d : 1.0;
+    }
+    return SH_OK;
+  });
 }
 
 int sh_sssp_graph_free(sh_engine *e, sh_sssp_graph *g) { return free_handle(e, g); }
 
-int sh_sssp_graph_footprint(const sh_sssp_graph *g, uint64_t *device_bytes) {
-  if (!g || !device_bytes)
-    return SH_EINVAL;
-  *device_bytes = (uint64_t)g->dev.bytes;
-  return SH_OK;
-}
+int sh_sssp_graph_footprint(const sh_sssp_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
 
-int sh_sssp_graph_edges(const sh_sssp_graph *g, int64_t *edges) {
-  if (!g || !edges)
-    return SH_EINVAL;
-  *edges = g->edges;
-  return SH_OK;
-}
+int sh_sssp_graph_edges(const sh_sssp_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
 
-int sh_sssp_graph_delta(const sh_sssp_graph *g, double *delta) {
-  if (!g || !delta)
-    return SH_EINVAL;
-  *delta = g->delta;
-  return SH_OK;
-}
+int sh_sssp_graph_delta(const sh_sssp_graph *g, double *delta) { return HANDLE_GET(g, delta, g->delta); }
 
 int sh_sssp(sh_engine *e, sh_sssp_graph *g, const sh_vec *x0, sh_vec *dist, sh_vec *pred, double delta,
             int32_t max_rounds, int32_t *rounds, int32_t *buckets, int64_t *reached, int32_t *complete,
@@ -2542,48 +2527,31 @@ extern "C" {
 
 int sh_scc_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                         const void *val, sh_scc_graph **out) {
-  if (out) *out = nullptr;
-  int rc = check_host_csr(e, "sh_scc_graph_create", rows, nnz, row_ptr, col_idx, val, out);
-  if (rc)
-    return rc;
-  HIP_TRY(e, hipSetDevice(e->device));
-  std::unique_ptr<sh_scc_graph> g(new (std::nothrow) sh_scc_graph());
-  if (!g)
-    return fail(e, SH_ENOMEM, "out of host memory");
-  if ((rc = build_edge_lists<BfsKeep, SCC_ROW_PIECE>(e, g.get(), rows, nnz, row_ptr, col_idx, val, false)))
-    return rc;
-  const int64_t E = g->edges;
-  HIP_TRY(e, g->dev.alloc(&g->d_colour, rows * 4));
-  HIP_TRY(e, g->dev.alloc(&g->d_stamp, rows * 4));
-  HIP_TRY(e, g->dev.alloc(&g->d_cand, rows * 4));
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(e, g->dev.alloc(&g->d_list[i], rows * 4));
-    HIP_TRY(e, g->dev.alloc(&g->d_opieces[i], (E / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: lists longer than 2048
-    HIP_TRY(e, g->dev.alloc(&g->d_ipieces[i], (E / 1024 + 1) * sizeof(WlPiece)));
-  }
-  if ((rc = open_control(e, g.get(), SCC_CTL_BYTES, SCC_CTL_BYTES + SCC_PART_BYTES + SCC_PICK_BYTES)))
-    return rc;
-  g->d_pick = (SccPick *)((char *)g->d_ctl + SCC_CTL_BYTES + SCC_PART_BYTES);
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  *out = g.release();
-  return SH_OK;
+  return create_graph_handle<sh_scc_graph>(e, "sh_scc_graph_create", rows, nnz, row_ptr, col_idx, val, out, [&](sh_scc_graph *g) -> int {
+    int rc;
+    if ((rc = build_edge_lists<BfsKeep, SCC_ROW_PIECE>(e, g, rows, nnz, row_ptr, col_idx, val, false)))
+      return rc;
+    const int64_t E = g->edges;
+    HIP_TRY(e, g->dev.alloc(&g->d_colour, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->d_stamp, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->d_cand, rows * 4));
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(e, g->dev.alloc(&g->d_list[i], rows * 4));
+      HIP_TRY(e, g->dev.alloc(&g->d_opieces[i], (E / 1024 + 1) * sizeof(WlPiece)));   // see wl_push_pieces: lists longer than 2048
+      HIP_TRY(e, g->dev.alloc(&g->d_ipieces[i], (E / 1024 + 1) * sizeof(WlPiece)));
+    }
+    if ((rc = open_control(e, g, SCC_CTL_BYTES, SCC_CTL_BYTES + SCC_PART_BYTES + SCC_PICK_BYTES)))
+      return rc;
+    g->d_pick = (SccPick *)((char *)g->d_ctl + SCC_CTL_BYTES + SCC_PART_BYTES);
+    return SH_OK;
+  });
 }
 
 int sh_scc_graph_free(sh_engine *e, sh_scc_graph *g) { return free_handle(e, g); }
 
-int sh_scc_graph_footprint(const sh_scc_graph *g, uint64_t *device_bytes) {
-  if (!g || !device_bytes)
-    return SH_EINVAL;
-  *device_bytes = (uint64_t)g->dev.bytes;
-  return SH_OK;
-}
+int sh_scc_graph_footprint(const sh_scc_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
 
-int sh_scc_graph_edges(const sh_scc_graph *g, int64_t *edges) {
-  if (!g || !edges)
-    return SH_EINVAL;
-  *edges = g->edges;
-  return SH_OK;
-}
+int sh_scc_graph_edges(const sh_scc_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
 
 int sh_scc(sh_engine *e, sh_scc_graph *g, sh_vec *comp, int32_t trim, int32_t pivot, int32_t max_steps,
            int64_t *components, int64_t *settled, int64_t *trimmed, int32_t *rounds, int32_t *steps, int32_t *complete,
@@ -2688,44 +2656,27 @@ extern "C" {
 
 int sh_wcc_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                         const void *val, sh_wcc_graph **out) {
-  if (out) *out = nullptr;
-  int rc = check_host_csr(e, "sh_wcc_graph_create", rows, nnz, row_ptr, col_idx, val, out);
-  if (rc)
-    return rc;
-  HIP_TRY(e, hipSetDevice(e->device));
-  std::unique_ptr<sh_wcc_graph> g(new (std::nothrow) sh_wcc_graph());
-  if (!g)
-    return fail(e, SH_ENOMEM, "out of host memory");
-  if ((rc = build_edge_lists<BfsKeep, WCC_ROW_PIECE>(e, g.get(), rows, nnz, row_ptr, col_idx, val, false)))
-    return rc;
-  const int64_t E = g->edges;
-  HIP_TRY(e, g->dev.alloc(&g->d_parent, rows * 4));
-  HIP_TRY(e, g->dev.alloc(&g->d_list, rows * 4));   // a vertex joins the work list at most once per call (wcc_compact)
-  HIP_TRY(e, g->dev.alloc(&g->d_ipieces, (E / (WCC_PIECE / 2) + 1) * sizeof(WlPiece)));   // see wl_push_pieces
-  HIP_TRY(e, g->dev.alloc(&g->d_opieces, (E / (WCC_PIECE / 2) + 1) * sizeof(WlPiece)));
-  if ((rc = open_control(e, g.get(), WCC_CTL_BYTES, WCC_CTL_BYTES + 2 * WCC_PART_BYTES)))
-    return rc;
-  g->d_jpart = (WlPart *)((char *)g->d_ctl + WCC_CTL_BYTES + WCC_PART_BYTES);
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  *out = g.release();
-  return SH_OK;
+  return create_graph_handle<sh_wcc_graph>(e, "sh_wcc_graph_create", rows, nnz, row_ptr, col_idx, val, out, [&](sh_wcc_graph *g) -> int {
+    int rc;
+    if ((rc = build_edge_lists<BfsKeep, WCC_ROW_PIECE>(e, g, rows, nnz, row_ptr, col_idx, val, false)))
+      return rc;
+    const int64_t E = g->edges;
+    HIP_TRY(e, g->dev.alloc(&g->d_parent, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->d_list, rows * 4));   // a vertex joins the work list at most once per call (wcc_compact)
+    HIP_TRY(e, g->dev.alloc(&g->d_ipieces, (E / (WCC_PIECE / 2) + 1) * sizeof(WlPiece)));   // see wl_push_pieces
+    HIP_TRY(e, g->dev.alloc(&g->d_opieces, (E / (WCC_PIECE / 2) + 1) * sizeof(WlPiece)));
+    if ((rc = open_control(e, g, WCC_CTL_BYTES, WCC_CTL_BYTES + 2 * WCC_PART_BYTES)))
+      return rc;
+    g->d_jpart = (WlPart *)((char *)g->d_ctl + WCC_CTL_BYTES + WCC_PART_BYTES);
+    return SH_OK;
+  });
 }
 
 int sh_wcc_graph_free(sh_engine *e, sh_wcc_graph *g) { return free_handle(e, g); }
 
-int sh_wcc_graph_footprint(const sh_wcc_graph *g, uint64_t *device_bytes) {
-  if (!g || !device_bytes)
-    return SH_EINVAL;
-  *device_bytes = (uint64_t)g->dev.bytes;
-  return SH_OK;
-}
+int sh_wcc_graph_footprint(const sh_wcc_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
 
-int sh_wcc_graph_edges(const sh_wcc_graph *g, int64_t *edges) {
-  if (!g || !edges)
-    return SH_EINVAL;
-  *edges = g->edges;
-  return SH_OK;
-}
+int sh_wcc_graph_edges(const sh_wcc_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
 
 int sh_wcc(sh_engine *e, sh_wcc_graph *g, sh_vec *comp, int32_t sample, int32_t max_rounds,
            int64_t *components, int64_t *skipped, int32_t *rounds, int32_t *complete,
@@ -2807,13 +2758,14 @@ int sh_wcc(sh_engine *e, sh_wcc_graph *g, sh_vec *comp, int32_t sample, int32_t 
 } // extern "C"
 
 // ---- triangle counts by intersecting forward lists (tri.hip.h) -------------------------------------------------------
-struct sh_tri_graph {   // d_ctl: TRI_CTL_BYTES, followed by the TriParts of tri_count_light and those of tri_count_heavy
-  int64_t rows = 0, nnz = 0, edges = 0, max_forward = 0;
+// (a GraphBase, not a GraphHandle: sh_tri is a fixed handful of launches, so it needs neither the pinned copy of a control
+// block nor the events of a batch)
+struct sh_tri_graph : GraphBase {   // d_ctl: TRI_CTL_BYTES, followed by the TriParts of tri_count_light and those of tri_count_heavy
+  int64_t max_forward = 0;
   int32_t *d_fwd_ptr = nullptr, *d_fwd_col = nullptr;
   uint32_t *d_deg = nullptr;
   TriCtl *d_ctl = nullptr;
   TriPart *d_part = nullptr;
-  DevArrays dev;
 };
 static_assert(sizeof(TriCtl) <= TRI_CTL_BYTES, "the control block is accounted as TRI_CTL_BYTES (sh_tri_graph_footprint)");
 static_assert(sizeof(TriPart) * TRI_MAX_BLOCKS == TRI_PART_BYTES, "one TriPart per workgroup");
@@ -2930,43 +2882,20 @@ extern "C" {
 int sh_tri_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                         const void *val, int32_t order, sh_tri_graph **out) {
   if (out) *out = nullptr;
-  if (order != 0 && order != 1)
+  if (order != 0 && order != 1)   // (what the scalar alone decides comes before what the arrays do)
     return fail(e, SH_EINVAL, "sh_tri_graph_create: order = %d, must be 0 (by index) or 1 (by degree, then index)", (int)order);
-  int rc = check_host_csr(e, "sh_tri_graph_create", rows, nnz, row_ptr, col_idx, val, out);
-  if (rc)
-    return rc;
-  HIP_TRY(e, hipSetDevice(e->device));
-  std::unique_ptr<sh_tri_graph> g(new (std::nothrow) sh_tri_graph());
-  if (!g)
-    return fail(e, SH_ENOMEM, "out of host memory");
-  if ((rc = build_forward_lists(e, g.get(), rows, nnz, row_ptr, col_idx, val, order)))
-    return rc;
-  *out = g.release();
-  return SH_OK;
+  return create_graph_handle<sh_tri_graph>(e, "sh_tri_graph_create", rows, nnz, row_ptr, col_idx, val, out, [&](sh_tri_graph *g) -> int {
+    return build_forward_lists(e, g, rows, nnz, row_ptr, col_idx, val, order);
+  });
 }
 
 int sh_tri_graph_free(sh_engine *e, sh_tri_graph *g) { return free_handle(e, g); }
 
-int sh_tri_graph_footprint(const sh_tri_graph *g, uint64_t *device_bytes) {
-  if (!g || !device_bytes)
-    return SH_EINVAL;
-  *device_bytes = (uint64_t)g->dev.bytes;
-  return SH_OK;
-}
+int sh_tri_graph_footprint(const sh_tri_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
 
-int sh_tri_graph_edges(const sh_tri_graph *g, int64_t *edges) {
-  if (!g || !edges)
-    return SH_EINVAL;
-  *edges = g->edges;
-  return SH_OK;
-}
+int sh_tri_graph_edges(const sh_tri_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
 
-int sh_tri_graph_max_forward(const sh_tri_graph *g, int64_t *entries) {
-  if (!g || !entries)
-    return SH_EINVAL;
-  *entries = g->max_forward;
-  return SH_OK;
-}
+int sh_tri_graph_max_forward(const sh_tri_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->max_forward); }
 
 int sh_tri(sh_engine *e, sh_tri_graph *g, sh_vec *tri, sh_vec *deg, uint64_t *triangles, uint64_t *probes, uint64_t *total_ns) {
   if (!e || !g || !triangles)
@@ -3080,46 +3009,24 @@ extern "C" {
 
 int sh_core_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                          const void *val, sh_core_graph **out) {
-  if (out) *out = nullptr;
-  int rc = check_host_csr(e, "sh_core_graph_create", rows, nnz, row_ptr, col_idx, val, out);
-  if (rc)
-    return rc;
-  HIP_TRY(e, hipSetDevice(e->device));
-  std::unique_ptr<sh_core_graph> g(new (std::nothrow) sh_core_graph());
-  if (!g)
-    return fail(e, SH_ENOMEM, "out of host memory");
-  if ((rc = build_symmetric_lists(e, g.get(), rows, nnz, row_ptr, col_idx, val)))
-    return rc;
-  if ((rc = open_control(e, g.get(), CORE_CTL_BYTES, CORE_CTL_BYTES + 2 * CORE_PART_BYTES)))
-    return rc;
-  g->d_mins = (WlPart *)((char *)g->d_ctl + CORE_CTL_BYTES + CORE_PART_BYTES);
-  HIP_TRY(e, hipStreamSynchronize(e->stream));
-  *out = g.release();
-  return SH_OK;
+  return create_graph_handle<sh_core_graph>(e, "sh_core_graph_create", rows, nnz, row_ptr, col_idx, val, out, [&](sh_core_graph *g) -> int {
+    int rc;
+    if ((rc = build_symmetric_lists(e, g, rows, nnz, row_ptr, col_idx, val)))
+      return rc;
+    if ((rc = open_control(e, g, CORE_CTL_BYTES, CORE_CTL_BYTES + 2 * CORE_PART_BYTES)))
+      return rc;
+    g->d_mins = (WlPart *)((char *)g->d_ctl + CORE_CTL_BYTES + CORE_PART_BYTES);
+    return SH_OK;
+  });
 }
 
 int sh_core_graph_free(sh_engine *e, sh_core_graph *g) { return free_handle(e, g); }
 
-int sh_core_graph_footprint(const sh_core_graph *g, uint64_t *device_bytes) {
-  if (!g || !device_bytes)
-    return SH_EINVAL;
-  *device_bytes = (uint64_t)g->dev.bytes;
-  return SH_OK;
-}
+int sh_core_graph_footprint(const sh_core_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
 
-int sh_core_graph_edges(const sh_core_graph *g, int64_t *edges) {
-  if (!g || !edges)
-    return SH_EINVAL;
-  *edges = g->edges;
-  return SH_OK;
-}
+int sh_core_graph_edges(const sh_core_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
 
-int sh_core_graph_max_degree(const sh_core_graph *g, int64_t *entries) {
-  if (!g || !entries)
-    return SH_EINVAL;
-  *entries = g->max_degree;
-  return SH_OK;
-}
+int sh_core_graph_max_degree(const sh_core_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->max_degree); }
 
 int sh_core(sh_engine *e, sh_core_graph *g, sh_vec *core, sh_vec *deg, int32_t chase, int32_t max_rounds,
             int32_t *degeneracy, int32_t *levels, int32_t *rounds, int32_t *complete,

@@ -28,6 +28,25 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _csr_args(row_ptr, col_idx, val):
+    """The CSR arrays as the engine reads them: contiguous, int32 indices, values of 4 bytes."""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+    col_idx = np.ascontiguousarray(col_idx, np.int32)
+    val = np.ascontiguousarray(val)
+    assert val.dtype.itemsize == 4
+    return row_ptr, col_idx, val
+
+
+_CTYPE_OF = {np.int32: C.c_int32, np.int64: C.c_int64, np.uint64: C.c_uint64}
+
+
+def _outs(cap, *dtypes):
+    """(arrays, pointers): one zeroed host array of `cap` elements per dtype for the per-round figures of a driver, and
+    the typed pointers the engine writes them through."""
+    arrays = tuple(np.zeros(cap, dt) for dt in dtypes)
+    return arrays, tuple(a.ctypes.data_as(C.POINTER(_CTYPE_OF[dt])) for a, dt in zip(arrays, dtypes))
+
+
 class Vec:
     """Device vector of 4-byte elements (x, y, output of the harness)."""
 
@@ -115,12 +134,44 @@ class CsrMatrix:
             self.h = None
 
 
-class Frontier:
-    """What the sparse launches of Engine.iterate_frontier need for one square matrix: its CSR arrays (borrowed from
-    the matrix when it keeps them, copied otherwise), the pattern of its transpose, worklists."""
+class _Handle:
+    """A device-side handle made by the engine: `h` is the C handle, `n` its rows, `_c` the prefix of its C functions
+    (<_c>_create, <_c>_free, <_c>_footprint, ...)."""
+    _c = None
 
     def __init__(self, engine, handle, n):
         self.engine, self.h, self.n = engine, handle, n
+
+    def _get(self, suffix, ctype):
+        """What <_c>_<suffix> writes through its one out-pointer."""
+        v = ctype()
+        self.engine._chk(getattr(abi.load(), f"{self._c}_{suffix}")(self.h, C.byref(v)))
+        return v.value
+
+    def free(self):
+        if self.h is not None:
+            getattr(abi.load(), self._c + "_free")(self.engine.h, self.h)
+            self.h = None
+
+
+def _getter(suffix, ctype, doc):
+    """The read-only property behind <_c>_<suffix> (tests/test_abi.py checks `reads` against abi.SIGNATURES)."""
+    def get(self):
+        return self._get(suffix, ctype)
+    get.reads = (suffix, ctype)
+    return property(get, doc=doc)
+
+
+class _Graph(_Handle):
+    """A handle made from the host CSR arrays alone (Engine._graph): it needs no CsrMatrix."""
+    edges = _getter("edges", C.c_int64, "Entries kept as edges (non-zero value bits, column inside the matrix).")
+    footprint = _getter("footprint", C.c_uint64, "Device bytes held by the handle (the formula: include/sparseharness_hip.h).")
+
+
+class Frontier(_Handle):
+    """What the sparse launches of Engine.iterate_frontier need for one square matrix: its CSR arrays (borrowed from
+    the matrix when it keeps them, copied otherwise), the pattern of its transpose, worklists."""
+    _c = "sh_frontier"
 
     def transpose(self):
         """(col_ptr[n + 1], row_of[col_ptr[n]]); the order of the rows inside one column is unspecified."""
@@ -133,198 +184,51 @@ class Frontier:
 
     def footprint(self):
         """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
-        b = C.c_uint64()
-        self.engine._chk(abi.load().sh_frontier_footprint(self.h, C.byref(b)))
-        return b.value
-
-    def free(self):
-        if self.h is not None:
-            abi.load().sh_frontier_free(self.engine.h, self.h)
-            self.h = None
+        return self._get("footprint", C.c_uint64)
 
 
-class BfsGraph:
+class BfsGraph(_Graph):
     """What Engine.bfs_levels searches: the edge pattern of a square matrix by rows and its transpose, queues, bitmaps
     (made from the host CSR arrays alone; needs no CsrMatrix)."""
-
-    def __init__(self, engine, handle, n):
-        self.engine, self.h, self.n = engine, handle, n
-
-    @property
-    def edges(self):
-        """Entries kept as edges (non-zero value bits, column inside the matrix)."""
-        k = C.c_int64()
-        self.engine._chk(abi.load().sh_bfs_graph_edges(self.h, C.byref(k)))
-        return k.value
-
-    @property
-    def footprint(self):
-        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
-        b = C.c_uint64()
-        self.engine._chk(abi.load().sh_bfs_graph_footprint(self.h, C.byref(b)))
-        return b.value
-
-    def free(self):
-        if self.h is not None:
-            abi.load().sh_bfs_graph_free(self.engine.h, self.h)
-            self.h = None
+    _c = "sh_bfs_graph"
 
 
-class SsspGraph:
+class SsspGraph(_Graph):
     """What Engine.sssp searches: the weighted out-edges of a square matrix by source vertex, its in-edges by row, work
     lists (made from the host CSR arrays alone; needs no CsrMatrix)."""
-
-    def __init__(self, engine, handle, n):
-        self.engine, self.h, self.n = engine, handle, n
-
-    @property
-    def edges(self):
-        """Entries kept as edges (finite value, column inside the matrix; a stored zero is an edge of weight 0)."""
-        k = C.c_int64()
-        self.engine._chk(abi.load().sh_sssp_graph_edges(self.h, C.byref(k)))
-        return k.value
-
-    @property
-    def footprint(self):
-        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
-        b = C.c_uint64()
-        self.engine._chk(abi.load().sh_sssp_graph_footprint(self.h, C.byref(b)))
-        return b.value
-
-    @property
-    def delta(self):
-        """The default bucket width (0 for a graph without edges)."""
-        d = C.c_double()
-        self.engine._chk(abi.load().sh_sssp_graph_delta(self.h, C.byref(d)))
-        return d.value
-
-    def free(self):
-        if self.h is not None:
-            abi.load().sh_sssp_graph_free(self.engine.h, self.h)
-            self.h = None
+    _c = "sh_sssp_graph"
+    edges = _getter("edges", C.c_int64,
+                    "Entries kept as edges (finite value, column inside the matrix; a stored zero is an edge of weight 0).")
+    delta = _getter("delta", C.c_double, "The default bucket width (0 for a graph without edges).")
 
 
-class SccGraph:
+class SccGraph(_Graph):
     """What Engine.scc searches: the edge pattern of a square matrix by rows and its transpose, colours, work lists
     (made from the host CSR arrays alone; needs no CsrMatrix)."""
-
-    def __init__(self, engine, handle, n):
-        self.engine, self.h, self.n = engine, handle, n
-
-    @property
-    def edges(self):
-        """Entries kept as edges (non-zero value bits, column inside the matrix)."""
-        k = C.c_int64()
-        self.engine._chk(abi.load().sh_scc_graph_edges(self.h, C.byref(k)))
-        return k.value
-
-    @property
-    def footprint(self):
-        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
-        b = C.c_uint64()
-        self.engine._chk(abi.load().sh_scc_graph_footprint(self.h, C.byref(b)))
-        return b.value
-
-    def free(self):
-        if self.h is not None:
-            abi.load().sh_scc_graph_free(self.engine.h, self.h)
-            self.h = None
+    _c = "sh_scc_graph"
 
 
-class WccGraph:
+class WccGraph(_Graph):
     """What Engine.wcc searches: the edge pattern of a square matrix by rows and its transpose, a parent word per vertex,
     a work list (made from the host CSR arrays alone; needs no CsrMatrix)."""
-
-    def __init__(self, engine, handle, n):
-        self.engine, self.h, self.n = engine, handle, n
-
-    @property
-    def edges(self):
-        """Entries kept as edges (non-zero value bits, column inside the matrix)."""
-        k = C.c_int64()
-        self.engine._chk(abi.load().sh_wcc_graph_edges(self.h, C.byref(k)))
-        return k.value
-
-    @property
-    def footprint(self):
-        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
-        b = C.c_uint64()
-        self.engine._chk(abi.load().sh_wcc_graph_footprint(self.h, C.byref(b)))
-        return b.value
-
-    def free(self):
-        if self.h is not None:
-            abi.load().sh_wcc_graph_free(self.engine.h, self.h)
-            self.h = None
+    _c = "sh_wcc_graph"
 
 
-class TriGraph:
+class TriGraph(_Graph):
     """What Engine.triangles counts in: the simple undirected graph under the entries of a square matrix, oriented, as
     ascending forward lists, with its degrees (made from the host CSR arrays alone; needs no CsrMatrix)."""
-
-    def __init__(self, engine, handle, n):
-        self.engine, self.h, self.n = engine, handle, n
-
-    @property
-    def edges(self):
-        """M: the edges of the simple undirected graph."""
-        k = C.c_int64()
-        self.engine._chk(abi.load().sh_tri_graph_edges(self.h, C.byref(k)))
-        return k.value
-
-    @property
-    def max_forward(self):
-        """The length of the longest forward list."""
-        k = C.c_int64()
-        self.engine._chk(abi.load().sh_tri_graph_max_forward(self.h, C.byref(k)))
-        return k.value
-
-    @property
-    def footprint(self):
-        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
-        b = C.c_uint64()
-        self.engine._chk(abi.load().sh_tri_graph_footprint(self.h, C.byref(b)))
-        return b.value
-
-    def free(self):
-        if self.h is not None:
-            abi.load().sh_tri_graph_free(self.engine.h, self.h)
-            self.h = None
+    _c = "sh_tri_graph"
+    edges = _getter("edges", C.c_int64, "M: the edges of the simple undirected graph.")
+    max_forward = _getter("max_forward", C.c_int64, "The length of the longest forward list.")
 
 
-class CoreGraph:
+class CoreGraph(_Graph):
     """What Engine.core_numbers peels: the simple undirected graph under the entries of a square matrix as symmetric
     ascending lists, with its degrees, the remaining degrees of a call and two work lists (made from the host CSR
     arrays alone; needs no CsrMatrix)."""
-
-    def __init__(self, engine, handle, n):
-        self.engine, self.h, self.n = engine, handle, n
-
-    @property
-    def edges(self):
-        """M: the edges of the simple undirected graph."""
-        k = C.c_int64()
-        self.engine._chk(abi.load().sh_core_graph_edges(self.h, C.byref(k)))
-        return k.value
-
-    @property
-    def max_degree(self):
-        """The largest degree (the length of the longest list)."""
-        k = C.c_int64()
-        self.engine._chk(abi.load().sh_core_graph_max_degree(self.h, C.byref(k)))
-        return k.value
-
-    @property
-    def footprint(self):
-        """Device bytes held by the handle (the formula: include/sparseharness_hip.h)."""
-        b = C.c_uint64()
-        self.engine._chk(abi.load().sh_core_graph_footprint(self.h, C.byref(b)))
-        return b.value
-
-    def free(self):
-        if self.h is not None:
-            abi.load().sh_core_graph_free(self.engine.h, self.h)
-            self.h = None
+    _c = "sh_core_graph"
+    edges = _getter("edges", C.c_int64, "M: the edges of the simple undirected graph.")
+    max_degree = _getter("max_degree", C.c_int64, "The largest degree (the length of the longest list).")
 
 
 class Engine:
@@ -375,10 +279,7 @@ class Engine:
     def upload_csr(self, rows, cols, row_ptr, col_idx, val, **options):
         """options: fields of sh_plan_options (plan=0|1|2, value_coding=0|8|-1, fold=0, ...) on top of the
         SH_* environment; without any the environment alone decides (sh_csr_upload)."""
-        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-        col_idx = np.ascontiguousarray(col_idx, np.int32)
-        val = np.ascontiguousarray(val)
-        assert val.dtype.itemsize == 4
+        row_ptr, col_idx, val = _csr_args(row_ptr, col_idx, val)
         nnz = int(row_ptr[-1]) if len(row_ptr) else 0
         h = C.c_void_p()
         lib = abi.load()
@@ -441,10 +342,7 @@ class Engine:
     # ---- frontier-driven iteration: only the rows whose inputs changed are recomputed while the wavefront is thin
     def frontier(self, A, row_ptr, col_idx, val):
         """The handle Engine.iterate_frontier needs; the arrays are the ones A was uploaded from (A must outlive it)."""
-        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-        col_idx = np.ascontiguousarray(col_idx, np.int32)
-        val = np.ascontiguousarray(val)
-        assert val.dtype.itemsize == 4
+        row_ptr, col_idx, val = _csr_args(row_ptr, col_idx, val)
         h = C.c_void_p()
         self._chk(abi.load().sh_frontier_create(self.h, A.h, int(row_ptr[-1]), _ptr(row_ptr), _ptr(col_idx), _ptr(val), C.byref(h)))
         return Frontier(self, h, A.rows)
@@ -464,30 +362,30 @@ class Engine:
         n = iters.value
         return n, bool(conv.value), list(modes[:n]), list(changed[:n]), list(active[:n]), list(per[:n]), total.value
 
+    def _graph(self, cls, row_ptr, col_idx, val, *extra):
+        """A cls from the CSR arrays of a square matrix, by <cls._c>_create (extra: what it takes between val and out)."""
+        row_ptr, col_idx, val = _csr_args(row_ptr, col_idx, val)
+        h = C.c_void_p()
+        self._chk(getattr(abi.load(), cls._c + "_create")(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx),
+                                                          _ptr(val), *extra, C.byref(h)))
+        return cls(self, h, len(row_ptr) - 1)
+
     # ---- direction-optimising BFS: the level of every vertex and, on request, its canonical parent
     def bfs_graph(self, row_ptr, col_idx, val):
         """The handle Engine.bfs_levels needs, from the CSR arrays of a square matrix."""
-        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-        col_idx = np.ascontiguousarray(col_idx, np.int32)
-        val = np.ascontiguousarray(val)
-        assert val.dtype.itemsize == 4
-        h = C.c_void_p()
-        self._chk(abi.load().sh_bfs_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
-                                                 C.byref(h)))
-        return BfsGraph(self, h, len(row_ptr) - 1)
+        return self._graph(BfsGraph, row_ptr, col_idx, val)
 
     def bfs_levels(self, G, x0, level, parent=None, max_levels=1 << 20, up_share=-1.0, down_share=-1.0):
         """-> (depth, reached, complete, modes, sizes, edges, ns_per_level, total_ns); per step that ran: 0 top-down /
         1 bottom-up, edges it looked at, device ns; sizes[l] = vertices at level l (one entry more than the steps)."""
         depth, reached, complete, total = C.c_int32(), C.c_int64(), C.c_int32(), C.c_uint64()
         cap = max(int(max_levels), 1)
-        modes, sizes = np.zeros(cap, np.int32), np.full(cap + 1, -1, np.int64)
-        edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
+        (modes, edges, per), (p_modes, p_edges, p_per) = _outs(cap, np.int32, np.int64, np.uint64)
+        (sizes,), (p_sizes,) = _outs(cap + 1, np.int64)
+        sizes[:] = -1
         self._chk(abi.load().sh_bfs_levels(self.h, G.h, x0.h, level.h, None if parent is None else parent.h, max_levels,
                                            up_share, down_share, C.byref(depth), C.byref(reached), C.byref(complete),
-                                           modes.ctypes.data_as(C.POINTER(C.c_int32)), sizes.ctypes.data_as(C.POINTER(C.c_int64)),
-                                           edges.ctypes.data_as(C.POINTER(C.c_int64)), per.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                           C.byref(total)))
+                                           p_modes, p_sizes, p_edges, p_per, C.byref(total)))
         n = int(np.count_nonzero(sizes >= 0)) - 1   # steps that ran (sizes holds one entry per step, plus the sources)
         if n < 0:   # (a graph without rows: nothing ran and nothing was written)
             n, sizes[0] = 0, 0
@@ -497,14 +395,7 @@ class Engine:
     # ---- bucketed SSSP: the distance of every vertex and, on request, its canonical predecessor
     def sssp_graph(self, row_ptr, col_idx, val):
         """The handle Engine.sssp needs, from the CSR arrays of a square matrix (val: float32 bit patterns)."""
-        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-        col_idx = np.ascontiguousarray(col_idx, np.int32)
-        val = np.ascontiguousarray(val)
-        assert val.dtype.itemsize == 4
-        h = C.c_void_p()
-        self._chk(abi.load().sh_sssp_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
-                                                  C.byref(h)))
-        return SsspGraph(self, h, len(row_ptr) - 1)
+        return self._graph(SsspGraph, row_ptr, col_idx, val)
 
     def sssp(self, G, x0, dist, pred=None, delta=-1.0, max_rounds=1 << 20):
         """-> (rounds, buckets, reached, complete, relaxed, sizes, edges, ns_per_round, total_ns); per round that ran:
@@ -512,11 +403,10 @@ class Engine:
         rounds, buckets, reached, complete = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
         relaxed, total = C.c_int64(), C.c_uint64()
         cap = max(int(max_rounds), 1)
-        sizes, edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
+        (sizes, edges, per), ptrs = _outs(cap, np.int64, np.int64, np.uint64)
         self._chk(abi.load().sh_sssp(self.h, G.h, x0.h, dist.h, None if pred is None else pred.h, delta, max_rounds,
                                      C.byref(rounds), C.byref(buckets), C.byref(reached), C.byref(complete), C.byref(relaxed),
-                                     sizes.ctypes.data_as(C.POINTER(C.c_int64)), edges.ctypes.data_as(C.POINTER(C.c_int64)),
-                                     per.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)))
+                                     *ptrs, C.byref(total)))
         n = rounds.value
         return (n, buckets.value, reached.value, bool(complete.value), relaxed.value, sizes[:n].copy(), edges[:n].copy(),
                 per[:n].copy(), total.value)
@@ -524,14 +414,7 @@ class Engine:
     # ---- strongly connected components: comp[v] = the largest vertex index of v's component
     def scc_graph(self, row_ptr, col_idx, val):
         """The handle Engine.scc needs, from the CSR arrays of a square matrix."""
-        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-        col_idx = np.ascontiguousarray(col_idx, np.int32)
-        val = np.ascontiguousarray(val)
-        assert val.dtype.itemsize == 4
-        h = C.c_void_p()
-        self._chk(abi.load().sh_scc_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
-                                                 C.byref(h)))
-        return SccGraph(self, h, len(row_ptr) - 1)
+        return self._graph(SccGraph, row_ptr, col_idx, val)
 
     def scc(self, G, comp, trim=True, pivot=True, max_steps=1 << 20):
         """-> (components, settled, trimmed, rounds, steps, complete, kinds, sizes, steps_per, edges, ns, total_ns); per
@@ -539,13 +422,10 @@ class Engine:
         components, settled, trimmed = C.c_int64(), C.c_int64(), C.c_int64()
         rounds, steps, complete, total = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
         cap = max(int(max_steps), 1)
-        kinds, sizes, steps_per = np.zeros(cap, np.int32), np.zeros(cap, np.int64), np.zeros(cap, np.int32)
-        edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
-        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        (kinds, sizes, steps_per, edges, per), ptrs = _outs(cap, np.int32, np.int64, np.int32, np.int64, np.uint64)
         self._chk(abi.load().sh_scc(self.h, G.h, comp.h, int(bool(trim)), int(bool(pivot)), max_steps, C.byref(components),
-                                    C.byref(settled), C.byref(trimmed), C.byref(rounds), C.byref(steps), C.byref(complete),
-                                    kinds.ctypes.data_as(i32p), sizes.ctypes.data_as(i64p), steps_per.ctypes.data_as(i32p),
-                                    edges.ctypes.data_as(i64p), per.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)))
+                                    C.byref(settled), C.byref(trimmed), C.byref(rounds), C.byref(steps), C.byref(complete), *ptrs,
+                                    C.byref(total)))
         n = rounds.value
         return (components.value, settled.value, trimmed.value, n, steps.value, bool(complete.value), kinds[:n].copy(),
                 sizes[:n].copy(), steps_per[:n].copy(), edges[:n].copy(), per[:n].copy(), total.value)
@@ -553,14 +433,7 @@ class Engine:
     # ---- weakly connected components: comp[v] = the largest vertex index of v's weak component
     def wcc_graph(self, row_ptr, col_idx, val):
         """The handle Engine.wcc needs, from the CSR arrays of a square matrix."""
-        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-        col_idx = np.ascontiguousarray(col_idx, np.int32)
-        val = np.ascontiguousarray(val)
-        assert val.dtype.itemsize == 4
-        h = C.c_void_p()
-        self._chk(abi.load().sh_wcc_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
-                                                 C.byref(h)))
-        return WccGraph(self, h, len(row_ptr) - 1)
+        return self._graph(WccGraph, row_ptr, col_idx, val)
 
     def wcc(self, G, comp, sample=2, max_rounds=1 << 20):
         """-> (components, skipped, rounds, complete, kinds, hooks, jumps, edges, ns, total_ns); per round: 0 sampling /
@@ -568,13 +441,9 @@ class Engine:
         components, skipped = C.c_int64(), C.c_int64()
         rounds, complete, total = C.c_int32(), C.c_int32(), C.c_uint64()
         cap = max(int(max_rounds), 1)
-        kinds, hooks, jumps = np.zeros(cap, np.int32), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
-        edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
-        i64p = C.POINTER(C.c_int64)
+        (kinds, hooks, jumps, edges, per), ptrs = _outs(cap, np.int32, np.int64, np.int64, np.int64, np.uint64)
         self._chk(abi.load().sh_wcc(self.h, G.h, comp.h, sample, max_rounds, C.byref(components), C.byref(skipped),
-                                    C.byref(rounds), C.byref(complete), kinds.ctypes.data_as(C.POINTER(C.c_int32)),
-                                    hooks.ctypes.data_as(i64p), jumps.ctypes.data_as(i64p), edges.ctypes.data_as(i64p),
-                                    per.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)))
+                                    C.byref(rounds), C.byref(complete), *ptrs, C.byref(total)))
         n = rounds.value
         return (components.value, skipped.value, n, bool(complete.value), kinds[:n].copy(), hooks[:n].copy(), jumps[:n].copy(),
                 edges[:n].copy(), per[:n].copy(), total.value)
@@ -583,14 +452,7 @@ class Engine:
     def tri_graph(self, row_ptr, col_idx, val, order=1):
         """The handle Engine.triangles needs, from the CSR arrays of a square matrix.  order 0: edges run from the
         smaller index to the larger; 1: from the smaller (degree, index) to the larger."""
-        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-        col_idx = np.ascontiguousarray(col_idx, np.int32)
-        val = np.ascontiguousarray(val)
-        assert val.dtype.itemsize == 4
-        h = C.c_void_p()
-        self._chk(abi.load().sh_tri_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
-                                                 order, C.byref(h)))
-        return TriGraph(self, h, len(row_ptr) - 1)
+        return self._graph(TriGraph, row_ptr, col_idx, val, order)
 
     def triangles(self, G, tri=None, deg=None):
         """-> (triangles, probes, total_ns).  tri: None or a vector of >= 2 * rows 4-byte elements (rows uint64 counts);
@@ -603,14 +465,7 @@ class Engine:
     # ---- core numbers: core[v] = the largest k such that v lies in a subgraph of minimum degree k
     def core_graph(self, row_ptr, col_idx, val):
         """The handle Engine.core_numbers needs, from the CSR arrays of a square matrix."""
-        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-        col_idx = np.ascontiguousarray(col_idx, np.int32)
-        val = np.ascontiguousarray(val)
-        assert val.dtype.itemsize == 4
-        h = C.c_void_p()
-        self._chk(abi.load().sh_core_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), _ptr(val),
-                                                  C.byref(h)))
-        return CoreGraph(self, h, len(row_ptr) - 1)
+        return self._graph(CoreGraph, row_ptr, col_idx, val)
 
     # chase = 0: the fastest arm of tools/core_bench.py on the 2048 x 2048 grid and no slower than any on R-MAT-18
     # (DESIGN.md 6j); chasing pays for chains of degree-2 vertices only
@@ -623,14 +478,9 @@ class Engine:
             max_rounds = G.n + 1
         degeneracy, levels, rounds, complete, total = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
         cap = max(int(max_rounds), 1)
-        ks, sizes, chased = np.zeros(cap, np.int32), np.zeros(cap, np.int64), np.zeros(cap, np.int64)
-        edges, per = np.zeros(cap, np.int64), np.zeros(cap, np.uint64)
-        i64p = C.POINTER(C.c_int64)
+        (ks, sizes, chased, edges, per), ptrs = _outs(cap, np.int32, np.int64, np.int64, np.int64, np.uint64)
         self._chk(abi.load().sh_core(self.h, G.h, core.h, None if deg is None else deg.h, chase, max_rounds,
-                                     C.byref(degeneracy), C.byref(levels), C.byref(rounds), C.byref(complete),
-                                     ks.ctypes.data_as(C.POINTER(C.c_int32)), sizes.ctypes.data_as(i64p),
-                                     chased.ctypes.data_as(i64p), edges.ctypes.data_as(i64p),
-                                     per.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(total)))
+                                     C.byref(degeneracy), C.byref(levels), C.byref(rounds), C.byref(complete), *ptrs, C.byref(total)))
         n = rounds.value
         return (degeneracy.value, levels.value, n, bool(complete.value), ks[:n].copy(), sizes[:n].copy(), chased[:n].copy(),
                 edges[:n].copy(), per[:n].copy(), total.value)

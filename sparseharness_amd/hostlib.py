@@ -24,6 +24,21 @@ class _HostCsr(C.Structure):
                 ("row_ptr", C.POINTER(C.c_int32)), ("col_idx", C.POINTER(C.c_int32)), ("val", C.c_void_p)]
 
 
+_vp, _i64 = C.c_void_p, C.c_int64
+_csr = [_i64, _i64, _vp, _vp, _vp]   # rows, nnz, row_ptr, col_idx, val: what every host gold starts with
+# name -> (restype, argtypes): what load() binds (declared in host/inc/sh_host.h)
+SIGNATURES = {
+    "sh_synth_powerlaw": (C.c_int, [_i64, _i64, _i64, C.c_double, _i64, C.c_uint64, _vp, _vp, _vp]),
+    "sh_synth_rmat": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_int, _vp, _vp, _vp]),
+    "sh_scc_labels": (C.c_int, _csr + [_vp]),
+    "sh_wcc_labels": (C.c_int, _csr + [_vp]),
+    "sh_triangle_counts": (C.c_int, _csr + [_vp, _vp]),
+    "sh_core_numbers": (C.c_int, _csr + [_vp, _vp, C.POINTER(_i64)]),
+    "sh_mm_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]),
+    "sh_mm_load_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]),
+    "sh_host_csr_release": (None, [C.POINTER(_HostCsr)]),
+}
+
 _lib = None
 
 
@@ -38,27 +53,9 @@ def load():
             raise ImportError(f"{LIB_PATH} is missing: build it with `make -C {HOST_DIR}`")
         os.environ.setdefault("SH_QUIET_TIMERS", "1")
         _lib = C.CDLL(LIB_PATH)
-        _lib.sh_synth_powerlaw.restype = C.c_int
-        _lib.sh_synth_powerlaw.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int64, C.c_uint64,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.sh_synth_rmat.restype = C.c_int
-        _lib.sh_synth_rmat.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_int,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.sh_scc_labels.restype = C.c_int
-        _lib.sh_scc_labels.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.sh_wcc_labels.restype = C.c_int
-        _lib.sh_wcc_labels.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.sh_triangle_counts.restype = C.c_int
-        _lib.sh_triangle_counts.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.sh_core_numbers.restype = C.c_int
-        _lib.sh_core_numbers.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.POINTER(C.c_int64)]
-        _lib.sh_mm_load.restype = C.c_int
-        _lib.sh_mm_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]
-        _lib.sh_mm_load_ex.restype = C.c_int
-        _lib.sh_mm_load_ex.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]
-        _lib.sh_host_csr_release.restype = None
-        _lib.sh_host_csr_release.argtypes = [C.POINTER(_HostCsr)]
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = res, args
     return _lib
 
 
@@ -96,33 +93,30 @@ def scircuit_like(seed=SEED_SCIRCUIT):
     return powerlaw(170_998, 958_936, dmax=353, seed=seed)
 
 
-def scc_labels(row_ptr, col_idx, val):
-    """label[v] = the largest vertex index of v's strongly connected component (Engine.scc's comp), by a single-threaded
-    Tarjan on the host.  Entry (r, c) is the edge c -> r when 0 <= c < rows and its 32 value bits are not all zero."""
+def _gold(name, row_ptr, col_idx, val, *outs):
+    """Run the host gold `name` over the CSR arrays of a square matrix; outs: the pointers it writes its results through."""
     row_ptr = np.ascontiguousarray(row_ptr, np.int32)
     col_idx = np.ascontiguousarray(col_idx, np.int32)
     val = np.ascontiguousarray(val)
     assert val.dtype.itemsize == 4 and len(val) == len(col_idx)
-    n = len(row_ptr) - 1
-    label = np.empty(n, np.int32)
-    rc = load().sh_scc_labels(n, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), _p(label))
+    rc = getattr(load(), name)(len(row_ptr) - 1, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), *outs)
     if rc:
-        raise RuntimeError(f"sh_scc_labels failed: {rc}")
+        raise RuntimeError(f"{name} failed: {rc}")
+
+
+def scc_labels(row_ptr, col_idx, val):
+    """label[v] = the largest vertex index of v's strongly connected component (Engine.scc's comp), by a single-threaded
+    Tarjan on the host.  Entry (r, c) is the edge c -> r when 0 <= c < rows and its 32 value bits are not all zero."""
+    label = np.empty(len(row_ptr) - 1, np.int32)
+    _gold("sh_scc_labels", row_ptr, col_idx, val, _p(label))
     return label
 
 
 def wcc_labels(row_ptr, col_idx, val):
     """label[v] = the largest vertex index of v's weakly connected component (Engine.wcc's comp), by a single-threaded
     union-find on the host.  Entry (r, c) joins r and c when 0 <= c < rows and its 32 value bits are not all zero."""
-    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-    col_idx = np.ascontiguousarray(col_idx, np.int32)
-    val = np.ascontiguousarray(val)
-    assert val.dtype.itemsize == 4 and len(val) == len(col_idx)
-    n = len(row_ptr) - 1
-    label = np.empty(n, np.int32)
-    rc = load().sh_wcc_labels(n, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), _p(label))
-    if rc:
-        raise RuntimeError(f"sh_wcc_labels failed: {rc}")
+    label = np.empty(len(row_ptr) - 1, np.int32)
+    _gold("sh_wcc_labels", row_ptr, col_idx, val, _p(label))
     return label
 
 
@@ -130,15 +124,9 @@ def triangle_counts(row_ptr, col_idx, val):
     """-> (tri, deg): tri[v] (uint64) = the triangles through v of the simple undirected graph under the entries,
     deg[v] (int32) = its degree there (Engine.triangles' tri and deg), by a single-threaded forward algorithm on the
     host.  Entry (r, c) counts when 0 <= c < rows, c != r and its 32 value bits are not all zero."""
-    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-    col_idx = np.ascontiguousarray(col_idx, np.int32)
-    val = np.ascontiguousarray(val)
-    assert val.dtype.itemsize == 4 and len(val) == len(col_idx)
     n = len(row_ptr) - 1
     tri, deg = np.empty(n, np.uint64), np.empty(n, np.int32)
-    rc = load().sh_triangle_counts(n, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), _p(tri), _p(deg))
-    if rc:
-        raise RuntimeError(f"sh_triangle_counts failed: {rc}")
+    _gold("sh_triangle_counts", row_ptr, col_idx, val, _p(tri), _p(deg))
     return tri, deg
 
 
@@ -147,15 +135,9 @@ def core_numbers(row_ptr, col_idx, val):
     deg[v] (int32) = its degree there (Engine.core_numbers' core and deg), M = the number of edges, by the single-threaded
     bucket algorithm of Batagelj and Zaversnik on the host.  Entry (r, c) counts when 0 <= c < rows, c != r and its 32
     value bits are not all zero."""
-    row_ptr = np.ascontiguousarray(row_ptr, np.int32)
-    col_idx = np.ascontiguousarray(col_idx, np.int32)
-    val = np.ascontiguousarray(val)
-    assert val.dtype.itemsize == 4 and len(val) == len(col_idx)
     n = len(row_ptr) - 1
     core, deg, m = np.empty(n, np.int32), np.empty(n, np.int32), C.c_int64()
-    rc = load().sh_core_numbers(n, len(col_idx), _p(row_ptr), _p(col_idx), _p(val), _p(core), _p(deg), C.byref(m))
-    if rc:
-        raise RuntimeError(f"sh_core_numbers failed: {rc}")
+    _gold("sh_core_numbers", row_ptr, col_idx, val, _p(core), _p(deg), C.byref(m))
     return core, deg, m.value
 
 

@@ -35,6 +35,34 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert lib.sh_abi_version() == 3
 
 
+def test_handle_classes_look_up_symbols_that_are_bound():
+    """The handle classes of engine.py find their C functions by prefix: <_c>_free, <_c>_footprint, <_c>_create for a
+    graph, and the accessor behind every property made by _getter.  Each must be in abi.SIGNATURES with the result and
+    argument types the class passes, so that a mistyped prefix or suffix shows here and not only on a GPU."""
+    from sparseharness_amd import engine
+    vp, i64 = C.c_void_p, C.c_int64
+    want = {"Frontier": {"footprint"}, "BfsGraph": {"footprint", "edges"}, "SsspGraph": {"footprint", "edges", "delta"},
+            "SccGraph": {"footprint", "edges"}, "WccGraph": {"footprint", "edges"},
+            "TriGraph": {"footprint", "edges", "max_forward"}, "CoreGraph": {"footprint", "edges", "max_degree"}}
+    handles = {n: c for n, c in vars(engine).items() if isinstance(c, type) and issubclass(c, engine._Handle) and c._c}
+    assert sorted(handles) == sorted(want)
+    for name, cls in handles.items():
+        assert abi.SIGNATURES[cls._c + "_free"] == (C.c_int, [vp, vp]), name
+        reads = {"footprint": C.c_uint64}   # (Frontier reads it in a method, the graphs in a property)
+        for klass in cls.__mro__:
+            for attr in vars(klass).values():
+                if isinstance(attr, property) and hasattr(attr.fget, "reads"):
+                    reads.setdefault(*attr.fget.reads)
+        assert set(reads) == want[name], name
+        for suffix, ctype in reads.items():
+            assert abi.SIGNATURES[f"{cls._c}_{suffix}"] == (C.c_int, [vp, C.POINTER(ctype)]), (name, suffix)
+            assert hasattr(cls, suffix), (name, suffix)
+        if issubclass(cls, engine._Graph):   # Engine._graph: engine, rows, nnz, three arrays, the extras, the handle
+            res, args = abi.SIGNATURES[cls._c + "_create"]
+            assert res is C.c_int and args[:6] == [vp, i64, i64, vp, vp, vp] and args[-1] is C.POINTER(vp), name
+            assert len(args) == (8 if name == "TriGraph" else 7), name
+
+
 def test_no_cpu_fallback_without_device():
     lib = abi.load()
     if lib.sh_device_count() > 0:

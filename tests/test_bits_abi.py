@@ -3,20 +3,11 @@ declared in include/sparseharness_hip.h, exported by the library and bound in ab
 types.  No compute is called here (no GPU needed)."""
 import ctypes as C
 import os
-import re
 
+from abi_checks import check_entry_points, last_error, section_comment
 from conftest import ROOT
 from sparseharness_amd import abi
 
-HEADER = os.path.join(ROOT, "include", "sparseharness_hip.h")
-
-_vp, _i32, _i64, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_int
-_u64p, _i32p, _u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
-# C parameter type (name stripped, blanks squeezed) -> ctypes type of the binding
-CTYPE = {
-    "sh_engine *": _vp, "const sh_csr *": _vp, "int32_t": _i32, "int64_t": _i64, "const sh_vec *": _vp, "sh_vec *": _vp,
-    "const void *": _vp, "uint64_t *": _u64p, "int32_t *": _i32p, "uint32_t *": _u32p,
-}
 WANT = {
     "sh_bits_spmv": ["sh_engine *", "const sh_csr *", "int32_t", "const sh_vec *", "const sh_vec *", "const void *",
                      "const void *", "sh_vec *", "uint64_t *"],
@@ -28,42 +19,14 @@ WANT = {
 }
 
 
-def declared_parameters(name):
-    """The parameter types of `name` as the header declares them, or None."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    if not m:
-        return None
-    types = []
-    for p in m.group(1).split(","):
-        p = " ".join(p.split())
-        t = re.sub(r"[A-Za-z_0-9]+$", "", p).strip()   # drop the parameter's name
-        types.append(re.sub(r"\s*\*", " *", t))
-    return types
-
-
 def test_packed_bit_entry_points_are_declared_exported_and_bound():
-    lib = abi.load()
-    for name, want in WANT.items():
-        assert declared_parameters(name) == want, f"{name}: not declared in the header with the agreed parameters"
-        assert hasattr(lib, name), f"{name} is not exported by the library"
-        assert name in abi.SIGNATURES, f"{name} is not bound in abi.SIGNATURES"
-        res, args = abi.SIGNATURES[name]
-        assert res is _int
-        assert list(args) == [CTYPE[t] for t in want], f"{name}: abi.SIGNATURES disagrees with the header"
-    assert lib.sh_abi_version() == 3   # functions were added, no struct changed
+    check_entry_points(WANT)
 
 
 def test_section_comment_cites_what_it_extends():
-    text = open(HEADER).read()
-    at = text.index("int sh_bits_spmv(")
-    comment = text[text.rindex("/* ----", 0, at):at]
+    comment = section_comment("int sh_bits_spmv(")
     for cite in ("inc/harness.h:149-195", "app/bfs.cpp:94-174", "no counterpart", "NOT covered"):
         assert cite in comment
-
-
-def last_error():
-    return (abi.load().sh_last_error(None) or b"").decode()
 
 
 def test_argument_errors_need_no_device():

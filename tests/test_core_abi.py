@@ -8,21 +8,11 @@ import re
 
 import numpy as np
 
+from abi_checks import CSRC, check_create_errors, check_entry_points, last_error, section_comment
 from conftest import ROOT
 from sparseharness_amd import abi
 
-HEADER = os.path.join(ROOT, "include", "sparseharness_hip.h")
-CSRC = os.path.join(ROOT, "sparseharness_amd", "csrc")
-
-_vp, _i32, _i64, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_int
-_pp = C.POINTER(C.c_void_p)
-_u64p, _i64p, _i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
-# C parameter type (name stripped, blanks squeezed) -> ctypes type of the binding
-CTYPE = {
-    "sh_engine *": _vp, "sh_core_graph *": _vp, "const sh_core_graph *": _vp, "sh_core_graph * *": _pp,
-    "int32_t": _i32, "int64_t": _i64, "sh_vec *": _vp, "const void *": _vp, "const int32_t *": _vp,
-    "uint64_t *": _u64p, "int64_t *": _i64p, "int32_t *": _i32p,
-}
+SECTION = "typedef struct sh_core_graph sh_core_graph;"
 WANT = {
     "sh_core_graph_create": ["sh_engine *", "int64_t", "int64_t", "const int32_t *", "const int32_t *", "const void *",
                              "sh_core_graph * *"],
@@ -35,40 +25,12 @@ WANT = {
 }
 
 
-def declared_parameters(name):
-    """The parameter types of `name` as the header declares them, or None."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    if not m:
-        return None
-    types = []
-    for p in m.group(1).split(","):
-        p = " ".join(p.split())
-        t = re.sub(r"[A-Za-z_0-9]+$", "", p).strip()   # drop the parameter's name
-        types.append(re.sub(r"\s*\*", " *", t))
-    return types
-
-
 def test_core_entry_points_are_declared_exported_and_bound():
-    lib = abi.load()
-    for name, want in WANT.items():
-        assert declared_parameters(name) == want, f"{name}: not declared in the header with the agreed parameters"
-        assert hasattr(lib, name), f"{name} is not exported by the library"
-        assert name in abi.SIGNATURES, f"{name} is not bound in abi.SIGNATURES"
-        res, args = abi.SIGNATURES[name]
-        assert res is _int
-        assert list(args) == [CTYPE[t] for t in want], f"{name}: abi.SIGNATURES disagrees with the header"
-    assert lib.sh_abi_version() == 3   # functions were added, no struct changed
-
-
-def section_comment():
-    text = open(HEADER).read()
-    at = text.index("typedef struct sh_core_graph sh_core_graph;")
-    return re.sub(r"\n \*", "\n", text[text.rindex("/* ----", 0, at):at])   # (without the comment's leading stars)
+    check_entry_points(WANT)
 
 
 def test_section_comment_states_the_contract_and_what_it_leaves_out():
-    comment = " ".join(section_comment().split())
+    comment = " ".join(section_comment(SECTION, stars=False).split())
     for cite in ("app/scc.cpp:96-176", "inc/harness.h:149-195", "the reference has no counterpart",
                  "row r storing column c with 0 <= c < rows", "not all zero", "SIMPLE UNDIRECTED", "Self-loops",
                  "do not depend on chase", "deterministic", "exactly the vertices whose remaining degree fell to <= k",
@@ -88,7 +50,7 @@ def test_footprint_formula_is_stated_in_the_header_and_matches_the_constants():
     """The formula tests/test_core_gpu.py compares sh_core_graph_footprint with is the header's, and its numbers are
     those of core.hip.h: adj_ptr, adj_col (2M words), deg + cur + two work lists (4 words per row), two piece lists of
     2M / (CORE_PIECE / 2) + 1 places of 8 bytes, the control block and two WlParts (16 bytes) per workgroup."""
-    text = " ".join(section_comment().split())
+    text = " ".join(section_comment(SECTION, stars=False).split())
     assert "4 * (rows + 1) + 8 * edges + 16 * rows + 16 * (2 * edges / 1024 + 1) + 34816" in text
     code = open(os.path.join(CSRC, "core.hip.h")).read()
     const = {k: int(re.search(r"constexpr int " + k + r" = (\d+);", code).group(1))
@@ -98,35 +60,11 @@ def test_footprint_formula_is_stated_in_the_header_and_matches_the_constants():
     assert "wl_expand<CORE_SHORT, CORE_PIECE>" in code
 
 
-def last_error():
-    return (abi.load().sh_last_error(None) or b"").decode()
-
-
-def create(rows, nnz, rp, ci=None, va=None, out=True):
-    h = C.c_void_p()
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
-    rc = abi.load().sh_core_graph_create(None, rows, nnz, p(rp), p(ci), p(va), C.byref(h) if out else None)
-    assert not h.value
-    return rc
-
-
 def test_argument_errors_need_no_device():
     """Every argument error named in the header comes back with a message that names the argument before anything
     touches a device (without an engine the message is the thread's, as for sh_engine_create)."""
     lib = abi.load()
-    rp = np.array([0, 1, 3], np.int32)
-    ci, va = np.array([0, 1, 0], np.int32), np.ones(3, np.float32)
-    assert create(-1, 3, rp, ci, va) == abi.SH_EINVAL and "rows" in last_error()
-    assert create(2, -3, rp, ci, va) == abi.SH_EINVAL and "nnz" in last_error()
-    assert create(2, 3, None, ci, va) == abi.SH_EINVAL and "NULL" in last_error() and "row_ptr" in last_error()
-    assert create(2, 3, rp, None, va) == abi.SH_EINVAL and "NULL" in last_error() and "col_idx" in last_error()
-    assert create(2, 3, rp, ci, None) == abi.SH_EINVAL and "NULL" in last_error() and "val" in last_error()
-    assert create(2, 3, rp, ci, va, out=False) == abi.SH_EINVAL and "NULL" in last_error() and "out" in last_error()
-    assert create(2, 3, np.array([1, 1, 3], np.int32), ci, va) == abi.SH_ESHAPE and "row_ptr[0]" in last_error()
-    assert create(2, 2, rp, ci, va) == abi.SH_ESHAPE and "row_ptr[rows]" in last_error()
-    assert create(2, 3, np.array([0, 4, 3], np.int32), ci, va) == abi.SH_ESHAPE and "decreases" in last_error()
-    assert create(2, 3, rp, ci, va) == abi.SH_EINVAL and "NULL" in last_error() and "engine" in last_error()
-    assert "sh_core_graph_create" in last_error()   # (all else was fine)
+    check_create_errors("sh_core_graph_create")
     b, k = C.c_uint64(), C.c_int64()
     assert lib.sh_core_graph_footprint(None, C.byref(b)) == abi.SH_EINVAL
     assert lib.sh_core_graph_edges(None, C.byref(k)) == abi.SH_EINVAL
@@ -154,8 +92,12 @@ def test_resource_check_and_kernel_file():
     assert "core.hip.h" in mk
     hip = open(os.path.join(CSRC, "engine.hip")).read()
     assert '#include "core.hip.h"' in hip
-    for k in kernels + ("run_batches(e, \"sh_core: round\"", "check_host_csr(e, \"sh_core_graph_create\"", "build_und_edges"):
+    # (sh_core_graph_create checks its host arrays through the helper every sh_*_graph_create goes through)
+    for k in kernels + ("run_batches(e, \"sh_core: round\"", "create_graph_handle<sh_core_graph>(e, \"sh_core_graph_create\"",
+                        "build_und_edges"):
         assert k in hip
+    helper = hip[hip.index("static int create_graph_handle("):]
+    assert "check_host_csr(e, fn, rows, nnz, row_ptr, col_idx, val, out)" in helper[:helper.index("\n}\n")]
     assert hip.count("build_und_edges(e, tmp") == 2   # sh_tri_graph_create and sh_core_graph_create share the first half
     code = open(os.path.join(CSRC, "core.hip.h")).read()
     for phrase in ("NO KERNEL EVER WAITS", "EVERY VERTEX IS SETTLED ONCE", "EVERY LOOP IS BOUNDED", "PEELING IS MONOTONE",

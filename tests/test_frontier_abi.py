@@ -3,22 +3,11 @@ declared in include/sparseharness_hip.h, exported by the library and bound in ab
 types; argument errors come back before any device is touched.  No compute is called here (no GPU needed)."""
 import ctypes as C
 import os
-import re
 
+from abi_checks import check_entry_points, last_error, section_comment
 from conftest import ROOT
 from sparseharness_amd import abi
 
-HEADER = os.path.join(ROOT, "include", "sparseharness_hip.h")
-
-_vp, _i32, _i64, _int, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_double
-_pp = C.POINTER(C.c_void_p)
-_u64p, _i32p, _i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
-# C parameter type (name stripped, blanks squeezed) -> ctypes type of the binding
-CTYPE = {
-    "sh_engine *": _vp, "const sh_csr *": _vp, "sh_frontier *": _vp, "const sh_frontier *": _vp, "sh_frontier * *": _pp,
-    "sh_semiring": _int, "int32_t": _i32, "int64_t": _i64, "double": _dbl, "const sh_vec *": _vp, "sh_vec *": _vp,
-    "const void *": _vp, "const int32_t *": _vp, "uint64_t *": _u64p, "int32_t *": _i32p, "int64_t *": _i64p,
-}
 WANT = {
     "sh_frontier_create": ["sh_engine *", "const sh_csr *", "int64_t", "const int32_t *", "const int32_t *", "const void *",
                            "sh_frontier * *"],
@@ -31,43 +20,15 @@ WANT = {
 }
 
 
-def declared_parameters(name):
-    """The parameter types of `name` as the header declares them, or None."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    if not m:
-        return None
-    types = []
-    for p in m.group(1).split(","):
-        p = " ".join(p.split())
-        t = re.sub(r"[A-Za-z_0-9]+$", "", p).strip()   # drop the parameter's name
-        types.append(re.sub(r"\s*\*", " *", t))
-    return types
-
-
 def test_frontier_entry_points_are_declared_exported_and_bound():
-    lib = abi.load()
-    for name, want in WANT.items():
-        assert declared_parameters(name) == want, f"{name}: not declared in the header with the agreed parameters"
-        assert hasattr(lib, name), f"{name} is not exported by the library"
-        assert name in abi.SIGNATURES, f"{name} is not bound in abi.SIGNATURES"
-        res, args = abi.SIGNATURES[name]
-        assert res is _int
-        assert list(args) == [CTYPE[t] for t in want], f"{name}: abi.SIGNATURES disagrees with the header"
-    assert lib.sh_abi_version() == 3   # functions were added, no struct changed
+    check_entry_points(WANT)
 
 
 def test_section_comment_cites_what_it_extends():
-    text = open(HEADER).read()
-    at = text.index("typedef struct sh_frontier sh_frontier;")
-    comment = text[text.rindex("/* ----", 0, at):at]
+    comment = section_comment("typedef struct sh_frontier sh_frontier;")
     for cite in ("app/sssp.cpp:97-176", "app/bfs.cpp:94-174", "inc/harness.h:149-195", "no counterpart", "NOT covered",
                  "SH_PLUS_TIMES_F32", "sh_iterate_multi", "sh_bits_iterate", "row pieces", "multi-GPU", "C++ harness apps"):
         assert cite in comment, cite
-
-
-def last_error():
-    return (abi.load().sh_last_error(None) or b"").decode()
 
 
 def iterate(sr, delta, max_iters):

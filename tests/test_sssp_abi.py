@@ -3,24 +3,11 @@ include/sparseharness_hip.h with the agreed parameter lists, exported by the lib
 declared argument types; argument errors come back before any device is touched.  No compute is called here (no GPU needed)."""
 import ctypes as C
 import os
-import re
 
-import numpy as np
-
+from abi_checks import HEADER, check_create_errors, check_entry_points, last_error, section_comment
 from conftest import ROOT
 from sparseharness_amd import abi
 
-HEADER = os.path.join(ROOT, "include", "sparseharness_hip.h")
-
-_vp, _i32, _i64, _int, _dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_int, C.c_double
-_pp = C.POINTER(C.c_void_p)
-_u64p, _i32p, _i64p, _dblp = C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
-# C parameter type (name stripped, blanks squeezed) -> ctypes type of the binding
-CTYPE = {
-    "sh_engine *": _vp, "sh_sssp_graph *": _vp, "const sh_sssp_graph *": _vp, "sh_sssp_graph * *": _pp,
-    "int32_t": _i32, "int64_t": _i64, "double": _dbl, "const sh_vec *": _vp, "sh_vec *": _vp,
-    "const void *": _vp, "const int32_t *": _vp, "uint64_t *": _u64p, "int32_t *": _i32p, "int64_t *": _i64p, "double *": _dblp,
-}
 WANT = {
     "sh_sssp_graph_create": ["sh_engine *", "int64_t", "int64_t", "const int32_t *", "const int32_t *", "const void *",
                              "sh_sssp_graph * *"],
@@ -34,36 +21,12 @@ WANT = {
 }
 
 
-def declared_parameters(name):
-    """The parameter types of `name` as the header declares them, or None."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    if not m:
-        return None
-    types = []
-    for p in m.group(1).split(","):
-        p = " ".join(p.split())
-        t = re.sub(r"[A-Za-z_0-9]+$", "", p).strip()   # drop the parameter's name
-        types.append(re.sub(r"\s*\*", " *", t))
-    return types
-
-
 def test_sssp_entry_points_are_declared_exported_and_bound():
-    lib = abi.load()
-    for name, want in WANT.items():
-        assert declared_parameters(name) == want, f"{name}: not declared in the header with the agreed parameters"
-        assert hasattr(lib, name), f"{name} is not exported by the library"
-        assert name in abi.SIGNATURES, f"{name} is not bound in abi.SIGNATURES"
-        res, args = abi.SIGNATURES[name]
-        assert res is _int
-        assert list(args) == [CTYPE[t] for t in want], f"{name}: abi.SIGNATURES disagrees with the header"
-    assert lib.sh_abi_version() == 3   # functions were added, no struct changed
+    check_entry_points(WANT)
 
 
 def test_section_comment_cites_what_it_extends_and_what_it_leaves_out():
-    text = open(HEADER).read()
-    at = text.index("typedef struct sh_sssp_graph sh_sssp_graph;")
-    comment = text[text.rindex("/* ----", 0, at):at]
+    comment = section_comment("typedef struct sh_sssp_graph sh_sssp_graph;")
     for cite in ("app/sssp.cpp:97-176", "inc/harness.h:149-195", "no counterpart", "NOT covered", "other semirings",
                  "sh_iterate_multi", "row pieces", "multi-GPU", "C++ harness apps", "Measured on an MI355X", "Rule:",
                  "sh_iterate(SH_MIN_PLUS_F32, alpha = 0, beta = 0, y0 = x0)", "A stored zero IS an edge", "FOREST",
@@ -78,40 +41,17 @@ def test_footprint_formula_is_stated_in_the_header():
     assert "8 * (rows + 1) + 16 * edges + 20 * rows + 16 * (edges / 1024 + 1) + 8 * (edges / 2048 + 1) + 22528" in text
 
 
-def last_error():
-    return (abi.load().sh_last_error(None) or b"").decode()
-
-
 def sssp(max_rounds, delta=-1.0):
     r, b, n, c, x = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32(), C.c_int64()
     return abi.load().sh_sssp(None, None, None, None, None, delta, max_rounds, C.byref(r), C.byref(b), C.byref(n), C.byref(c),
                               C.byref(x), None, None, None, None)
 
 
-def create(rows, nnz, rp, ci=None, va=None, out=True):
-    h = C.c_void_p()
-    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)   # noqa: E731
-    rc = abi.load().sh_sssp_graph_create(None, rows, nnz, p(rp), p(ci), p(va), C.byref(h) if out else None)
-    assert not h.value
-    return rc
-
-
 def test_argument_errors_need_no_device():
     """Every argument error named in the header comes back with a message that names the argument before anything
     touches a device (without an engine the message is the thread's, as for sh_engine_create)."""
     lib = abi.load()
-    rp = np.array([0, 1, 3], np.int32)
-    ci, va = np.array([0, 1, 0], np.int32), np.ones(3, np.float32)
-    assert create(-1, 3, rp, ci, va) == abi.SH_EINVAL and "rows" in last_error()
-    assert create(2, -3, rp, ci, va) == abi.SH_EINVAL and "nnz" in last_error()
-    assert create(2, 3, None, ci, va) == abi.SH_EINVAL and "NULL" in last_error() and "row_ptr" in last_error()
-    assert create(2, 3, rp, None, va) == abi.SH_EINVAL and "NULL" in last_error() and "col_idx" in last_error()
-    assert create(2, 3, rp, ci, None) == abi.SH_EINVAL and "NULL" in last_error() and "val" in last_error()
-    assert create(2, 3, rp, ci, va, out=False) == abi.SH_EINVAL and "NULL" in last_error() and "out" in last_error()
-    assert create(2, 3, np.array([1, 1, 3], np.int32), ci, va) == abi.SH_ESHAPE and "row_ptr[0]" in last_error()
-    assert create(2, 2, rp, ci, va) == abi.SH_ESHAPE and "row_ptr[rows]" in last_error()
-    assert create(2, 3, np.array([0, 4, 3], np.int32), ci, va) == abi.SH_ESHAPE and "decreases" in last_error()
-    assert create(2, 3, rp, ci, va) == abi.SH_EINVAL and "NULL" in last_error() and "engine" in last_error()   # (all else is fine)
+    check_create_errors("sh_sssp_graph_create")
     b, k, d = C.c_uint64(), C.c_int64(), C.c_double()
     assert lib.sh_sssp_graph_footprint(None, C.byref(b)) == abi.SH_EINVAL
     assert lib.sh_sssp_graph_edges(None, C.byref(k)) == abi.SH_EINVAL
