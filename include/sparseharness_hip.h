@@ -883,7 +883,7 @@ int sh_wcc(sh_engine *e, sh_wcc_graph *g, sh_vec *comp, int32_t sample, int32_t 
  * tri that is not 8-byte aligned.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases, tri
  * shorter than 2 * rows, deg shorter than rows.  All are reported before any device work, with the buffers untouched.
  * NOT covered: per-edge support and k-truss, the multi-GPU driver, row pieces (sh_spmv_step_pieces), the C++ harness
- * apps, incremental updates.
+ * apps, incremental updates.  (Per-edge support and truss numbers on the same graph are sh_truss's, below.)
  */
 typedef struct sh_tri_graph sh_tri_graph;
 int sh_tri_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
@@ -993,7 +993,7 @@ int sh_tri(sh_engine *e, sh_tri_graph *g, sh_vec *tri, sh_vec *deg,
  * nnz < 0, chase < 0, max_rounds < 1.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases, core
  * or deg shorter than rows.  All are reported before any device work, with the buffers untouched.
  * NOT covered: the removal order / degeneracy ordering as an output, k-truss, the multi-GPU driver, row pieces
- * (sh_spmv_step_pieces), the C++ harness apps, incremental updates.
+ * (sh_spmv_step_pieces), the C++ harness apps, incremental updates.  (Truss numbers on the same lists are sh_truss's, below.)
  */
 typedef struct sh_core_graph sh_core_graph;
 int sh_core_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
@@ -1006,6 +1006,114 @@ int sh_core(sh_engine *e, sh_core_graph *g, sh_vec *core, sh_vec *deg, int32_t c
             int32_t *degeneracy, int32_t *levels, int32_t *rounds, int32_t *complete,
             int32_t *k_per_round, int64_t *size_per_round, int64_t *chased_per_round, int64_t *edges_per_round,
             uint64_t *ns_per_round, uint64_t *total_ns);
+
+/* ---- k-truss decomposition: the triangles through every edge and its truss number, by parallel peeling ---------------
+ * (the reference has no counterpart: its apps are SpMV, PageRank, BFS, SSSP and SCC label propagation; this is the third
+ * piece on sh_tri's graph, after the triangles per vertex and sh_core's core numbers, and the first whose work item and
+ * output are an edge)
+ *
+ * The graph and the edge rule are sh_tri's, word for word: the matrix is square (rows x rows); entry j of row r storing
+ * column c with 0 <= c < rows counts when its 32 value bits are not all zero (a float -0.0 counts, a stored zero does
+ * not); the graph is the SIMPLE UNDIRECTED graph under those entries.  Self-loops, parallel entries, stored zeros, the
+ * direction of an entry and columns outside the matrix change nothing.  M is its number of edges.
+ *      Edge ids: edge e, 0 <= e < M, is the e-th smallest pair (u, v) with u < v, in lexicographic order (in numpy: the
+ *      sorted unique pairs); edge_u[e] and edge_v[e] make the indexing visible.
+ *      support[e] = |N(u) & N(v)|, the triangles through e; the supports sum to three times the triangles.
+ *      truss[e] follows Cohen's convention: the largest k such that e lies in a subgraph all of whose edges are in at
+ *      least k - 2 triangles of that subgraph.  An edge in no triangle has truss 2, and every edge of K_n has truss n.
+ *      truss[e] is 0 until the edge is settled, which a caller sees only after a call cut short by max_rounds.
+ *      *max_truss is the largest truss number (0 when M == 0), *levels the number of distinct ones, *triangles the sum of
+ *      the supports / 3.  Per round: k_per_round, size_per_round (the edges settled) and walked_per_round, the sum of
+ *      min(deg u, deg v) over the round's edges -- defined so that it is deterministic, whatever the kernel skips.
+ *      Truss numbers are integers and a graph has one vector of them: every comparison is ==.
+ *
+ *      Schedule (csrc/truss.hip.h; PKT: Kabir, Madduri 2017).  Per edge: sup[e], the remaining support; stamp[e], 0 while
+ *      the edge is alive and in no list, else the round (counted from 1) whose list holds it; truss[e].  In round r an
+ *      edge is current if stamp == r, gone if 0 < stamp < r, and alive otherwise (0, or r + 1: owned during this very
+ *      launch; a racing reader sees either and acts the same).  Before round 1 the support pass counts, for every edge,
+ *      the entries of the shorter of its ends' two lists that the longer one holds too (a bisection per entry).  Work
+ *      goes by the length of that shorter list: up to 8 entries one lane, up to 2048 one wave, longer lists in pieces of
+ *      2048, one wave per piece; the first two store their count, a piece does one atomic add per piece, and the total
+ *      goes into a sum per workgroup, never one word hit by every wave.  A round is one fixed set of four launches
+ *      enqueued ahead of the host in batches (8, 16, 32, 32, ...), each of which returns at once unless the control
+ *      block on the device gives it work.  When the work list is empty and edges remain, the round opens a level: one
+ *      pass takes the smallest sup among the unsettled (a minimum per workgroup), that minimum becomes s and k = s + 2
+ *      -- empty levels are skipped, not walked -- and a second pass stamps every unsettled e with sup[e] <= s and puts
+ *      it on the list.  The peel walks, for each current e = {u, v}, the shorter list again; an entry w with the edge
+ *      e1 = {u, w} that the longer list holds too gives e2 = {v, w} (no bisection when e1 is gone).  The rule for the
+ *      triangle {e, e1, e2}: if e1 or e2 is gone, nothing -- it was taken apart in an earlier round; if both are
+ *      current, nothing; if only e1 is current, e2 is decremented when e < e1 and not otherwise (the same with e1 and e2
+ *      swapped), so of the two current edges exactly one acts; if neither is current, both are decremented.  Every
+ *      triangle costs each surviving edge one decrement.  The decrement is sh_core's: if the word is <= s, skip; else
+ *      one atomic decrement; the one lane that gets the old value s + 1 owns the edge, stamps it r + 1 and appends it to
+ *      the next list; a lane that gets an old value <= s restores it with one add.  There is no compare-and-swap, no
+ *      retry and no waiting.  A last small launch sums the workgroups' counts, takes the settled from the remaining,
+ *      swaps the lists, records the round and finishes when nothing remains.
+ *      Why that is right: peeling is monotone -- removing more only lowers remaining supports further.  A level ends when
+ *      no unsettled edge has sup <= s; the set settled in it is the closure of "delete an edge of remaining support
+ *      <= s", the same in whatever order, so every level starts from one state and truss[e] is the level e fell in.  A
+ *      round's list is exactly the edges whose remaining support fell to <= s in the round before, so *rounds and the
+ *      records per round are deterministic too; there is no chase option.  Once the word of an edge has gone from s + 1
+ *      to s it never exceeds s again, so the owner is unique, and every reader only compares with `> s`, so a transient
+ *      value below s answers like s.  Every edge is settled once (a list of M places cannot overflow); no kernel ever
+ *      waits for another kernel's write; every loop is bounded by a list length, M or 32 halvings.
+ *      Worst cases: the number of rounds is the depth of the peeling -- the triangulated 128 x 128 grid needs 128 rounds
+ *      for its one level.  Every non-empty level costs two passes over all edges.  An edge between two hubs costs its
+ *      shorter list, bisected into the longer, in the support pass and in the round in which it is current.  A clique of
+ *      n vertices costs n^3 / 2 bisections in the support pass.
+ *
+ *      Measured on an MI355X (DESIGN.md "6k k-truss decomposition"; tools/truss_bench.py, one process per matrix, the
+ *        two arms alternating, 5 rounds, device time against the wall time of hostlib.truss_numbers in that process),
+ *        median (min-max) in ms: the triangulated 2048 x 2048 grid (4 194 304 rows, 12 574 721 edges, 8 380 418
+ *        triangles, every truss 3, one level; host gold 1545): 74.8 (74.6-75.1), 2048 rounds, of which the support pass
+ *        0.58.  R-MAT-14 (16 384 rows, 213 008 edges, 2 836 521 triangles, max_truss 78, 65 levels, largest degree
+ *        3639; host gold 1368): 302.6 (301.2-303.1), 586 rounds, the support pass 0.50.  The handle is built in 0.06 s
+ *        on either.  A round of the grid costs 37 us, launch cost; a round of R-MAT-14 costs 516 us on average -- the
+ *        rounds that walk hub-hub edges, one workgroup per long item, are what the call costs, not the support pass.
+ *        Rule: a call is 0.05 (grid) to 0.22 (R-MAT-14) of the host's bucket algorithm.  Each round costs its four
+ *        launches however small its list is, so a deep peeling on a small graph loses to the host; below which size
+ *        is unmeasured, as is any R-MAT above scale 14.
+ *
+ * sh_truss_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  The handle holds on the device:
+ * adj_ptr[rows + 1], adj_col[2M] (sh_core_graph's symmetric lists, every list strictly ascending) and adj_eid[2M], the edge
+ * id of every list entry; edge_u[M], edge_v[M], deg[rows], sup[M], stamp[M]; two work lists of M entries (an edge enters a
+ * list at most once per call: they cannot overflow), which keep the items of the piece class at their far end, so that
+ * no list of pieces is stored -- an item is cut by the SHORTER of two lists and the number of pieces is not linear in M;
+ * and a control block with the workgroups' counts.  rows == 0 gives a valid handle.  Freeing NULL is SH_OK.  The build
+ * runs on the device, once, and is sh_core_graph_create's (one helper serves both), followed by two kernels: the ends of
+ * every edge from the run heads of the sorted keys, and the edge id of every list entry by one bisection into them.
+ * While it runs the build needs 4 * (rows + 1) + 16 * nnz + 8 bytes for the arrays as given, their flags and scan, 16 bytes
+ * per surviving entry for the keys and the sorted keys, 32 bytes per edge for the keys both ways and their sorted copy,
+ * and the sort's own scratch; all of it is released before the call returns.  nnz is bounded as for the other handles,
+ * and 2M by 2^31 - 256.
+ * sh_truss_graph_footprint: device bytes held =
+ *     4 * (rows + 1) + 4 * rows + 40 * edges + 51200.
+ * sh_truss_graph_edges: M.  sh_truss_graph_max_degree: the largest degree (the length of the longest list).
+ *
+ * sh_truss: truss: an int32 vector of >= M elements; exactly M elements are overwritten.  support, edge_u, edge_v: each
+ * NULL, or an int32 vector of >= M elements.  max_rounds >= 0 bounds the rounds; M + 1 can never cut a run short (the
+ * Python binding's default); with 0 the call stops after the support pass (support, *triangles and the ends are valid,
+ * truss is 0).  M == 0 gives 0 rounds and *complete = 1.  The per-round arrays (capacity max_rounds; each may be NULL)
+ * are listed above; ns_per_round is device time, and *total_ns (may be NULL) the device time of the support pass and
+ * all rounds (hipEvent) as elsewhere.  A call cut short leaves the handle reusable; g may serve any number of calls,
+ * one at a time; every call starts from the support pass.
+ * SH_EINVAL: NULL arguments (engine, graph, truss, max_truss, levels, rounds, complete, triangles, out, the arrays),
+ * rows < 0, nnz < 0, max_rounds < 0.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases;
+ * truss, support, edge_u or edge_v shorter than M.  All are reported before any device work, with the buffers untouched.
+ * NOT covered: k-truss subgraph extraction (the edges with truss >= k are one numpy line from truss, edge_u and edge_v),
+ * triangle listing, the multi-GPU driver, row pieces (sh_spmv_step_pieces), the C++ harness apps, incremental updates.
+ */
+typedef struct sh_truss_graph sh_truss_graph;
+int sh_truss_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                          const void *val, sh_truss_graph **out);
+int sh_truss_graph_free(sh_engine *e, sh_truss_graph *g);
+int sh_truss_graph_footprint(const sh_truss_graph *g, uint64_t *device_bytes);
+int sh_truss_graph_edges(const sh_truss_graph *g, int64_t *edges);          /* M */
+int sh_truss_graph_max_degree(const sh_truss_graph *g, int64_t *entries);
+int sh_truss(sh_engine *e, sh_truss_graph *g, sh_vec *truss, sh_vec *support, sh_vec *edge_u, sh_vec *edge_v, int32_t max_rounds,
+             int32_t *max_truss, int32_t *levels, int32_t *rounds, int32_t *complete, uint64_t *triangles,
+             int32_t *k_per_round, int64_t *size_per_round, int64_t *walked_per_round, uint64_t *ns_per_round,
+             uint64_t *total_ns);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,7 @@ Harness / Run / KernelConfig surface.
   csrc/      hand-written HIP (gfx950) kernels + the C ABI of include/sparseharness_hip.h
   host/      C++ mirror of the reference's host interface (Harness<>, SparseMatrix<>,
              Gold<>, KernelConfig<>, Run, SqlStat, the three apps) on top of the C ABI
-  abi.py / engine.py / hostlib.py   ctypes bindings used by tests/ and bench.py
+  abi.py / engine.py / hostlib.py   ctypes bindings used by tests/ and bench.py (truss.py: the handle of Engine.truss_graph)
   partition.py / distributed.py     row sharding + per-iteration all-gather driver
 
 There is no CPU compute path in this package.

@@ -8,17 +8,19 @@ sssp_preds, sssp.hip.h), or one of the SCC kernels (scc_init / scc_trim / scc_pi
 scc_label / scc_decide, scc.hip.h), or one of the WCC kernels (wcc_init / wcc_sample / wcc_compact / wcc_full / wcc_jump /
 wcc_decide / wcc_label, wcc.hip.h), or one of the triangle kernels (tri_count_light / tri_count_heavy, each with and without
 per-vertex counts, and tri_finish, tri.hip.h), or one of the core-number kernels (core_init / core_min / core_open / core_peel /
-core_close, core.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+core_close, core.hip.h), or one of the truss kernels (truss_init / truss_support / truss_total / truss_min / truss_open /
+truss_peel / truss_close, truss.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set()
+bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core, seen_truss = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
 BFS_KERNELS = ("bfs_init", "bfs_topdown", "bfs_bottomup", "bfs_queue_from_bitmap", "bfs_decide", "bfs_parents")
 SSSP_KERNELS = ("sssp_init", "sssp_relax", "sssp_split", "sssp_decide", "sssp_preds")
 SCC_KERNELS = ("scc_init", "scc_trim", "scc_pick", "scc_seed", "scc_propagate", "scc_claim", "scc_label", "scc_decide")
 TRI_KERNELS = ("tri_count_light", "tri_count_heavy", "tri_finish")
 CORE_KERNELS = ("core_init", "core_min", "core_open", "core_peel", "core_close")
+TRUSS_KERNELS = ("truss_init", "truss_support", "truss_total", "truss_min", "truss_open", "truss_peel", "truss_close")
 WCC_KERNELS = ("wcc_init", "wcc_sample", "wcc_compact", "wcc_full", "wcc_jump", "wcc_decide", "wcc_label")
 for blk in text.split("remark: Function Name: ")[1:]:
     name = blk.split()[0]
@@ -31,9 +33,12 @@ for blk in text.split("remark: Function Name: ")[1:]:
     wcc = any(k in name for k in WCC_KERNELS)
     tri = any(k in name for k in TRI_KERNELS)
     core = any(k in name for k in CORE_KERNELS)
-    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core:
+    truss = any(k in name for k in TRUSS_KERNELS)
+    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core and not truss:
         continue
-    if core:
+    if truss:
+        seen_truss.add(name)
+    elif core:
         seen_core.add(name)
     elif tri:
         seen_tri.add(name)
@@ -98,7 +103,10 @@ if len(seen_tri) != 5:
 # the five kernels of sh_core, under the limits of the BFS kernels
 if len(seen_core) != len(CORE_KERNELS):
     sys.exit(f"expected {len(CORE_KERNELS)} core-number kernels in the remarks, found {len(seen_core)}: {sorted(seen_core)}")
+# the seven kernels of sh_truss, under the limits of the BFS kernels
+if len(seen_truss) != len(TRUSS_KERNELS):
+    sys.exit(f"expected {len(TRUSS_KERNELS)} truss kernels in the remarks, found {len(seen_truss)}: {sorted(seen_truss)}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle and {len(seen_core)} core-number kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle, {len(seen_core)} core-number and {len(seen_truss)} truss kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

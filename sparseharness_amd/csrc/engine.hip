@@ -17,6 +17,7 @@
 #include "wcc.hip.h"
 #include "tri.hip.h"
 #include "core.hip.h"
+#include "truss.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 
@@ -1856,7 +1857,7 @@ struct GraphHandle : GraphBase {
   }
 };
 
-// What the scalars and the host arrays of fn = sh_bfs_graph_create / ... / sh_tri_graph_create / sh_core_graph_create alone decide: no device is
+// What the scalars and the host arrays of fn = sh_bfs_graph_create / ... / sh_core_graph_create / sh_truss_graph_create alone decide: no device is
 // needed to be told.
 static int check_host_csr(sh_engine *e, const char *fn, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                           const void *val, const void *out) {
@@ -1948,7 +1949,7 @@ static int open_control(sh_engine *e, GraphHandle<Ctl> *g, int64_t ctl_bytes, in
   return SH_OK;
 }
 
-// What fn = sh_bfs_graph_create / ... / sh_core_graph_create share: *out is cleared, the host arrays are checked
+// What fn = sh_bfs_graph_create / ... / sh_truss_graph_create share: *out is cleared, the host arrays are checked
 // (check_host_csr), the handle is made, build(g) fills it, and once the stream has drained the handle is the caller's.
 // On any error the handle and what it allocated so far are released and *out stays NULL.  (A build that has to wait for
 // the stream itself, as sh_sssp_graph's for its weight sum and sh_tri_graph's for its longest list, leaves it idle.)
@@ -1970,7 +1971,7 @@ static int create_graph_handle(sh_engine *e, const char *fn, int64_t rows, int64
   return SH_OK;
 }
 
-// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc and sh_core: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core and sh_truss: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
 // next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
 // enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
 // step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
@@ -2953,33 +2954,32 @@ static_assert(sizeof(CoreCtl) <= CORE_CTL_BYTES, "the control block is accounted
 static_assert(sizeof(WlPart) * CORE_MAX_BLOCKS == CORE_PART_BYTES, "one WlPart per workgroup");
 static_assert(sizeof(CoreCtl::rec) / sizeof(CoreRec) == CORE_BATCH, "one record per round of a batch");
 
-// The symmetric lists of a core handle from host CSR arrays: the edges of the simple graph and the degrees
-// (build_und_edges), every edge as two keys (src << bits | dst), sorted, the row starts taken from them.  Returns with
-// the stream synchronised: the host arrays are done with.
-static int build_symmetric_lists(sh_engine *e, sh_core_graph *g, int64_t rows, int64_t nnz, const int32_t *row_ptr,
-                                 const int32_t *col_idx, const void *val) {
-  g->rows = rows; g->nnz = nnz;
-  DevArrays &own = g->dev;
-  HIP_TRY(e, own.alloc(&g->d_in_ptr, (rows + 1) * 4));
-  HIP_TRY(e, own.alloc(&g->d_deg, rows * 4));
-  HIP_TRY(e, own.alloc(&g->d_cur, rows * 4));
-  HIP_TRY(e, hipMemsetAsync(g->d_in_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
-  HIP_TRY(e, hipMemsetAsync(g->d_deg, 0, (size_t)std::max<int64_t>(rows, 1) * 4, e->stream));
-  DevArrays tmp;
+// The symmetric lists of a core or truss handle (fn = sh_core_graph_create / sh_truss_graph_create) from host CSR arrays:
+// the edges of the simple graph and the degrees (build_und_edges), every edge as two keys (src << bits | dst), sorted,
+// the row starts taken from them.  ptr, col and deg are the handle's (`own`); `tmp` keeps what build_und_edges left (u)
+// until the caller lets go of it.  Returns with the stream synchronised: the host arrays are done with.
+struct SymLists {
+  int32_t *ptr = nullptr, *col = nullptr;
+  uint32_t *deg = nullptr;
+  int64_t max_degree = 0;
   UndEdges u;
-  const int rc = build_und_edges(e, tmp, rows, nnz, row_ptr, col_idx, val, g->d_deg, &u);
+};
+static int build_symmetric_lists(sh_engine *e, const char *fn, DevArrays &own, DevArrays &tmp, int64_t rows, int64_t nnz,
+                                 const int32_t *row_ptr, const int32_t *col_idx, const void *val, SymLists *out) {
+  SymLists &g = *out;
+  HIP_TRY(e, own.alloc(&g.ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g.deg, rows * 4));
+  HIP_TRY(e, hipMemsetAsync(g.ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g.deg, 0, (size_t)std::max<int64_t>(rows, 1) * 4, e->stream));
+  UndEdges &u = g.u;
+  const int rc = build_und_edges(e, tmp, rows, nnz, row_ptr, col_idx, val, g.deg, &u);
   if (rc)
     return rc;
   const int64_t S = u.S, M = u.M, E = 2 * M;
   if (E > 0x7FFFFF00ll)
-    return fail(e, SH_EINVAL, "sh_core_graph_create: the lists hold %lld entries (twice the %lld edges), must be at most 2^31 - 256",
+    return fail(e, SH_EINVAL, "%s: the lists hold %lld entries (twice the %lld edges), must be at most 2^31 - 256", fn,
                 (long long)E, (long long)M);
-  g->edges = M;
-  HIP_TRY(e, own.alloc(&g->d_in_col, E * 4));
-  for (int i = 0; i < 2; i++) {
-    HIP_TRY(e, own.alloc(&g->lists.list[i], rows * 4));   // a vertex joins a work list at most once per call (core.hip.h, invariant 1)
-    HIP_TRY(e, own.alloc(&g->lists.pieces[i], (E / (CORE_PIECE / 2) + 1) * sizeof(WlPiece)));   // see wl_push_pieces
-  }
+  HIP_TRY(e, own.alloc(&g.col, E * 4));
   uint32_t *t_longest = nullptr;
   HIP_TRY(e, tmp.alloc(&t_longest, 4));
   HIP_TRY(e, hipMemsetAsync(t_longest, 0, 4, e->stream));
@@ -2992,16 +2992,16 @@ static int build_symmetric_lists(sh_engine *e, sh_core_graph *g, int64_t rows, i
     hipLaunchKernelGGL(wl_both_ways, grid_for(S), blk, 0, e->stream, u.sorted, u.head, u.pos, S, u.bits, t_key);
     HIP_TRY(e, hipGetLastError());
     HIP_TRY(e, device_sort_keys_u64(e->stream, t_key, t_sorted, E, 2 * u.bits));
-    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(E, rows + 1)), blk, 0, e->stream, t_sorted, E, rows, u.bits, g->d_in_ptr, g->d_in_col);
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(E, rows + 1)), blk, 0, e->stream, t_sorted, E, rows, u.bits, g.ptr, g.col);
     HIP_TRY(e, hipGetLastError());
-    hipLaunchKernelGGL(wl_max_len, dim3((unsigned)std::max(1, std::min(e->n_cus * 4, CORE_MAX_BLOCKS))), blk, 0, e->stream, g->d_in_ptr, rows,
+    hipLaunchKernelGGL(wl_max_len, dim3((unsigned)std::max(1, std::min(e->n_cus * 4, CORE_MAX_BLOCKS))), blk, 0, e->stream, g.ptr, rows,
                        t_longest);
     HIP_TRY(e, hipGetLastError());
   }
   uint32_t longest = 0;
   HIP_TRY(e, hipMemcpyAsync(&longest, t_longest, 4, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(e, hipStreamSynchronize(e->stream));
-  g->max_degree = (int64_t)longest;
+  g.max_degree = (int64_t)longest;
   return SH_OK;
 }
 
@@ -3011,8 +3011,20 @@ int sh_core_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t 
                          const void *val, sh_core_graph **out) {
   return create_graph_handle<sh_core_graph>(e, "sh_core_graph_create", rows, nnz, row_ptr, col_idx, val, out, [&](sh_core_graph *g) -> int {
     int rc;
-    if ((rc = build_symmetric_lists(e, g, rows, nnz, row_ptr, col_idx, val)))
-      return rc;
+    g->rows = rows; g->nnz = nnz;
+    SymLists s;
+    {
+      DevArrays tmp;
+      if ((rc = build_symmetric_lists(e, "sh_core_graph_create", g->dev, tmp, rows, nnz, row_ptr, col_idx, val, &s)))
+        return rc;
+    }
+    g->d_in_ptr = s.ptr; g->d_in_col = s.col; g->d_deg = s.deg;
+    g->edges = s.u.M; g->max_degree = s.max_degree;
+    HIP_TRY(e, g->dev.alloc(&g->d_cur, rows * 4));
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(e, g->dev.alloc(&g->lists.list[i], rows * 4));   // a vertex joins a work list at most once per call (core.hip.h, invariant 1)
+      HIP_TRY(e, g->dev.alloc(&g->lists.pieces[i], (2 * s.u.M / (CORE_PIECE / 2) + 1) * sizeof(WlPiece)));   // see wl_push_pieces
+    }
     if ((rc = open_control(e, g, CORE_CTL_BYTES, CORE_CTL_BYTES + 2 * CORE_PART_BYTES)))
       return rc;
     g->d_mins = (WlPart *)((char *)g->d_ctl + CORE_CTL_BYTES + CORE_PART_BYTES);
@@ -3091,6 +3103,149 @@ int sh_core(sh_engine *e, sh_core_graph *g, sh_vec *core, sh_vec *deg, int32_t c
   *levels = g->h_ctl->levels;
   *rounds = it;
   *complete = done ? 1 : 0;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- truss numbers by parallel peeling (truss.hip.h) -----------------------------------------------------------------
+// The GraphHandle base serves run_batches (control block, pinned copy, events).  As in sh_core_graph the symmetric lists
+// use d_in_ptr / d_in_col alone (adj_ptr / adj_col).  d_ctl: TRUSS_CTL_BYTES, followed by the TrussParts of truss_peel,
+// the WlParts of truss_min and the TrussParts of truss_support.
+struct sh_truss_graph : GraphHandle<TrussCtl> {
+  int64_t max_degree = 0;
+  uint32_t *d_deg = nullptr;
+  int32_t *d_eid = nullptr, *d_eu = nullptr, *d_ev = nullptr, *d_sup = nullptr, *d_stamp = nullptr;
+  TrussLists lists = {};
+  WlPart *d_mins = nullptr;
+  TrussPart *d_sparts = nullptr;
+};
+static_assert(sizeof(TrussCtl) <= TRUSS_CTL_BYTES, "the control block is accounted as TRUSS_CTL_BYTES (sh_truss_graph_footprint)");
+static_assert(sizeof(TrussPart) * TRUSS_MAX_BLOCKS == TRUSS_PART_BYTES && sizeof(WlPart) == sizeof(TrussPart), "one part per workgroup");
+static_assert(sizeof(TrussCtl::rec) / sizeof(TrussRec) == TRUSS_BATCH, "one record per round of a batch");
+
+extern "C" {
+
+int sh_truss_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                          const void *val, sh_truss_graph **out) {
+  return create_graph_handle<sh_truss_graph>(e, "sh_truss_graph_create", rows, nnz, row_ptr, col_idx, val, out, [&](sh_truss_graph *g) -> int {
+    int rc;
+    g->rows = rows; g->nnz = nnz;
+    DevArrays &own = g->dev;
+    DevArrays tmp;   // (what build_und_edges left: the sorted keys, their run heads and the scan of those)
+    SymLists s;
+    if ((rc = build_symmetric_lists(e, "sh_truss_graph_create", own, tmp, rows, nnz, row_ptr, col_idx, val, &s)))
+      return rc;
+    const int64_t M = s.u.M;
+    g->d_in_ptr = s.ptr; g->d_in_col = s.col; g->d_deg = s.deg;
+    g->edges = M; g->max_degree = s.max_degree;
+    HIP_TRY(e, own.alloc(&g->d_eid, 2 * M * 4));
+    HIP_TRY(e, own.alloc(&g->d_eu, M * 4));
+    HIP_TRY(e, own.alloc(&g->d_ev, M * 4));
+    HIP_TRY(e, own.alloc(&g->d_sup, M * 4));
+    HIP_TRY(e, own.alloc(&g->d_stamp, M * 4));
+    for (int i = 0; i < 2; i++)
+      HIP_TRY(e, own.alloc(&g->lists.list[i], M * 4));   // an edge joins a work list at most once per call (truss.hip.h, invariant 1)
+    if (M > 0) {
+      const dim3 blk(WL_BS);
+      const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
+      hipLaunchKernelGGL(wl_edge_ends, grid_for(s.u.S), blk, 0, e->stream, s.u.sorted, s.u.head, s.u.pos, s.u.S, s.u.bits, g->d_eu, g->d_ev);
+      HIP_TRY(e, hipGetLastError());
+      hipLaunchKernelGGL(wl_edge_ids, grid_for(2 * M), blk, 0, e->stream, g->d_in_ptr, g->d_in_col, 2 * M, (int32_t)rows, g->d_eu, g->d_ev, M,
+                         g->d_eid);
+      HIP_TRY(e, hipGetLastError());
+    }
+    if ((rc = open_control(e, g, TRUSS_CTL_BYTES, TRUSS_CTL_BYTES + 3 * TRUSS_PART_BYTES)))
+      return rc;
+    g->d_mins = (WlPart *)((char *)g->d_ctl + TRUSS_CTL_BYTES + TRUSS_PART_BYTES);
+    g->d_sparts = (TrussPart *)((char *)g->d_ctl + TRUSS_CTL_BYTES + 2 * TRUSS_PART_BYTES);
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the kernels above read `tmp`)
+    return SH_OK;
+  });
+}
+
+int sh_truss_graph_free(sh_engine *e, sh_truss_graph *g) { return free_handle(e, g); }
+
+int sh_truss_graph_footprint(const sh_truss_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
+
+int sh_truss_graph_edges(const sh_truss_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
+
+int sh_truss_graph_max_degree(const sh_truss_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->max_degree); }
+
+int sh_truss(sh_engine *e, sh_truss_graph *g, sh_vec *truss, sh_vec *support, sh_vec *edge_u, sh_vec *edge_v, int32_t max_rounds,
+             int32_t *max_truss, int32_t *levels, int32_t *rounds, int32_t *complete, uint64_t *triangles,
+             int32_t *k_per_round, int64_t *size_per_round, int64_t *walked_per_round, uint64_t *ns_per_round, uint64_t *total_ns) {
+  // what the scalar alone decides comes first: no handle is needed to be told
+  if (max_rounds < 0)
+    return fail(e, SH_EINVAL, "sh_truss: max_rounds = %d, must not be negative", (int)max_rounds);
+  if (!e || !g || !truss || !max_truss || !levels || !rounds || !complete || !triangles)
+    return fail(e, SH_EINVAL, "sh_truss: NULL argument (engine, graph, truss, max_truss, levels, rounds, complete or triangles)");
+  const int64_t M = g->edges;
+  const struct { const sh_vec *v; const char *name; } vecs[] = {{truss, "truss"}, {support, "support"}, {edge_u, "edge_u"}, {edge_v, "edge_v"}};
+  for (const auto &x : vecs)
+    if (x.v && x.v->n < M)
+      return fail(e, SH_ESHAPE, "sh_truss: %s is shorter than the graph's %lld edges", x.name, (long long)M);
+  *max_truss = 0; *levels = 0; *rounds = 0; *complete = 1; *triangles = 0;
+  if (total_ns) *total_ns = 0;
+  if (M == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, TRUSS_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
+  const TrussGraph G{(int32_t)g->rows, (int32_t)M, g->d_in_ptr, g->d_in_col, g->d_eid, g->d_eu, g->d_ev};
+  int32_t *t = (int32_t *)truss->d;
+  uint64_t total = 0;
+  // every edge alive and unsettled, its remaining support its support
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, TRUSS_CTL_BYTES, e->stream));
+  if (edge_u) HIP_TRY(e, hipMemcpyAsync(edge_u->d, g->d_eu, (size_t)M * 4, hipMemcpyDeviceToDevice, e->stream));
+  if (edge_v) HIP_TRY(e, hipMemcpyAsync(edge_v->d, g->d_ev, (size_t)M * 4, hipMemcpyDeviceToDevice, e->stream));
+  uint32_t *far1 = g->lists.list[1] + (M - 1);   // (list 1 is empty until round 1 fills it: its far end lends itself)
+  hipLaunchKernelGGL(truss_init, grid, block, 0, e->stream, g->d_ctl, G, g->d_sup, g->d_stamp, t, far1);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(truss_support, grid, block, 0, e->stream, g->d_ctl, G, g->d_sup, far1, g->d_sparts);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(truss_total, dim3(1), block, 0, e->stream, g->d_ctl, nblocks, g->d_sparts);
+  HIP_TRY(e, hipGetLastError());
+  if (support) HIP_TRY(e, hipMemcpyAsync(support->d, g->d_sup, (size_t)M * 4, hipMemcpyDeviceToDevice, e->stream));
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  int32_t it = 0;
+  bool done = false;
+  // the launches of a round: each returns at once unless the control block says the round is its turn (and, for the
+  // two passes that open a level, unless the work list is empty)
+  const auto enqueue = [&](int s, int k) {
+    hipLaunchKernelGGL(truss_min, grid, block, 0, e->stream, g->d_ctl, s, (int32_t)M, g->d_sup, g->d_stamp, g->d_mins);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(truss_open, grid, block, 0, e->stream, g->d_ctl, s, G, g->d_sup, g->d_stamp, g->d_mins, g->lists);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(truss_peel, grid, block, 0, e->stream, g->d_ctl, s, G, g->d_sup, g->d_stamp, t, g->lists, (TrussPart *)g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(truss_close, dim3(1), block, 0, e->stream, g->d_ctl, k, s, nblocks, (const TrussPart *)g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    return (int)SH_OK;
+  };
+  const auto take = [&](int s, const TrussRec &rc, uint64_t round_ns) {
+    if (k_per_round) k_per_round[s] = rc.k;
+    if (size_per_round) size_per_round[s] = (int64_t)rc.size;
+    if (walked_per_round) walked_per_round[s] = (int64_t)rc.walked;
+    if (ns_per_round) ns_per_round[s] = round_ns;
+  };
+  const int rc = run_batches(e, "sh_truss: round", g, max_rounds, &it, &done, &total, enqueue, take);
+  if (rc)
+    return rc;
+  if (max_rounds == 0) {   // (no batch ran, so nothing was read back: the support pass alone)
+    HIP_TRY(e, hipMemcpyAsync(g->h_ctl, g->d_ctl, sizeof(TrussCtl), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, ms_between(e->ev0, e->ev1, &total));
+  }
+  // (the control block as the last readback left it in h_ctl)
+  *max_truss = g->h_ctl->max_truss;
+  *levels = g->h_ctl->levels;
+  *rounds = it;
+  *complete = done ? 1 : 0;
+  *triangles = g->h_ctl->hits / 3;
   if (total_ns)
     *total_ns = total;
   return SH_OK;

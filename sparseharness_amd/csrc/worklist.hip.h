@@ -1,4 +1,4 @@
-// worklist.hip.h -- what the worklist algorithms share (frontier.hip.h, bfs.hip.h, sssp.hip.h, ..., core.hip.h): list cursors, the cutting
+// worklist.hip.h -- what the worklist algorithms share (frontier.hip.h, bfs.hip.h, sssp.hip.h, ..., core.hip.h, truss.hip.h): list cursors, the cutting
 // of long lists into pieces, per-workgroup sums, the two traversal skeletons and the kernels that build a graph handle.
 //
 // Work distribution: every kernel runs a fixed grid whose waves stride over a device-side list length (the host does
@@ -312,6 +312,33 @@ __global__ __launch_bounds__(WL_BS) void wl_both_ways(const uint64_t *__restrict
     okey[2 * (int64_t)pos[i]] = (u << bits) | v;
     okey[2 * (int64_t)pos[i] + 1] = (v << bits) | u;
   }
+}
+// Edge i of the simple graph (pos = exclusive scan of head) is edge pos[i] of sh_truss_graph -- the keys are sorted, so the
+// ids run in the order of the pairs (u, v), u < v: eu[pos[i]] = u, ev[pos[i]] = v
+__global__ __launch_bounds__(WL_BS) void wl_edge_ends(const uint64_t *__restrict__ key, const uint32_t *__restrict__ head,
+                                                      const uint32_t *__restrict__ pos, int64_t n, int bits,
+                                                      int32_t *__restrict__ eu, int32_t *__restrict__ ev) {
+  const int64_t i = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (i < n && head[i]) {
+    eu[pos[i]] = (int32_t)(key[i] >> bits);
+    ev[pos[i]] = (int32_t)(key[i] & ((1ull << bits) - 1ull));
+  }
+}
+// eid[j] = the edge that entry j of the symmetric lists ptr / col (n entries) stands for: the row of j by bisection of ptr
+// (wl_row_of), the pair (min, max) by bisection of the m edges eu / ev, which hold it (one-off work)
+__global__ __launch_bounds__(WL_BS) void wl_edge_ids(const int32_t *__restrict__ ptr, const int32_t *__restrict__ col, int64_t n,
+                                                     int32_t rows, const int32_t *__restrict__ eu, const int32_t *__restrict__ ev,
+                                                     int64_t m, int32_t *__restrict__ eid) {
+  const int64_t j = (int64_t)blockIdx.x * WL_BS + threadIdx.x;
+  if (j >= n) return;
+  const int32_t r = wl_row_of(ptr, rows, j), c = col[j];
+  const int32_t a = min(r, c), b = max(r, c);
+  int64_t lo = 0, hi = m;   // the first edge that is not below (a, b)
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (eu[mid] < a || (eu[mid] == a && ev[mid] < b)) lo = mid + 1; else hi = mid;
+  }
+  eid[j] = (int32_t)min(lo, m - 1);
 }
 // From the sorted oriented keys: fwd_col, and fwd_ptr[r] = the first key of a source >= r (r in [0, rows]; a bisection
 // over m keys per row)

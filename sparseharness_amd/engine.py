@@ -485,6 +485,32 @@ class Engine:
         return (degeneracy.value, levels.value, n, bool(complete.value), ks[:n].copy(), sizes[:n].copy(), chased[:n].copy(),
                 edges[:n].copy(), per[:n].copy(), total.value)
 
+    # ---- truss numbers: truss[e] = the largest k such that edge e lies in a subgraph whose edges are all in >= k - 2 of
+    # its triangles; edge e = the e-th smallest pair (u, v), u < v
+    def truss_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.truss_numbers needs (truss.TrussGraph), from the CSR arrays of a square matrix."""
+        from .truss import TrussGraph   # (truss.py imports this module)
+        return self._graph(TrussGraph, row_ptr, col_idx, val)
+
+    def truss_numbers(self, G, truss, support=None, edge_u=None, edge_v=None, max_rounds=None):
+        """-> (max_truss, levels, rounds, complete, triangles, ks, sizes, walked, ns, total_ns); per round: the k being
+        peeled, edges settled, the sum of min(deg u, deg v) over them, device ns.  truss: an int32 vector of >= M = G.edges
+        elements; support, edge_u, edge_v: None or one more each.  max_rounds = None: M + 1, which cannot cut a run
+        short."""
+        if max_rounds is None:
+            max_rounds = G.edges + 1
+        max_truss, levels, rounds, complete = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        triangles, total = C.c_uint64(), C.c_uint64()
+        cap = max(int(max_rounds), 1)
+        (ks, sizes, walked, per), ptrs = _outs(cap, np.int32, np.int64, np.int64, np.uint64)
+        h = lambda v: None if v is None else v.h   # noqa: E731
+        self._chk(abi.load().sh_truss(self.h, G.h, truss.h, h(support), h(edge_u), h(edge_v), max_rounds, C.byref(max_truss),
+                                      C.byref(levels), C.byref(rounds), C.byref(complete), C.byref(triangles), *ptrs,
+                                      C.byref(total)))
+        n = rounds.value
+        return (max_truss.value, levels.value, n, bool(complete.value), triangles.value, ks[:n].copy(), sizes[:n].copy(),
+                walked[:n].copy(), per[:n].copy(), total.value)
+
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
         dt = elem_dtype(semiring)

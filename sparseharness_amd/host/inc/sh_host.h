@@ -42,6 +42,15 @@ int sh_triangle_counts(int64_t rows, int64_t nnz, const int32_t *row_ptr, const 
 int sh_core_numbers(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                     int32_t *core, int32_t *deg, int64_t *edges);
 
+/* The support and the truss number of every edge of the simple undirected graph under a square CSR pattern (clean,
+ * count the triangles through every edge, then the bucket algorithm of Wang and Cheng; single-threaded): the gold for
+ * sh_truss.  Entry (r, c) counts when 0 <= c < rows, c != r and its 32 value bits are not all zero, in either direction,
+ * once.  Edge e of the *edges = M is the e-th smallest pair (u, v) with u < v: edge_u[e], edge_v[e]; support[e] the
+ * triangles through it; truss[e] the largest k such that e lies in a subgraph all of whose edges are in at least k - 2
+ * triangles of it (2 for an edge in no triangle).  The four arrays hold M <= nnz words each.  Return 0, -1 bad argument. */
+int sh_truss_numbers(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                     int32_t *edge_u, int32_t *edge_v, int32_t *support, int32_t *truss, int64_t *edges);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

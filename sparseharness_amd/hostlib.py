@@ -2,7 +2,7 @@
 loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
 host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp), sh_tri
-(host/src/triangle_counts.cpp) and sh_core (host/src/core_numbers.cpp)."""
+(host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp) and sh_truss (host/src/truss_numbers.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -34,6 +34,7 @@ SIGNATURES = {
     "sh_wcc_labels": (C.c_int, _csr + [_vp]),
     "sh_triangle_counts": (C.c_int, _csr + [_vp, _vp]),
     "sh_core_numbers": (C.c_int, _csr + [_vp, _vp, C.POINTER(_i64)]),
+    "sh_truss_numbers": (C.c_int, _csr + [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sh_mm_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]),
     "sh_mm_load_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]),
     "sh_host_csr_release": (None, [C.POINTER(_HostCsr)]),
@@ -139,6 +140,18 @@ def core_numbers(row_ptr, col_idx, val):
     core, deg, m = np.empty(n, np.int32), np.empty(n, np.int32), C.c_int64()
     _gold("sh_core_numbers", row_ptr, col_idx, val, _p(core), _p(deg), C.byref(m))
     return core, deg, m.value
+
+
+def truss_numbers(row_ptr, col_idx, val):
+    """-> (edge_u, edge_v, support, truss, M): for edge e of the simple undirected graph under the entries -- the e-th
+    smallest pair (u, v) with u < v -- its ends, the triangles through it and its truss number (Engine.truss_numbers'
+    edge_u, edge_v, support and truss; all int32), M = the number of edges, by the single-threaded bucket algorithm of
+    Wang and Cheng on the host.  Entry (r, c) counts when 0 <= c < rows, c != r and its 32 value bits are not all zero."""
+    cap = max(len(col_idx), 1)   # (M <= nnz)
+    eu, ev, sup, truss = (np.empty(cap, np.int32) for _ in range(4))
+    m = C.c_int64()
+    _gold("sh_truss_numbers", row_ptr, col_idx, val, _p(eu), _p(ev), _p(sup), _p(truss), C.byref(m))
+    return eu[:m.value].copy(), ev[:m.value].copy(), sup[:m.value].copy(), truss[:m.value].copy(), m.value
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
