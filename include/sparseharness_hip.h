@@ -239,7 +239,10 @@ typedef struct sh_row_pieces {
   int32_t reserved;
   const int32_t *gate;   /* device word or NULL: a launch whose gate word is 0 when it starts returns at once and writes nothing
                             (what sh_iterate does internally: a caller that enqueues iteration k + 1 before it has read the
-                            flags of iteration k passes the device-side OR of those flags here) */
+                            flags of iteration k passes the device-side OR of those flags here).
+                            A gated launch cannot report: report != 0 together with a gate is refused with SH_EINVAL (a
+                            launch that writes nothing has no piece to report, and a caller polling *done_words would
+                            wait for a round that never comes).  A refused call leaves *round where it was. */
 } sh_row_pieces;
 int sh_spmv_step_pieces(sh_engine *e, sh_semiring sr, sh_csr *A, const sh_vec *x, const sh_vec *y,
                         const void *alpha, const void *beta, sh_vec *out, const sh_row_pieces *pieces, double delta,

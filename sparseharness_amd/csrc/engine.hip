@@ -1155,6 +1155,25 @@ int sh_spmv_step_pieces(sh_engine *e, sh_semiring sr, sh_csr *A, const sh_vec *x
     return fail(e, SH_ESHAPE, "sh_spmv_step_pieces: x has %lld elements, matrix has %lld columns", (long long)x->n, (long long)A->cols);
   if (out->d == x->d && A->rows > 0)
     return fail(e, SH_EINVAL, "sh_spmv_step_pieces: out must not alias x");
+  // A gated launch cannot report: behind a gate that reads 0 the tiled plan's phase 2 never arrives (the host words
+  // would stay below *round for ever) while the other plans would report a round in which nothing was written.
+  if (pc->report && pc->gate)
+    return fail(e, SH_EINVAL, "sh_spmv_step_pieces: a gated launch cannot report its pieces (report != 0 with a gate)");
+  // What the launch itself would refuse is refused here, before the round moves: a refused call leaves *round alone.
+  {
+    bool reads_y = true;
+    switch (sr) {
+    case SH_PLUS_TIMES_F32: { float b; memcpy(&b, beta, 4); reads_y = PlusTimesF32::reads_y(b); break; }
+    case SH_MIN_PLUS_F32: break;
+    case SH_OR_AND_I32: { int32_t b; memcpy(&b, beta, 4); reads_y = OrAndI32::reads_y(b); break; }
+    case SH_MAX_MIN_I32: { int32_t b; memcpy(&b, beta, 4); reads_y = MaxMinI32::reads_y(b); break; }
+    default: return fail(e, SH_EINVAL, "unknown semiring %d", (int)sr);
+    }
+    if (reads_y && !y)
+      return fail(e, SH_EINVAL, "sh_spmv_step_pieces: y is NULL but the epilogue reads it (beta != 0 or min-plus)");
+    if (A->bits_only && sr != SH_OR_AND_I32)
+      return fail(e, SH_EINVAL, "this matrix was uploaded with or_and_bits = 2: it serves SH_OR_AND_I32 launches only");
+  }
   HIP_TRY(e, hipSetDevice(e->device));
   StepDev st{changed_flag_device, (const uint32_t *)x->d, 0, delta, pc->gate};
   PieceDev pd{};
