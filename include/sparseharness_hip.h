@@ -143,6 +143,10 @@ void sh_plan_options_from_env(sh_plan_options *o);
  * entries).  Host-only: needs no device.  opt == NULL: the defaults. */
 int sh_plan_row_work(int64_t rows, int64_t cols, int64_t nnz, const int32_t *row_ptr, const sh_plan_options *opt,
                      uint64_t *work_prefix);
+/* sh_csr_upload with the plan options given instead of read from the environment (opt == NULL: the defaults).  A forced
+ * plan = 2 that the tiled layout's limits rule out (more than 65535 column tiles, more than 2^30 - 4 products, padding
+ * above 25 %, ...: DESIGN.md 3, "Limits of the tiled layout") is not an error: the matrix runs on the CSR-stream plan,
+ * and sh_csr_plan tells. */
 int sh_csr_upload_ex(sh_engine *e, int64_t rows, int64_t cols, int64_t nnz,
                      const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                      const sh_plan_options *opt, sh_csr **out);

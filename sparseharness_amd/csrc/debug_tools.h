@@ -1,6 +1,7 @@
 // debug_tools.h -- included by engine.hip under -DSH_PLAN_EMULATE only (the tools build, sparseharness_amd/variants/
 // emulate.so; never the product build): the host emulator of the tiled / bit plans, the host-vs-device builder
-// comparison and the placement probes (sh_debug_*), used by tests/test_plan_cpu.py, tests/test_builder_gpu.py and tools/.
+// comparison, the builders' verdicts, the switches that lower the limit on P or fail a device build step, and the placement
+// probes (sh_debug_*), used by tests/test_plan_cpu.py, tests/test_plan_limits_*.py, tests/test_builder_gpu.py and tools/.
 #pragma once
 // Tools / CPU tests only (never in the product build): build the tiled plan on the host and execute BOTH phases
 // on the host, entry by entry, through exactly the tables the kernels read (fold flags, obase, gdest, gblk / ptab,
@@ -258,6 +259,54 @@ extern "C" int sh_debug_compare_builds(sh_engine *e, int64_t rows, int64_t cols,
   dev_bytes("obase", hh.obase.data(), hh.obase.size() * 4, td.obase, td.n_obase, 4);
   if (!hip_ok) { rep += "hipMemcpy (download) failed\n"; return finish(-3); }
   return finish(diffs);
+}
+// The limit on the products in P (plan_common.h::max_p_len) for the tests: products > 0 lowers it to that many products,
+// 0 restores the real one, a negative value changes nothing.  Returns the REAL bound (the constant of the product build).
+extern "C" int64_t sh_debug_set_p_limit(int64_t products) {
+  if (products >= 0) g_debug_p_limit = products;
+  return P_LEN_MAX;
+}
+// Makes the NEXT call of build_tiled_plan_gpu report a failed device step (-1, why = "injected"): where = 1 before its
+// first allocation, where = 2 immediately before it would return 1 (the layout complete, the big arrays in
+// TiledDevArrays, TiledHost filled, the stream idle); 0 turns it off.  A host-side switch: no launched kernel changes.
+// It applies to one call and clears itself.
+extern "C" void sh_debug_fail_device_build(int where) { g_debug_fail_device_build = where; }
+// How many arrays of an abandoned device build sh_csr_upload_ex still held when it last started the host builder (a
+// fallback releases them first: the host-built layout must not need room beside them).
+extern "C" int sh_debug_held_at_host_build(void) { return g_debug_held_at_host_build; }
+// Both builders run independently on one matrix: *host_verdict = 1 built / 0 refused, *device_verdict = 1 built /
+// 0 refused / -1 a device step failed, `why` (cap bytes) = what the device builder said.  Everything made here is freed
+// before it returns.  0, or -3 when a HIP call of this function itself failed (why then names it).
+extern "C" int sh_debug_build_verdicts(sh_engine *e, int64_t rows, int64_t cols, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                                       const void *val, const sh_plan_options *opt_p, int32_t *host_verdict, int32_t *device_verdict,
+                                       char *why_out, int64_t cap) {
+  sh_plan_options opt;
+  if (opt_p) opt = *opt_p; else sh_plan_options_default(&opt);
+  std::string why;
+  auto finish = [&](int rc) { if (why_out && cap > 0) snprintf(why_out, (size_t)cap, "%s", why.c_str()); return rc; };
+  if (!e || nnz <= 0 || rows <= 0 || !host_verdict || !device_verdict) { why = "bad argument"; return finish(-3); }
+  if (hipSetDevice(e->device) != hipSuccess) { why = "hipSetDevice"; return finish(-3); }
+  {
+    TiledHost hh;
+    *host_verdict = build_tiled_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, e->n_cus, hh) ? 1 : 0;
+  }
+  TiledHost hg;
+  TiledDevArrays td;
+  struct Guard { TiledDevArrays &t; std::vector<void *> p; ~Guard() { t.release(); for (void *q : p) (void)hipFree(q); } } guard{td, {}};
+  int32_t *d_rp = nullptr, *d_ci = nullptr;
+  uint32_t *d_val = nullptr;
+  if (hipMalloc((void **)&d_rp, (size_t)(rows + 1) * 4) != hipSuccess) { why = "hipMalloc"; return finish(-3); }
+  guard.p.push_back(d_rp);
+  if (hipMalloc((void **)&d_ci, (size_t)nnz * 4 + 32) != hipSuccess) { why = "hipMalloc"; return finish(-3); }
+  guard.p.push_back(d_ci);
+  if (hipMalloc((void **)&d_val, (size_t)nnz * 4 + 32) != hipSuccess) { why = "hipMalloc"; return finish(-3); }
+  guard.p.push_back(d_val);
+  if (hipMemcpy(d_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess) { why = "hipMemcpy"; return finish(-3); }
+  *device_verdict = build_tiled_plan_gpu(e->stream, rows, cols, nnz, row_ptr, d_rp, d_ci, d_val, opt, e->n_cus, hg, td, why);
+  if (hipStreamSynchronize(e->stream) != hipSuccess) { why = "hipStreamSynchronize"; return finish(-3); }
+  return finish(0);
 }
 // The bit-blocked (or,and) layout built by both builders and compared: 0 = identical, else the number of differing
 // arrays; -1 host refused, -2 device refused / failed, -3 HIP error here.

@@ -594,6 +594,14 @@ int sh_csr_upload_ex(sh_engine *e, int64_t rows, int64_t cols, int64_t nnz, cons
       if (g == 0) want_tiled = false;   // the layout does not suit this matrix: the host builder would refuse as well
     }
   }
+#ifdef SH_PLAN_EMULATE
+  if (want_tiled && !tiled) {   // (tools builds: sh_debug_held_at_host_build)
+    g_debug_held_at_host_build = 0;
+    for (const void *p : {(const void *)td.tcol, (const void *)td.pslot, (const void *)td.tcode, (const void *)td.tval, (const void *)td.gdest,
+                          (const void *)td.gblk, (const void *)td.obase, (const void *)td.lrp, (const void *)td.ptab, (const void *)td.ptile})
+      if (p) g_debug_held_at_host_build++;
+  }
+#endif
   if (want_tiled && !tiled)
     tiled = build_tiled_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, e->n_cus, th);
   // (only worth timing when the bins touch few of the column tiles, i.e. the columns are local: with

@@ -1273,7 +1273,7 @@ __device__ __forceinline__ void tiled_phase2_run(
         // a piece of a dead tile (tiled_mark_dead): the group of identity words behind the last product
         if (SR::has_absorbing && (int32_t)g[k] == PIECE_DEAD) pg = last_group + 1;
 #endif
-        async_load_at(p[k], P4, (uint32_t)pg * 16u);   // (P < 4 GB: checked at upload)
+        async_load_at(p[k], P4, (uint32_t)pg * 16u);   // (a 32-bit byte offset: both builders refuse p_len > plan_common.h::max_p_len())
       }
     };
     auto wait8 = [&](v4u32 (&p)[P2S_K], v2u32 (&s)[P2S_K], uint32_t (&g)[P2S_K]) {

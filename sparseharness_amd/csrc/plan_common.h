@@ -109,6 +109,27 @@ __host__ __device__ static inline PiecePack pack_piece(int64_t np, int64_t ns) {
   return PiecePack{(int32_t)blocks, (int32_t)sg, (int32_t)(2 * blocks + sg), (int32_t)(4 * (blocks + sg))};
 }
 
+// The largest p_len (products in P, a multiple of 4) the tiled kernels can address.  Phase 2 loads a group of four
+// products with a 32-bit BYTE offset from the base of P (kernels.hip.h, issue_ps: `(uint32_t)pg * 16u`), and the highest
+// group it ever names is the dead-piece group last_group + 1 = max(p_len, 4) / 4, the 16 bytes of identity words behind
+// the last product (P holds max(p_len, 4) * 4 + 16 bytes).  Its last byte lies at 4 * max(p_len, 4) + 15, which must
+// stay below 2^32: p_len <= 2^30 - 4.  (The int32 indices of P -- RowBin::pstart, obase -- are covered by the same
+// bound.)  Both builders refuse a matrix beyond it; the CSR-stream plan serves such a matrix.
+constexpr int64_t P_LEN_MAX = ((int64_t)1 << 30) - 4;
+#ifdef SH_PLAN_EMULATE
+// tools builds only (debug_tools.h): a lower limit for the tests (0 = the real one), and the one-shot switch that makes
+// the device builder report a failed step (sh_debug_fail_device_build)
+inline int64_t g_debug_p_limit = 0;
+inline int g_debug_fail_device_build = 0;
+inline int g_debug_held_at_host_build = 0;   // device arrays of an abandoned device build still held when the host builder last started
+#endif
+static inline int64_t max_p_len() {
+#ifdef SH_PLAN_EMULATE
+  if (g_debug_p_limit > 0) return g_debug_p_limit;
+#endif
+  return P_LEN_MAX;
+}
+
 // Phase timers of the plan build and the upload (tools builds only: SH_BUILD_TIMES=1 prints them); lap(nullptr) restarts the clock.
 #ifdef SH_PLAN_EMULATE
 static void lap(const char *what) {

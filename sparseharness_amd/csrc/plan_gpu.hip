@@ -577,6 +577,12 @@ struct CubTemp {
 int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *h_rp, const int32_t *d_rp,
                           const int32_t *d_ci, const uint32_t *d_val, const sh_plan_options &opt, int n_cus, TiledHost &H,
                           TiledDevArrays &D, std::string &why) {
+#ifdef SH_PLAN_EMULATE
+  // (tools builds: sh_debug_fail_device_build -- one call, then off again; host side only, no kernel changes)
+  const int inject = g_debug_fail_device_build;
+  g_debug_fail_device_build = 0;
+  if (inject == 1) { why = "injected"; return -1; }
+#endif
   const int CT = (int)std::max<int64_t>(1, (cols + TCOLS - 1) / TCOLS);
   if (CT > 65535 || nnz <= 0 || rows <= 0) { why = "not applicable"; return 0; }
   const bool fold = opt.fold != 0 && TCOL_FOLD != 0;
@@ -820,7 +826,7 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
       RowBin &b = H.bins[(size_t)bi];
       const int64_t bn = (int64_t)(o1[(size_t)bi] - o0[(size_t)bi]);
       if (bn > TBIN) { why = "a bin exceeds TBIN products"; return 0; }
-      if (p_off_total + bn > INT32_MAX) { why = "P exceeds int32 indexing"; return 0; }
+      if (p_off_total + bn > max_p_len()) { why = "P exceeds 32-bit byte offsets"; return 0; }   // (plan_common.h)
       b.n = (int32_t)bn;
       b.pstart = (int32_t)p_off_total;
       p_off_total += bn;
@@ -896,6 +902,7 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
     dctl = pool.get<uint32_t>(4, true);
     POOL_OK();
     hipLaunchKernelGGL(k_distinct, dim3((unsigned)((n + (int64_t)PBS * 64 - 1) / ((int64_t)PBS * 64))), dim3(PBS), 0, stream, d_val, n, dtable, dctl);
+    GT(hipGetLastError());
     std::vector<unsigned long long> tab((size_t)DT);
     uint32_t ctl[4] = {0, 0, 0, 0};
     GT(hipMemcpyAsync(tab.data(), dtable, (size_t)DT * 8, hipMemcpyDeviceToHost, stream));
@@ -910,6 +917,7 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
       uint32_t *dctl16 = pool.get<uint32_t>(4, true);
       POOL_OK();
       hipLaunchKernelGGL(k_distinct16, dim3((unsigned)((n + (int64_t)PBS * 64 - 1) / ((int64_t)PBS * 64))), dim3(PBS), 0, stream, d_val, n, dtable16, dctl16);
+      GT(hipGetLastError());   // (a launch that failed would read as "no distinct words")
       std::vector<unsigned long long> tab16((size_t)DT16);
       GT(hipMemcpyAsync(tab16.data(), dtable16, (size_t)DT16 * 8, hipMemcpyDeviceToHost, stream));
       GT(hipMemcpyAsync(ctl, dctl16, 16, hipMemcpyDeviceToHost, stream));
@@ -1005,6 +1013,9 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
   GT(hipGetLastError());
   PHASE("  obase");
   cut_work_items(CT, run_start, run_len, heavy_start, hrel, ob0, opt, n_cus, H);
+#ifdef SH_PLAN_EMULATE
+  if (inject == 2) { why = "injected"; return -1; }   // everything built, the big arrays still in D, the stream idle
+#endif
   return 1;
 
 hip_failed:

@@ -278,7 +278,7 @@ static bool build_tiled_plan(int64_t rows, int64_t cols, int64_t nnz, const int3
   for (int64_t bi = 0; bi < n_bins; bi++) {
     RowBin &b = H.bins[(size_t)bi];
     if (b.n > TBIN) return false;   // cannot happen with the limits above; phase 2 holds exactly TBIN products
-    if (p_off + b.n > INT32_MAX) return false;
+    if (p_off + b.n > max_p_len()) return false;   // P is addressed with 32-bit byte offsets (plan_common.h)
     b.pstart = (int32_t)p_off;
     p_off += b.n;
     b.pt0 = (int32_t)n_pieces_total;                         // its pieces in ptab[]

@@ -295,7 +295,9 @@ class ShardedIteration:
         # i + 1 is enqueued BEFORE the host has read the flags of iteration i, behind a device word that holds their OR
         # -- its launch returns at once when that word is 0 (sh_row_pieces::gate), so a converged loop costs one empty
         # launch, and the host's enqueue work and wake-up run under the device's work instead of between iterations.
-        run_ahead = in_order and exchanging and dist.get_backend() != "gloo" and os.environ.get("SH_RUN_AHEAD", "1") != "0"
+        # (max_iters <= 0: nothing is enqueued, as in the plain loop below: 0 iterations, not converged, the vector as it came)
+        run_ahead = (in_order and exchanging and dist.get_backend() != "gloo" and os.environ.get("SH_RUN_AHEAD", "1") != "0"
+                     and max_iters > 0)
         if run_ahead:
             sets = [(torch.zeros(world, dtype=torch.int32, device=dev), torch.zeros(world, dtype=torch.int32).pin_memory(),
                      torch.zeros((), dtype=torch.int32, device=dev), torch.cuda.Event()) for _ in range(2)]

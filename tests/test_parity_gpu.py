@@ -998,7 +998,7 @@ def _nccl_world1_worker(rendezvous, sr, chunks, exchange, q, log_dir):
         raise
 
 
-@pytest.mark.parametrize("chunks,exchange", [(1, "collective"), (4, "collective"), (4, "p2p")])
+@pytest.mark.parametrize("chunks,exchange", [(1, "collective"), (1, "p2p"), (4, "collective"), (4, "p2p")])
 def test_nccl_branch_of_the_driver_runs_beside_the_live_launch(chunks, exchange, plan):
     """The branch of ShardedIteration that runs on real hardware -- backend nccl (= RCCL), in-place
     all_gather_into_tensor (or the grouped isend / irecv fan-out) of every finished piece on a side stream WHILE the
@@ -1035,6 +1035,104 @@ def test_nccl_branch_of_the_driver_runs_beside_the_live_launch(chunks, exchange,
     assert layout.startswith("tiled"), layout
     assert (iters, conv) == (w_it, w_conv)
     np.testing.assert_array_equal(bits(final), bits(want))
+
+
+def _nccl_caps_worker(rendezvous, caps, q, log_dir):
+    """One rank under RCCL, one piece: every cap through the run-ahead loop, then -- SH_RUN_AHEAD=0 set before the driver
+    is built again -- through the plain loop.  Reports (run-ahead?, cap, final, iters, converged, gated launches)."""
+    import datetime
+    import sys
+    import traceback
+    sys.stderr = open(os.path.join(log_dir, "rank0.stderr"), "w", buffering=1)
+    try:
+        import torch
+        import torch.distributed as dist
+        torch.cuda.set_device(0)
+        dist.init_process_group("nccl", init_method=f"file://{rendezvous}", rank=0, world_size=1,
+                                timeout=datetime.timedelta(seconds=120), device_id=torch.device("cuda", 0))
+        try:
+            from sparseharness_amd.distributed import HipLocalStep, ShardedIteration, ShardPlan
+            sr = O.MIN_PLUS_F32
+            rp, ci, va = H.rmat(15, seed=5)
+            x0 = O.initial_vector(sr, len(rp) - 1)
+            out = []
+            for ahead in (True, False):
+                if ahead:
+                    os.environ.pop("SH_RUN_AHEAD", None)
+                else:
+                    os.environ["SH_RUN_AHEAD"] = "0"
+                plan = ShardPlan(rp, ci, va.astype(np.float32), 0, 1, 1)
+                step = HipLocalStep(plan, sr, 0)
+                gated = [0]
+                launch = step.launch
+
+                def counted(*args, _launch=launch, _gated=gated, **kw):
+                    _gated[0] += kw.get("gate") is not None
+                    return _launch(*args, **kw)
+                step.launch = counted
+                driver = ShardedIteration(plan, sr, step)
+                for cap in caps:
+                    gated[0] = 0
+                    final, iters, conv = driver.run(x0, x0, 0.0, 0.0, 1e-4, cap)
+                    out.append((ahead, cap, final, iters, conv, gated[0]))
+            q.put((0, out))
+        finally:
+            dist.destroy_process_group()
+    except BaseException:   # noqa: BLE001
+        q.put((0, "error", traceback.format_exc()))
+        raise
+
+
+def test_both_loops_of_the_driver_stop_at_the_iteration_cap(plan):
+    """ShardedIteration's run-ahead loop (iteration i + 1 enqueued behind a gate before the host has read the flags of
+    iteration i) and its plain loop at the cap: max_iters in {0, 1, w_it - 1, w_it, w_it + 1} where the uncapped loop
+    takes w_it iterations -- one below the confirming launch, exactly it, one more than needed -- R-MAT-15 SSSP, one
+    rank under RCCL, one piece, all ten runs in one worker process.  (iters, converged, final) equal O.iterate with
+    that cap, bit for bit.  Cap 0 is the one place where O.iterate cannot serve: it is the reference's do / while and
+    runs its first launch whatever the cap, while every loop of this project launches nothing for max_iters <= 0
+    (sh_iterate_multi, sh_bits_iterate, the driver's plain loop): there both loops must return 0 iterations, not
+    converged, and x0 itself."""
+    if plan != "tiled":
+        pytest.skip("once per run")
+    import tempfile
+
+    import torch.multiprocessing as mp
+    sr = O.MIN_PLUS_F32
+    rp, ci, va = H.rmat(15, seed=5)
+    vals = va.astype(np.float32)
+    x0 = O.initial_vector(sr, len(rp) - 1)
+    _, w_it, w_conv = O.iterate(sr, rp, ci, vals, x0, x0, 0.0, 0.0, 1e-4, 60)
+    assert w_conv and w_it >= 3
+    caps = [0, 1, w_it - 1, w_it, w_it + 1]
+    want = {cap: O.iterate(sr, rp, ci, vals, x0, x0, 0.0, 0.0, 1e-4, cap) for cap in caps if cap > 0}
+    want[0] = (x0, 0, False)
+    assert [(want[c][1], want[c][2]) for c in caps] == [(0, False), (1, False), (w_it - 1, False), (w_it, True), (w_it, True)]
+    tmp = tempfile.mkdtemp(prefix="sh_nccl_caps_")
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_nccl_caps_worker, args=(os.path.join(tmp, "store"), caps, q, tmp))
+    p.start()
+    try:
+        try:
+            item = q.get(timeout=300)
+        except Exception:   # noqa: BLE001
+            pytest.fail("the worker neither finished nor reported an error within 300 s\n" + open(os.path.join(tmp, "rank0.stderr")).read()[-4000:])
+        if isinstance(item[1], str) and item[1] == "error":
+            pytest.fail(item[2] + "\n" + open(os.path.join(tmp, "rank0.stderr")).read()[-4000:])
+        p.join(timeout=60)
+    finally:
+        if p.is_alive():
+            p.kill()
+            p.join(timeout=30)
+    runs = item[1]
+    assert [(a, c) for a, c, *_ in runs] == [(a, c) for a in (True, False) for c in caps]
+    for ahead, cap, final, iters, conv, gated in runs:
+        w_final, w_iters, w_c = want[cap]
+        assert (iters, conv) == (w_iters, w_c), (ahead, cap, iters, conv)
+        np.testing.assert_array_equal(bits(final), bits(w_final), err_msg=f"run-ahead {ahead}, cap {cap}")
+        # the loop asked for is the loop that ran: the run-ahead loop enqueues iteration k + 1 <= cap - 1 behind a gate
+        # while it waits for iteration k <= w_it - 1 (one empty launch past convergence when the cap allows it)
+        assert gated == (min(cap - 1, w_it) if ahead and cap > 0 else 0), (ahead, cap, gated)
 
 
 @pytest.mark.parametrize("name", ["powerlaw_int", "rmat15", "ragged"])
