@@ -182,6 +182,18 @@ extern "C" int sh_debug_emulate_plan(int64_t rows, int64_t cols, int64_t nnz, co
   if (semiring == 3) return emulate<HMaxMin>(H, rows, cols, (const uint32_t *)x, (uint32_t *)y, stats);
   return -2;
 }
+// The CSR arrays of a matrix on the device as the device builders take them, owned by `own`: NULL, or the HIP call that failed.
+static const char *debug_upload_csr(DevArrays &own, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                                    int32_t **d_rp, int32_t **d_ci, uint32_t **d_val) {
+  if (own.alloc_exact(d_rp, (size_t)(rows + 1) * 4) != hipSuccess || own.alloc_exact(d_ci, (size_t)nnz * 4 + 32) != hipSuccess ||
+      own.alloc_exact(d_val, (size_t)nnz * 4 + 32) != hipSuccess)
+    return "hipMalloc";
+  if (hipMemcpy(*d_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(*d_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(*d_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return "hipMemcpy";
+  return nullptr;
+}
 // Builds the tiled layout of one matrix twice -- host builder and device builder -- and compares every array.
 // Returns the number of arrays (or scalars) that differ, 0 = identical byte for byte; -1: the host builder refused the
 // matrix, -2: the device builder refused or failed (report says why), -3: a HIP call of this function failed.
@@ -196,19 +208,12 @@ extern "C" int sh_debug_compare_builds(sh_engine *e, int64_t rows, int64_t cols,
   if (hipSetDevice(e->device) != hipSuccess) { rep = "hipSetDevice"; return finish(-3); }
   TiledHost hh, hg;
   TiledDevArrays td;
-  struct Guard { TiledDevArrays &t; std::vector<void *> p; ~Guard() { t.release(); for (void *q : p) (void)hipFree(q); } } guard{td, {}};
+  struct Guard { TiledDevArrays &t; ~Guard() { t.release(); } } guard{td};
+  DevArrays own;   // the CSR arrays on the device
   if (!build_tiled_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, e->n_cus, hh)) { rep = "host builder refused"; return finish(-1); }
   int32_t *d_rp = nullptr, *d_ci = nullptr;
   uint32_t *d_val = nullptr;
-  if (hipMalloc((void **)&d_rp, (size_t)(rows + 1) * 4) != hipSuccess) { rep = "hipMalloc"; return finish(-3); }
-  guard.p.push_back(d_rp);
-  if (hipMalloc((void **)&d_ci, (size_t)nnz * 4 + 32) != hipSuccess) { rep = "hipMalloc"; return finish(-3); }
-  guard.p.push_back(d_ci);
-  if (hipMalloc((void **)&d_val, (size_t)nnz * 4 + 32) != hipSuccess) { rep = "hipMalloc"; return finish(-3); }
-  guard.p.push_back(d_val);
-  if (hipMemcpy(d_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess) { rep = "hipMemcpy"; return finish(-3); }
+  if (const char *bad = debug_upload_csr(own, rows, nnz, row_ptr, col_idx, val, &d_rp, &d_ci, &d_val)) { rep = bad; return finish(-3); }
   std::string why;
   const int g = build_tiled_plan_gpu(e->stream, rows, cols, nnz, row_ptr, d_rp, d_ci, d_val, opt, e->n_cus, hg, td, why);
   if (g != 1) { rep = "device builder: " + why; return finish(-2); }
@@ -292,18 +297,11 @@ extern "C" int sh_debug_build_verdicts(sh_engine *e, int64_t rows, int64_t cols,
   }
   TiledHost hg;
   TiledDevArrays td;
-  struct Guard { TiledDevArrays &t; std::vector<void *> p; ~Guard() { t.release(); for (void *q : p) (void)hipFree(q); } } guard{td, {}};
+  struct Guard { TiledDevArrays &t; ~Guard() { t.release(); } } guard{td};
+  DevArrays own;   // the CSR arrays on the device
   int32_t *d_rp = nullptr, *d_ci = nullptr;
   uint32_t *d_val = nullptr;
-  if (hipMalloc((void **)&d_rp, (size_t)(rows + 1) * 4) != hipSuccess) { why = "hipMalloc"; return finish(-3); }
-  guard.p.push_back(d_rp);
-  if (hipMalloc((void **)&d_ci, (size_t)nnz * 4 + 32) != hipSuccess) { why = "hipMalloc"; return finish(-3); }
-  guard.p.push_back(d_ci);
-  if (hipMalloc((void **)&d_val, (size_t)nnz * 4 + 32) != hipSuccess) { why = "hipMalloc"; return finish(-3); }
-  guard.p.push_back(d_val);
-  if (hipMemcpy(d_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess) { why = "hipMemcpy"; return finish(-3); }
+  if (const char *bad = debug_upload_csr(own, rows, nnz, row_ptr, col_idx, val, &d_rp, &d_ci, &d_val)) { why = bad; return finish(-3); }
   *device_verdict = build_tiled_plan_gpu(e->stream, rows, cols, nnz, row_ptr, d_rp, d_ci, d_val, opt, e->n_cus, hg, td, why);
   if (hipStreamSynchronize(e->stream) != hipSuccess) { why = "hipStreamSynchronize"; return finish(-3); }
   return finish(0);
@@ -320,21 +318,13 @@ extern "C" int sh_debug_compare_bits_builds(sh_engine *e, int64_t rows, int64_t 
   sh_plan_options_default(&opt);
   BitsHost hh, hg;
   if (!build_bits_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, hh)) { rep = "host builder refused"; return finish(-1); }
-  struct Guard { std::vector<void *> p; ~Guard() { for (void *q : p) (void)hipFree(q); } } guard;
+  DevArrays own;   // the CSR arrays and the entry array on the device
   int32_t *d_rp = nullptr, *d_ci = nullptr;
   uint32_t *d_val = nullptr, *d_ent = nullptr;
-  if (hipMalloc((void **)&d_rp, (size_t)(rows + 1) * 4) != hipSuccess) { rep = "hipMalloc"; return finish(-3); }
-  guard.p.push_back(d_rp);
-  if (hipMalloc((void **)&d_ci, (size_t)nnz * 4 + 32) != hipSuccess) { rep = "hipMalloc"; return finish(-3); }
-  guard.p.push_back(d_ci);
-  if (hipMalloc((void **)&d_val, (size_t)nnz * 4 + 32) != hipSuccess) { rep = "hipMalloc"; return finish(-3); }
-  guard.p.push_back(d_val);
-  if (hipMemcpy(d_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice) != hipSuccess) { rep = "hipMemcpy"; return finish(-3); }
+  if (const char *bad = debug_upload_csr(own, rows, nnz, row_ptr, col_idx, val, &d_rp, &d_ci, &d_val)) { rep = bad; return finish(-3); }
   std::string why;
   if (build_bits_plan_gpu(e->stream, rows, cols, nnz, d_rp, d_ci, d_val, hg, &d_ent, why) != 1) { rep = "device builder: " + why; return finish(-2); }
-  guard.p.push_back(d_ent);
+  own.adopt(d_ent, (size_t)hg.ent_len * 4 + SLACK_WIDE);
   int diffs = 0;
   char line[256];
   auto same = [&](const char *name, const void *a, size_t na, const void *b, size_t nb) {
@@ -363,34 +353,34 @@ extern "C" int sh_debug_compare_bits_builds(sh_engine *e, int64_t rows, int64_t 
 extern "C" int sh_debug_move_array(sh_engine *e, sh_csr *m, int which, int hold, int align_log2, uint64_t *address) {
   if (!e || !m || m->plan != PLAN_TILED) return SH_EINVAL;
   if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return SH_EHIP;
+  TiledLayout &t = m->tiled;
   void **slot = nullptr;
-  size_t bytes = 0;
-  const bool coded = m->n_vdict != 0;
   switch (which) {
-    case 0: slot = (void **)&m->d_P; bytes = (size_t)std::max<int64_t>(m->p_len, 4) * 4 + 16; break;
-    case 1: slot = (void **)&m->d_tcol; bytes = (size_t)m->stream_len * 2 + 16; break;
-    case 2: if (coded) { slot = (void **)&m->d_tcode; bytes = tcode_bytes(m->code_bits, m->stream_len) + 64; }
-            else { slot = (void **)&m->d_tval; bytes = (size_t)m->stream_len * 4 + 16; }
-            break;
-    case 3: slot = (void **)&m->d_pslot; bytes = (size_t)m->p_len * 2 + 16; break;
+    case 0: slot = (void **)&t.d_P; break;
+    case 1: slot = (void **)&t.d_tcol; break;
+    case 2: slot = t.n_vdict ? (void **)&t.d_tcode : (void **)&t.d_tval; break;
+    case 3: slot = (void **)&t.d_pslot; break;
     default: return SH_EINVAL;
   }
+  const size_t bytes = t.dev.size_of(*slot);   // (as allocated at upload, slack included)
   void *fresh = nullptr;
   const size_t align = align_log2 > 21 ? (size_t)1 << align_log2 : 0;
   if (hipMalloc(&fresh, bytes + align) != hipSuccess) return SH_ENOMEM;
   if (align) fresh = (void *)(((uintptr_t)fresh + align - 1) & ~(uintptr_t)(align - 1));
   if (hipMemcpy(fresh, *slot, bytes, hipMemcpyDeviceToDevice) != hipSuccess) return SH_EHIP;
+  t.dev.replace(*slot, fresh);
   if (!hold) (void)hipFree(*slot);
   *slot = fresh;
   if (address) *address = (uint64_t)(uintptr_t)fresh;
   return SH_OK;
 }
-// (placement experiments) point the matrix at another product array allocated by sh_debug_move_array(which = 0, hold = 1)
+// (placement experiments) point the matrix at another product array allocated by sh_debug_move_array(which = 0, hold = 1);
+// its own stays with its layout, the other one with the matrix that moved to it
 extern "C" int sh_debug_set_P(sh_engine *e, sh_csr *m, uint64_t address) {
   if (!e || !m || m->plan != PLAN_TILED || !address) return SH_EINVAL;
   if (hipStreamSynchronize(e->stream) != hipSuccess) return SH_EHIP;
-  m->d_P = (uint32_t *)(uintptr_t)address;
+  m->tiled.d_P = (uint32_t *)(uintptr_t)address;
   return SH_OK;
 }
 // (slab experiments, tools/slab_probe.py) words of the matrix's product array, for a host-side bounds check before matrices share one
-extern "C" int64_t sh_debug_p_len(const sh_csr *m) { return m && m->plan == PLAN_TILED ? m->p_len : -1; }
+extern "C" int64_t sh_debug_p_len(const sh_csr *m) { return m && m->plan == PLAN_TILED ? m->tiled.p_len : -1; }

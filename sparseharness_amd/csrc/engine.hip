@@ -20,6 +20,7 @@
 #include "truss.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
+#include "dev_arrays.h"
 
 #include <hip/hip_runtime.h>
 
@@ -54,22 +55,21 @@ struct sh_engine {
   std::string err;
 };
 
-struct sh_csr {
-  int64_t rows = 0, cols = 0, nnz = 0;
+// A matrix handle is up to three device layouts and the state of its piece reports.  Each part owns its arrays
+// (dev_arrays.h): dropping a layout is assigning an empty one, and freeing the handle is deleting it.
+struct StreamLayout {   // the CSR-stream plan (plan A); its first three arrays are also the device builders' input
+  DevArrays dev;
   int32_t *d_row_ptr = nullptr, *d_col = nullptr;
   uint32_t *d_val = nullptr;
   int32_t *d_blk_row = nullptr;
-  int32_t n_stream = 0;
   LongSeg *d_segs = nullptr;
-  int32_t n_segs = 0;
   LongRow *d_long = nullptr;
-  int32_t n_long = 0;
   uint32_t *d_partial = nullptr;
   uint32_t *d_partial_multi = nullptr;   // sh_spmm: SPMM_MAX_WIDTH partials per long-row segment
-  // x-tiled two-phase plan (kernels.hip.h); built when plan == PLAN_TILED
-  int plan = 0;
-  bool tuned = false;           // plan confirmed by timing both at upload (autotune_plan)
-  float tuned_ms[2] = {0, 0};   // [stream, tiled]
+  int32_t n_stream = 0, n_segs = 0, n_long = 0;
+};
+struct TiledLayout {   // the x-tiled two-phase plan (kernels.hip.h); built when plan == PLAN_TILED
+  DevArrays dev;
   RowBin *d_bins = nullptr;
   int32_t n_bins = 0;
   TileChunk *d_chunks = nullptr;
@@ -93,28 +93,46 @@ struct sh_csr {
   int64_t light_len = 0, light_entries = 0;   // light part of the stream (padding included) / light entries of the matrix
   int64_t stream_len = 0, p_len = 0;          // stream entries in all / products in P
   int fold = 0;                               // phase 1 folds a row's entries inside a tile into one product
-  size_t stream_bytes = 0, tiled_bytes = 0;   // device memory held by the arrays of plan A / plan B
+  bool skip_minplus = false;                  // every |value| < 2^103: FLT_MAX + |a| == FLT_MAX, so tiles of unreached x words may be skipped
   std::vector<int32_t> bin_r0;                // first row of every row bin (host copy: piece reporting)
-  // the (or,and) semiring on bits (bits.hip.h); built when sh_plan_options::or_and_bits asks for it
+};
+struct BitsLayout {   // the (or,and) semiring on bits (bits.hip.h); built when sh_plan_options::or_and_bits asks for it
+  DevArrays dev;
   BitsItem *d_bits_items = nullptr;
   uint32_t *d_bits_ent = nullptr, *d_bits_partial = nullptr;
   int32_t *d_bits_sub = nullptr, *d_bits_rr0 = nullptr;
   uint64_t *d_xbits = nullptr;
   int32_t n_bits_items = 0, bits_ct = 0;
   int64_t bits_entries = 0;
-  size_t bits_bytes = 0;
-  bool bits_only = false;                     // no other plan was built: only SH_OR_AND_I32 launches are served
-  uint32_t *d_done = nullptr, *h_done = nullptr;   // piece reporting (sh_spmv_step_pieces): arrival counters / host-visible round words
+};
+struct PieceReport {   // piece reporting (sh_spmv_step_pieces); made whole by the first such launch (open_piece_report)
+  DevArrays dev;                              // (not part of the footprint)
+  uint32_t *d_done = nullptr, *h_done = nullptr;   // arrival counters / host-visible round words (pinned)
   PieceDev *d_pcs = nullptr;                  // the pieces' geometry as the kernels read it (device copy of pcs_host)
   PieceDev pcs_host{};                        // what d_pcs holds (rewritten only when a call brings another geometry)
   bool pcs_valid = false;
   uint32_t round = 0;                         // reporting launches so far
   uint32_t last_expected = 0;                 // arrivals per piece the latest reporting launch waits for (sh_csr_piece_state)
+  ~PieceReport() {
+    if (h_done) (void)hipHostFree(h_done);
+  }
+};
+
+struct sh_csr {
+  int64_t rows = 0, cols = 0, nnz = 0;
+  int plan = 0;
+  bool tuned = false;           // plan confirmed by timing both at upload (autotune_plan)
+  float tuned_ms[2] = {0, 0};   // [stream, tiled]
+  StreamLayout stream;
+  TiledLayout tiled;
+  BitsLayout bits;
+  std::unique_ptr<PieceReport> pieces;
+  bool bits_only = false;                     // no other plan was built: only SH_OR_AND_I32 launches are served
   bool built_on_device = false;               // the tiled layout was built by plan_gpu.hip
   int placement_tries = 1;                    // placements of the big arrays timed at upload (tune_placement)
   float placement_ms[2] = {0, 0};             // [first placement, the one kept]
-  bool skip_minplus = false;                  // every |value| < 2^103: FLT_MAX + |a| == FLT_MAX, so tiles of unreached x words may be skipped
   std::string build_note;                     // why the device builder was not used / fell back (empty: nothing to say)
+  size_t device_bytes() const { return stream.dev.bytes + tiled.dev.bytes + bits.dev.bytes; }
 };
 enum { PLAN_STREAM = 0, PLAN_TILED = 1 };
 constexpr int SPMM_MAX_WIDTH = 32;   // widest sh_spmm
@@ -148,6 +166,42 @@ static int fail(sh_engine *e, int code, const char *fmt, ...) {
                   "%s failed: %s (%s:%d)", #call, hipGetErrorString(_r),        \
                   __FILE__, __LINE__);                                          \
   } while (0)
+
+// What every sh_*_free is: the stream drains (copies from host arrays may be in flight), then the handle goes with all it owns.
+template <class H>
+static int free_handle(sh_engine *e, H *h) {
+  if (!h)
+    return SH_OK;
+  if (e) {
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->stream);
+  }
+  delete h;
+  return SH_OK;
+}
+
+#define RC_TRY(call) do { if (const int _rc = (call)) return _rc; } while (0)   // for the functions that set the message themselves
+
+// Device array of `bytes` (+ slack for the kernels' wide loads) owned by `own` and counted in its footprint, filled from
+// `host` when given.  Enqueued only: `host` lives until the stream has been synchronised.
+template <class T>
+static int dev_array(sh_engine *e, DevArrays &own, T **p, const void *host, size_t bytes, size_t slack) {
+  HIP_TRY(e, own.alloc_exact(p, bytes + slack));
+  if (host && bytes > 0)
+    HIP_TRY(e, hipMemcpyAsync(*p, host, bytes, hipMemcpyHostToDevice, e->stream));
+  return SH_OK;
+}
+
+// One big array of the tiled layout: handed over by the device builder (`dev`, n_dev elements and the slack behind
+// them) or uploaded from the host builder's vector.
+template <class T, class D>
+static int plan_array(sh_engine *e, sh_csr *m, T **p, D *&dev, size_t n_dev, const std::vector<T> &host, size_t slack) {
+  if (!m->built_on_device) return dev_array(e, m->tiled.dev, p, host.data(), host.size() * sizeof(T), slack);
+  *p = (T *)dev;
+  m->tiled.dev.adopt(dev, n_dev * sizeof(T) + slack);
+  dev = nullptr;
+  return SH_OK;
+}
 
 extern "C" {
 
@@ -258,6 +312,34 @@ int sh_engine_synchronize(sh_engine *e) {
 static int dispatch(sh_engine *e, sh_semiring sr, const sh_csr *A, const sh_vec *x, const sh_vec *y,
                     const void *alpha, const void *beta, sh_vec *out, StepDev st);
 
+// The zeroed x and the out vector that the timings at upload launch on (autotune_plan, tune_placement); released
+// with the object.
+struct TrialVectors {
+  DevArrays dev;
+  sh_vec x, out;
+  bool open(sh_engine *e, const sh_csr *m) {
+    const size_t xbytes = (size_t)std::max<int64_t>(m->cols, 1) * 4;
+    if (dev.alloc_exact(&x.d, xbytes) != hipSuccess || dev.alloc_exact(&out.d, (size_t)std::max<int64_t>(m->rows, 1) * 4) != hipSuccess)
+      return false;
+    x.n = m->cols; out.n = m->rows;
+    (void)hipMemsetAsync(x.d, 0, xbytes, e->stream);
+    return true;
+  }
+  // ms per (+,x) launch on the matrix's current plan and placement: `warm` launches, then `reps` back to back as one
+  // interval; < 0: a call failed
+  float time_launches(sh_engine *e, const sh_csr *m, int warm, int reps) {
+    const float one = 1.0f, zero = 0.0f;
+    float ms = 0;
+    bool ok = true;
+    for (int rep = -warm; rep < reps && ok; rep++)
+      ok = (rep != 0 || hipEventRecord(e->ev0, e->stream) == hipSuccess) &&
+           dispatch(e, SH_PLUS_TIMES_F32, m, &x, nullptr, &one, &zero, &out, StepDev{nullptr, nullptr, 0, 0.0}) == SH_OK;
+    ok = ok && hipEventRecord(e->ev1, e->stream) == hipSuccess && hipEventSynchronize(e->ev1) == hipSuccess &&
+         hipEventElapsedTime(&ms, e->ev0, e->ev1) == hipSuccess;
+    return ok ? ms / reps : -1.f;
+  }
+};
+
 // The size rule picks the tiled plan for every large matrix, but a large matrix whose columns are
 // local (banded, FEM-like) keeps its x window in L2 and streams 8 B/entry under plan A, which the
 // tiled plan cannot match.  So when the rule says "tiled" and nobody forced a plan, both are
@@ -265,46 +347,23 @@ static int dispatch(sh_engine *e, sh_semiring sr, const sh_csr *A, const sh_vec 
 // and plan A is kept only if it is clearly faster -- 10 % -- so that near-ties, where the two
 // plans' float rounding of heavy rows could differ, always resolve the same way.
 static void autotune_plan(sh_engine *e, sh_csr *m) {
-  sh_vec xv, ov;
-  if (hipMalloc(&xv.d, (size_t)std::max<int64_t>(m->cols, 1) * 4) != hipSuccess) return;
-  if (hipMalloc(&ov.d, (size_t)std::max<int64_t>(m->rows, 1) * 4) != hipSuccess) { (void)hipFree(xv.d); return; }
-  xv.n = m->cols; ov.n = m->rows;
-  (void)hipMemsetAsync(xv.d, 0, (size_t)std::max<int64_t>(m->cols, 1) * 4, e->stream);
-  const float one = 1.0f, zero = 0.0f;
+  TrialVectors v;
+  if (!v.open(e, m)) return;
   float ms[2] = {0, 0};
   bool ok = true;
   for (int plan : {PLAN_TILED, PLAN_STREAM}) {
     m->plan = plan;
     for (int rep = 0; rep < 3 && ok; rep++) {   // one warm-up, then the faster of two
-      ok = hipEventRecord(e->ev0, e->stream) == hipSuccess &&
-           dispatch(e, SH_PLUS_TIMES_F32, m, &xv, nullptr, &one, &zero, &ov, StepDev{nullptr, nullptr, 0, 0.0}) == SH_OK &&
-           hipEventRecord(e->ev1, e->stream) == hipSuccess && hipEventSynchronize(e->ev1) == hipSuccess;
-      float t = 0;
-      if (ok) ok = hipEventElapsedTime(&t, e->ev0, e->ev1) == hipSuccess;
+      const float t = v.time_launches(e, m, 0, 1);
+      ok = t >= 0;
       if (ok && rep > 0) ms[plan] = (rep == 1) ? t : std::min(ms[plan], t);
     }
   }
   (void)hipStreamSynchronize(e->stream);
-  (void)hipFree(xv.d);
-  (void)hipFree(ov.d);
   m->plan = (ok && ms[PLAN_STREAM] < 0.9f * ms[PLAN_TILED]) ? PLAN_STREAM : PLAN_TILED;
   // the layout of the plan that lost is of no further use
-  if (m->plan == PLAN_STREAM) {
-    m->tiled_bytes = 0;
-    for (void **p : {(void **)&m->d_bins, (void **)&m->d_chunks, (void **)&m->d_tval, (void **)&m->d_tcol, (void **)&m->d_gdest,
-                     (void **)&m->d_pslot, (void **)&m->d_gblk, (void **)&m->d_ptab, (void **)&m->d_P, (void **)&m->d_tlong, (void **)&m->d_tpartial,
-                     (void **)&m->d_ptile, (void **)&m->d_ptab_live, (void **)&m->d_tile_live, (void **)&m->d_lrp, (void **)&m->d_tcode, (void **)&m->d_vdict, (void **)&m->d_obase}) {
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-    }
-  } else {
-    m->stream_bytes = 0;
-    for (void **p : {(void **)&m->d_row_ptr, (void **)&m->d_col, (void **)&m->d_val, (void **)&m->d_blk_row, (void **)&m->d_segs,
-                     (void **)&m->d_long, (void **)&m->d_partial, (void **)&m->d_partial_multi}) {
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-    }
-  }
+  if (m->plan == PLAN_STREAM) m->tiled = TiledLayout();
+  else m->stream = StreamLayout();
   m->tuned = ok;
   m->tuned_ms[0] = ms[PLAN_STREAM];
   m->tuned_ms[1] = ms[PLAN_TILED];
@@ -317,51 +376,32 @@ static void autotune_plan(sh_engine *e, sh_csr *m) {
 // and keeps the fastest; the others are freed.  All candidates stay allocated until the choice is made, or the allocator
 // would hand the same place out again.  Costs about 5 ms and one copy of the arrays per try, at upload only.
 static void tune_placement(sh_engine *e, sh_csr *m, int tries) {
-  if (tries <= 1 || m->plan != PLAN_TILED || m->n_bins <= 0 || m->n_chunks <= 0) return;
-  sh_vec xv, ov;
-  if (hipMalloc(&xv.d, (size_t)std::max<int64_t>(m->cols, 1) * 4) != hipSuccess) return;
-  if (hipMalloc(&ov.d, (size_t)std::max<int64_t>(m->rows, 1) * 4) != hipSuccess) { (void)hipFree(xv.d); return; }
-  xv.n = m->cols; ov.n = m->rows;
-  (void)hipMemsetAsync(xv.d, 0, (size_t)std::max<int64_t>(m->cols, 1) * 4, e->stream);
-  const bool coded = m->n_vdict != 0;
-  struct Slot { void **field; size_t bytes; bool copy; };
-  const Slot slots[4] = {
-      {(void **)&m->d_P, (size_t)std::max<int64_t>(m->p_len, 4) * 4 + 16, false},   // (rewritten by every launch)
-      {(void **)&m->d_tcol, (size_t)m->stream_len * 2 + SLACK_WIDE, true},
-      {coded ? (void **)&m->d_tcode : (void **)&m->d_tval,
-       coded ? tcode_bytes(m->code_bits, m->stream_len) + SLACK_TCODE : (size_t)m->stream_len * 4 + SLACK_WIDE, true},
-      {(void **)&m->d_pslot, (size_t)m->p_len * 2 + SLACK_WIDE, true}};
-  const float one = 1.0f, zero = 0.0f;
-  auto time_it = [&]() -> float {   // one warm-up, then four launch pairs back to back as one interval (the steady state of a loop)
-    constexpr int REPS = 4;
-    float t = 0;
-    const StepDev none{nullptr, nullptr, 0, 0.0};
-    if (dispatch(e, SH_PLUS_TIMES_F32, m, &xv, nullptr, &one, &zero, &ov, none) != SH_OK ||
-        hipEventRecord(e->ev0, e->stream) != hipSuccess)
-      return -1.f;
-    for (int rep = 0; rep < REPS; rep++)
-      if (dispatch(e, SH_PLUS_TIMES_F32, m, &xv, nullptr, &one, &zero, &ov, none) != SH_OK) return -1.f;
-    if (hipEventRecord(e->ev1, e->stream) != hipSuccess || hipEventSynchronize(e->ev1) != hipSuccess ||
-        hipEventElapsedTime(&t, e->ev0, e->ev1) != hipSuccess)
-      return -1.f;
-    return t / REPS;
-  };
+  TiledLayout &t = m->tiled;
+  if (tries <= 1 || m->plan != PLAN_TILED || t.n_bins <= 0 || t.n_chunks <= 0) return;
+  TrialVectors v;
+  if (!v.open(e, m)) return;
+  struct Slot { void **field; bool copy; };
+  const Slot slots[4] = {{(void **)&t.d_P, false},   // (rewritten by every launch)
+                         {(void **)&t.d_tcol, true},
+                         {t.n_vdict ? (void **)&t.d_tcode : (void **)&t.d_tval, true},
+                         {(void **)&t.d_pslot, true}};
+  auto time_it = [&]() { return v.time_launches(e, m, 1, 4); };   // (four launch pairs back to back: the steady state of a loop)
   struct Set { void *p[4]; float ms; };
   std::vector<Set> sets;
   Set cur{{*slots[0].field, *slots[1].field, *slots[2].field, *slots[3].field}, time_it()};
   sets.push_back(cur);
   size_t best = 0;
-  size_t set_bytes = 0;
-  for (const Slot &sl : slots) set_bytes += sl.bytes;
-  for (int t = 1; t < tries && sets[0].ms > 0; t++) {
+  size_t bytes[4], set_bytes = 0;   // (as allocated at upload: the owner remembers)
+  for (int i = 0; i < 4; i++) set_bytes += bytes[i] = t.dev.size_of(cur.p[i]);
+  for (int k = 1; k < tries && sets[0].ms > 0; k++) {
     size_t fr = 0, tot = 0;   // (the candidates are all held until the end: never take more than half of what is free)
     if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < 2 * set_bytes + ((size_t)1 << 30)) break;
     Set fresh{{nullptr, nullptr, nullptr, nullptr}, -1.f};
     bool ok = true;
     for (int i = 0; i < 4 && ok; i++) {
-      ok = hipMalloc(&fresh.p[i], slots[i].bytes) == hipSuccess;
+      ok = hipMalloc(&fresh.p[i], bytes[i]) == hipSuccess;
       if (ok && slots[i].copy)
-        ok = hipMemcpyAsync(fresh.p[i], sets[0].p[i], slots[i].bytes, hipMemcpyDeviceToDevice, e->stream) == hipSuccess;
+        ok = hipMemcpyAsync(fresh.p[i], sets[0].p[i], bytes[i], hipMemcpyDeviceToDevice, e->stream) == hipSuccess;
     }
     if (!ok) {
       (void)hipStreamSynchronize(e->stream);
@@ -380,14 +420,15 @@ static void tune_placement(sh_engine *e, sh_csr *m, int tries) {
       fprintf(stderr, "[placement] %2zu  P %p  tcol %p  tcode %p  pslot %p  %.4f ms%s\n", k, sets[k].p[0], sets[k].p[1], sets[k].p[2], sets[k].p[3],
               sets[k].ms, k == best ? "  <- kept" : "");
 #endif
-  for (int i = 0; i < 4; i++) *slots[i].field = sets[best].p[i];
+  for (int i = 0; i < 4; i++) {   // the layout owns the set kept; every other one goes
+    t.dev.replace(sets[0].p[i], sets[best].p[i]);
+    *slots[i].field = sets[best].p[i];
+  }
   for (size_t k = 0; k < sets.size(); k++)
     if (k != best)
       for (void *q : sets[k].p) (void)hipFree(q);
   m->placement_tries = (int)sets.size();
   m->placement_ms[0] = sets[0].ms; m->placement_ms[1] = sets[best].ms;
-  (void)hipFree(xv.d);
-  (void)hipFree(ov.d);
 }
 
 static int choose_plan(const sh_plan_options &opt, int64_t cols, int64_t nnz) {
@@ -462,6 +503,182 @@ int sh_csr_upload(sh_engine *e, int64_t rows, int64_t cols, int64_t nnz, const i
   return sh_csr_upload_ex(e, rows, cols, nnz, row_ptr, col_idx, val, &opt, out);
 }
 
+// The host arrays of an upload, as the caller gave them.
+struct HostCsr {
+  int64_t rows, cols, nnz;
+  const int32_t *row_ptr, *col_idx;
+  const uint32_t *val;
+};
+
+// row_ptr / col_idx / val as they are: plan A's arrays, and the device builders' input (nothing to do when they are there)
+static int upload_csr_arrays(sh_engine *e, sh_csr *m, const HostCsr &h) {
+  StreamLayout &s = m->stream;
+  if (s.d_row_ptr) return SH_OK;
+  const int64_t padded = ((h.nnz + 3) & ~int64_t(3)) + 4;   // the tail is padded so that 16-byte loads at the end stay in bounds
+  RC_TRY(dev_array(e, s.dev, &s.d_row_ptr, h.row_ptr, (h.rows + 1) * 4, 0));
+  RC_TRY(dev_array(e, s.dev, &s.d_col, nullptr, padded * 4, 0));
+  RC_TRY(dev_array(e, s.dev, &s.d_val, nullptr, padded * 4, 0));
+  HIP_TRY(e, hipMemsetAsync(s.d_col + (padded - 8 > 0 ? padded - 8 : 0), 0xFF, (padded >= 8 ? 8 : padded) * 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(s.d_val + (padded - 8 > 0 ? padded - 8 : 0), 0, (padded >= 8 ? 8 : padded) * 4, e->stream));
+  if (h.nnz > 0) {
+    HIP_TRY(e, hipMemcpyAsync(s.d_col, h.col_idx, h.nnz * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(s.d_val, h.val, h.nnz * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  return SH_OK;
+}
+
+static void drop_stream_layout(sh_engine *e, sh_csr *m) {
+  if (!m->stream.d_row_ptr) return;
+  (void)hipStreamSynchronize(e->stream);
+  m->stream = StreamLayout();
+}
+
+// The bit-blocked layout of the (or,and) semiring: built on the device from the CSR arrays (`device_build`) or, also when
+// a device step fails, on the host.  Leaves m->bits empty when the layout does not apply to the matrix.
+static int build_bits_layout(sh_engine *e, sh_csr *m, const HostCsr &h, const sh_plan_options &opt, bool device_build) {
+  BitsHost bh;
+  int built = -1;   // 1 built, 0 the layout does not apply, -1 not tried / a device step failed: the host builder
+  uint32_t *dev_ent = nullptr;
+  if (device_build) {
+    RC_TRY(upload_csr_arrays(e, m, h));
+    std::string why;
+    built = build_bits_plan_gpu(e->stream, h.rows, h.cols, h.nnz, m->stream.d_row_ptr, m->stream.d_col, m->stream.d_val, bh, &dev_ent, why);
+    if (built != 1) { m->build_note = why; bh = BitsHost(); }
+  }
+  if (built < 0) built = build_bits_plan(h.rows, h.cols, h.nnz, h.row_ptr, h.col_idx, h.val, opt, bh) ? 1 : 0;
+  if (built != 1) return SH_OK;
+  BitsLayout &b = m->bits;
+  b.n_bits_items = (int32_t)bh.items.size();
+  b.bits_ct = bh.n_ct;
+  b.bits_entries = bh.entries;
+  m->bits_only = opt.or_and_bits >= 2;
+  if (dev_ent) { b.d_bits_ent = dev_ent; b.dev.adopt(dev_ent, (size_t)bh.ent_len * 4 + SLACK_WIDE); m->built_on_device = true; }
+  else RC_TRY(dev_array(e, b.dev, &b.d_bits_ent, bh.ent.data(), bh.ent.size() * 4, SLACK_WIDE));
+  RC_TRY(dev_array(e, b.dev, &b.d_bits_items, bh.items.data(), bh.items.size() * sizeof(BitsItem), 32));
+  RC_TRY(dev_array(e, b.dev, &b.d_bits_sub, bh.bsub.data(), bh.bsub.size() * 4, 16));
+  RC_TRY(dev_array(e, b.dev, &b.d_bits_rr0, bh.rr_item0.data(), bh.rr_item0.size() * 4, 0));
+  RC_TRY(dev_array(e, b.dev, &b.d_xbits, nullptr, (size_t)bh.n_ct * (BITS_BC / 8), 0));
+  RC_TRY(dev_array(e, b.dev, &b.d_bits_partial, nullptr, (size_t)std::max<size_t>(bh.items.size(), 1) * (BITS_BR / 8), 0));
+  HIP_TRY(e, hipStreamSynchronize(e->stream)); // host vectors die at return
+  return SH_OK;
+}
+
+// Where the tiled layout is built (sh_plan_options::build): on the device from the CSR arrays (plan_gpu.hip; the
+// default), or by the host builder -- also the fallback when a device step fails.  Same bytes either way.
+// *tiled: the layout is in th (and, built on the device, its big arrays in td).
+static int build_tiled_layout(sh_engine *e, sh_csr *m, const HostCsr &h, const sh_plan_options &opt, bool device_build,
+                              TiledHost &th, TiledDevArrays &td, bool *tiled) {
+  bool want_tiled = choose_plan(opt, h.cols, h.nnz) == PLAN_TILED && h.nnz > 0;
+  *tiled = false;
+  if (want_tiled && device_build) {
+    RC_TRY(upload_csr_arrays(e, m, h));
+    lap("H2D of the CSR arrays");
+    std::string why;
+    const int g = build_tiled_plan_gpu(e->stream, h.rows, h.cols, h.nnz, h.row_ptr, m->stream.d_row_ptr, m->stream.d_col, m->stream.d_val, opt,
+                                       e->n_cus, th, td, why);
+    lap("device build");
+    if (g == 1) {
+      *tiled = true;
+      m->built_on_device = true;
+    } else {
+      td.release();
+      th = TiledHost();
+      m->build_note = why;
+      if (g == 0) want_tiled = false;   // the layout does not suit this matrix: the host builder would refuse as well
+    }
+  }
+#ifdef SH_PLAN_EMULATE
+  if (want_tiled && !*tiled) {   // (tools builds: sh_debug_held_at_host_build)
+    g_debug_held_at_host_build = 0;
+    for (const void *p : {(const void *)td.tcol, (const void *)td.pslot, (const void *)td.tcode, (const void *)td.tval, (const void *)td.gdest,
+                          (const void *)td.gblk, (const void *)td.obase, (const void *)td.lrp, (const void *)td.ptab, (const void *)td.ptile})
+      if (p) g_debug_held_at_host_build++;
+  }
+#endif
+  if (want_tiled && !*tiled)
+    *tiled = build_tiled_plan(h.rows, h.cols, h.nnz, h.row_ptr, h.col_idx, h.val, opt, e->n_cus, th);
+  return SH_OK;
+}
+
+// The tiled layout on the device: the small tables from th, the big arrays from td or th (plan_array).
+static int upload_tiled_layout(sh_engine *e, sh_csr *m, const sh_plan_options &opt, const TiledHost &th, TiledDevArrays &td) {
+  TiledLayout &t = m->tiled;
+  t.n_bins = (int32_t)th.bins.size();
+  t.n_chunks = (int32_t)th.chunks.size();
+  t.n_tlong = (int32_t)th.heavy.size();
+  t.light_len = th.light_len;
+  t.stream_len = th.stream_len;
+  t.p_len = th.p_len;
+  t.light_entries = th.light_entries;
+  t.fold = opt.fold != 0 && TCOL_FOLD != 0;
+  t.bin_r0.reserve(th.bins.size());
+  for (const RowBin &b : th.bins) t.bin_r0.push_back(b.r0);
+  RC_TRY(dev_array(e, t.dev, &t.d_bins, th.bins.data(), th.bins.size() * sizeof(RowBin), 0));
+  RC_TRY(dev_array(e, t.dev, &t.d_chunks, th.chunks.data(), th.chunks.size() * sizeof(TileChunk), 0));
+  if (!th.vdict.empty()) {
+    t.n_vdict = (int)th.vdict.size();
+    t.n_vdict_used = th.vdict_used;
+    t.code_bits = th.code_bits;
+    t.skip_minplus = true;   // (known from the dictionary alone; raw values would need a pass over the matrix: not skipped)
+    for (int k = 0; k < th.vdict_used; k++) t.skip_minplus = t.skip_minplus && (th.vdict[(size_t)k] & 0x7FFFFFFFu) < 0x73000000u;   // |a| < 2^103
+    RC_TRY(plan_array(e, m, &t.d_tcode, td.tcode, td.n_tcode, th.tcode, SLACK_TCODE));
+    RC_TRY(dev_array(e, t.dev, &t.d_vdict, th.vdict.data(), th.vdict.size() * 4, 0));
+  } else {
+    RC_TRY(plan_array(e, m, &t.d_tval, td.tval, td.n_tval, th.tval, SLACK_WIDE));
+  }
+  RC_TRY(plan_array(e, m, &t.d_tcol, td.tcol, td.n_tcol, th.tcol, SLACK_WIDE));
+  RC_TRY(plan_array(e, m, &t.d_gdest, td.gdest, td.n_gdest, th.gdest, SLACK_WIDE));
+  RC_TRY(plan_array(e, m, &t.d_gblk, td.gblk, td.n_gblk, th.gblk, SLACK_WIDE));
+  RC_TRY(plan_array(e, m, &t.d_ptab, td.ptab, td.n_ptab, th.ptab, SLACK_WIDE));
+  RC_TRY(plan_array(e, m, &t.d_ptile, td.ptile, td.n_ptab, th.ptile, SLACK_WIDE));
+  t.n_pieces = (int64_t)(m->built_on_device ? td.n_ptab : th.ptab.size());
+  // dead pieces (launches of a semiring with absorbing words): the marked copy of ptab, the tiles' live words (all live until a launch says otherwise)
+  RC_TRY(dev_array(e, t.dev, &t.d_ptab_live, nullptr, (size_t)t.n_pieces * 4, SLACK_WIDE));
+  const size_t ct = (size_t)std::max<int64_t>(1, (m->cols + TCOLS - 1) / TCOLS);
+  RC_TRY(dev_array(e, t.dev, &t.d_tile_live, nullptr, ct * 4, 0));
+  HIP_TRY(e, hipMemsetD32Async((hipDeviceptr_t)t.d_tile_live, 1, ct, e->stream));
+  RC_TRY(plan_array(e, m, &t.d_pslot, td.pslot, td.n_pslot, th.pslot, SLACK_WIDE));
+  RC_TRY(plan_array(e, m, &t.d_obase, td.obase, td.n_obase, th.obase, SLACK_WIDE));
+  RC_TRY(dev_array(e, t.dev, &t.d_P, nullptr, (size_t)std::max<int64_t>(t.p_len, 4) * 4, 16));
+  RC_TRY(plan_array(e, m, (uint32_t **)&t.d_lrp, td.lrp, td.n_lrp, th.lrp, 16));   // (+16: see plan_gpu.hip)
+  if (t.n_tlong) {
+    RC_TRY(dev_array(e, t.dev, &t.d_tlong, th.heavy.data(), th.heavy.size() * sizeof(LongRow), 0));
+    RC_TRY(dev_array(e, t.dev, &t.d_tpartial, nullptr, (size_t)th.n_partials * 4, 16));
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream)); // host vectors die with the caller's th
+  lap("hipMalloc + H2D of the plan");
+  return SH_OK;
+}
+
+// The CSR-stream layout: the CSR arrays (uploaded unless a device builder had them already) and the block schedule.
+static int upload_stream_layout(sh_engine *e, sh_csr *m, const HostCsr &h) {
+  StreamLayout &s = m->stream;
+  std::vector<int32_t> pairs;
+  std::vector<LongSeg> segs;
+  std::vector<LongRow> longs;
+  build_schedule(h.rows, h.row_ptr, pairs, segs, longs);
+  s.n_stream = (int32_t)(pairs.size() / 2);
+  s.n_segs = (int32_t)segs.size();
+  s.n_long = (int32_t)longs.size();
+  RC_TRY(upload_csr_arrays(e, m, h));
+  // The kernel reads blk_row[b] and blk_row[b+1]; with long rows in between the
+  // blocks are not contiguous, so upload the pair list and index it as 2*b.
+  RC_TRY(dev_array(e, s.dev, &s.d_blk_row, pairs.data(), pairs.size() * 4, 8));
+  if (s.n_segs) {
+    RC_TRY(dev_array(e, s.dev, &s.d_segs, segs.data(), segs.size() * sizeof(LongSeg), 0));
+    RC_TRY(dev_array(e, s.dev, &s.d_long, longs.data(), longs.size() * sizeof(LongRow), 0));
+    RC_TRY(dev_array(e, s.dev, &s.d_partial, nullptr, segs.size() * 4, 0));
+    RC_TRY(dev_array(e, s.dev, &s.d_partial_multi, nullptr, segs.size() * 4 * SPMM_MAX_WIDTH, 0));
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream)); // host vectors die at return
+  return SH_OK;
+}
+
+struct CsrDeleter {   // (a matrix given up half-way: the copies enqueued from host vectors have to land first)
+  sh_engine *e;
+  void operator()(sh_csr *m) const { free_handle(e, m); }
+};
+
 int sh_csr_upload_ex(sh_engine *e, int64_t rows, int64_t cols, int64_t nnz, const int32_t *row_ptr,
                      const int32_t *col_idx, const void *val, const sh_plan_options *opt_p, sh_csr **out) {
   sh_plan_options opt;
@@ -475,93 +692,24 @@ int sh_csr_upload_ex(sh_engine *e, int64_t rows, int64_t cols, int64_t nnz, cons
                 row_ptr[rows], (long long)nnz);
   *out = nullptr;
   HIP_TRY(e, hipSetDevice(e->device));
-  sh_csr *m = new (std::nothrow) sh_csr();
+  std::unique_ptr<sh_csr, CsrDeleter> m(new (std::nothrow) sh_csr(), CsrDeleter{e});
   if (!m)
     return fail(e, SH_ENOMEM, "out of host memory");
   m->rows = rows; m->cols = cols; m->nnz = nnz;
-
   for (int64_t r = 0; r < rows; r++)
-    if (row_ptr[r + 1] < row_ptr[r]) {
-      delete m;
+    if (row_ptr[r + 1] < row_ptr[r])
       return fail(e, SH_ESHAPE, "sh_csr_upload: row_ptr not monotone at row %lld", (long long)r);
-    }
-  auto cleanup = [&](int rc) { sh_csr_free(e, m); return rc; };
-#define HIP_TRY_M(call)                                                         \
-  do {                                                                          \
-    hipError_t _r = (call);                                                     \
-    if (_r != hipSuccess)                                                       \
-      return cleanup(fail(e, _r == hipErrorOutOfMemory ? SH_ENOMEM : SH_EHIP,   \
-                          "%s failed: %s", #call, hipGetErrorString(_r)));      \
-  } while (0)
-  // device array of `bytes` (+ slack for the kernels' wide loads), filled from `host` when given; counted in the footprint
-#define DEV_ARRAY(ptr, host, bytes, slack)                                                                    \
-  do {                                                                                                        \
-    HIP_TRY_M(hipMalloc((void **)&(ptr), (size_t)(bytes) + (slack)));                                         \
-    *acct += (size_t)(bytes) + (slack);                                                                       \
-    if ((host) != nullptr && (bytes) > 0)                                                                     \
-      HIP_TRY_M(hipMemcpyAsync((ptr), (host), (size_t)(bytes), hipMemcpyHostToDevice, e->stream));            \
-  } while (0)
+  const HostCsr h{rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val};
+  const bool device_build = opt.build == 2 || (opt.build == 0 && nnz >= DEVICE_BUILD_MIN_NNZ);
 
   // The (or,and) semiring on bits, when asked for (or_and_bits: 1 = beside the ordinary plan, 2 = instead of it: a BFS
   // harness never launches another semiring on its matrix)
-  size_t *acct = &m->bits_bytes;
-  const int64_t padded = ((nnz + 3) & ~int64_t(3)) + 4;   // the tail is padded so that 16-byte loads at the end stay in bounds
-  bool csr_on_device = false;
-  auto upload_csr_arrays = [&]() -> int {   // row_ptr / col_idx / val as they are: plan A's arrays, and the device builder's input
-    size_t *const acct_before = acct;
-    acct = &m->stream_bytes;
-    DEV_ARRAY(m->d_row_ptr, row_ptr, (rows + 1) * 4, 0);
-    DEV_ARRAY(m->d_col, (const int32_t *)nullptr, padded * 4, 0);
-    DEV_ARRAY(m->d_val, (const uint32_t *)nullptr, padded * 4, 0);
-    HIP_TRY_M(hipMemsetAsync(m->d_col + (padded - 8 > 0 ? padded - 8 : 0), 0xFF, (padded >= 8 ? 8 : padded) * 4, e->stream));
-    HIP_TRY_M(hipMemsetAsync(m->d_val + (padded - 8 > 0 ? padded - 8 : 0), 0, (padded >= 8 ? 8 : padded) * 4, e->stream));
-    if (nnz > 0) {
-      HIP_TRY_M(hipMemcpyAsync(m->d_col, col_idx, nnz * 4, hipMemcpyHostToDevice, e->stream));
-      HIP_TRY_M(hipMemcpyAsync(m->d_val, val, nnz * 4, hipMemcpyHostToDevice, e->stream));
-    }
-    csr_on_device = true;
-    acct = acct_before;
-    return SH_OK;
-  };
-  const bool device_build = opt.build == 2 || (opt.build == 0 && nnz >= DEVICE_BUILD_MIN_NNZ);
-  auto drop_csr_arrays = [&]() {
-    (void)hipStreamSynchronize(e->stream);
-    (void)hipFree(m->d_row_ptr); (void)hipFree(m->d_col); (void)hipFree(m->d_val);
-    m->d_row_ptr = nullptr; m->d_col = nullptr; m->d_val = nullptr;
-    m->stream_bytes = 0;
-    csr_on_device = false;
-  };
-  if (opt.or_and_bits > 0 && nnz > 0) {
-    BitsHost bh;
-    int built = -1;   // 1 built, 0 the layout does not apply, -1 not tried / a device step failed: the host builder
-    uint32_t *dev_ent = nullptr;
-    if (device_build) {
-      if (const int rc = upload_csr_arrays()) return rc;
-      std::string why;
-      built = build_bits_plan_gpu(e->stream, rows, cols, nnz, m->d_row_ptr, m->d_col, m->d_val, bh, &dev_ent, why);
-      if (built != 1) { m->build_note = why; bh = BitsHost(); }
-    }
-    if (built < 0) built = build_bits_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, bh) ? 1 : 0;
-    if (built == 1) {
-      acct = &m->bits_bytes;
-      m->n_bits_items = (int32_t)bh.items.size();
-      m->bits_ct = bh.n_ct;
-      m->bits_entries = bh.entries;
-      m->bits_only = opt.or_and_bits >= 2;
-      if (dev_ent) { m->d_bits_ent = dev_ent; *acct += (size_t)bh.ent_len * 4 + SLACK_WIDE; m->built_on_device = true; }
-      else DEV_ARRAY(m->d_bits_ent, bh.ent.data(), bh.ent.size() * 4, SLACK_WIDE);
-      DEV_ARRAY(m->d_bits_items, bh.items.data(), bh.items.size() * sizeof(BitsItem), 32);
-      DEV_ARRAY(m->d_bits_sub, bh.bsub.data(), bh.bsub.size() * 4, 16);
-      DEV_ARRAY(m->d_bits_rr0, bh.rr_item0.data(), bh.rr_item0.size() * 4, 0);
-      DEV_ARRAY(m->d_xbits, (const uint64_t *)nullptr, (size_t)bh.n_ct * (BITS_BC / 8), 0);
-      DEV_ARRAY(m->d_bits_partial, (const uint32_t *)nullptr, (size_t)std::max<size_t>(bh.items.size(), 1) * (BITS_BR / 8), 0);
-      HIP_TRY_M(hipStreamSynchronize(e->stream)); // host vectors die at the end of this block
-    }
-  }
-  if (m->bits_only && m->d_bits_items) {
-    if (csr_on_device) drop_csr_arrays();
+  if (opt.or_and_bits > 0 && nnz > 0)
+    RC_TRY(build_bits_layout(e, m.get(), h, opt, device_build));
+  if (m->bits_only && m->bits.d_bits_items) {
+    drop_stream_layout(e, m.get());
     m->plan = PLAN_STREAM;
-    *out = m;
+    *out = m.release();
     return SH_OK;
   }
   m->bits_only = false;
@@ -571,167 +719,37 @@ int sh_csr_upload_ex(sh_engine *e, int64_t rows, int64_t cols, int64_t nnz, cons
   TiledDevArrays td;   // the big arrays when the layout was built on the device
   struct TdGuard { TiledDevArrays &t; ~TdGuard() { t.release(); } } td_guard{td};   // (whatever was not adopted below)
   lap(nullptr);
-  // Where the tiled layout is built (sh_plan_options::build): on the device from the CSR arrays (plan_gpu.hip; the
-  // default), or by the host builder below -- also the fallback when a device step fails.  Same bytes either way.
-  bool want_tiled = choose_plan(opt, cols, nnz) == PLAN_TILED && nnz > 0;
-  bool tiled = false;
   const bool bits_on_device = m->built_on_device;
   m->built_on_device = false;   // (from here on: the tiled layout)
-  if (want_tiled && device_build) {
-    if (!csr_on_device)
-      if (const int rc = upload_csr_arrays()) return rc;
-    lap("H2D of the CSR arrays");
-    std::string why;
-    const int g = build_tiled_plan_gpu(e->stream, rows, cols, nnz, row_ptr, m->d_row_ptr, m->d_col, m->d_val, opt, e->n_cus, th, td, why);
-    lap("device build");
-    if (g == 1) {
-      tiled = true;
-      m->built_on_device = true;
-    } else {
-      td.release();
-      th = TiledHost();
-      m->build_note = why;
-      if (g == 0) want_tiled = false;   // the layout does not suit this matrix: the host builder would refuse as well
-    }
-  }
-#ifdef SH_PLAN_EMULATE
-  if (want_tiled && !tiled) {   // (tools builds: sh_debug_held_at_host_build)
-    g_debug_held_at_host_build = 0;
-    for (const void *p : {(const void *)td.tcol, (const void *)td.pslot, (const void *)td.tcode, (const void *)td.tval, (const void *)td.gdest,
-                          (const void *)td.gblk, (const void *)td.obase, (const void *)td.lrp, (const void *)td.ptab, (const void *)td.ptile})
-      if (p) g_debug_held_at_host_build++;
-  }
-#endif
-  if (want_tiled && !tiled)
-    tiled = build_tiled_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, e->n_cus, th);
+  bool tiled = false;
+  RC_TRY(build_tiled_layout(e, m.get(), h, opt, device_build, th, td, &tiled));
   // (only worth timing when the bins touch few of the column tiles, i.e. the columns are local: with
   // scattered columns -- every bin has a piece in nearly every tile -- plan A is several times slower)
   const bool tune = tiled && opt.plan == 0 && opt.autotune && th.tile_fill < 0.5;
   m->plan = tiled ? PLAN_TILED : PLAN_STREAM;
   // The CSR arrays (8 B per entry) stay on the device only for plan A, or while both plans are timed.
-  if (!tiled || tune) {
-    std::vector<int32_t> pairs;
-    std::vector<LongSeg> segs;
-    std::vector<LongRow> longs;
-    build_schedule(rows, row_ptr, pairs, segs, longs);
-    m->n_stream = (int32_t)(pairs.size() / 2);
-    m->n_segs = (int32_t)segs.size();
-    m->n_long = (int32_t)longs.size();
-    if (!csr_on_device)
-      if (const int rc = upload_csr_arrays()) return rc;
-    acct = &m->stream_bytes;
-    // The kernel reads blk_row[b] and blk_row[b+1]; with long rows in between the
-    // blocks are not contiguous, so upload the pair list and index it as 2*b.
-    DEV_ARRAY(m->d_blk_row, pairs.data(), pairs.size() * 4, 8);
-    if (m->n_segs) {
-      DEV_ARRAY(m->d_segs, segs.data(), segs.size() * sizeof(LongSeg), 0);
-      DEV_ARRAY(m->d_long, longs.data(), longs.size() * sizeof(LongRow), 0);
-      DEV_ARRAY(m->d_partial, (const uint32_t *)nullptr, segs.size() * 4, 0);
-      DEV_ARRAY(m->d_partial_multi, (const uint32_t *)nullptr, segs.size() * 4 * SPMM_MAX_WIDTH, 0);
-    }
-    HIP_TRY_M(hipStreamSynchronize(e->stream)); // host vectors die at the end of this block
-  } else if (csr_on_device) {
-    drop_csr_arrays();
-  }
-  acct = &m->tiled_bytes;
-  if (tiled) {
-    m->n_bins = (int32_t)th.bins.size();
-    m->n_chunks = (int32_t)th.chunks.size();
-    m->n_tlong = (int32_t)th.heavy.size();
-    m->light_len = th.light_len;
-    m->stream_len = th.stream_len;
-    m->p_len = th.p_len;
-    m->light_entries = th.light_entries;
-    m->fold = opt.fold != 0 && TCOL_FOLD != 0;
-    m->bin_r0.reserve(th.bins.size());
-    for (const RowBin &b : th.bins) m->bin_r0.push_back(b.r0);
-    DEV_ARRAY(m->d_bins, th.bins.data(), th.bins.size() * sizeof(RowBin), 0);
-    DEV_ARRAY(m->d_chunks, th.chunks.data(), th.chunks.size() * sizeof(TileChunk), 0);
-    // the big arrays: already on the device (device builder) or uploaded from the host builder's vectors
-#define PLAN_ARRAY(ptr, dev, host_vec, elem_bytes, slack)                                                       \
-  do {                                                                                                        \
-    if (m->built_on_device) { (ptr) = (dev); (dev) = nullptr; *acct += (size_t)(td_n) * (elem_bytes) + (slack); } \
-    else DEV_ARRAY(ptr, (host_vec).data(), (host_vec).size() * (elem_bytes), slack);                          \
-  } while (0)
-    size_t td_n = 0;
-    if (!th.vdict.empty()) {
-      m->n_vdict = (int)th.vdict.size();
-      m->n_vdict_used = th.vdict_used;
-      m->code_bits = th.code_bits;
-      m->skip_minplus = true;   // (known from the dictionary alone; raw values would need a pass over the matrix: not skipped)
-      for (int k = 0; k < th.vdict_used; k++) m->skip_minplus = m->skip_minplus && (th.vdict[(size_t)k] & 0x7FFFFFFFu) < 0x73000000u;   // |a| < 2^103
-      td_n = td.n_tcode; PLAN_ARRAY(m->d_tcode, td.tcode, th.tcode, 1, SLACK_TCODE);
-      DEV_ARRAY(m->d_vdict, th.vdict.data(), th.vdict.size() * 4, 0);
-    } else {
-      td_n = td.n_tval; PLAN_ARRAY(m->d_tval, td.tval, th.tval, 4, SLACK_WIDE);
-    }
-    td_n = td.n_tcol; PLAN_ARRAY(m->d_tcol, td.tcol, th.tcol, 2, SLACK_WIDE);
-    td_n = td.n_gdest; PLAN_ARRAY(m->d_gdest, td.gdest, th.gdest, 4, SLACK_WIDE);
-    td_n = td.n_gblk; PLAN_ARRAY(m->d_gblk, td.gblk, th.gblk, 4, SLACK_WIDE);
-    td_n = td.n_ptab; PLAN_ARRAY(m->d_ptab, td.ptab, th.ptab, 4, SLACK_WIDE);
-    td_n = td.n_ptab; PLAN_ARRAY(m->d_ptile, td.ptile, th.ptile, 2, SLACK_WIDE);
-    m->n_pieces = (int64_t)(m->built_on_device ? td.n_ptab : th.ptab.size());
-    // dead pieces (launches of a semiring with absorbing words): the marked copy of ptab, the tiles' live words (all live until a launch says otherwise)
-    DEV_ARRAY(m->d_ptab_live, (const int32_t *)nullptr, (size_t)m->n_pieces * 4, SLACK_WIDE);
-    {
-      const size_t ct = (size_t)std::max<int64_t>(1, (m->cols + TCOLS - 1) / TCOLS);
-      DEV_ARRAY(m->d_tile_live, (const uint32_t *)nullptr, ct * 4, 0);
-      HIP_TRY_M(hipMemsetD32Async((hipDeviceptr_t)m->d_tile_live, 1, ct, e->stream));
-    }
-    td_n = td.n_pslot; PLAN_ARRAY(m->d_pslot, td.pslot, th.pslot, 2, SLACK_WIDE);
-    td_n = td.n_obase; PLAN_ARRAY(m->d_obase, td.obase, th.obase, 4, SLACK_WIDE);
-    DEV_ARRAY(m->d_P, (const uint32_t *)nullptr, (size_t)std::max<int64_t>(m->p_len, 4) * 4, 16);
-    if (m->built_on_device) { m->d_lrp = (int32_t *)td.lrp; td.lrp = nullptr; *acct += td.n_lrp * 4 + 16; }
-    else DEV_ARRAY(m->d_lrp, th.lrp.data(), th.lrp.size() * 4, 16);   // (+16: see plan_gpu.hip)
-    if (m->n_tlong) {
-      DEV_ARRAY(m->d_tlong, th.heavy.data(), th.heavy.size() * sizeof(LongRow), 0);
-      DEV_ARRAY(m->d_tpartial, (const uint32_t *)nullptr, (size_t)th.n_partials * 4, 16);
-    }
-    HIP_TRY_M(hipStreamSynchronize(e->stream)); // host vectors die at return
-    lap("hipMalloc + H2D of the plan");
-  }
-#undef PLAN_ARRAY
-#undef DEV_ARRAY
-#undef HIP_TRY_M
+  if (!tiled || tune)
+    RC_TRY(upload_stream_layout(e, m.get(), h));
+  else
+    drop_stream_layout(e, m.get());
+  if (tiled)
+    RC_TRY(upload_tiled_layout(e, m.get(), opt, th, td));
   if (tune)
-    autotune_plan(e, m);   // frees the arrays of the plan that lost
+    autotune_plan(e, m.get());   // drops the layout of the plan that lost
   {
     // placements of the big arrays to try: the option, else six for a matrix whose product array has >= 2^22 words.
     // Eight fresh processes per setting, one box each time (profiles/r03_ab_placement_tries*.log): 1 / 3 / 6 tries
     // 0.4476 / 0.4384 / 0.4331 ms; on another box 1 / 6 / 12 / 24 tries 0.4456 / 0.4413 / 0.4391 / 0.4417 (means): a trial
     // predicts the steady state of the caller's loop (other x and out vectors) only in part, and past six nothing is gained.
-    const int tries = opt.placement_tries > 0 ? opt.placement_tries : (m->plan == PLAN_TILED && m->p_len >= ((int64_t)1 << 22) ? 6 : 1);
-    tune_placement(e, m, tries);
+    const int tries = opt.placement_tries > 0 ? opt.placement_tries : (m->plan == PLAN_TILED && m->tiled.p_len >= ((int64_t)1 << 22) ? 6 : 1);
+    tune_placement(e, m.get(), tries);
   }
   if (bits_on_device && !tiled) m->built_on_device = true;   // (a matrix whose only device-built layout is the bit-blocked one)
-  *out = m;
+  *out = m.release();
   return SH_OK;
 }
 
-int sh_csr_free(sh_engine *e, sh_csr *m) {
-  if (!m)
-    return SH_OK;
-  if (e) {
-    (void)hipSetDevice(e->device);
-    (void)hipStreamSynchronize(e->stream);
-  }
-  if (m->d_row_ptr) (void)hipFree(m->d_row_ptr);
-  if (m->d_col) (void)hipFree(m->d_col);
-  if (m->d_val) (void)hipFree(m->d_val);
-  if (m->d_blk_row) (void)hipFree(m->d_blk_row);
-  if (m->d_segs) (void)hipFree(m->d_segs);
-  if (m->d_long) (void)hipFree(m->d_long);
-  if (m->d_partial) (void)hipFree(m->d_partial);
-  if (m->d_partial_multi) (void)hipFree(m->d_partial_multi);
-  for (void *p : {(void *)m->d_bins, (void *)m->d_chunks, (void *)m->d_tval, (void *)m->d_tcol, (void *)m->d_gdest,
-                  (void *)m->d_pslot, (void *)m->d_gblk, (void *)m->d_ptab, (void *)m->d_ptile, (void *)m->d_ptab_live, (void *)m->d_tile_live, (void *)m->d_P, (void *)m->d_tlong, (void *)m->d_tpartial, (void *)m->d_lrp,
-                  (void *)m->d_tcode, (void *)m->d_vdict, (void *)m->d_obase, (void *)m->d_done, (void *)m->d_pcs, (void *)m->d_bits_items,
-                  (void *)m->d_bits_ent, (void *)m->d_bits_partial, (void *)m->d_bits_sub, (void *)m->d_bits_rr0, (void *)m->d_xbits})
-    if (p) (void)hipFree(p);
-  if (m->h_done) (void)hipHostFree(m->h_done);
-  delete m;
-  return SH_OK;
-}
+int sh_csr_free(sh_engine *e, sh_csr *m) { return free_handle(e, m); }
 
 int sh_csr_builder(const sh_csr *m, int32_t *where, char *note, int64_t cap) {
   if (!m)
@@ -772,16 +790,16 @@ int sh_csr_plan(const sh_csr *m, int32_t *plan, uint64_t *streamed_bytes) {
     return SH_EINVAL;
   if (plan) *plan = m->bits_only ? 2 : m->plan;
   if (streamed_bytes && m->bits_only) {   // 4 B per entry, the x bitmap and the partial result bitmaps written and read once, the vectors
-    *streamed_bytes = 4ull * (uint64_t)m->bits_entries + 2ull * (uint64_t)m->n_bits_items * (BITS_BR / 8) +
-                      (uint64_t)m->n_bits_items * (BITS_BC / 8) + 4ull * m->cols + 8ull * m->rows;
+    *streamed_bytes = 4ull * (uint64_t)m->bits.bits_entries + 2ull * (uint64_t)m->bits.n_bits_items * (BITS_BR / 8) +
+                      (uint64_t)m->bits.n_bits_items * (BITS_BC / 8) + 4ull * m->cols + 8ull * m->rows;
     return SH_OK;
   }
   if (streamed_bytes) {
     const uint64_t vec = 4ull * (m->rows + 1) + 4ull * m->cols + 4ull * m->rows;
     *streamed_bytes = (m->plan == PLAN_TILED)
-                          ? (m->n_vdict ? 2ull : 6ull) * m->stream_len + (m->n_vdict ? (uint64_t)m->stream_len * m->code_bits / 8 : 0ull) + (uint64_t)(m->stream_len - m->light_len) / 4 /* gdest: 4 B per 16-entry strip */ +
-                                (uint64_t)m->light_len / 64 /* obase: 4 B per 64 groups */ +
-                                4ull * m->p_len /* P written */ + 6ull * m->p_len + m->p_len / 6 /* phase 2: P, slot; piece tables ~0.14 B per product */ +
+                          ? (m->tiled.n_vdict ? 2ull : 6ull) * m->tiled.stream_len + (m->tiled.n_vdict ? (uint64_t)m->tiled.stream_len * m->tiled.code_bits / 8 : 0ull) + (uint64_t)(m->tiled.stream_len - m->tiled.light_len) / 4 /* gdest: 4 B per 16-entry strip */ +
+                                (uint64_t)m->tiled.light_len / 64 /* obase: 4 B per 64 groups */ +
+                                4ull * m->tiled.p_len /* P written */ + 6ull * m->tiled.p_len + m->tiled.p_len / 6 /* phase 2: P, slot; piece tables ~0.14 B per product */ +
                                 vec /* x once: a tile is re-staged per phase-1 workgroup, but out of its XCD's L2 */
                           : 8ull * m->nnz + vec;
   }
@@ -793,15 +811,15 @@ int sh_csr_describe(const sh_csr *m, char *buf, size_t buflen) {
     return SH_EINVAL;
   if (m->plan == PLAN_TILED) {
     char vals[32];
-    if (m->n_vdict) snprintf(vals, sizeof vals, "dict%d(%d)", m->code_bits, m->n_vdict_used);
+    if (m->tiled.n_vdict) snprintf(vals, sizeof vals, "dict%d(%d)", m->tiled.code_bits, m->tiled.n_vdict_used);
     else snprintf(vals, sizeof vals, "raw");
     snprintf(buf, buflen, "tiled values=%s tiles=%lld chunks=%d bins=%d heavy_rows=%d stream=%.1fM light=%.1fM products=%.1fM%s", vals,
-             (long long)((m->cols + TCOLS - 1) / TCOLS), m->n_chunks, m->n_bins, m->n_tlong, m->stream_len / 1e6,
-             m->light_entries / 1e6, m->p_len / 1e6, m->fold ? " folded" : "");
+             (long long)((m->cols + TCOLS - 1) / TCOLS), m->tiled.n_chunks, m->tiled.n_bins, m->tiled.n_tlong, m->tiled.stream_len / 1e6,
+             m->tiled.light_entries / 1e6, m->tiled.p_len / 1e6, m->tiled.fold ? " folded" : "");
   } else if (m->bits_only) {
     snprintf(buf, buflen, "bits-only");
   } else {
-    snprintf(buf, buflen, "stream values=raw blocks=%d long_rows=%d segments=%d", m->n_stream, m->n_long, m->n_segs);
+    snprintf(buf, buflen, "stream values=raw blocks=%d long_rows=%d segments=%d", m->stream.n_stream, m->stream.n_long, m->stream.n_segs);
   }
   if (m->tuned) {
     const size_t len = strlen(buf);
@@ -809,10 +827,10 @@ int sh_csr_describe(const sh_csr *m, char *buf, size_t buflen) {
   }
   {
     const size_t len = strlen(buf);
-    if (m->d_bits_items)
-      snprintf(buf + len, buflen - len, " or_and=bits(items=%d,entries=%.1fM%s)", m->n_bits_items, m->bits_entries / 1e6, m->bits_only ? ",only" : "");
+    if (m->bits.d_bits_items)
+      snprintf(buf + len, buflen - len, " or_and=bits(items=%d,entries=%.1fM%s)", m->bits.n_bits_items, m->bits.bits_entries / 1e6, m->bits_only ? ",only" : "");
     const size_t len2 = strlen(buf);
-    snprintf(buf + len2, buflen - len2, " device=%.3fGB", (double)(m->stream_bytes + m->tiled_bytes + m->bits_bytes) / 1e9);
+    snprintf(buf + len2, buflen - len2, " device=%.3fGB", (double)m->device_bytes() / 1e9);
   }
   return SH_OK;
 }
@@ -820,7 +838,7 @@ int sh_csr_describe(const sh_csr *m, char *buf, size_t buflen) {
 int sh_csr_footprint(const sh_csr *m, uint64_t *device_bytes) {
   if (!m || !device_bytes)
     return SH_EINVAL;
-  *device_bytes = (uint64_t)(m->stream_bytes + m->tiled_bytes + m->bits_bytes);
+  *device_bytes = (uint64_t)m->device_bytes();
   return SH_OK;
 }
 
@@ -915,6 +933,126 @@ void *sh_vec_device_ptr(const sh_vec *v) { return v ? v->d : nullptr; }
 } // extern "C"
 
 // ---------------------------------------------------------------- launches
+#ifdef SH_STATS
+#include "stats_dump.h"
+#endif
+
+// The (or,and) semiring on bits: x -> bitmap, blocks -> partial result bitmaps, rows
+template <class SR>
+static int launch_bits_layout(sh_engine *e, const sh_csr *A, const sh_vec *x, const sh_vec *y, typename SR::T alpha, typename SR::T beta,
+                              sh_vec *out, StepDev st) {
+  const BitsLayout &b = A->bits;
+  const uint32_t *yp = y ? (const uint32_t *)y->d : nullptr;
+  const int64_t words32 = (int64_t)b.bits_ct * (BITS_BC / 32);
+  hipLaunchKernelGGL(bits_pack_x, dim3((unsigned)((words32 * 8 + 255) / 256)), dim3(256), 0, e->stream, (const uint32_t *)x->d,
+                     (int32_t)A->cols, (uint32_t *)b.d_xbits, words32, st.gate);
+  HIP_TRY(e, hipGetLastError());
+  if (b.n_bits_items > 0) {
+    hipLaunchKernelGGL(bits_blocks, dim3((unsigned)b.n_bits_items), dim3(BITS_TBS), 0, e->stream, b.d_bits_items,
+                       b.d_bits_ent, b.d_bits_sub, (const uint32_t *)b.d_xbits, b.d_bits_partial, st.gate);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (A->rows > 0) {
+    hipLaunchKernelGGL(bits_finish, dim3((unsigned)((A->rows + BITS_FIN_ROWS - 1) / BITS_FIN_ROWS)), dim3(256), 0, e->stream, b.d_bits_rr0,
+                       b.d_bits_partial, (int32_t)A->rows, yp, alpha, beta, y ? 1 : 0, (uint32_t *)out->d, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (st.expected) {
+    hipLaunchKernelGGL(report_all_pieces, dim3(1), dim3(64), 0, e->stream, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  return SH_OK;
+}
+
+// Phase 1 of the tiled plan for one way of storing the values: CODE 0 raw words (d_tval), 1 / 2 / 3 dictionary codes of
+// 8 / 4 / 16 bits (d_tcode, d_vdict).
+template <class SR, int CODE>
+static void launch_phase1(sh_engine *e, const sh_csr *A, const sh_vec *x, StepDev st, int32_t skip_dead, uint32_t *tile_live) {
+  const TiledLayout &t = A->tiled;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_tiled_phase1<SR, CODE>), dim3((unsigned)t.n_chunks), dim3(TBS), 0, e->stream,
+                     (const TileChunk *)t.d_chunks, CODE ? (const void *)t.d_tcode : (const void *)t.d_tval,
+                     CODE ? (const uint32_t *)t.d_vdict : (const uint32_t *)nullptr, t.d_tcol, t.d_gdest, t.d_obase,
+                     (const uint32_t *)x->d, (int32_t)A->cols, t.d_P, t.d_tpartial, st.gate, skip_dead, tile_live);
+}
+
+template <class SR>
+static int launch_tiled(sh_engine *e, const sh_csr *A, const sh_vec *x, const sh_vec *y, typename SR::T alpha, typename SR::T beta,
+                        sh_vec *out, StepDev st) {
+  const TiledLayout &t = A->tiled;
+  const uint32_t *yp = y ? (const uint32_t *)y->d : nullptr;
+#ifdef SH_STATS
+  stats_before_tiled(e);
+#endif
+  // tiles whose x words are all absorbing are not streamed (semiring.hip.h); (min,+) needs every |value| < 2^103
+  const int32_t skip_dead = SR::id == 1 ? (t.skip_minplus ? 1 : 0) : 1;
+  // ... and their products are neither written by phase 1 nor read by phase 2: phase 1 leaves a live word per tile,
+  // tiled_mark_dead turns it into a copy of the piece table whose dead pieces point at one group of identity
+  // words, phase 2 reads the pieces through that copy (semirings with absorbing words only)
+  const bool mark_dead = SR::has_absorbing && skip_dead && t.n_bins > 0 && t.n_pieces > 0;
+  uint32_t *tile_live = mark_dead ? t.d_tile_live : nullptr;
+  if (t.n_chunks > 0) {
+    if (!t.n_vdict) launch_phase1<SR, 0>(e, A, x, st, skip_dead, tile_live);
+    else if (t.code_bits == 16) launch_phase1<SR, 3>(e, A, x, st, skip_dead, tile_live);
+    else if (t.code_bits == 4) launch_phase1<SR, 2>(e, A, x, st, skip_dead, tile_live);
+    else launch_phase1<SR, 1>(e, A, x, st, skip_dead, tile_live);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (mark_dead) {
+    const uint32_t ident = SR::identity_bits;
+    hipLaunchKernelGGL(tiled_mark_dead, dim3((unsigned)((t.n_pieces + 255) / 256)), dim3(256), 0, e->stream, t.d_ptab, t.d_ptile,
+                       (const uint32_t *)t.d_tile_live, t.d_ptab_live, t.n_pieces, t.d_P + std::max<int64_t>(t.p_len, 4), ident, st.gate);
+    HIP_TRY(e, hipGetLastError());
+  }
+  // phase 2; its reducer waves also add up the heavy rows' partials while the loaders fill the first bin
+  if (t.n_bins > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_tiled_phase2s<SR>), dim3(std::min(t.n_bins, e->n_cus)), dim3(P2S_BS), 0,
+                       e->stream, t.d_bins, t.n_bins, t.d_lrp, t.d_P, (int32_t)(std::max<int64_t>(t.p_len, 4) / 4 - 1), t.d_pslot,
+                       (const uint4 *)t.d_gblk, mark_dead ? t.d_ptab_live : t.d_ptab, t.d_tlong, t.n_tlong, t.d_tpartial, yp, alpha, beta, y ? 1 : 0,
+                       (uint32_t *)out->d, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+#ifdef SH_STATS
+  stats_after_tiled(e, t.n_bins, t.n_chunks);
+#endif
+  if (t.n_bins == 0 && t.n_tlong > 0) {   // every row is heavy: no phase 2 to host the sums
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_heavy_fixup<SR>), dim3(t.n_tlong), dim3(HFIX_BS), 0, e->stream, t.d_tlong,
+                       t.d_tpartial, yp, alpha, beta, y ? 1 : 0, (uint32_t *)out->d, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (st.expected && t.n_bins == 0) {      // nobody reported: one arrival per piece behind everything
+    hipLaunchKernelGGL(report_all_pieces, dim3(1), dim3(64), 0, e->stream, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  return SH_OK;
+}
+
+template <class SR>
+static int launch_stream(sh_engine *e, const sh_csr *A, const sh_vec *x, const sh_vec *y, typename SR::T alpha, typename SR::T beta,
+                         sh_vec *out, StepDev st) {
+  const StreamLayout &s = A->stream;
+  const uint32_t *yp = y ? (const uint32_t *)y->d : nullptr;
+  CsrDev dev{s.d_row_ptr, s.d_col, s.d_val, (int32_t)A->rows, (int32_t)A->cols};
+  const int grid = s.n_stream + s.n_segs;
+  if (grid > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_csr_kernel<SR>), dim3(grid), dim3(BS), 0, e->stream, dev,
+                       (const uint32_t *)x->d, yp, alpha, beta, y ? 1 : 0, (uint32_t *)out->d, s.d_blk_row, s.n_stream, s.d_segs,
+                       s.d_partial, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (s.n_long > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_long_fixup<SR>), dim3((s.n_long + 63) / 64), dim3(64), 0,
+                       e->stream, s.d_long, s.n_long, s.d_partial, yp, alpha, beta, y ? 1 : 0, (uint32_t *)out->d, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (st.expected) {   // the CSR-stream kernels do not report pieces: one arrival per piece behind them
+    hipLaunchKernelGGL(report_all_pieces, dim3(1), dim3(64), 0, e->stream, st);
+    HIP_TRY(e, hipGetLastError());
+  }
+  return SH_OK;
+}
+
+// One launch of the layout that serves the semiring: the bit-blocked one for (or,and) where the matrix has it, else the
+// matrix's plan.  They get y where the epilogue reads it, else NULL.
 template <class SR>
 static int launch_spmv(sh_engine *e, const sh_csr *A, const sh_vec *x, const sh_vec *y,
                        const void *alpha_p, const void *beta_p, sh_vec *out, StepDev st) {
@@ -927,162 +1065,41 @@ static int launch_spmv(sh_engine *e, const sh_csr *A, const sh_vec *x, const sh_
     return fail(e, SH_EINVAL, "sh_spmv: y is NULL but the epilogue reads it (beta != 0 or min-plus)");
   if (use_y && y->n < A->rows)
     return fail(e, SH_ESHAPE, "sh_spmv: y has %lld elements, matrix has %lld rows", (long long)y->n, (long long)A->rows);
-  if constexpr (std::is_same<SR, OrAndI32>::value) {
-    if (A->d_bits_items) {   // the (or,and) semiring on bits: x -> bitmap, blocks -> partial result bitmaps, rows
-      const int64_t words32 = (int64_t)A->bits_ct * (BITS_BC / 32);
-      hipLaunchKernelGGL(bits_pack_x, dim3((unsigned)((words32 * 8 + 255) / 256)), dim3(256), 0, e->stream, (const uint32_t *)x->d,
-                         (int32_t)A->cols, (uint32_t *)A->d_xbits, words32, st.gate);
-      HIP_TRY(e, hipGetLastError());
-      if (A->n_bits_items > 0) {
-        hipLaunchKernelGGL(bits_blocks, dim3((unsigned)A->n_bits_items), dim3(BITS_TBS), 0, e->stream, A->d_bits_items,
-                           A->d_bits_ent, A->d_bits_sub, (const uint32_t *)A->d_xbits, A->d_bits_partial, st.gate);
-        HIP_TRY(e, hipGetLastError());
-      }
-      if (A->rows > 0) {
-        hipLaunchKernelGGL(bits_finish, dim3((unsigned)((A->rows + BITS_FIN_ROWS - 1) / BITS_FIN_ROWS)), dim3(256), 0, e->stream, A->d_bits_rr0,
-                           A->d_bits_partial, (int32_t)A->rows, use_y ? (const uint32_t *)y->d : nullptr, alpha, beta, use_y ? 1 : 0,
-                           (uint32_t *)out->d, st);
-        HIP_TRY(e, hipGetLastError());
-      }
-      if (st.expected) {
-        hipLaunchKernelGGL(report_all_pieces, dim3(1), dim3(64), 0, e->stream, st);
-        HIP_TRY(e, hipGetLastError());
-      }
-      return SH_OK;
-    }
-  }
+  if (!use_y) y = nullptr;
+  if constexpr (std::is_same<SR, OrAndI32>::value)
+    if (A->bits.d_bits_items) return launch_bits_layout<SR>(e, A, x, y, alpha, beta, out, st);
   if (A->bits_only)
     return fail(e, SH_EINVAL, "this matrix was uploaded with or_and_bits = 2: it serves SH_OR_AND_I32 launches only");
-  if (A->plan == PLAN_TILED) {
-    const uint32_t *yp = use_y ? (const uint32_t *)y->d : nullptr;
-#ifdef SH_STATS
-    static uint64_t *p1_stats = nullptr;   // tools builds: per-chunk timeline of phase 1
-    if (getenv("SH_STATS_DUMP")) {
-      if (!p1_stats) (void)hipMalloc((void **)&p1_stats, (size_t)1 << 22);
-      (void)hipMemsetAsync(p1_stats, 0, (size_t)1 << 22, e->stream);
-      (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_p1_stats), &p1_stats, sizeof p1_stats, 0, hipMemcpyHostToDevice, e->stream);
-    }
-#endif
-    bool mark_dead = false;
-    {
-      const TileChunk *ch = A->d_chunks;
-      const dim3 grid((unsigned)A->n_chunks), block(TBS);
-      // tiles whose x words are all absorbing are not streamed (semiring.hip.h); (min,+) needs every |value| < 2^103
-      const int32_t skip_dead = SR::id == 1 ? (A->skip_minplus ? 1 : 0) : 1;
-      // ... and their products are neither written by phase 1 nor read by phase 2: phase 1 leaves a live word per tile,
-      // tiled_mark_dead turns it into a copy of the piece table whose dead pieces point at one group of identity
-      // words, phase 2 reads the pieces through that copy (semirings with absorbing words only)
-      mark_dead = SR::has_absorbing && skip_dead && A->n_bins > 0 && A->n_pieces > 0;
-      uint32_t *tile_live = mark_dead ? A->d_tile_live : nullptr;
-      if (A->n_chunks > 0) {
-        if (A->n_vdict && A->code_bits == 16)
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_tiled_phase1<SR, 3>), grid, block, 0, e->stream,
-                             ch, (const void *)A->d_tcode, A->d_vdict, A->d_tcol, A->d_gdest, A->d_obase,
-                             (const uint32_t *)x->d, (int32_t)A->cols, A->d_P, A->d_tpartial, st.gate, skip_dead, tile_live);
-        else if (A->n_vdict && A->code_bits == 4)
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_tiled_phase1<SR, 2>), grid, block, 0, e->stream,
-                             ch, (const void *)A->d_tcode, A->d_vdict, A->d_tcol, A->d_gdest, A->d_obase,
-                             (const uint32_t *)x->d, (int32_t)A->cols, A->d_P, A->d_tpartial, st.gate, skip_dead, tile_live);
-        else if (A->n_vdict)
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_tiled_phase1<SR, 1>), grid, block, 0, e->stream,
-                             ch, (const void *)A->d_tcode, A->d_vdict, A->d_tcol, A->d_gdest, A->d_obase,
-                             (const uint32_t *)x->d, (int32_t)A->cols, A->d_P, A->d_tpartial, st.gate, skip_dead, tile_live);
-        else
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_tiled_phase1<SR, 0>), grid, block, 0, e->stream,
-                             ch, (const void *)A->d_tval, (const uint32_t *)nullptr, A->d_tcol, A->d_gdest, A->d_obase,
-                             (const uint32_t *)x->d, (int32_t)A->cols, A->d_P, A->d_tpartial, st.gate, skip_dead, tile_live);
-        HIP_TRY(e, hipGetLastError());
-      }
-    }
-    if (mark_dead) {
-      const uint32_t ident = SR::identity_bits;
-      hipLaunchKernelGGL(tiled_mark_dead, dim3((unsigned)((A->n_pieces + 255) / 256)), dim3(256), 0, e->stream, A->d_ptab, A->d_ptile,
-                         (const uint32_t *)A->d_tile_live, A->d_ptab_live, A->n_pieces, A->d_P + std::max<int64_t>(A->p_len, 4), ident, st.gate);
-      HIP_TRY(e, hipGetLastError());
-    }
-    // phase 2; its reducer waves also add up the heavy rows' partials while the loaders fill the first bin
-    if (A->n_bins > 0) {
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_tiled_phase2s<SR>), dim3(std::min(A->n_bins, e->n_cus)), dim3(P2S_BS), 0,
-                         e->stream, A->d_bins, A->n_bins, A->d_lrp, A->d_P, (int32_t)(std::max<int64_t>(A->p_len, 4) / 4 - 1), A->d_pslot,
-                         (const uint4 *)A->d_gblk, mark_dead ? A->d_ptab_live : A->d_ptab, A->d_tlong, A->n_tlong, A->d_tpartial, yp, alpha, beta, use_y ? 1 : 0,
-                         (uint32_t *)out->d, st);
-      HIP_TRY(e, hipGetLastError());
-    }
-#ifdef SH_STATS
-    if (getenv("SH_STATS_DUMP") && A->n_bins > 0) {   // where the two roles of phase 2 spent their cycles (wave 0 of each role, per workgroup)
-      (void)hipStreamSynchronize(e->stream);
-      std::vector<uint64_t> pf(256 * 16);
-      (void)hipMemcpyFromSymbol(pf.data(), HIP_SYMBOL(g_p2_prof), pf.size() * 8);
-      const int G = std::min(A->n_bins, 256);
-      double a[16] = {0};
-      for (int w = 0; w < G; w++) for (int k = 0; k < 16; k++) a[k] += (double)pf[(size_t)w * 16 + k] / G;
-      fprintf(stderr, "[stats] phase 2 per workgroup (%d, %.1f bins each), shader cycles: loaders total %.0f, in vmcnt waits %.0f (%.1f %%), in barriers %.0f (%.1f %%), issuing/scattering %.0f | "
-                      "reducers total %.0f, in barriers %.0f (%.1f %%), reducing %.0f (one-lane pass %.0f, 8-lane rows %.0f, 64-lane rows %.0f)\n",
-              G, a[3], a[0], a[1], 100 * a[1] / a[0], a[2], 100 * a[2] / a[0], a[0] - a[1] - a[2], a[4], a[5], 100 * a[5] / a[4], a[6], a[8], a[9], a[10]);
-    }
-    if (getenv("SH_STATS_DUMP") && A->n_bins > 0) {   // the same per reducer wave: who a bin waits for
-      std::vector<uint64_t> pw(256 * 12 * 4);
-      (void)hipMemcpyFromSymbol(pw.data(), HIP_SYMBOL(g_p2_wave), pw.size() * 8);
-      const int G = std::min(A->n_bins, 256);
-      fprintf(stderr, "[stats] phase 2 reducer waves (K cycles: at barriers / classifying pass / cooperative rows / total):");
-      for (int w = 0; w < 12; w++) {
-        double a[4] = {0, 0, 0, 0};
-        for (int g = 0; g < G; g++) for (int k = 0; k < 4; k++) a[k] += (double)pw[((size_t)g * 12 + w) * 4 + k] / G;
-        fprintf(stderr, "  w%d %.0f/%.0f/%.0f/%.0f", w, a[0] / 1e3, a[1] / 1e3, a[2] / 1e3, a[3] / 1e3);
-      }
-      fprintf(stderr, "\n");
-    }
-    if (getenv("SH_STATS_DUMP") && p1_stats) {
-      const int nch = A->n_chunks;
-      std::vector<uint64_t> hs((size_t)nch * 5);
-      (void)hipStreamSynchronize(e->stream);
-      (void)hipMemcpy(hs.data(), p1_stats, hs.size() * 8, hipMemcpyDeviceToHost);
-      for (int kind = 0; kind < 2; kind++) {
-        double n = 0, ent = 0, stage = 0, total = 0;
-        uint64_t t0 = ~0ull, t1 = 0;
-        for (int i = 0; i < nch; i++) {
-          const uint64_t *S = &hs[(size_t)i * 5];
-          if (S[1] == 0 || (int)S[0] != kind) continue;
-          n++; ent += S[1]; stage += (S[3] - S[2]) / 100.0; total += (S[4] - S[2]) / 100.0;
-          t0 = std::min(t0, S[2]); t1 = std::max(t1, S[4]);
-        }
-        if (n > 0)
-          fprintf(stderr, "[stats] phase 1 %s chunks: %.0f, %.0f entries each, staging %.2f us, whole chunk %.2f us (incl. store drain); span %.1f us\n",
-                  kind ? "heavy" : "light", n, ent / n, stage / n, total / n, (t1 - t0) / 100.0);
-      }
-    }
-#endif
-    if (A->n_bins == 0 && A->n_tlong > 0) {   // every row is heavy: no phase 2 to host the sums
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_heavy_fixup<SR>), dim3(A->n_tlong), dim3(HFIX_BS), 0, e->stream, A->d_tlong,
-                         A->d_tpartial, yp, alpha, beta, use_y ? 1 : 0, (uint32_t *)out->d, st);
-      HIP_TRY(e, hipGetLastError());
-    }
-    if (st.expected && A->n_bins == 0) {      // nobody reported: one arrival per piece behind everything
-      hipLaunchKernelGGL(report_all_pieces, dim3(1), dim3(64), 0, e->stream, st);
-      HIP_TRY(e, hipGetLastError());
-    }
-    return SH_OK;
+  if (A->plan == PLAN_TILED)
+    return launch_tiled<SR>(e, A, x, y, alpha, beta, out, st);
+  return launch_stream<SR>(e, A, x, y, alpha, beta, out, st);
+}
+
+// Whether the epilogue of the semiring reads y (any other value of sr: refused by the dispatch).
+static bool reads_y(sh_semiring sr, const void *beta_p) {
+  float bf;
+  int32_t bi;
+  memcpy(&bf, beta_p, 4);
+  memcpy(&bi, beta_p, 4);
+  switch (sr) {
+  case SH_PLUS_TIMES_F32: return PlusTimesF32::reads_y(bf);
+  case SH_MIN_PLUS_F32: return MinPlusF32::reads_y(bf);
+  case SH_OR_AND_I32: return OrAndI32::reads_y(bi);
+  default: return MaxMinI32::reads_y(bi);
   }
-  CsrDev dev{A->d_row_ptr, A->d_col, A->d_val, (int32_t)A->rows, (int32_t)A->cols};
-  const int grid = A->n_stream + A->n_segs;
-  if (grid > 0) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_csr_kernel<SR>), dim3(grid), dim3(BS), 0, e->stream, dev,
-                       (const uint32_t *)x->d, use_y ? (const uint32_t *)y->d : nullptr, alpha, beta,
-                       use_y ? 1 : 0, (uint32_t *)out->d, A->d_blk_row, A->n_stream, A->d_segs,
-                       A->d_partial, st);
-    HIP_TRY(e, hipGetLastError());
-  }
-  if (A->n_long > 0) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_long_fixup<SR>), dim3((A->n_long + 63) / 64), dim3(64), 0,
-                       e->stream, A->d_long, A->n_long, A->d_partial,
-                       use_y ? (const uint32_t *)y->d : nullptr, alpha, beta, use_y ? 1 : 0,
-                       (uint32_t *)out->d, st);
-    HIP_TRY(e, hipGetLastError());
-  }
-  if (st.expected) {   // the CSR-stream kernels do not report pieces: one arrival per piece behind them
-    hipLaunchKernelGGL(report_all_pieces, dim3(1), dim3(64), 0, e->stream, st);
-    HIP_TRY(e, hipGetLastError());
-  }
+}
+
+// The state of a matrix's piece reports, made by its first sh_spmv_step_pieces launch: whole, or not at all.
+static int open_piece_report(sh_engine *e, sh_csr *A) {
+  std::unique_ptr<PieceReport> p(new (std::nothrow) PieceReport());
+  if (!p)
+    return fail(e, SH_ENOMEM, "out of host memory");
+  HIP_TRY(e, p->dev.alloc_exact(&p->d_done, MAX_PIECES * 4));
+  HIP_TRY(e, p->dev.alloc_exact(&p->d_pcs, sizeof(PieceDev)));
+  HIP_TRY(e, hipHostMalloc((void **)&p->h_done, 64, hipHostMallocDefault));
+  memset(p->h_done, 0, 64);
+  HIP_TRY(e, hipMemsetAsync(p->d_done, 0, MAX_PIECES * 4, e->stream));
+  A->pieces = std::move(p);
   return SH_OK;
 }
 
@@ -1168,20 +1185,12 @@ int sh_spmv_step_pieces(sh_engine *e, sh_semiring sr, sh_csr *A, const sh_vec *x
   if (pc->report && pc->gate)
     return fail(e, SH_EINVAL, "sh_spmv_step_pieces: a gated launch cannot report its pieces (report != 0 with a gate)");
   // What the launch itself would refuse is refused here, before the round moves: a refused call leaves *round alone.
-  {
-    bool reads_y = true;
-    switch (sr) {
-    case SH_PLUS_TIMES_F32: { float b; memcpy(&b, beta, 4); reads_y = PlusTimesF32::reads_y(b); break; }
-    case SH_MIN_PLUS_F32: break;
-    case SH_OR_AND_I32: { int32_t b; memcpy(&b, beta, 4); reads_y = OrAndI32::reads_y(b); break; }
-    case SH_MAX_MIN_I32: { int32_t b; memcpy(&b, beta, 4); reads_y = MaxMinI32::reads_y(b); break; }
-    default: return fail(e, SH_EINVAL, "unknown semiring %d", (int)sr);
-    }
-    if (reads_y && !y)
-      return fail(e, SH_EINVAL, "sh_spmv_step_pieces: y is NULL but the epilogue reads it (beta != 0 or min-plus)");
-    if (A->bits_only && sr != SH_OR_AND_I32)
-      return fail(e, SH_EINVAL, "this matrix was uploaded with or_and_bits = 2: it serves SH_OR_AND_I32 launches only");
-  }
+  if ((int)sr < SH_PLUS_TIMES_F32 || (int)sr > SH_MAX_MIN_I32)
+    return fail(e, SH_EINVAL, "unknown semiring %d", (int)sr);
+  if (reads_y(sr, beta) && !y)
+    return fail(e, SH_EINVAL, "sh_spmv_step_pieces: y is NULL but the epilogue reads it (beta != 0 or min-plus)");
+  if (A->bits_only && sr != SH_OR_AND_I32)
+    return fail(e, SH_EINVAL, "this matrix was uploaded with or_and_bits = 2: it serves SH_OR_AND_I32 launches only");
   HIP_TRY(e, hipSetDevice(e->device));
   StepDev st{changed_flag_device, (const uint32_t *)x->d, 0, delta, pc->gate};
   PieceDev pd{};
@@ -1194,35 +1203,31 @@ int sh_spmv_step_pieces(sh_engine *e, sh_semiring sr, sh_csr *A, const sh_vec *x
       return fail(e, SH_ESHAPE, "sh_spmv_step_pieces: piece %d (%lld rows at element %lld) does not fit the vectors", c, (long long)rows_c, (long long)at);
     pd.piece_delta[c] = at - first;
     // tiled plan: the piece is complete once every bin that starts below its last row + 1 is reduced
-    pd.piece_bin_end[c] = (int32_t)(std::lower_bound(A->bin_r0.begin(), A->bin_r0.end(), (int32_t)std::min<int64_t>(first + pc->piece_rows, A->rows)) - A->bin_r0.begin());
+    pd.piece_bin_end[c] = (int32_t)(std::lower_bound(A->tiled.bin_r0.begin(), A->tiled.bin_r0.end(), (int32_t)std::min<int64_t>(first + pc->piece_rows, A->rows)) - A->tiled.bin_r0.begin());
   }
-  if (pc->n_pieces > 0) pd.piece_bin_end[pc->n_pieces - 1] = (int32_t)A->bin_r0.size();
-  if (!A->d_done) {
-    HIP_TRY(e, hipMalloc((void **)&A->d_done, MAX_PIECES * 4));
-    HIP_TRY(e, hipMemsetAsync(A->d_done, 0, MAX_PIECES * 4, e->stream));
-    HIP_TRY(e, hipHostMalloc((void **)&A->h_done, 64, hipHostMallocDefault));
-    memset(A->h_done, 0, 64);
-    HIP_TRY(e, hipMalloc((void **)&A->d_pcs, sizeof(PieceDev)));
-  }
-  pd.done = A->d_done;
-  pd.done_host = A->h_done;
+  if (pc->n_pieces > 0) pd.piece_bin_end[pc->n_pieces - 1] = (int32_t)A->tiled.bin_r0.size();
+  if (!A->pieces)
+    RC_TRY(open_piece_report(e, A));
+  PieceReport &pr = *A->pieces;
+  pd.done = pr.d_done;
+  pd.done_host = pr.h_done;
   // the geometry goes to device memory once (an iteration loop brings the same one every time); a changed one is
   // copied behind the launches already enqueued on this stream, which keep reading the old bytes until then
-  if (!A->pcs_valid || memcmp(&pd, &A->pcs_host, sizeof pd) != 0) {
+  if (!pr.pcs_valid || memcmp(&pd, &pr.pcs_host, sizeof pd) != 0) {
     HIP_TRY(e, hipStreamSynchronize(e->stream));   // (pcs_host is the copy's source: it must not change under a copy in flight)
-    A->pcs_host = pd;
-    HIP_TRY(e, hipMemcpyAsync(A->d_pcs, &A->pcs_host, sizeof pd, hipMemcpyHostToDevice, e->stream));
-    A->pcs_valid = true;
+    pr.pcs_host = pd;
+    HIP_TRY(e, hipMemcpyAsync(pr.d_pcs, &pr.pcs_host, sizeof pd, hipMemcpyHostToDevice, e->stream));
+    pr.pcs_valid = true;
   }
-  st.pcs = A->d_pcs;
+  st.pcs = pr.d_pcs;
   if (pc->report) {
     // arrivals per piece and launch: one per workgroup of phase 2, or the single one of report_all_pieces
-    st.expected = (A->plan == PLAN_TILED && A->n_bins > 0 && !(sr == SH_OR_AND_I32 && A->d_bits_items)) ? (uint32_t)std::min(A->n_bins, e->n_cus) : 1u;
-    A->round++;
-    st.round = A->round;
-    A->last_expected = st.expected;
-    if (round) *round = A->round;
-    if (done_words) *done_words = A->h_done;
+    st.expected = (A->plan == PLAN_TILED && A->tiled.n_bins > 0 && !(sr == SH_OR_AND_I32 && A->bits.d_bits_items)) ? (uint32_t)std::min(A->tiled.n_bins, e->n_cus) : 1u;
+    pr.round++;
+    st.round = pr.round;
+    pr.last_expected = st.expected;
+    if (round) *round = pr.round;
+    if (done_words) *done_words = pr.h_done;
   }
   // the epilogue reads y through the same row -> element mapping; an epilogue that does not read y gets none
   sh_vec yfull;
@@ -1236,22 +1241,24 @@ int sh_spmv_step_pieces(sh_engine *e, sh_semiring sr, sh_csr *A, const sh_vec *x
 int sh_csr_piece_state(sh_engine *e, sh_csr *A, uint32_t *arrivals, uint32_t *host_words, uint32_t *expected, uint32_t *round) {
   if (!e || !A || !arrivals || !host_words)
     return fail(e, SH_EINVAL, "sh_csr_piece_state: NULL argument");
-  if (expected) *expected = A->last_expected;
-  if (round) *round = A->round;
-  for (int c = 0; c < MAX_PIECES; c++) { arrivals[c] = 0xFFFFFFFFu; host_words[c] = A->h_done ? ((volatile uint32_t *)A->h_done)[c] : 0u; }
-  if (!A->d_done)
+  const PieceReport *rep = A->pieces.get();   // (NULL: the matrix has not reported yet)
+  if (expected) *expected = rep ? rep->last_expected : 0u;
+  if (round) *round = rep ? rep->round : 0u;
+  for (int c = 0; c < MAX_PIECES; c++) { arrivals[c] = 0xFFFFFFFFu; host_words[c] = rep ? ((volatile uint32_t *)rep->h_done)[c] : 0u; }
+  if (!rep)
     return SH_OK;
+  const PieceReport &pr = *rep;
   HIP_TRY(e, hipSetDevice(e->device));
   hipStream_t side;
   HIP_TRY(e, hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
   // (h_done is 16 words of pinned host memory: the upper 8 receive the counters)
-  if (hipMemcpyAsync(A->h_done + MAX_PIECES, A->d_done, MAX_PIECES * 4, hipMemcpyDeviceToHost, side) == hipSuccess) {
+  if (hipMemcpyAsync(pr.h_done + MAX_PIECES, pr.d_done, MAX_PIECES * 4, hipMemcpyDeviceToHost, side) == hipSuccess) {
     const auto t0 = std::chrono::steady_clock::now();
     bool ready = false;
     while (!(ready = hipStreamQuery(side) == hipSuccess) && std::chrono::steady_clock::now() - t0 < std::chrono::seconds(2))
       std::this_thread::sleep_for(std::chrono::milliseconds(1));
     if (ready)
-      for (int c = 0; c < MAX_PIECES; c++) arrivals[c] = ((volatile uint32_t *)A->h_done)[MAX_PIECES + c];
+      for (int c = 0; c < MAX_PIECES; c++) arrivals[c] = ((volatile uint32_t *)pr.h_done)[MAX_PIECES + c];
   }
   (void)hipStreamDestroy(side);
   return SH_OK;
@@ -1344,17 +1351,17 @@ static int launch_spmm(sh_engine *e, const sh_csr *A, const sh_vec *X, const sh_
   memcpy(&alpha, alpha_p, 4);
   memcpy(&beta, beta_p, 4);
   const bool use_y = SR::reads_y(beta);
-  CsrDev dev{A->d_row_ptr, A->d_col, A->d_val, (int32_t)A->rows, (int32_t)A->cols};
+  CsrDev dev{A->stream.d_row_ptr, A->stream.d_col, A->stream.d_val, (int32_t)A->rows, (int32_t)A->cols};
   const uint32_t *yp = use_y ? (const uint32_t *)Y->d : nullptr;
-  const int grid = A->n_stream + A->n_segs;
+  const int grid = A->stream.n_stream + A->stream.n_segs;
   if (grid > 0) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(spmm_csr_kernel<SR, K>), dim3(grid), dim3(BS), 0, e->stream, dev, (const uint32_t *)X->d, yp,
-                       alpha, beta, use_y ? 1 : 0, (uint32_t *)Out->d, A->d_blk_row, A->n_stream, A->d_segs, A->d_partial_multi, st);
+                       alpha, beta, use_y ? 1 : 0, (uint32_t *)Out->d, A->stream.d_blk_row, A->stream.n_stream, A->stream.d_segs, A->stream.d_partial_multi, st);
     HIP_TRY(e, hipGetLastError());
   }
-  if (A->n_long > 0) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmm_long_fixup<SR, K>), dim3((A->n_long * K + 63) / 64), dim3(64), 0, e->stream, A->d_long,
-                       A->n_long, A->d_partial_multi, yp, alpha, beta, use_y ? 1 : 0, (uint32_t *)Out->d, st);
+  if (A->stream.n_long > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spmm_long_fixup<SR, K>), dim3((A->stream.n_long * K + 63) / 64), dim3(64), 0, e->stream, A->stream.d_long,
+                       A->stream.n_long, A->stream.d_partial_multi, yp, alpha, beta, use_y ? 1 : 0, (uint32_t *)Out->d, st);
     HIP_TRY(e, hipGetLastError());
   }
   return SH_OK;
@@ -1383,19 +1390,6 @@ static int dispatch_spmm(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t 
   }
 }
 
-static bool reads_y(sh_semiring sr, const void *beta_p) {
-  float bf;
-  int32_t bi;
-  memcpy(&bf, beta_p, 4);
-  memcpy(&bi, beta_p, 4);
-  switch (sr) {
-  case SH_PLUS_TIMES_F32: return PlusTimesF32::reads_y(bf);
-  case SH_MIN_PLUS_F32: return MinPlusF32::reads_y(bf);
-  case SH_OR_AND_I32: return OrAndI32::reads_y(bi);
-  default: return MaxMinI32::reads_y(bi);
-  }
-}
-
 // What sh_spmm and sh_iterate_multi ask of their operands (Y == NULL is legal where the epilogue does not read it).
 static int check_multi(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t width, const sh_vec *X, const sh_vec *Y,
                        const void *alpha, const void *beta, const sh_vec *Out, const char *who) {
@@ -1405,7 +1399,7 @@ static int check_multi(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t wi
     return fail(e, SH_EINVAL, "%s: unknown semiring %d", who, (int)sr);
   if (width != 4 && width != 8 && width != 16 && width != 32)
     return fail(e, SH_EINVAL, "%s: width %d, must be 4, 8, 16 or 32", who, (int)width);
-  if (!A->d_row_ptr || !A->d_blk_row)
+  if (!A->stream.d_row_ptr || !A->stream.d_blk_row)
     return fail(e, SH_EINVAL, "%s: the matrix does not hold its CSR arrays on the device (it runs the tiled or the bit-blocked "
                 "plan); upload it with sh_plan_options::plan = 1 (SH_PLAN=stream)", who);
   const bool use_y = reads_y(sr, beta);
@@ -1549,17 +1543,17 @@ static_assert(BITS_MAX_WORDS <= SPMM_MAX_WIDTH, "the long-row partials live in d
 template <int W, bool COUNTS>
 static int launch_bits(sh_engine *e, const sh_csr *A, const sh_vec *X, const sh_vec *Y, uint32_t amask, uint32_t bmask,
                        sh_vec *Out, BitsStep st) {
-  CsrDev dev{A->d_row_ptr, A->d_col, A->d_val, (int32_t)A->rows, (int32_t)A->cols};
+  CsrDev dev{A->stream.d_row_ptr, A->stream.d_col, A->stream.d_val, (int32_t)A->rows, (int32_t)A->cols};
   const uint32_t *yp = bmask ? (const uint32_t *)Y->d : nullptr;
-  const int grid = A->n_stream + A->n_segs;
+  const int grid = A->stream.n_stream + A->stream.n_segs;
   if (grid > 0) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(msbfs_csr_kernel<W, COUNTS>), dim3(grid), dim3(BS), 0, e->stream, dev, (const uint32_t *)X->d, yp,
-                       amask, bmask, (uint32_t *)Out->d, A->d_blk_row, A->n_stream, A->d_segs, A->d_partial_multi, st);
+                       amask, bmask, (uint32_t *)Out->d, A->stream.d_blk_row, A->stream.n_stream, A->stream.d_segs, A->stream.d_partial_multi, st);
     HIP_TRY(e, hipGetLastError());
   }
-  if (A->n_long > 0) {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(msbfs_long_fixup<W, COUNTS>), dim3((A->n_long * W + 63) / 64), dim3(64), 0, e->stream, A->d_long,
-                       A->n_long, A->d_partial_multi, yp, amask, bmask, (uint32_t *)Out->d, st);
+  if (A->stream.n_long > 0) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(msbfs_long_fixup<W, COUNTS>), dim3((A->stream.n_long * W + 63) / 64), dim3(64), 0, e->stream, A->stream.d_long,
+                       A->stream.n_long, A->stream.d_partial_multi, yp, amask, bmask, (uint32_t *)Out->d, st);
     HIP_TRY(e, hipGetLastError());
   }
   return SH_OK;
@@ -1586,7 +1580,7 @@ static int check_bits(sh_engine *e, const sh_csr *A, int32_t words, const sh_vec
     return fail(e, SH_EINVAL, "%s: words %d, must be 1, 2, 4 or 8", who, (int)words);
   if (!e || !A || !X || !alpha || !beta || !Out)
     return fail(e, SH_EINVAL, "%s: NULL argument", who);
-  if (!A->d_row_ptr || !A->d_blk_row)
+  if (!A->stream.d_row_ptr || !A->stream.d_blk_row)
     return fail(e, SH_EINVAL, "%s: the matrix does not hold its CSR arrays on the device (it runs the tiled or the bit-blocked "
                 "plan); upload it with sh_plan_options::plan = 1 (SH_PLAN=stream)", who);
   int32_t b;
@@ -1791,42 +1785,6 @@ int sh_bits_to_column(sh_engine *e, const sh_vec *B, int64_t n, int32_t words, i
 
 
 // ---- what the worklist handles share (worklist.hip.h) ----------------------------------------------------------------
-// Owner of device arrays: whatever it allocated is released with it.  A handle holds one for its arrays, and a create
-// function a second one for the temporaries of the build, which so go on every return path.
-struct DevArrays {
-  std::vector<void *> ptrs;
-  size_t bytes = 0;   // what a handle's footprint reports
-  DevArrays() = default;
-  DevArrays(const DevArrays &) = delete;
-  DevArrays &operator=(const DevArrays &) = delete;
-  ~DevArrays() {
-    for (void *p : ptrs) (void)hipFree(p);
-  }
-  // (an array of `nbytes` counts as that in the footprint; an empty one still gets a few bytes to point at)
-  template <class T>
-  hipError_t alloc(T **p, int64_t nbytes) {
-    void *q = nullptr;
-    const hipError_t r = hipMalloc(&q, std::max<size_t>((size_t)nbytes, 16));
-    if (r != hipSuccess) return r;
-    ptrs.push_back(q);
-    bytes += (size_t)nbytes;
-    *p = (T *)q;
-    return hipSuccess;
-  }
-};
-
-template <class H>
-static int free_handle(sh_engine *e, H *h) {
-  if (!h)
-    return SH_OK;
-  if (e) {
-    (void)hipSetDevice(e->device);
-    (void)hipStreamSynchronize(e->stream);
-  }
-  delete h;
-  return SH_OK;
-}
-
 // What every sh_*_footprint / _edges / _max_forward / _max_degree / _delta accessor is: SH_EINVAL for a NULL handle or
 // out pointer (no message is set: there is no engine to hold one), else the value.
 #define HANDLE_GET(h, out, value) ((h) && (out) ? (*(out) = (value), (int)SH_OK) : (int)SH_EINVAL)
@@ -1864,7 +1822,7 @@ static int build_transpose(sh_engine *e, DevArrays &tmp, const int32_t *ptr, con
 // What every sh_*_graph has: the shape it was made from, the edges it kept, and the device arrays it owns.
 struct GraphBase {
   int64_t rows = 0, nnz = 0, edges = 0;
-  DevArrays dev;   // (released after whatever a derived handle's destructor lets go of)
+  DevArrays dev;   // (dev_arrays.h; released after whatever a derived handle's destructor lets go of)
 };
 
 template <class Ctl>
@@ -2111,9 +2069,9 @@ int sh_frontier_create(sh_engine *e, const sh_csr *A, int64_t nnz, const int32_t
   const int64_t rows = A->rows, cols = A->cols;
   f->rows = rows; f->nnz = nnz; f->A = A;
   DevArrays &own = f->dev, tmp;
-  f->borrowed = A->d_row_ptr && (nnz == 0 || (A->d_col && A->d_val));
+  f->borrowed = A->stream.d_row_ptr && (nnz == 0 || (A->stream.d_col && A->stream.d_val));
   if (f->borrowed) {
-    f->d_row_ptr = A->d_row_ptr; f->d_col = A->d_col; f->d_val = A->d_val;
+    f->d_row_ptr = A->stream.d_row_ptr; f->d_col = A->stream.d_col; f->d_val = A->stream.d_val;
   } else {
     HIP_TRY(e, own.alloc(&f->d_row_ptr, (rows + 1) * 4));
     HIP_TRY(e, own.alloc(&f->d_col, nnz * 4));
