@@ -39,17 +39,37 @@
 
 using namespace sh;
 
+// The words a batch of launches writes on the device and their pinned copy.  Each half is allocated when first missing.
+template <class T>
+struct BatchWords {
+  T *d = nullptr, *h = nullptr;
+  hipError_t open(size_t bytes) {
+    hipError_t r = d ? hipSuccess : hipMalloc((void **)&d, bytes);
+    if (r == hipSuccess && !h) r = hipHostMalloc((void **)&h, bytes, hipHostMallocDefault);
+    return r;
+  }
+  void close() {
+    if (d) (void)hipFree(d);
+    if (h) (void)hipHostFree(h);
+  }
+};
+struct DenseLoopState {   // what run_dense_batches and its four users keep between calls
+  hipEvent_t ev[9] = {};          // one per launch of a batch, and one in front
+  BatchWords<int32_t> flags;      // sh_iterate: 64 B, the convergence flags of a batch (the pinned half is the engine's from the start)
+  BatchWords<int32_t> mflags;     // sh_iterate_multi: MULTI_FLAG_WORDS per-column flags of a batch
+  BatchWords<uint32_t> bstate;    // sh_bits_iterate: BITS_STATE_WORDS changed words and level counts of a batch
+  void close() {
+    flags.close(); mflags.close(); bstate.close();
+    for (auto e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+
 struct sh_engine {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t ev_iter[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // sh_iterate: one per launch of a batch
-  int32_t *d_flags = nullptr;   // per-iteration convergence flags
-  int32_t n_flags = 0;
-  int32_t *h_flag = nullptr;    // pinned, 64 B: convergence flags of a batch of iterations, read back
-  int32_t *d_mflags = nullptr, *h_mflags = nullptr;   // sh_iterate_multi: MULTI_FLAG_WORDS per-column flags of a batch (device / pinned copy)
-  uint32_t *d_bstate = nullptr, *h_bstate = nullptr;   // sh_bits_iterate: BITS_STATE_WORDS changed words and level counts of a batch (device / pinned copy)
+  DenseLoopState dense;
   char name[256] = {0};
   int n_cus = 256;
   std::string err;
@@ -243,8 +263,8 @@ static int engine_create(int device, void *stream, bool borrow, sh_engine **out)
   }
   if (r == hipSuccess) r = hipEventCreate(&e->ev0);
   if (r == hipSuccess) r = hipEventCreate(&e->ev1);
-  if (r == hipSuccess) r = hipHostMalloc((void **)&e->h_flag, 64, hipHostMallocDefault);
-  if (r == hipSuccess) memset(e->h_flag, 0, 64);
+  if (r == hipSuccess) r = hipHostMalloc((void **)&e->dense.flags.h, 64, hipHostMallocDefault);
+  if (r == hipSuccess) memset(e->dense.flags.h, 0, 64);
   hipDeviceProp_t prop;
   if (r == hipSuccess) r = hipGetDeviceProperties(&prop, device);
   if (r != hipSuccess) {
@@ -270,15 +290,9 @@ int sh_engine_destroy(sh_engine *e) {
     return SH_OK;
   (void)hipSetDevice(e->device);
   (void)hipStreamSynchronize(e->stream);
-  if (e->d_flags) (void)hipFree(e->d_flags);
-  if (e->h_flag) (void)hipHostFree(e->h_flag);
-  if (e->d_mflags) (void)hipFree(e->d_mflags);
-  if (e->h_mflags) (void)hipHostFree(e->h_mflags);
-  if (e->d_bstate) (void)hipFree(e->d_bstate);
-  if (e->h_bstate) (void)hipHostFree(e->h_bstate);
+  e->dense.close();
   if (e->ev0) (void)hipEventDestroy(e->ev0);
   if (e->ev1) (void)hipEventDestroy(e->ev1);
-  for (auto ev : e->ev_iter) if (ev) (void)hipEventDestroy(ev);
   if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
   return SH_OK;
@@ -1127,6 +1141,131 @@ static int dispatch(sh_engine *e, sh_semiring sr, const sh_csr *A, const sh_vec 
   }
 }
 
+// ---- the dense iteration loops ---------------------------------------------------------------------------------------
+static hipError_t ms_between(hipEvent_t a, hipEvent_t b, uint64_t *ns) {
+  float ms = 0.f;
+  const hipError_t r = hipEventElapsedTime(&ms, a, b);
+  *ns = (uint64_t)((double)ms * 1e6);
+  return r;
+}
+
+// The vectors of an iteration: a launch reads `in` (and `y`) and writes `out`; one that swaps hands its output to the next.
+struct PingPong {
+  sh_vec *in, *out;
+  const sh_vec *y;
+  uint32_t swapped = 0;   // bit k: launch k of the batch under way exchanged the buffers
+  void swap(int k) {
+    std::swap(in, out);   // std::swap(input, output), app/sssp.cpp:143
+    y = in;               // setGlobalArg(3, input_mem_ptr), :150
+    swapped |= 1u << k;
+  }
+  // The batch is over.  Its launches from `ran` on returned at their gate and wrote nothing: the result is what launch
+  // ran - 1 produced, so the exchanges that were enqueued for them are taken back.
+  void end_batch(int ran) {
+    if (__builtin_popcount(swapped >> ran) % 2) std::swap(in, out);
+    y = in;
+    swapped = 0;
+  }
+  int hand_back(sh_engine *e, sh_vec *x, size_t bytes) const {   // the final vector may live in the scratch vector
+    if (in == x)
+      return SH_OK;
+    HIP_TRY(e, hipMemcpyAsync(x->d, in->d, bytes, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return SH_OK;
+  }
+};
+
+struct Readback { void *host; const void *dev; size_t bytes; };   // what a batch copies back before the host joins in
+struct DenseRun { int32_t launches = 0; bool over = false; uint64_t total_ns = 0; };
+
+// The loop of sh_iterate, sh_iterate_multi, sh_bits_iterate and sh_iterate_frontier: up to BATCH gated launches are
+// enqueued ahead of the host, which joins in once per batch (DESIGN.md "The dense batch loop").  Per batch: begin()
+// clears the state the launches write; enqueue(launch, k, pp, &swaps) enqueues launch `launch` as number k of the batch
+// on pp.in / pp.y / pp.out and clears `swaps` if it leaves its result in pp.in; `rb` is copied back and the stream joined;
+// settle(first, nb, &ran, &over) reads it: how many of the nb launches ran, whether the iteration is over, and the
+// caller's per-launch outputs of launches first .. first + ran - 1.  The loop owns the events, the time of every launch
+// that ran (ns_per_launch may be NULL), the buffers of the launches that did not, and the cap.
+template <int BATCH, class Begin, class Enqueue, class Settle>
+static int run_dense_batches(sh_engine *e, PingPong &pp, int32_t cap, Readback rb, uint64_t *ns_per_launch, DenseRun *run,
+                             Begin begin, Enqueue enqueue, Settle settle) {
+  hipEvent_t *ev = e->dense.ev;
+  static_assert(BATCH <= 8, "one event per launch of a batch, and one bit of PingPong::swapped");
+  if (!ev[0])
+    for (auto &v : e->dense.ev) HIP_TRY(e, hipEventCreate(&v));
+  int32_t it = 0;
+  bool over = false;
+  while (!over && it < cap) {
+    const int nb = std::min<int32_t>(BATCH, cap - it);
+    RC_TRY(begin());
+    HIP_TRY(e, hipEventRecord(ev[0], e->stream));
+    for (int k = 0; k < nb; k++) {
+      bool swaps = true;
+      RC_TRY(enqueue(it + k, k, pp, &swaps));
+      HIP_TRY(e, hipEventRecord(ev[k + 1], e->stream));
+      if (swaps) pp.swap(k);
+    }
+    HIP_TRY(e, hipMemcpyAsync(rb.host, rb.dev, rb.bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    int ran = 0;
+    RC_TRY(settle(it, nb, &ran, &over));
+    for (int k = 0; k < ran; k++) {
+      uint64_t ns = 0;
+      HIP_TRY(e, ms_between(ev[k], ev[k + 1], &ns));
+      if (ns_per_launch)
+        ns_per_launch[it + k] = ns;
+      run->total_ns += ns;
+    }
+    pp.end_batch(ran);
+    it += ran;
+  }
+  run->launches = it;
+  run->over = over;
+  return SH_OK;
+}
+
+// sh_iterate_multi and sh_bits_iterate: the n columns (sources) of one vector converge each on its own.  `d` / `h` hold
+// BATCH + 1 slots of SLOT words and `state_words` in all.  Slot k + 1 takes the flags of launch k of the batch, which
+// launch k + 1 reads as its live mask; slot 0 carries those of the previous batch's last launch, and the first launch
+// ever has no mask (NULL: everything is live).  launch(k, pp, flags, live) enqueues; flag(slot, j) reads column j's flag
+// from a slot of `h`; extra(launch, k) takes whatever else launch k of the batch left behind slot BATCH.  A column's
+// count = index of its first flag that stayed 0, plus one (the confirming launch included), or every launch made.
+template <int SLOT, class W, class Launch, class Flag, class Extra>
+static int iterate_slots(sh_engine *e, PingPong &pp, BatchWords<W> st, int state_words, int read_words, int n, int32_t max_iters,
+                         int32_t *iters_of, int32_t *converged_of, uint64_t *ns_per_launch, DenseRun *run, Launch launch,
+                         Flag flag, Extra extra) {
+  constexpr int BATCH = 8;
+  int n_live = n, last_slot = -1;   // slot of the latest launch that ran (-1: none yet)
+  auto begin = [&]() -> int {
+    if (last_slot > 0)
+      HIP_TRY(e, hipMemcpyAsync(st.d, st.d + last_slot * SLOT, SLOT * 4, hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(e, hipMemsetAsync(st.d + SLOT, 0, (state_words - SLOT) * 4, e->stream));
+    return SH_OK;
+  };
+  auto enqueue = [&](int32_t, int k, const PingPong &p, bool *) -> int {
+    return launch(k, p, st.d + (k + 1) * SLOT, (k == 0 && last_slot < 0) ? nullptr : st.d + k * SLOT);
+  };
+  auto settle = [&](int32_t first, int nb, int *ran, bool *over) -> int {
+    while (*ran < nb && n_live > 0) {   // every launch up to the first that left nothing live did run
+      for (int j = 0; j < n; j++)
+        if (!converged_of[j] && !flag(st.h + (*ran + 1) * SLOT, j)) {
+          converged_of[j] = 1;
+          iters_of[j] = first + *ran + 1;
+          n_live--;
+        }
+      extra(first + *ran, *ran);
+      ++*ran;
+    }
+    last_slot = *ran;
+    *over = n_live == 0;
+    return SH_OK;
+  };
+  RC_TRY(run_dense_batches<BATCH>(e, pp, max_iters, Readback{st.h, st.d, (size_t)read_words * 4}, ns_per_launch, run, begin, enqueue, settle));
+  for (int j = 0; j < n; j++)
+    if (!converged_of[j])
+      iters_of[j] = run->launches;
+  return SH_OK;
+}
+
 extern "C" {
 
 int sh_spmv(sh_engine *e, sh_semiring sr, const sh_csr *A, const sh_vec *x, const sh_vec *y,
@@ -1278,65 +1417,38 @@ int sh_iterate(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_vec *x, const s
   if (scratch->d == x->d && A->rows > 0)
     return fail(e, SH_EINVAL, "sh_iterate: scratch must not alias x");
   HIP_TRY(e, hipSetDevice(e->device));
-  if (e->n_flags < 1) {
-    HIP_TRY(e, hipMalloc((void **)&e->d_flags, 64));
-    e->n_flags = 16;
-  }
-  // Launches are enqueued ITER_BATCH iterations ahead of the host: iteration i carries the flag word of
-  // iteration i - 1 as its gate and returns at once when that flag stayed 0 (nothing changed: the loop is
-  // over), so the host only joins in once per batch -- one memset, one 32-byte read-back, one synchronise
-  // per 8 iterations instead of per iteration.  The launch count of the reference's do/while
-  // (app/sssp.cpp:112-153, confirming launch included) = index of the first flag that stayed 0, plus one.
+  HIP_TRY(e, e->dense.flags.open(64));
+  const BatchWords<int32_t> &fl = e->dense.flags;
+  // Iteration i carries the flag word of iteration i - 1 as its gate and returns at once when that flag stayed 0 (nothing
+  // changed: the loop is over).  The launch count of the reference's do/while (app/sssp.cpp:112-153, confirming launch
+  // included) = index of the first flag that stayed 0, plus one.
 #ifndef SH_ITER_BATCH
 #define SH_ITER_BATCH 8
 #endif
   constexpr int ITER_BATCH = SH_ITER_BATCH;   // (1 = one host round trip per iteration, the round-1 loop: tools A/B builds)
-  static_assert(ITER_BATCH <= 8, "the flags of a batch are read back into the first 8 words of h_flag");
-  if (!e->ev_iter[0])
-    for (auto &ev : e->ev_iter) HIP_TRY(e, hipEventCreate(&ev));
-  sh_vec *in = x, *out = scratch;
-  const sh_vec *y = y0;
-  int32_t it = 0;
-  bool term = false;
-  uint64_t total = 0;
-  while (!term && it < max_iters) {
-    const int nb = std::min<int32_t>(ITER_BATCH, max_iters - it);
-    HIP_TRY(e, hipMemsetAsync(e->d_flags, 0, ITER_BATCH * 4, e->stream));
-    HIP_TRY(e, hipEventRecord(e->ev_iter[0], e->stream));
-    for (int k = 0; k < nb; k++) {
-      StepDev st{e->d_flags + k, (const uint32_t *)in->d, 0, delta, k > 0 ? e->d_flags + (k - 1) : nullptr};
-      int rc = dispatch(e, sr, A, in, y, alpha, beta, out, st);
-      if (rc)
-        return rc;
-      HIP_TRY(e, hipEventRecord(e->ev_iter[k + 1], e->stream));
-      sh_vec *t = in; in = out; out = t;   // std::swap(input, output), app/sssp.cpp:143
-      y = in;                              // setGlobalArg(3, input_mem_ptr), :150
-    }
-    HIP_TRY(e, hipMemcpyAsync(e->h_flag, e->d_flags, ITER_BATCH * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    int ran = nb;                          // launches of this batch that did run
-    for (int k = 0; k < nb; k++)
-      if (e->h_flag[k] == 0) { ran = k + 1; term = true; break; }
-    for (int k = 0; k < ran; k++) {
-      float ms = 0.f;
-      HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_iter[k], e->ev_iter[k + 1]));
-      const uint64_t ns = (uint64_t)((double)ms * 1e6);
-      if (ns_per_iter)
-        ns_per_iter[it + k] = ns;
-      total += ns;
-    }
-    // the gated launches behind the confirming one wrote nothing: the result is what launch `ran` produced
-    if ((nb - ran) % 2) { sh_vec *t = in; in = out; out = t; }
-    it += ran;
-  }
-  if (in != x) {   // the final vector lives in `scratch`: hand it back in x
-    HIP_TRY(e, hipMemcpyAsync(x->d, in->d, A->rows * 4, hipMemcpyDeviceToDevice, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-  }
-  *iters = it;
-  *converged = term ? 1 : 0;
+  static_assert(ITER_BATCH <= 8, "the flags of a batch are read back into the first 8 words of the pinned copy");
+  PingPong pp{x, scratch, y0};
+  DenseRun run;
+  auto begin = [&]() -> int {
+    HIP_TRY(e, hipMemsetAsync(fl.d, 0, ITER_BATCH * 4, e->stream));
+    return SH_OK;
+  };
+  auto enqueue = [&](int32_t, int k, const PingPong &p, bool *) -> int {
+    StepDev st{fl.d + k, (const uint32_t *)p.in->d, 0, delta, k > 0 ? fl.d + (k - 1) : nullptr};
+    return dispatch(e, sr, A, p.in, p.y, alpha, beta, p.out, st);
+  };
+  auto settle = [&](int32_t, int nb, int *ran, bool *over) -> int {
+    *ran = nb;
+    for (int k = 0; k < nb && !*over; k++)
+      if (fl.h[k] == 0) { *ran = k + 1; *over = true; }
+    return SH_OK;
+  };
+  RC_TRY(run_dense_batches<ITER_BATCH>(e, pp, max_iters, Readback{fl.h, fl.d, ITER_BATCH * 4}, ns_per_iter, &run, begin, enqueue, settle));
+  RC_TRY(pp.hand_back(e, x, A->rows * 4));
+  *iters = run.launches;
+  *converged = run.over ? 1 : 0;
   if (total_ns)
-    *total_ns = total;
+    *total_ns = run.total_ns;
   return SH_OK;
 }
 
@@ -1464,73 +1576,20 @@ int sh_iterate_multi(sh_engine *e, sh_semiring sr, const sh_csr *A, int32_t widt
   if (max_iters <= 0)
     return SH_OK;
   HIP_TRY(e, hipSetDevice(e->device));
-  // As sh_iterate: launches are enqueued MULTI_BATCH ahead of the host.  Slot k + 1 of d_mflags holds the per-column flags
-  // of launch k of the batch, which launch k + 1 reads as its live columns; slot 0 holds the flags of the previous batch's
-  // last launch.  A column's count = index of its first flag that stayed 0, plus one (the confirming launch included).
-  constexpr int MULTI_BATCH = 8, SLOT = SPMM_MAX_WIDTH, MULTI_FLAG_WORDS = (MULTI_BATCH + 1) * SLOT;
-  if (!e->d_mflags)
-    HIP_TRY(e, hipMalloc((void **)&e->d_mflags, MULTI_FLAG_WORDS * 4));
-  if (!e->h_mflags)
-    HIP_TRY(e, hipHostMalloc((void **)&e->h_mflags, MULTI_FLAG_WORDS * 4, hipHostMallocDefault));
-  if (!e->ev_iter[0])
-    for (auto &ev : e->ev_iter) HIP_TRY(e, hipEventCreate(&ev));
-  sh_vec *in = X, *out = scratch;
-  const sh_vec *y = Y0;
-  int32_t it = 0, n_live = width;
-  uint64_t total = 0;
-  int last_slot = -1;   // slot of the latest launch that ran (-1: none yet, every column is live)
-  while (n_live > 0 && it < max_iters) {
-    const int nb = std::min<int32_t>(MULTI_BATCH, max_iters - it);
-    if (last_slot > 0)
-      HIP_TRY(e, hipMemcpyAsync(e->d_mflags, e->d_mflags + last_slot * SLOT, SLOT * 4, hipMemcpyDeviceToDevice, e->stream));
-    HIP_TRY(e, hipMemsetAsync(e->d_mflags + SLOT, 0, MULTI_BATCH * SLOT * 4, e->stream));
-    HIP_TRY(e, hipEventRecord(e->ev_iter[0], e->stream));
-    for (int k = 0; k < nb; k++) {
-      const int32_t *active = (k == 0 && last_slot < 0) ? nullptr : e->d_mflags + k * SLOT;
-      MultiStep st{e->d_mflags + (k + 1) * SLOT, (const uint32_t *)in->d, delta, active};
-      rc = dispatch_spmm(e, sr, A, width, in, y, alpha, beta, out, st);
-      if (rc)
-        return rc;
-      HIP_TRY(e, hipEventRecord(e->ev_iter[k + 1], e->stream));
-      std::swap(in, out);   // std::swap(input, output), app/sssp.cpp:143
-      y = in;               // setGlobalArg(3, input_mem_ptr), :150
-    }
-    HIP_TRY(e, hipMemcpyAsync(e->h_mflags, e->d_mflags, MULTI_FLAG_WORDS * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    int ran = 0;   // launches of this batch that did run: every one up to the first that left no column live
-    while (ran < nb && n_live > 0) {
-      const int32_t *f = e->h_mflags + (ran + 1) * SLOT;
-      for (int j = 0; j < width; j++)
-        if (!converged_of_column[j] && f[j] == 0) {
-          converged_of_column[j] = 1;
-          iters_of_column[j] = it + ran + 1;
-          n_live--;
-        }
-      ran++;
-    }
-    for (int k = 0; k < ran; k++) {
-      float ms = 0.f;
-      HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_iter[k], e->ev_iter[k + 1]));
-      const uint64_t ns = (uint64_t)((double)ms * 1e6);
-      if (ns_per_launch)
-        ns_per_launch[it + k] = ns;
-      total += ns;
-    }
-    // the gated launches behind the last one that ran wrote nothing: the result is what launch `ran` produced
-    if ((nb - ran) % 2) std::swap(in, out);
-    last_slot = ran;
-    it += ran;
-  }
-  for (int j = 0; j < width; j++)
-    if (!converged_of_column[j])
-      iters_of_column[j] = it;
-  if (in != X) {   // the final vectors live in `scratch`: hand them back in X
-    HIP_TRY(e, hipMemcpyAsync(X->d, in->d, (size_t)A->rows * width * 4, hipMemcpyDeviceToDevice, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-  }
-  *launches = it;
+  constexpr int SLOT = SPMM_MAX_WIDTH, MULTI_FLAG_WORDS = (8 + 1) * SLOT;   // (iterate_slots: 8 launches to a batch)
+  HIP_TRY(e, e->dense.mflags.open(MULTI_FLAG_WORDS * 4));
+  PingPong pp{X, scratch, Y0};
+  DenseRun run;
+  auto launch = [&](int, const PingPong &p, int32_t *flags, const int32_t *active) -> int {
+    return dispatch_spmm(e, sr, A, width, p.in, p.y, alpha, beta, p.out, MultiStep{flags, (const uint32_t *)p.in->d, delta, active});
+  };
+  auto flag = [](const int32_t *slot, int j) { return slot[j] != 0; };
+  RC_TRY(iterate_slots<SLOT>(e, pp, e->dense.mflags, MULTI_FLAG_WORDS, MULTI_FLAG_WORDS, width, max_iters, iters_of_column,
+                             converged_of_column, ns_per_launch, &run, launch, flag, [](int32_t, int) {}));
+  RC_TRY(pp.hand_back(e, X, (size_t)A->rows * width * 4));
+  *launches = run.launches;
   if (total_ns)
-    *total_ns = total;
+    *total_ns = run.total_ns;
   return SH_OK;
 }
 
@@ -1664,78 +1723,29 @@ int sh_bits_iterate(sh_engine *e, const sh_csr *A, int32_t words, sh_vec *X, con
   uint32_t amask, bmask;
   bits_masks(alpha, beta, &amask, &bmask);
   HIP_TRY(e, hipSetDevice(e->device));
-  // As sh_iterate_multi: launches are enqueued BITS_BATCH ahead of the host.  Slot k + 1 of the state holds the changed
-  // words of launch k of the batch, which launch k + 1 reads as its live mask; slot 0 holds those of the previous batch's
-  // last launch.  Behind the slots: 32 * BITS_MAX_WORDS level counts per launch of the batch.  A source's count = index
-  // of its first changed bit that stayed 0, plus one (the confirming launch included).
-  constexpr int BITS_BATCH = 8, SLOT = BITS_MAX_WORDS, CNT = 32 * BITS_MAX_WORDS, CNT0 = (BITS_BATCH + 1) * SLOT,
-                BITS_STATE_WORDS = CNT0 + BITS_BATCH * CNT;
-  if (!e->d_bstate)
-    HIP_TRY(e, hipMalloc((void **)&e->d_bstate, BITS_STATE_WORDS * 4));
-  if (!e->h_bstate)
-    HIP_TRY(e, hipHostMalloc((void **)&e->h_bstate, BITS_STATE_WORDS * 4, hipHostMallocDefault));
-  if (!e->ev_iter[0])
-    for (auto &ev : e->ev_iter) HIP_TRY(e, hipEventCreate(&ev));
-  sh_vec *in = X, *out = scratch;
-  const sh_vec *y = Y0;
-  int32_t it = 0, n_live = n_src;
-  uint64_t total = 0;
-  int last_slot = -1;   // slot of the latest launch that ran (-1: none yet, every source is live)
-  while (n_live > 0 && it < max_iters) {
-    const int nb = std::min<int32_t>(BITS_BATCH, max_iters - it);
-    if (last_slot > 0)
-      HIP_TRY(e, hipMemcpyAsync(e->d_bstate, e->d_bstate + last_slot * SLOT, SLOT * 4, hipMemcpyDeviceToDevice, e->stream));
-    HIP_TRY(e, hipMemsetAsync(e->d_bstate + SLOT, 0, (BITS_STATE_WORDS - SLOT) * 4, e->stream));
-    HIP_TRY(e, hipEventRecord(e->ev_iter[0], e->stream));
-    for (int k = 0; k < nb; k++) {
-      const uint32_t *live = (k == 0 && last_slot < 0) ? nullptr : e->d_bstate + k * SLOT;
-      BitsStep st{e->d_bstate + (k + 1) * SLOT, (const uint32_t *)in->d, live, e->d_bstate + CNT0 + k * CNT};
-      rc = newly_set ? launch_bits_words<true>(e, A, words, in, y, amask, bmask, out, st)
-                     : launch_bits_words<false>(e, A, words, in, y, amask, bmask, out, st);
-      if (rc)
-        return rc;
-      HIP_TRY(e, hipEventRecord(e->ev_iter[k + 1], e->stream));
-      std::swap(in, out);   // std::swap(input, output), app/bfs.cpp as app/sssp.cpp:143
-      y = in;               // setGlobalArg(3, input_mem_ptr), :150
-    }
-    HIP_TRY(e, hipMemcpyAsync(e->h_bstate, e->d_bstate, (newly_set ? BITS_STATE_WORDS : CNT0) * 4, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    int ran = 0;   // launches of this batch that did run: every one up to the first that left no source live
-    while (ran < nb && n_live > 0) {
-      const uint32_t *f = e->h_bstate + (ran + 1) * SLOT;
-      for (int s = 0; s < n_src; s++)
-        if (!converged_of_source[s] && ((f[s >> 5] >> (s & 31)) & 1u) == 0u) {
-          converged_of_source[s] = 1;
-          iters_of_source[s] = it + ran + 1;
-          n_live--;
-        }
-      if (newly_set)   // (the kernel's counts are word-major, 32 per word: source s at s)
-        memcpy(newly_set + (size_t)(it + ran) * n_src, e->h_bstate + CNT0 + ran * CNT, (size_t)n_src * 4);
-      ran++;
-    }
-    for (int k = 0; k < ran; k++) {
-      float ms = 0.f;
-      HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_iter[k], e->ev_iter[k + 1]));
-      const uint64_t ns = (uint64_t)((double)ms * 1e6);
-      if (ns_per_launch)
-        ns_per_launch[it + k] = ns;
-      total += ns;
-    }
-    // the gated launches behind the last one that ran wrote nothing: the result is what launch `ran` produced
-    if ((nb - ran) % 2) std::swap(in, out);
-    last_slot = ran;
-    it += ran;
-  }
-  for (int s = 0; s < n_src; s++)
-    if (!converged_of_source[s])
-      iters_of_source[s] = it;
-  if (in != X && A->rows > 0) {   // the final vector lives in `scratch`: hand it back in X
-    HIP_TRY(e, hipMemcpyAsync(X->d, in->d, (size_t)A->rows * words * 4, hipMemcpyDeviceToDevice, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-  }
-  *launches = it;
+  // Behind the slots of iterate_slots (8 launches to a batch): 32 * BITS_MAX_WORDS level counts per launch of the batch.
+  constexpr int SLOT = BITS_MAX_WORDS, CNT = 32 * BITS_MAX_WORDS, CNT0 = (8 + 1) * SLOT, BITS_STATE_WORDS = CNT0 + 8 * CNT;
+  HIP_TRY(e, e->dense.bstate.open(BITS_STATE_WORDS * 4));
+  const BatchWords<uint32_t> &bs = e->dense.bstate;
+  PingPong pp{X, scratch, Y0};
+  DenseRun run;
+  auto launch = [&](int k, const PingPong &p, uint32_t *changed, const uint32_t *live) -> int {
+    BitsStep st{changed, (const uint32_t *)p.in->d, live, bs.d + CNT0 + k * CNT};
+    return newly_set ? launch_bits_words<true>(e, A, words, p.in, p.y, amask, bmask, p.out, st)
+                     : launch_bits_words<false>(e, A, words, p.in, p.y, amask, bmask, p.out, st);
+  };
+  auto flag = [](const uint32_t *slot, int s) { return ((slot[s >> 5] >> (s & 31)) & 1u) != 0u; };
+  auto counts = [&](int32_t l, int k) {
+    if (newly_set)   // (the kernel's counts are word-major, 32 per word: source s at s)
+      memcpy(newly_set + (size_t)l * n_src, bs.h + CNT0 + k * CNT, (size_t)n_src * 4);
+  };
+  RC_TRY(iterate_slots<SLOT>(e, pp, bs, BITS_STATE_WORDS, newly_set ? BITS_STATE_WORDS : CNT0, n_src, max_iters, iters_of_source,
+                             converged_of_source, ns_per_launch, &run, launch, flag, counts));
+  if (A->rows > 0)
+    RC_TRY(pp.hand_back(e, X, (size_t)A->rows * words * 4));
+  *launches = run.launches;
   if (total_ns)
-    *total_ns = total;
+    *total_ns = run.total_ns;
   return SH_OK;
 }
 
@@ -1788,13 +1798,6 @@ int sh_bits_to_column(sh_engine *e, const sh_vec *B, int64_t n, int32_t words, i
 // What every sh_*_footprint / _edges / _max_forward / _max_degree / _delta accessor is: SH_EINVAL for a NULL handle or
 // out pointer (no message is set: there is no engine to hold one), else the value.
 #define HANDLE_GET(h, out, value) ((h) && (out) ? (*(out) = (value), (int)SH_OK) : (int)SH_EINVAL)
-
-static hipError_t ms_between(hipEvent_t a, hipEvent_t b, uint64_t *ns) {
-  float ms = 0.f;
-  const hipError_t r = hipEventElapsedTime(&ms, a, b);
-  *ns = (uint64_t)((double)ms * 1e6);
-  return r;
-}
 
 // The transpose of the pattern ptr / col with `n` entries (and of its weights when w != NULL): column histogram,
 // exclusive scan, scatter through per-column cursors.  Enqueued only: `tmp` lives until the stream has been synchronised.
@@ -2144,84 +2147,62 @@ int sh_iterate_frontier(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_fronti
   if (scratch->d == x->d && A->rows > 0)
     return fail(e, SH_EINVAL, "sh_iterate_frontier: scratch must not alias x");
   HIP_TRY(e, hipSetDevice(e->device));
-  if (!e->ev_iter[0])
-    for (auto &ev : e->ev_iter) HIP_TRY(e, hipEventCreate(&ev));
-  static_assert(FR_BATCH <= 8, "one event per launch of a batch, as sh_iterate");
   if (dense_share < 0) dense_share = FRONTIER_DENSE_SHARE;
   const bool never_sparse = dense_share == 0.0;
   const uint32_t max_entries = dense_share >= 1.0 ? 0xFFFFFFFFu : (uint32_t)(dense_share * (double)A->nnz);
   HIP_TRY(e, hipMemsetAsync(f->d_ctl, 0, FR_CTL_BYTES, e->stream));
   const dim3 dgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((A->rows + WL_BS - 1) / WL_BS, (int64_t)e->n_cus * 8)));
-  sh_vec *in = x, *out = scratch;
-  const sh_vec *y = y0;
-  int32_t it = 0;
-  bool term = false, sparse = false;
-  uint64_t total = 0;
-  while (!term && it < max_iters) {
-    // A batch holds launches of ONE mode: which buffer a launch reads must be known when it is enqueued, and that
-    // depends on how many dense launches (which swap the buffers) ran before it.
-    const int nb = std::min<int32_t>(FR_BATCH, max_iters - it);
+  // A batch holds launches of ONE mode: which buffer a launch reads must be known when it is enqueued, and that
+  // depends on how many dense launches (which swap the buffers) ran before it.
+  bool sparse = false;
+  PingPong pp{x, scratch, y0};
+  DenseRun run;
+  auto begin = [&]() -> int {
     hipLaunchKernelGGL(frontier_begin, dim3(1), dim3(64), 0, e->stream, f->d_ctl);
     HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, hipEventRecord(e->ev_iter[0], e->stream));
-    for (int k = 0; k < nb; k++) {
-      const int L = it + k, p = L & 1;
-      if (sparse) {
-        int rc;
-        switch (sr) {
-        case SH_MIN_PLUS_F32: rc = launch_sparse<MinPlusF32>(e, f, A, in, alpha, beta, delta, k, p); break;
-        case SH_OR_AND_I32: rc = launch_sparse<OrAndI32>(e, f, A, in, alpha, beta, delta, k, p); break;
-        default: rc = launch_sparse<MaxMinI32>(e, f, A, in, alpha, beta, delta, k, p); break;
-        }
-        if (rc)
-          return rc;
-      } else {
-        StepDev st{f->d_ctl->flag + k, (const uint32_t *)in->d, 0, delta, f->d_ctl->go + k};
-        int rc = dispatch(e, sr, A, in, y, alpha, beta, out, st);
-        if (rc)
-          return rc;
-        hipLaunchKernelGGL(frontier_detect, dgrid, dim3(WL_BS), 0, e->stream, f->d_ctl, k, p ^ 1, (const uint32_t *)in->d,
-                           (const uint32_t *)out->d, (int32_t)A->rows, f->d_col_ptr, f->d_clist, f->d_cplist);
-        HIP_TRY(e, hipGetLastError());
-        sh_vec *t = in; in = out; out = t;
-        y = in;
+    return SH_OK;
+  };
+  auto enqueue = [&](int32_t L, int k, const PingPong &b, bool *swaps) -> int {
+    const int p = L & 1;
+    *swaps = !sparse;
+    if (sparse) {
+      switch (sr) {
+      case SH_MIN_PLUS_F32: RC_TRY(launch_sparse<MinPlusF32>(e, f, A, b.in, alpha, beta, delta, k, p)); break;
+      case SH_OR_AND_I32: RC_TRY(launch_sparse<OrAndI32>(e, f, A, b.in, alpha, beta, delta, k, p)); break;
+      default: RC_TRY(launch_sparse<MaxMinI32>(e, f, A, b.in, alpha, beta, delta, k, p)); break;
       }
-      hipLaunchKernelGGL(frontier_decide, dim3(1), dim3(64), 0, e->stream, f->d_ctl, k, p, sparse ? 0 : 1, (int32_t)A->rows, max_entries,
-                         (!never_sparse && L + 1 >= 2) ? 1 : 0, sparse ? 1 : 0);
+    } else {
+      StepDev st{f->d_ctl->flag + k, (const uint32_t *)b.in->d, 0, delta, f->d_ctl->go + k};
+      RC_TRY(dispatch(e, sr, A, b.in, b.y, alpha, beta, b.out, st));
+      hipLaunchKernelGGL(frontier_detect, dgrid, dim3(WL_BS), 0, e->stream, f->d_ctl, k, p ^ 1, (const uint32_t *)b.in->d,
+                         (const uint32_t *)b.out->d, (int32_t)A->rows, f->d_col_ptr, f->d_clist, f->d_cplist);
       HIP_TRY(e, hipGetLastError());
-      HIP_TRY(e, hipEventRecord(e->ev_iter[k + 1], e->stream));
     }
-    HIP_TRY(e, hipMemcpyAsync(f->h_rec, f->d_ctl->rec, sizeof(FrontierRec) * FR_BATCH, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-    int ran = 0;
-    while (ran < nb && f->h_rec[ran].ran) ran++;
-    if (ran < 1)
+    hipLaunchKernelGGL(frontier_decide, dim3(1), dim3(64), 0, e->stream, f->d_ctl, k, p, sparse ? 0 : 1, (int32_t)A->rows, max_entries,
+                       (!never_sparse && L + 1 >= 2) ? 1 : 0, sparse ? 1 : 0);
+    HIP_TRY(e, hipGetLastError());
+    return SH_OK;
+  };
+  auto settle = [&](int32_t first, int nb, int *ran, bool *over) -> int {
+    while (*ran < nb && f->h_rec[*ran].ran) ++*ran;
+    if (*ran < 1)
       return fail(e, SH_EHIP, "sh_iterate_frontier: the first launch of a batch did not report");
-    for (int k = 0; k < ran; k++) {
-      float ms = 0.f;
-      HIP_TRY(e, hipEventElapsedTime(&ms, e->ev_iter[k], e->ev_iter[k + 1]));
-      const uint64_t ns = (uint64_t)((double)ms * 1e6);
-      if (ns_per_iter) ns_per_iter[it + k] = ns;
-      if (mode_per_iter) mode_per_iter[it + k] = sparse ? 1 : 0;
-      if (changed_per_iter) changed_per_iter[it + k] = (int64_t)f->h_rec[k].changed;
-      if (active_per_iter) active_per_iter[it + k] = (int64_t)f->h_rec[k].active;
-      total += ns;
+    for (int k = 0; k < *ran; k++) {
+      if (mode_per_iter) mode_per_iter[first + k] = sparse ? 1 : 0;
+      if (changed_per_iter) changed_per_iter[first + k] = (int64_t)f->h_rec[k].changed;
+      if (active_per_iter) active_per_iter[first + k] = (int64_t)f->h_rec[k].active;
     }
-    // the gated launches behind the last one that ran wrote nothing; dense ones were enqueued with swapped buffers
-    if (!sparse && (nb - ran) % 2) { sh_vec *t = in; in = out; out = t; }
-    y = in;
-    term = f->h_rec[ran - 1].differs == 0;
-    sparse = f->h_rec[ran - 1].sparse_next != 0;
-    it += ran;
-  }
-  if (in != x) {
-    HIP_TRY(e, hipMemcpyAsync(x->d, in->d, A->rows * 4, hipMemcpyDeviceToDevice, e->stream));
-    HIP_TRY(e, hipStreamSynchronize(e->stream));
-  }
-  *iters = it;
-  *converged = term ? 1 : 0;
+    *over = f->h_rec[*ran - 1].differs == 0;
+    sparse = f->h_rec[*ran - 1].sparse_next != 0;
+    return SH_OK;
+  };
+  RC_TRY(run_dense_batches<FR_BATCH>(e, pp, max_iters, Readback{f->h_rec, f->d_ctl->rec, sizeof(FrontierRec) * FR_BATCH}, ns_per_iter,
+                                     &run, begin, enqueue, settle));
+  RC_TRY(pp.hand_back(e, x, A->rows * 4));
+  *iters = run.launches;
+  *converged = run.over ? 1 : 0;
   if (total_ns)
-    *total_ns = total;
+    *total_ns = run.total_ns;
   return SH_OK;
 }
 
