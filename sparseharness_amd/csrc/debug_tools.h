@@ -182,6 +182,18 @@ extern "C" int sh_debug_emulate_plan(int64_t rows, int64_t cols, int64_t nnz, co
   if (semiring == 3) return emulate<HMaxMin>(H, rows, cols, (const uint32_t *)x, (uint32_t *)y, stats);
   return -2;
 }
+// How the host builder codes the values of a matrix (CPU tests: which phase-1 instantiation a value set selects):
+// *code_bits = 0 raw words, else 4 / 8 / 16; *distinct = the dictionary's words in use.  0, or -1: the builder refused.
+extern "C" int sh_debug_plan_coding(int64_t rows, int64_t cols, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                                    const sh_plan_options *opt_p, int32_t *code_bits, int32_t *distinct) {
+  sh_plan_options opt;
+  if (opt_p) opt = *opt_p; else sh_plan_options_default(&opt);
+  TiledHost H;
+  if (!build_tiled_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, 256, H)) return -1;
+  *code_bits = H.vdict.empty() ? 0 : H.code_bits;
+  *distinct = H.vdict.empty() ? 0 : H.vdict_used;
+  return 0;
+}
 // The CSR arrays of a matrix on the device as the device builders take them, owned by `own`: NULL, or the HIP call that failed.
 static const char *debug_upload_csr(DevArrays &own, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                                     int32_t **d_rp, int32_t **d_ci, uint32_t **d_val) {
@@ -381,6 +393,51 @@ extern "C" int sh_debug_set_P(sh_engine *e, sh_csr *m, uint64_t address) {
   if (hipStreamSynchronize(e->stream) != hipSuccess) return SH_EHIP;
   m->tiled.d_P = (uint32_t *)(uintptr_t)address;
   return SH_OK;
+}
+// Launch hygiene (tests/test_hygiene_gpu.py): what a launch may read is what it wrote itself.  Drains the stream, then
+// fills the per-launch scratch of every layout the matrix holds -- data words and flags only, never a word that is read
+// as an address: data_word into P (the identity group behind the products included), the heavy rows' partials, the
+// long-row partials of the stream plan and the bitmap and partials of the bit-blocked layout; live_word into the
+// tiles' live words; PIECE_DEAD (which phase 2 handles in bounds) into the marked piece table when dead_piece != 0.
+// sizes[0..7]: the bytes filled of P, tpartial, tile_live, ptab_live, partial, partial_multi, xbits, bits_partial
+// (0: the matrix has no such array).
+extern "C" int sh_debug_poison_scratch(sh_engine *e, sh_csr *m, uint32_t data_word, uint32_t live_word, int dead_piece, int64_t *sizes) {
+  if (!e || !m || !sizes) return SH_EINVAL;
+  if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return SH_EHIP;
+  bool ok = true;
+  auto fill = [&](void *p, size_t bytes, uint32_t word) -> int64_t {
+    if (!p || bytes < 4) return 0;
+    ok = ok && hipMemsetD32Async((hipDeviceptr_t)p, (int)word, bytes / 4, e->stream) == hipSuccess;
+    return (int64_t)(bytes / 4 * 4);
+  };
+  const TiledLayout &t = m->tiled;
+  const StreamLayout &s = m->stream;
+  const BitsLayout &b = m->bits;
+  sizes[0] = fill(t.d_P, t.dev.size_of(t.d_P), data_word);
+  sizes[1] = fill(t.d_tpartial, t.dev.size_of(t.d_tpartial), data_word);
+  sizes[2] = fill(t.d_tile_live, t.dev.size_of(t.d_tile_live), live_word);
+  sizes[3] = dead_piece ? fill(t.d_ptab_live, t.d_ptab_live ? (size_t)t.n_pieces * 4 : 0, (uint32_t)PIECE_DEAD) : 0;
+  sizes[4] = fill(s.d_partial, s.dev.size_of(s.d_partial), data_word);
+  sizes[5] = fill(s.d_partial_multi, s.dev.size_of(s.d_partial_multi), data_word);
+  sizes[6] = fill(b.d_xbits, b.dev.size_of(b.d_xbits), data_word);
+  sizes[7] = fill(b.d_bits_partial, b.dev.size_of(b.d_bits_partial), data_word);
+  return ok && hipStreamSynchronize(e->stream) == hipSuccess ? SH_OK : SH_EHIP;
+}
+// ... and the device halves of the words a batch of dense launches writes (DenseLoopState), those that a loop has opened
+// so far.  sizes[0..2]: the bytes filled of flags, mflags, bstate (0: not open yet).
+extern "C" int sh_debug_poison_loop_words(sh_engine *e, uint32_t word, int64_t *sizes) {
+  if (!e || !sizes) return SH_EINVAL;
+  if (hipSetDevice(e->device) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) return SH_EHIP;
+  bool ok = true;
+  auto fill = [&](void *d, size_t bytes) -> int64_t {
+    if (!d || bytes < 4) return 0;
+    ok = ok && hipMemsetD32Async((hipDeviceptr_t)d, (int)word, bytes / 4, e->stream) == hipSuccess;
+    return (int64_t)(bytes / 4 * 4);
+  };
+  sizes[0] = fill(e->dense.flags.d, e->dense.flags.size);
+  sizes[1] = fill(e->dense.mflags.d, e->dense.mflags.size);
+  sizes[2] = fill(e->dense.bstate.d, e->dense.bstate.size);
+  return ok && hipStreamSynchronize(e->stream) == hipSuccess ? SH_OK : SH_EHIP;
 }
 // (slab experiments, tools/slab_probe.py) words of the matrix's product array, for a host-side bounds check before matrices share one
 extern "C" int64_t sh_debug_p_len(const sh_csr *m) { return m && m->plan == PLAN_TILED ? m->tiled.p_len : -1; }

@@ -43,7 +43,9 @@ using namespace sh;
 template <class T>
 struct BatchWords {
   T *d = nullptr, *h = nullptr;
+  size_t size = 0;   // the bytes behind each half
   hipError_t open(size_t bytes) {
+    size = bytes;
     hipError_t r = d ? hipSuccess : hipMalloc((void **)&d, bytes);
     if (r == hipSuccess && !h) r = hipHostMalloc((void **)&h, bytes, hipHostMallocDefault);
     return r;
