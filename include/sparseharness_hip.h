@@ -412,7 +412,8 @@ int sh_bits_to_column(sh_engine *e, const sh_vec *B, int64_t n, int32_t words, i
  * NULL.  The order of the rows inside one column is unspecified.
  *
  * sh_iterate_frontier: sh_iterate's contract for x / y0 / scratch / alpha / beta / delta / max_iters / iters / converged /
- * ns_per_iter / total_ns, and the same result bit for bit.  f may serve any number of calls, one at a time.
+ * ns_per_iter / total_ns, and the same result bit for bit.  Of x and scratch (vectors of >= rows elements) `rows` elements
+ * are overwritten, no more; y0 is only read.  f may serve any number of calls, one at a time.
  * dense_share: a launch k >= 2 runs sparse when (entries of the transposed columns in C_k) <= dense_share * nnz, dense
  *   otherwise (launches 0 and 1 are always dense).  0: every launch dense (sh_iterate plus the change detection);
  *   >= 1: every launch from 2 on sparse; negative: the engine's default.
@@ -490,8 +491,9 @@ int sh_iterate_frontier(sh_engine *e, sh_semiring sr, const sh_csr *A, sh_fronti
  *     8 * (rows + 1) + 8 * edges  +  8 * rows  +  8 * W  +  16 * (edges / 1024 + 1)  +  8 * (edges / 2048 + 1)  +  18432.
  * sh_bfs_graph_edges: the entries kept as edges.
  *
- * sh_bfs_levels: level, parent (may be NULL): int32 vectors of >= rows elements, written in full; x0 is only read; level
- * and parent must not alias x0 or each other.  g may serve any number of calls, one at a time.
+ * sh_bfs_levels: level, parent (may be NULL): int32 vectors of >= rows elements; `rows` elements of each are overwritten,
+ * no more; x0 is only read (`rows` elements, no more); level and parent must not alias x0 or each other.  g may serve
+ * any number of calls, one at a time.
  * max_levels >= 1.  The per-level arrays (each may be NULL) have capacity max_levels + 1 for size_per_level (entry 0 =
  * the number of sources, entry L + 1 = vertices step L assigned) and max_levels for the others; one entry per step that
  * ran, entries beyond are not written.
@@ -587,8 +589,9 @@ int sh_bfs_levels(sh_engine *e, sh_bfs_graph *g, const sh_vec *x0, sh_vec *level
  *     8 * (rows + 1) + 16 * edges + 20 * rows + 16 * (edges / 1024 + 1) + 8 * (edges / 2048 + 1) + 22528.
  * sh_sssp_graph_edges: the entries kept as edges.  sh_sssp_graph_delta: the default bucket width (0 for a graph without edges).
  *
- * sh_sssp: dist (float32) and pred (int32, may be NULL): vectors of >= rows elements, written in full (pred only by a
- * complete run); x0 is only read; dist and pred must not alias x0 or each other.  g may serve any number of calls, one at
+ * sh_sssp: dist (float32) and pred (int32, may be NULL): vectors of >= rows elements; `rows` elements of each are
+ * overwritten, no more (pred only by a complete run: a run cut short leaves every word of pred as it was); x0 is only
+ * read (`rows` elements, no more); dist and pred must not alias x0 or each other.  g may serve any number of calls, one at
  * a time.  max_rounds >= 1.  A ROUND relaxes the out-edges of every vertex of the near list; when the list ran empty the
  * next round opens by moving the threshold to the end of the bucket that holds the smallest far distance (empty buckets
  * cost no round) and carrying over what falls below it.  The per-round arrays (each may be NULL) have capacity max_rounds:
@@ -689,7 +692,8 @@ int sh_sssp(sh_engine *e, sh_sssp_graph *g, const sh_vec *x0, sh_vec *dist, sh_v
  *     8 * (rows + 1) + 8 * edges + 20 * rows + 32 * (edges / 1024 + 1) + 8 * (edges / 2048 + 1) + 34816.
  * sh_scc_graph_edges: the entries kept as edges.
  *
- * sh_scc: comp: an int32 vector of >= rows elements, written in full.  g may serve any number of calls, one at a time.
+ * sh_scc: comp: an int32 vector of >= rows elements; `rows` elements are overwritten, no more.  g may serve any number
+ * of calls, one at a time.
  * max_steps >= 1.  The per-round arrays (each may be NULL) have capacity max_steps; one entry per recorded round:
  * size_per_round = vertices the round settled; steps_per_round, edges_per_round (edges looked at), ns_per_round and
  * total_ns are informational (the sweeps race, so their number may differ from run to run); ns_per_round / total_ns are
@@ -790,7 +794,8 @@ int sh_scc(sh_engine *e, sh_scc_graph *g, sh_vec *comp, int32_t trim, int32_t pi
  *     8 * (rows + 1) + 8 * edges + 8 * rows + 16 * (edges / 1024 + 1) + 8 * (edges / 2048 + 1) + 34816.
  * sh_wcc_graph_edges: the entries kept as edges.
  *
- * sh_wcc: comp: an int32 vector of >= rows elements, written in full.  g may serve any number of calls, one at a time.
+ * sh_wcc: comp: an int32 vector of >= rows elements; `rows` elements are overwritten, no more.  g may serve any number
+ * of calls, one at a time.
  * sample >= 0: the number of stored neighbours per vertex that the sampling rounds look at (the Python binding's default
  * is 2).  max_rounds >= 1.  The per-round arrays (each may be NULL) have capacity max_rounds, one entry per round:
  * hooks_per_round (compare-and-swaps won), jumps_per_round (pointers changed), edges_per_round (entries looked at),
@@ -826,7 +831,7 @@ int sh_wcc(sh_engine *e, sh_wcc_graph *g, sh_vec *comp, int32_t sample, int32_t 
  *      whose 32 bits are not all zero is an entry that counts.  The graph is the SIMPLE UNDIRECTED graph under those
  *      entries: {u, v} with u != v is one edge if either row stores the other, once or many times.  Self-loops, parallel
  *      entries, stored zeros and columns outside the matrix are legal and change nothing.  M = the number of such edges.
- *        tri[v]      = the number of triangles {v, a, b} of that graph, an unsigned 64-bit count, written in full.
+ *        tri[v]      = the number of triangles {v, a, b} of that graph, an unsigned 64-bit count per vertex.
  *        deg[v]      = the degree of v in that graph (int32).  The local clustering coefficient is then
  *                      2 * tri / (deg * (deg - 1)), one line for the caller; there is no call for it.
  *        *triangles  = the number of triangles = (the sum of tri[v]) / 3.
@@ -881,7 +886,8 @@ int sh_wcc(sh_engine *e, sh_wcc_graph *g, sh_vec *comp, int32_t sample, int32_t 
  * sh_tri: tri: NULL, or a vector of >= 2 * rows four-byte elements, 8-byte aligned, read as `rows` little-endian uint64
  * (as the `words` per vertex of sh_bits_*: all elements are still 4 bytes); 2 * rows elements are overwritten, no more.
  * With tri == NULL the call gives the total only and does not pay for the per-vertex adds.  deg: NULL, or an int32 vector
- * of >= rows elements.  A per-vertex count above 2^32 needs a vertex in more than 4.29e9 triangles; no test reaches that:
+ * of >= rows elements; `rows` elements are overwritten, no more.  A per-vertex count above 2^32 needs a vertex in more
+ * than 4.29e9 triangles; no test reaches that:
  * the high word of tri[v] is untested beyond being zero.  *triangles above 2^31 is tested (K_2400).
  * *probes (may be NULL) is informational: the list entries the count looked at, each time it looked (the entries of N+(a)
  * once, every streamed entry of an N+(b) once, every entry a bisection compared with).  *total_ns (may be NULL) is device
@@ -912,7 +918,7 @@ int sh_tri(sh_engine *e, sh_tri_graph *g, sh_vec *tri, sh_vec *deg,
  *      u != v is one edge if either row stores the other, once or many times.  Self-loops, parallel entries, stored
  *      zeros, columns outside the matrix and direction are legal and change nothing.  M = the number of such edges.
  *        core[v]      = the core number of v: the largest k such that v lies in a subgraph whose vertices all have at
- *                       least k neighbours in it (int32, written in full).
+ *                       least k neighbours in it (int32, one per vertex).
  *        deg[v]       = the degree of v in that graph (int32), as sh_tri's.
  *        *degeneracy  = max core[v]; 0 for a graph without edges or rows.
  *        *levels      = the number of distinct values in core.
@@ -989,13 +995,13 @@ int sh_tri(sh_engine *e, sh_tri_graph *g, sh_vec *tri, sh_vec *deg,
  * sh_core_graph_edges: M.  sh_core_graph_max_degree: the largest degree (the length of the longest list).
  *
  * sh_core: core: an int32 vector of >= rows elements; `rows` elements are overwritten, no more.  deg: NULL, or an int32
- * vector of >= rows elements.  chase >= 0 (the Python binding's default: see the rule above).  max_rounds >= 1 bounds the
- * rounds; rows + 1 can never cut a run short (the Python binding's default).  The per-round arrays (capacity max_rounds;
- * each may be NULL): k_per_round the k being peeled, size_per_round the vertices taken from the round's work list,
- * chased_per_round the vertices settled inside the launch without passing through a list, edges_per_round the list
- * entries looked at, ns_per_round device time; size + chased over all rounds of a complete run is `rows`.  *total_ns
- * (may be NULL) is device time (hipEvent) as elsewhere.  g may serve any number of calls, one at a time; every call
- * starts from cur = deg.
+ * vector of >= rows elements, of which `rows` are overwritten, no more.  chase >= 0 (the Python binding's default: see
+ * the rule above).  max_rounds >= 1 bounds the rounds; rows + 1 can never cut a run short (the Python binding's
+ * default).  The per-round arrays (capacity max_rounds; each may be NULL): k_per_round the k being peeled,
+ * size_per_round the vertices taken from the round's work list, chased_per_round the vertices settled inside the launch
+ * without passing through a list, edges_per_round the list entries looked at, ns_per_round device time; size + chased
+ * over all rounds of a complete run is `rows`.  *total_ns (may be NULL) is device time (hipEvent) as elsewhere.  g may
+ * serve any number of calls, one at a time; every call starts from cur = deg.
  * SH_EINVAL: NULL arguments (engine, graph, core, degeneracy, levels, rounds, complete, out, the arrays), rows < 0,
  * nnz < 0, chase < 0, max_rounds < 1.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases, core
  * or deg shorter than rows.  All are reported before any device work, with the buffers untouched.
@@ -1097,13 +1103,13 @@ int sh_core(sh_engine *e, sh_core_graph *g, sh_vec *core, sh_vec *deg, int32_t c
  *     4 * (rows + 1) + 4 * rows + 40 * edges + 51200.
  * sh_truss_graph_edges: M.  sh_truss_graph_max_degree: the largest degree (the length of the longest list).
  *
- * sh_truss: truss: an int32 vector of >= M elements; exactly M elements are overwritten.  support, edge_u, edge_v: each
- * NULL, or an int32 vector of >= M elements.  max_rounds >= 0 bounds the rounds; M + 1 can never cut a run short (the
- * Python binding's default); with 0 the call stops after the support pass (support, *triangles and the ends are valid,
- * truss is 0).  M == 0 gives 0 rounds and *complete = 1.  The per-round arrays (capacity max_rounds; each may be NULL)
- * are listed above; ns_per_round is device time, and *total_ns (may be NULL) the device time of the support pass and
- * all rounds (hipEvent) as elsewhere.  A call cut short leaves the handle reusable; g may serve any number of calls,
- * one at a time; every call starts from the support pass.
+ * sh_truss: truss: an int32 vector of >= M elements; M = G.edges elements are overwritten, no more.  support, edge_u,
+ * edge_v: each NULL, or an int32 vector of >= M elements, of which M are overwritten, no more.  max_rounds >= 0 bounds
+ * the rounds; M + 1 can never cut a run short (the Python binding's default); with 0 the call stops after the support
+ * pass (support, *triangles and the ends are valid, truss is 0).  M == 0 gives 0 rounds and *complete = 1.  The
+ * per-round arrays (capacity max_rounds; each may be NULL) are listed above; ns_per_round is device time, and *total_ns
+ * (may be NULL) the device time of the support pass and all rounds (hipEvent) as elsewhere.  A call cut short leaves
+ * the handle reusable; g may serve any number of calls, one at a time; every call starts from the support pass.
  * SH_EINVAL: NULL arguments (engine, graph, truss, max_truss, levels, rounds, complete, triangles, out, the arrays),
  * rows < 0, nnz < 0, max_rounds < 0.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases;
  * truss, support, edge_u or edge_v shorter than M.  All are reported before any device work, with the buffers untouched.

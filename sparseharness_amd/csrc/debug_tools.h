@@ -2,6 +2,8 @@
 // emulate.so; never the product build): the host emulator of the tiled / bit plans, the host-vs-device builder
 // comparison, the builders' verdicts, the switches that lower the limit on P or fail a device build step, and the placement
 // probes (sh_debug_*), used by tests/test_plan_cpu.py, tests/test_plan_limits_*.py, tests/test_builder_gpu.py and tools/.
+// The poison hook of the graph handles, sh_debug_poison_graph, is the tools build's too but lives in debug_graph_tools.h:
+// it has to stand behind the handle structs of engine.hip, which are defined after this file is included.
 #pragma once
 // Tools / CPU tests only (never in the product build): build the tiled plan on the host and execute BOTH phases
 // on the host, entry by entry, through exactly the tables the kernels read (fold flags, obase, gdest, gblk / ptab,

@@ -3220,3 +3220,7 @@ int sh_truss(sh_engine *e, sh_truss_graph *g, sh_vec *truss, sh_vec *support, sh
 }
 
 } // extern "C"
+
+#ifdef SH_PLAN_EMULATE
+#include "debug_graph_tools.h"   // (behind the graph handles it fills)
+#endif
