@@ -1128,6 +1128,122 @@ int sh_truss(sh_engine *e, sh_truss_graph *g, sh_vec *truss, sh_vec *support, sh
              int32_t *k_per_round, int64_t *size_per_round, int64_t *walked_per_round, uint64_t *ns_per_round,
              uint64_t *total_ns);
 
+/* ---- greedy vertex colouring in a fixed priority order, in Jones-Plassmann rounds -------------------------------------
+ * (the reference has no counterpart: its apps are SpMV, PageRank, BFS, SSSP and SCC label propagation; this is the fourth
+ * piece on sh_tri's graph, after the triangles, sh_core's core numbers and sh_truss's truss numbers.  A colouring says
+ * which rows can be processed together because no entry couples them: the start of a multicolour Gauss-Seidel or SOR
+ * sweep, of an incomplete factorisation by colours, of a Jacobian compression, of a lock-free scatter; colour class 0 is
+ * a maximal independent set, the start of algebraic-multigrid coarsening.)
+ *
+ * The graph and the edge rule are sh_tri's, word for word: the matrix is square (rows x rows); entry j of row r storing
+ * column c with 0 <= c < rows counts when its 32 value bits are not all zero; the graph is the SIMPLE UNDIRECTED graph
+ * under those entries.  Self-loops, parallel entries, stored zeros, the direction of an entry and columns outside the
+ * matrix change nothing.  M is its number of edges.
+ *      The order.  Vertex v PRECEDES u when (primary(v), tie(v)) > (primary(u), tie(u)), compared lexicographically.
+ *      primary(v) is prio[v] (signed int32) when prio is given; otherwise deg[v] when order == 2, else 0.  For order == 0
+ *      the tie is "the smaller index first"; for order == 1 and order == 2 it is "the larger mix32(v ^ seed) first", with
+ *        mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (on uint32_t).
+ *      mix32 is a bijection of the 32-bit words (each step is one), so no two vertices tie and the order is total.  The
+ *      three orders are natural first-fit (0), random, JP-R (1) and largest-degree-first, JP-LF (2).  prio makes any other
+ *      order reachable: sh_core's core vector as prio approximates smallest-last (no bound on the colours is claimed
+ *      for that).
+ *      color[v]   = the smallest colour >= 0 held by no neighbour that precedes v: the first-fit colouring that a serial
+ *                   loop over the vertices in that order gives (int32, one per vertex).  -1 while v is uncoloured, which
+ *                   a caller sees only after a call cut short by max_rounds (*complete is 0 then).
+ *      *colors    = the largest colour plus 1 (at most the largest degree plus 1); 0 without rows.
+ *      *coloured  = the number of vertices with a colour.
+ *      *rounds    = the rounds run; in a complete run the number of vertices on the longest chain v1 precedes v2
+ *                   precedes ... along edges.
+ *      Round r's list is exactly the vertices whose chain depth is r, so *rounds, size_per_round and edges_per_round (the
+ *      sum of the list lengths of the round's vertices) are deterministic.  The colour of a vertex depends only on the
+ *      colours of the neighbours that precede it, so a graph and an order have one answer: every comparison is ==.  The
+ *      colours do not depend on window, the schedule or the run.
+ *
+ *      Schedule (csrc/color.hip.h; the work-efficient Jones-Plassmann of Hasenplaugh, Kaler, Schardl, Leiserson, SPAA
+ *      2014).  wait[v] is the number of uncoloured neighbours that precede v.  One pass over all lists counts it, the key
+ *      of a neighbour computed on the spot (one read of deg[u] or prio[u]; no key array is stored): lists of up to 8
+ *      entries one lane, up to 2048 one wave, longer ones in pieces of 2048 with one atomic add per piece.  Behind that
+ *      kernel boundary every v with wait[v] == 0 joins the list of round 0.  A round is one fixed set of two launches
+ *      enqueued ahead of the host in batches (8, 16, 32, 32, ...), each of which returns at once unless the control block
+ *      on the device gives it work.  The first walks the list of every vertex v of the round's work list once: an entry u
+ *      with color[u] >= 0 precedes v and its colour is marked as taken; an entry u with color[u] < 0 is preceded by v
+ *      and wait[u] gets one atomic decrement -- the one lane that reads the old value 1 owns u and appends it to the next
+ *      list.  No key is compared in a round and no restore is needed: each preceding neighbour decrements exactly once.
+ *      There is no compare-and-swap, no retry and no waiting.  The marks: one lane keeps a 32-bit mask in a register
+ *      (lists of up to 8 entries: the colour is at most 8); one wave a bitmap of 2049 bits in LDS (up to 2048 entries); a
+ *      longer list sits at the far end of the work list and a whole workgroup takes it, with an LDS bitmap of `window`
+ *      colours (0: 32768 bits, 4 KB) -- when every colour of the window is taken it walks the list again for the next
+ *      window, only the first walk decrements, at most len / window + 1 walks.  The second launch sums the workgroups'
+ *      counts, folds the largest colour, swaps the lists, records the round and finishes when coloured == rows.  The
+ *      work over all rounds is one pass over the lists plus the one for the counts, not one pass per round.
+ *      Why that is right: of two neighbours one precedes the other, and the later one's word stays above zero until the
+ *      launch that colours the earlier one, so two vertices of one list are never adjacent and no color[u] read in a
+ *      launch is written in it.  Every vertex is coloured once and joins a list once, so a list of `rows` places cannot
+ *      overflow; no kernel ever waits for another kernel's write; every loop is bounded by a list length, `rows` or
+ *      len / window + 1.
+ *      Worst cases: the number of rounds is the longest chain in the order, not the diameter -- the natural order on a
+ *      path of n vertices takes n rounds, each costing its two launches however small its list is; K_n takes n rounds
+ *      under every order, with n walks of n - 1 entries; a long list whose colour lies beyond the first window is walked
+ *      once per window up to its colour.
+ *
+ *      Measured on an MI355X (DESIGN.md "6l Greedy vertex colouring"; tools/color_bench.py, one process per matrix, the
+ *        three orders and the host gold alternating, 5 rounds, device time against the wall time of
+ *        hostlib.greedy_colors in the same order and process), median (min-max) in ms, rounds, colours: the 2048 x 2048
+ *        grid (4 194 304 rows, 8 384 512 edges, largest degree 4): order 0: 63.16 (63.06-63.30), 4095 rounds, 2 colours
+ *        (host gold 603); order 1: 3.91 (3.91-3.92), 15, 5 (1259); order 2: 3.93 (3.92-3.93), 15, 5 (1254).  R-MAT-18
+ *        (262 144 rows, 3 805 085 edges, largest degree 25 104, degeneracy 374): order 0: 97.74 (97.59-97.77), 943, 162
+ *        (281); order 1: 101.73 (101.72-102.15), 916, 168 (317); order 2: 70.20 (70.13-70.26), 883, 123 (311).  R-MAT-20
+ *        (1 048 576 rows, 15 702 281 edges, largest degree 64 290, degeneracy 609): order 0: 272.2 (271.9-272.8), 1639,
+ *        237 (1266); order 1: 265.1 (265.1-266.1), 1637, 242 (1457); order 2: 161.8 (161.4-162.1), 1506, 182 (1458).
+ *        The handle is built in 0.06 s on each.  A round of two launches costs about 15 us however small its list is
+ *        (the grid in natural order: 4095 rounds of at most 2048 vertices); on the R-MATs a round costs 79 to 166 us on
+ *        average, and the call costs its rounds.
+ *        Rule: the binding's default is order = 2, the fewest colours and the fastest arm on both R-MATs and within
+ *        0.5 % of order 1 on the grid; a call is 0.003 (grid, orders 1 and 2) to 0.35 (R-MAT-18, order 0) of the host's
+ *        serial loop.  Use order 0 only where the natural order is wanted as such: its rounds follow the numbering
+ *        (a path numbered end to end takes one round per vertex).  Graphs below 10^6 edges, prio vectors and windows
+ *        other than the default are unmeasured.
+ *
+ * sh_color_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  The handle holds on the device:
+ * adj_ptr[rows + 1], adj_col[2M] (sh_core_graph's symmetric lists, every list strictly ascending), deg[rows], wait[rows],
+ * two work lists of `rows` places each (a vertex joins a list once per call: they cannot overflow), which keep the
+ * vertices of the workgroup class at their far end, so that no list of pieces is stored, and a control block with one
+ * count per workgroup.  rows == 0 gives a valid handle.  Freeing NULL is SH_OK.  The build runs on the device, once, and
+ * is sh_core_graph_create's (one helper serves both): while it runs it needs 4 * (rows + 1) + 16 * nnz + 8 bytes for the
+ * arrays as given, their flags and scan, 16 bytes per surviving entry for the keys and the sorted keys, 32 bytes per edge
+ * for the keys both ways and their sorted copy, and the sort's own scratch; all of it is released before the call
+ * returns.  nnz is bounded as for the other handles, and 2M by 2^31 - 256.
+ * sh_color_graph_footprint: device bytes held =
+ *     4 * (rows + 1) + 16 * rows + 8 * edges + 17408.
+ * sh_color_graph_edges: M.  sh_color_graph_max_degree: the largest degree (the length of the longest list).
+ *
+ * sh_color: color: an int32 vector of >= rows elements; `rows` elements are overwritten, no more.  prio: NULL, or an
+ * int32 vector of >= rows elements, which is only read.  order in 0..2 (the Python binding's default: 2).  seed: any
+ * word.  window: 0, or a multiple of 64 in [64, 32768].  max_rounds >= 1 bounds the rounds; rows + 1 can never cut a run
+ * short (the Python binding's default).  coloured may be NULL.  The per-round arrays (capacity max_rounds; each may be
+ * NULL): size_per_round the vertices of the round's list, edges_per_round the sum of their list lengths, ns_per_round
+ * device time.  *total_ns (may be NULL) is the device time of the counting pass and all rounds (hipEvent) as elsewhere.
+ * A call cut short leaves the handle reusable; g may serve any number of calls, one at a time; every call starts from
+ * the counting pass.  rows == 0 gives SH_OK with zeros and *complete = 1.
+ * SH_EINVAL: order outside 0..2, window neither 0 nor a multiple of 64 in [64, 32768], max_rounds < 1 (the scalars are
+ * checked first); NULL arguments (engine, graph, color, colors, rounds, complete, out, the arrays), rows < 0, nnz < 0.
+ * SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases; color or prio shorter than rows.  All are
+ * reported before any device work, with the buffers untouched.
+ * NOT covered: distance-2 and bipartite colouring, balancing the classes, recolouring to fewer colours, the
+ * smallest-last order as such, the multi-GPU driver, row pieces (sh_spmv_step_pieces), the C++ harness apps, incremental
+ * updates.
+ */
+typedef struct sh_color_graph sh_color_graph;
+int sh_color_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                          const void *val, sh_color_graph **out);
+int sh_color_graph_free(sh_engine *e, sh_color_graph *g);
+int sh_color_graph_footprint(const sh_color_graph *g, uint64_t *device_bytes);
+int sh_color_graph_edges(const sh_color_graph *g, int64_t *edges);          /* M */
+int sh_color_graph_max_degree(const sh_color_graph *g, int64_t *entries);
+int sh_color(sh_engine *e, sh_color_graph *g, sh_vec *color, sh_vec *prio, int32_t order, uint32_t seed, int32_t window,
+             int32_t max_rounds, int32_t *colors, int32_t *rounds, int32_t *complete, int64_t *coloured,
+             int64_t *size_per_round, int64_t *edges_per_round, uint64_t *ns_per_round, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,18 +9,20 @@ scc_label / scc_decide, scc.hip.h), or one of the WCC kernels (wcc_init / wcc_sa
 wcc_decide / wcc_label, wcc.hip.h), or one of the triangle kernels (tri_count_light / tri_count_heavy, each with and without
 per-vertex counts, and tri_finish, tri.hip.h), or one of the core-number kernels (core_init / core_min / core_open / core_peel /
 core_close, core.hip.h), or one of the truss kernels (truss_init / truss_support / truss_total / truss_min / truss_open /
-truss_peel / truss_close, truss.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+truss_peel / truss_close, truss.hip.h), or one of the colouring kernels (gcol_init / gcol_count / gcol_ready / gcol_assign /
+gcol_close, color.hip.h; the prefix is their own because scc.hip.h speaks of colouring too), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core, seen_truss = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
+bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core, seen_truss, seen_gcol = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
 BFS_KERNELS = ("bfs_init", "bfs_topdown", "bfs_bottomup", "bfs_queue_from_bitmap", "bfs_decide", "bfs_parents")
 SSSP_KERNELS = ("sssp_init", "sssp_relax", "sssp_split", "sssp_decide", "sssp_preds")
 SCC_KERNELS = ("scc_init", "scc_trim", "scc_pick", "scc_seed", "scc_propagate", "scc_claim", "scc_label", "scc_decide")
 TRI_KERNELS = ("tri_count_light", "tri_count_heavy", "tri_finish")
 CORE_KERNELS = ("core_init", "core_min", "core_open", "core_peel", "core_close")
 TRUSS_KERNELS = ("truss_init", "truss_support", "truss_total", "truss_min", "truss_open", "truss_peel", "truss_close")
+GCOL_KERNELS = ("gcol_init", "gcol_count", "gcol_ready", "gcol_assign", "gcol_close")
 WCC_KERNELS = ("wcc_init", "wcc_sample", "wcc_compact", "wcc_full", "wcc_jump", "wcc_decide", "wcc_label")
 for blk in text.split("remark: Function Name: ")[1:]:
     name = blk.split()[0]
@@ -34,9 +36,12 @@ for blk in text.split("remark: Function Name: ")[1:]:
     tri = any(k in name for k in TRI_KERNELS)
     core = any(k in name for k in CORE_KERNELS)
     truss = any(k in name for k in TRUSS_KERNELS)
-    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core and not truss:
+    gcol = any(k in name for k in GCOL_KERNELS)
+    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core and not truss and not gcol:
         continue
-    if truss:
+    if gcol:
+        seen_gcol.add(name)
+    elif truss:
         seen_truss.add(name)
     elif core:
         seen_core.add(name)
@@ -106,7 +111,10 @@ if len(seen_core) != len(CORE_KERNELS):
 # the seven kernels of sh_truss, under the limits of the BFS kernels
 if len(seen_truss) != len(TRUSS_KERNELS):
     sys.exit(f"expected {len(TRUSS_KERNELS)} truss kernels in the remarks, found {len(seen_truss)}: {sorted(seen_truss)}")
+# the five kernels of sh_color, under the limits of the BFS kernels
+if len(seen_gcol) != len(GCOL_KERNELS):
+    sys.exit(f"expected {len(GCOL_KERNELS)} colouring kernels in the remarks, found {len(seen_gcol)}: {sorted(seen_gcol)}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle, {len(seen_core)} core-number and {len(seen_truss)} truss kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle, {len(seen_core)} core-number, {len(seen_truss)} truss and {len(seen_gcol)} colouring kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

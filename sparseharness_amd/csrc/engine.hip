@@ -18,6 +18,7 @@
 #include "tri.hip.h"
 #include "core.hip.h"
 #include "truss.hip.h"
+#include "color.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 #include "dev_arrays.h"
@@ -1961,7 +1962,7 @@ static int create_graph_handle(sh_engine *e, const char *fn, int64_t rows, int64
   return SH_OK;
 }
 
-// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core and sh_truss: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core, sh_truss and sh_color: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
 // next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
 // enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
 // step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
@@ -3214,6 +3215,122 @@ int sh_truss(sh_engine *e, sh_truss_graph *g, sh_vec *truss, sh_vec *support, sh
   *rounds = it;
   *complete = done ? 1 : 0;
   *triangles = g->h_ctl->hits / 3;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- greedy vertex colouring in Jones-Plassmann rounds (color.hip.h) ---------------------------------------------------
+// The GraphHandle base serves run_batches (control block, pinned copy, events).  As in sh_core_graph the symmetric lists
+// use d_in_ptr / d_in_col alone (adj_ptr / adj_col).  d_ctl: GCOL_CTL_BYTES, followed by the WlParts of gcol_assign.
+// There are no piece lists: a work list keeps the vertices of the workgroup class at its far end.
+struct sh_color_graph : GraphHandle<ColorCtl> {
+  int64_t max_degree = 0;
+  uint32_t *d_deg = nullptr;
+  int32_t *d_wait = nullptr;
+  ColorLists lists = {};
+};
+static_assert(sizeof(ColorCtl) <= GCOL_CTL_BYTES, "the control block is accounted as GCOL_CTL_BYTES (sh_color_graph_footprint)");
+static_assert(sizeof(WlPart) * GCOL_MAX_BLOCKS == GCOL_PART_BYTES, "one WlPart per workgroup");
+static_assert(sizeof(ColorCtl::rec) / sizeof(ColorRec) == GCOL_BATCH, "one record per round of a batch");
+static constexpr const char *COLOR_CREATE = "sh_color_graph_create";
+
+extern "C" {
+
+int sh_color_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                          const void *val, sh_color_graph **out) {
+  return create_graph_handle<sh_color_graph>(e, COLOR_CREATE, rows, nnz, row_ptr, col_idx, val, out, [&](sh_color_graph *g) -> int {
+    int rc;
+    g->rows = rows; g->nnz = nnz;
+    SymLists s;
+    {
+      DevArrays tmp;
+      if ((rc = build_symmetric_lists(e, COLOR_CREATE, g->dev, tmp, rows, nnz, row_ptr, col_idx, val, &s)))
+        return rc;
+    }
+    g->d_in_ptr = s.ptr; g->d_in_col = s.col; g->d_deg = s.deg;
+    g->edges = s.u.M; g->max_degree = s.max_degree;
+    HIP_TRY(e, g->dev.alloc(&g->d_wait, rows * 4));
+    for (int i = 0; i < 2; i++)
+      HIP_TRY(e, g->dev.alloc(&g->lists.list[i], rows * 4));   // a vertex joins a work list once per call (color.hip.h, invariant 1)
+    return open_control(e, g, GCOL_CTL_BYTES, GCOL_CTL_BYTES + GCOL_PART_BYTES);
+  });
+}
+
+int sh_color_graph_free(sh_engine *e, sh_color_graph *g) { return free_handle(e, g); }
+
+int sh_color_graph_footprint(const sh_color_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
+
+int sh_color_graph_edges(const sh_color_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
+
+int sh_color_graph_max_degree(const sh_color_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->max_degree); }
+
+int sh_color(sh_engine *e, sh_color_graph *g, sh_vec *color, sh_vec *prio, int32_t order, uint32_t seed, int32_t window,
+             int32_t max_rounds, int32_t *colors, int32_t *rounds, int32_t *complete, int64_t *coloured,
+             int64_t *size_per_round, int64_t *edges_per_round, uint64_t *ns_per_round, uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (order < 0 || order > 2)
+    return fail(e, SH_EINVAL, "sh_color: order = %d, must be 0 (natural), 1 (random) or 2 (largest degree first)", (int)order);
+  if (window != 0 && (window < 64 || window > GCOL_WINDOW || window % 64 != 0))
+    return fail(e, SH_EINVAL, "sh_color: window = %d, must be 0 or a multiple of 64 in [64, %d]", (int)window, GCOL_WINDOW);
+  if (max_rounds < 1)
+    return fail(e, SH_EINVAL, "sh_color: max_rounds = %d, must be at least 1", (int)max_rounds);
+  if (!e || !g || !color || !colors || !rounds || !complete)
+    return fail(e, SH_EINVAL, "sh_color: NULL argument (engine, graph, color, colors, rounds or complete)");
+  const int64_t rows = g->rows;
+  if (color->n < rows)
+    return fail(e, SH_ESHAPE, "sh_color: color is shorter than the graph's %lld rows", (long long)rows);
+  if (prio && prio->n < rows)
+    return fail(e, SH_ESHAPE, "sh_color: prio is shorter than the graph's %lld rows", (long long)rows);
+  *colors = 0; *rounds = 0; *complete = 1;
+  if (coloured) *coloured = 0;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, GCOL_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
+  const ColorGraph G{(int32_t)rows, g->d_in_ptr, g->d_in_col};
+  const ColorOrder O{prio ? (const int32_t *)prio->d : order == 2 ? (const int32_t *)g->d_deg : nullptr, order, seed};
+  const int32_t win = window == 0 ? GCOL_WINDOW : window;
+  int32_t *c = (int32_t *)color->d;
+  uint64_t total = 0;
+  // nothing coloured; every vertex waits for the neighbours that precede it; those that wait for none make round 0
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, GCOL_CTL_BYTES, e->stream));
+  uint32_t *far1 = g->lists.list[1] + (rows - 1);   // (list 1 is empty until round 0 fills it: its far end lends itself)
+  hipLaunchKernelGGL(gcol_init, grid, block, 0, e->stream, g->d_ctl, G, g->d_wait, c, far1);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(gcol_count, grid, block, 0, e->stream, g->d_ctl, G, O, g->d_wait, far1);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(gcol_ready, grid, block, 0, e->stream, g->d_ctl, G, g->d_wait, g->lists);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  int32_t it = 0;
+  bool done = false;
+  // the launches of a round: each returns at once unless the control block says the round is its turn
+  const auto enqueue = [&](int s, int k) {
+    hipLaunchKernelGGL(gcol_assign, grid, block, 0, e->stream, g->d_ctl, s, G, win, g->d_wait, c, g->lists, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(gcol_close, dim3(1), block, 0, e->stream, g->d_ctl, k, s, (int32_t)rows, nblocks, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    return (int)SH_OK;
+  };
+  const auto take = [&](int s, const ColorRec &rc, uint64_t round_ns) {
+    if (size_per_round) size_per_round[s] = (int64_t)rc.size;
+    if (edges_per_round) edges_per_round[s] = (int64_t)rc.edges;
+    if (ns_per_round) ns_per_round[s] = round_ns;
+  };
+  const int rc = run_batches(e, "sh_color: round", g, max_rounds, &it, &done, &total, enqueue, take);
+  if (rc)
+    return rc;
+  // (the control block as the last batch's readback left it in h_ctl)
+  *colors = g->h_ctl->colors;
+  *rounds = it;
+  *complete = done ? 1 : 0;
+  if (coloured) *coloured = (int64_t)g->h_ctl->coloured;
   if (total_ns)
     *total_ns = total;
   return SH_OK;

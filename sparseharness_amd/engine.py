@@ -511,6 +511,29 @@ class Engine:
         return (max_truss.value, levels.value, n, bool(complete.value), triangles.value, ks[:n].copy(), sizes[:n].copy(),
                 walked[:n].copy(), per[:n].copy(), total.value)
 
+    # ---- greedy colouring: color[v] = the smallest colour that no neighbour preceding v in a fixed order holds
+    def color_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.greedy_colors needs (color.ColorGraph), from the CSR arrays of a square matrix."""
+        from .color import ColorGraph   # (color.py imports this module)
+        return self._graph(ColorGraph, row_ptr, col_idx, val)
+
+    def greedy_colors(self, G, color, prio=None, order=2, seed=0, window=0, max_rounds=None):
+        """-> (colors, rounds, complete, coloured, sizes, edges, ns, total_ns); per round: the vertices coloured, the sum
+        of their list lengths, device ns.  color: an int32 vector of >= rows elements; prio: None or an int32 vector of
+        >= rows priorities that replace the primary key.  order: 0 natural, 1 random, 2 largest degree first; window: 0
+        or the colours per LDS bitmap of a long list.  max_rounds = None: rows + 1, which cannot cut a run short."""
+        if max_rounds is None:
+            max_rounds = G.n + 1
+        colors, rounds, complete, coloured, total = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_uint64()
+        cap = max(int(max_rounds), 1)
+        (sizes, edges, per), ptrs = _outs(cap, np.int64, np.int64, np.uint64)
+        self._chk(abi.load().sh_color(self.h, G.h, color.h, None if prio is None else prio.h, order, seed, window, max_rounds,
+                                      C.byref(colors), C.byref(rounds), C.byref(complete), C.byref(coloured), *ptrs,
+                                      C.byref(total)))
+        n = rounds.value
+        return (colors.value, n, bool(complete.value), coloured.value, sizes[:n].copy(), edges[:n].copy(), per[:n].copy(),
+                total.value)
+
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
         dt = elem_dtype(semiring)

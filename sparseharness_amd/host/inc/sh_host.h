@@ -51,6 +51,19 @@ int sh_core_numbers(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int
 int sh_truss_numbers(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                      int32_t *edge_u, int32_t *edge_v, int32_t *support, int32_t *truss, int64_t *edges);
 
+/* The first-fit colouring of the simple undirected graph under a square CSR pattern in a fixed priority order (clean,
+ * sort the vertices by their keys, one serial loop in that order; single-threaded): the gold for sh_color.  Entry (r, c)
+ * counts when 0 <= c < rows, c != r and its 32 value bits are not all zero, in either direction, once.  v precedes u when
+ * (primary(v), tie(v)) > (primary(u), tie(u)): primary = prio[v] when prio is not NULL, else the degree for order 2, else
+ * 0; tie = the smaller index first for order 0, the larger mix32(v ^ seed) first for orders 1 and 2 (sh_color's mix32).
+ * color[v] (rows words) becomes the smallest colour >= 0 that no preceding neighbour holds, depth[v] (rows words) the
+ * length of the longest chain of preceding neighbours that ends in v, counted from 0 (the round in which sh_color
+ * colours v), *colors (may be NULL) the largest colour plus 1, *edges (may be NULL) the number of edges.  Return 0, -1 bad
+ * argument (order outside 0..2 included). */
+int sh_greedy_colors(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                     int32_t order, uint32_t seed, const int32_t *prio, int32_t *color, int32_t *depth, int32_t *colors,
+                     int64_t *edges);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

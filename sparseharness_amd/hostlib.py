@@ -2,7 +2,8 @@
 loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
 host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp), sh_tri
-(host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp) and sh_truss (host/src/truss_numbers.cpp)."""
+(host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp), sh_truss (host/src/truss_numbers.cpp) and sh_color
+(host/src/greedy_colors.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -35,6 +36,7 @@ SIGNATURES = {
     "sh_triangle_counts": (C.c_int, _csr + [_vp, _vp]),
     "sh_core_numbers": (C.c_int, _csr + [_vp, _vp, C.POINTER(_i64)]),
     "sh_truss_numbers": (C.c_int, _csr + [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "sh_greedy_colors": (C.c_int, _csr + [C.c_int32, C.c_uint32, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(_i64)]),
     "sh_mm_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]),
     "sh_mm_load_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]),
     "sh_host_csr_release": (None, [C.POINTER(_HostCsr)]),
@@ -152,6 +154,23 @@ def truss_numbers(row_ptr, col_idx, val):
     m = C.c_int64()
     _gold("sh_truss_numbers", row_ptr, col_idx, val, _p(eu), _p(ev), _p(sup), _p(truss), C.byref(m))
     return eu[:m.value].copy(), ev[:m.value].copy(), sup[:m.value].copy(), truss[:m.value].copy(), m.value
+
+
+def greedy_colors(row_ptr, col_idx, val, order=0, seed=0, prio=None):
+    """-> (color, colors, depth): color[v] (int32) = the smallest colour >= 0 that no neighbour preceding v holds in the
+    simple undirected graph under the entries (Engine.greedy_colors' color), colors = the largest colour plus 1,
+    depth[v] (int32) = the round in which Engine.greedy_colors colours v (the longest chain of preceding neighbours that
+    ends in v, counted from 0), by one serial first-fit loop on the host.  The order is sh_color's: order 0 natural, 1
+    random by mix32(v ^ seed), 2 largest degree first; prio (int32 per vertex) replaces the primary key.  Entry (r, c)
+    counts when 0 <= c < rows, c != r and its 32 value bits are not all zero."""
+    n = len(row_ptr) - 1
+    color, depth, colors = np.empty(n, np.int32), np.empty(n, np.int32), C.c_int32()
+    if prio is not None:
+        prio = np.ascontiguousarray(prio, np.int32)
+        assert len(prio) >= n
+    _gold("sh_greedy_colors", row_ptr, col_idx, val, int(order), int(seed) & 0xFFFFFFFF, None if prio is None else _p(prio),
+          _p(color), _p(depth), C.byref(colors), None)
+    return color, colors.value, depth
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
