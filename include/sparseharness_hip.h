@@ -1244,6 +1244,134 @@ int sh_color(sh_engine *e, sh_color_graph *g, sh_vec *color, sh_vec *prio, int32
              int32_t max_rounds, int32_t *colors, int32_t *rounds, int32_t *complete, int64_t *coloured,
              int64_t *size_per_round, int64_t *edges_per_round, uint64_t *ns_per_round, uint64_t *total_ns);
 
+/* ---- minimum spanning forest by Boruvka rounds on an edge list ---------------------------------------------------------
+ * (the reference has no counterpart: its apps are SpMV, PageRank, BFS, SSSP and SCC label propagation.  sh_wcc, sh_tri,
+ * sh_core, sh_truss and sh_color read only the pattern; sh_sssp reads the weights but is directed and has a source.  This
+ * is the first weighted undirected entry point: which edges of a symmetric matrix of distances, conductances or
+ * similarities form the cheapest skeleton that keeps everything connected.)
+ *
+ * The graph.  The graph rule is sh_truss's, unchanged: the matrix is square (rows x rows); entry j of row r storing
+ * column c with 0 <= c < rows counts when its 32 value bits are not all zero; the graph is the SIMPLE UNDIRECTED graph
+ * under those entries.  Self-loops, stored zeros and columns outside the matrix change nothing.  Edge e, 0 <= e < M, is the
+ * e-th smallest pair u < v.
+ *      Weights.  The values are float32.  Weights are compared by the total order of their bit patterns: with b the bits,
+ *      k(b) = b ^ 0xFFFFFFFF if the sign bit is set, else b ^ 0x80000000.  This gives the order -NaN < -inf < ... < -0.0 <
+ *      denormals < ... < +inf < +NaN.  Nothing is refused: NaN and infinities are legal weights with a defined place.  A
+ *      stored +0.0 is no edge, by the graph rule.  The weight of edge {u, v} is the smallest, by k, over all counting
+ *      entries (u, v) and (v, u), parallel entries included: an unsymmetric or duplicated matrix has one answer.
+ *      KEY(e) = k(weight[e]) << 32 | e.  No two keys are equal.
+ *      The result is the unique minimum spanning forest under KEY: what Kruskal's algorithm returns when it takes the
+ *      edges in ascending KEY.
+ *      in_msf[e]   = 1 or 0 (int32).  M elements are overwritten, no more.
+ *      comp[v]     = the largest vertex index of v's component (optional; the convention of sh_wcc and sh_scc: it equals
+ *                    sh_wcc's comp on the same arrays).
+ *      edge_u, edge_v (optional): as in sh_truss.  weight[e] (optional): the 32 bits of the chosen entry.
+ *      *tree_edges = rows - *components.  *components = the number of v with comp[v] == v.
+ *      Every comparison is ==.  The result does not depend on the schedule or the run.
+ *
+ *      Schedule (csrc/msf.hip.h; Boruvka 1926 on a parent forest, as Vineet, Harish, Patidar and Narayanan did on a GPU in
+ *      2009).  There is no compare-and-swap, no retry, and no lane waits for another.  State on the device: p[v] the
+ *      parent word, best[v] one 64-bit word per vertex, to[v] the root that a root will hook to, eu[M], ev[M], wk[M] the
+ *      ends and k(weight) of every edge, two work lists of M edge ids.  The work item is an edge of a flat list: there are
+ *      no long rows and no pieces, every lane gets one edge.  At the start of every round every tree is a star: p[v] is a
+ *      root for all v.  Round 1 has p[v] = v and the list holds all M edges.  A round is one fixed set of launches
+ *      enqueued ahead of the host in batches (8, 16, 32, 32, ...), each of which returns at once unless the control block
+ *      on the device gives it work.
+ *      find: best[.] = MAX was written by a launch that ended before this one.  For every edge e of the list, a = p[eu[e]]
+ *      and b = p[ev[e]].  If a == b the edge is inside a tree for good and is dropped.  Otherwise it is appended to the
+ *      next list with a wave-aggregated push -- such an edge enters a list once per round, so M places cannot overflow --
+ *      and KEY(e) goes into best[a] and best[b] with one 64-bit atomic minimum each (one global_atomic_umin_x2).  The
+ *      atomic is issued only if KEY(e) is below a load of the word: the word only falls, so a stale read can only let a
+ *      needless atomic through and never suppresses a needed one.
+ *      pick: every root r with best[r] != MAX takes e = the low 32 bits and stores in_msf[e] = 1 (two roots that chose the
+ *      same edge store the same value), finds the other root o among p[eu[e]] and p[ev[e]] and writes to[r] = o.  The one
+ *      exception is a mutual pair with r > o: when best[o] == best[r], the smaller index hooks and the larger stays a
+ *      root.  pick reads p and writes only to and in_msf: the launch that decides the hooks must not read a word that the
+ *      same launch writes.
+ *      link: p[r] = to[r]; the lane puts best[r] back to MAX (nobody else looks at the word in that launch).
+ *      jump: each of MSF_SWEEPS = 8 launches runs over all vertices, with at most MSF_JUMPS = 16 stores of
+ *      p[v] = p[p[v]] per vertex; sweep i > 0 returns at once unless sweep i - 1 moved a pointer.  The bound holds for any
+ *      order of the lanes: a lane that runs before the vertices above it sees old pointers and gains only one hop per
+ *      jump, so a launch shortens a depth d to at most ceil(d / (MSF_JUMPS + 1)), not to d / 2^MSF_JUMPS.
+ *      (MSF_JUMPS + 1)^MSF_SWEEPS = 17^8 >= 2^31 (a static_assert): every tree is a star again when the round ends, on any
+ *      input and any schedule.
+ *      close: sums the workgroups' counts, records the round, swaps the lists.  It finishes when find kept no edge; in
+ *      that round pick, link and the jumps return at once.
+ *      After the last round top[root] = max v by one atomic maximum per vertex at most (top lives in best's memory; the
+ *      vertices are taken from the largest down and a lane sends nothing when the word is already at or above its
+ *      index), comp[v] = top[p[v]], and the roots are counted.
+ *      Why that is right: all keys differ, so the lightest edge leaving a tree is in the one minimum spanning forest (the
+ *      cut property), whatever the other trees do in that round.  In the graph "root -> chosen other root" every cycle
+ *      has length 2: along a cycle the chosen keys would have to fall strictly unless both ends chose one edge; the
+ *      mutual rule breaks exactly those cycles, so link builds a forest.  Pointers never leave a component.  A run ends
+ *      when no listed edge joins two trees; dropped edges were inside a tree and trees only merge, so every component is
+ *      one star.
+ *      Determinism: find sees one state, so the set of kept edges, best, the hooks, *rounds, walked_per_round (the list
+ *      length at the start), kept_per_round and hooks_per_round (to pointers applied) are functions of the input alone.
+ *      Only the order inside a list, jumps_per_round and the times may differ from run to run.
+ *      Rounds: every tree with a leaving edge merges, so a run has at most floor(log2(rows)) + 1 rounds, the empty last
+ *      one included.  The Python default max_rounds = 33 can never cut a run short.  After a run cut short
+ *      (*complete == 0) in_msf holds the tree edges found so far, every one of which belongs to the forest, *components
+ *      is the number of trees so far and *tree_edges = rows - *components the edges found so far; comp is -1 everywhere
+ *      and the handle is good for another call.
+ *      Worst cases: the work is the sum of the list lengths, M log(rows) at worst; an edge inside a tree is walked once
+ *      more before it goes.  Late rounds send every edge on the rim of the giant tree to one best word: the pre-check
+ *      keeps the atomics to the falling prefix minima, but the loads still meet on one line.  Every round costs its
+ *      launches (12, of which up to 11 return at once) however short its list is.
+ *
+ *      Measured on an MI355X (DESIGN.md "6m Minimum spanning forest"; tools/msf_bench.py, one process per matrix, sh_msf,
+ *        the host gold and sh_wcc alternating, 5 rounds, device time against the wall time of hostlib.msf_edges in the
+ *        same process; drawn weights: one float32 in [0, 1) per stored entry), median (min-max) in ms, rounds: the 2048 x
+ *        2048 grid (4 194 304 rows, 8 384 512 edges): drawn weights 6.71 (6.69-6.72), 13 rounds, 29.0 M edges walked (host
+ *        gold 1549); unit weights 1.88 (1.88-1.92), 2 rounds -- one round hooks 4 194 303 roots into chains that the sweeps
+ *        flatten with 74.6 M pointer stores -- (host gold 680).  R-MAT-18 (262 144 rows, 3 805 085 edges, 88 129
+ *        components), drawn weights: 3.88 (3.79-4.88), 5 rounds, 17.5 M edges walked (host gold 510); its rounds cost 778,
+ *        761, 780 and 698 us for lists of 3.81, 3.81, 3.64 and 3.54 M edges.  A star of 70 001 leaves (one best word
+ *        wanted by every edge): 0.36 (0.31-0.40), its merging round 298 us, the empty round behind it 25 us (host gold
+ *        3.87).  sh_wcc on the same arrays: 0.39, 0.38, 0.33 and 0.88 ms.  The handle is built in 0.05 to 0.07 s.
+ *        Rule: a call is 0.003 to 0.008 of the host's Kruskal on graphs of 4 to 8 million edges and 0.09 of it on the
+ *        star; the device lost on none of the inputs measured.  A round costs at least its twelve launches (25 us), so on
+ *        graphs of a few thousand edges the host is expected to win; where exactly, R-MAT-18 with unit weights and graphs
+ *        above 10^7 edges are unmeasured.  For the components alone call sh_wcc.
+ *
+ * sh_msf_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  The handle holds on the device:
+ * p[rows], to[rows], best[rows] (64-bit), eu[M], ev[M], wk[M], two work lists of M places each and a control block with
+ * two counts per workgroup; no adjacency lists.  rows == 0 gives a valid handle.  Freeing NULL is SH_OK.  The build runs
+ * on the device, once: the first half of sh_truss_graph_create's (the entries that count as sorted keys, the first of
+ * every run an edge), the ends of every edge, and one pass over the nnz entries as given that applies the edge rule
+ * again, bisects (min, max) into eu / ev and takes the atomic minimum of k(val) into wk[e].  While it runs it needs
+ * 4 * (rows + 1) + 16 * nnz + 8 bytes for the arrays as given, their flags and scan, 4 * rows for the degrees the shared
+ * builder counts, 16 bytes per surviving entry for the keys and the sorted keys, and the sort's own scratch; all of it is
+ * released before the call returns.  nnz is bounded as for the other handles, and 2M <= 2^31 - 256.
+ * sh_msf_graph_footprint: device bytes held =
+ *     16 * rows + 20 * edges + 33792.
+ * sh_msf_graph_edges: M.
+ *
+ * sh_msf: in_msf: an int32 vector of >= M elements.  comp: NULL, or an int32 vector of >= rows elements.  edge_u, edge_v,
+ * weight: NULL, or vectors of >= M elements each.  max_rounds >= 1 bounds the rounds.  The per-round arrays (capacity
+ * max_rounds; each may be NULL): walked_per_round, kept_per_round, hooks_per_round, jumps_per_round (pointers changed by
+ * the sweeps), ns_per_round device time.  *total_ns (may be NULL) is the device time of the start, all rounds and the
+ * labels (hipEvent) as elsewhere.  One handle serves any number of calls, one at a time.  rows == 0 gives SH_OK with
+ * zeros and *complete = 1.
+ * SH_EINVAL: max_rounds < 1 (the scalars are checked first); NULL arguments (engine, graph, in_msf, tree_edges,
+ * components, rounds, complete, out, the arrays), rows < 0, nnz < 0.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or
+ * a row_ptr that decreases; in_msf, edge_u, edge_v or weight shorter than M, comp shorter than rows.  All are reported
+ * before any device work, with the buffers untouched.
+ * NOT covered: the total weight (one numpy line: weight[in_msf == 1].astype(float64).sum() on the float32 view), maximum
+ * spanning forests (negate the values), a tree as parent pointers from a chosen root, the multi-GPU driver, row pieces
+ * (sh_spmv_step_pieces), the C++ harness apps, incremental updates.
+ */
+typedef struct sh_msf_graph sh_msf_graph;
+int sh_msf_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_msf_graph **out);
+int sh_msf_graph_free(sh_engine *e, sh_msf_graph *g);
+int sh_msf_graph_footprint(const sh_msf_graph *g, uint64_t *device_bytes);
+int sh_msf_graph_edges(const sh_msf_graph *g, int64_t *edges);            /* M */
+int sh_msf(sh_engine *e, sh_msf_graph *g, sh_vec *in_msf, sh_vec *comp, sh_vec *edge_u, sh_vec *edge_v, sh_vec *weight,
+           int32_t max_rounds, int64_t *tree_edges, int64_t *components, int32_t *rounds, int32_t *complete,
+           int64_t *walked_per_round, int64_t *kept_per_round, int64_t *hooks_per_round, int64_t *jumps_per_round,
+           uint64_t *ns_per_round, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

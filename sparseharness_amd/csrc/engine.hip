@@ -19,6 +19,7 @@
 #include "core.hip.h"
 #include "truss.hip.h"
 #include "color.hip.h"
+#include "msf.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 #include "dev_arrays.h"
@@ -1962,7 +1963,7 @@ static int create_graph_handle(sh_engine *e, const char *fn, int64_t rows, int64
   return SH_OK;
 }
 
-// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core, sh_truss and sh_color: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core, sh_truss, sh_color and sh_msf: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
 // next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
 // enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
 // step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
@@ -2749,6 +2750,8 @@ struct UndEdges {
   int bits = 1;           // of the largest index
   uint64_t *key = nullptr, *sorted = nullptr;
   uint32_t *head = nullptr, *pos = nullptr;
+  const int32_t *rp = nullptr, *ci = nullptr;   // the device copies of the arrays as given (NULL without entries), for
+  const uint32_t *val = nullptr;                // sh_msf_graph_create's pass over the values
 };
 static int build_und_edges(sh_engine *e, DevArrays &tmp, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
                            const void *val, uint32_t *deg, UndEdges *u) {
@@ -2794,7 +2797,7 @@ static int build_und_edges(sh_engine *e, DevArrays &tmp, int64_t rows, int64_t n
     hipLaunchKernelGGL(wl_und_degrees, grid_for(S), blk, 0, e->stream, t_sorted, t_flag, S, bits, deg);
     HIP_TRY(e, hipGetLastError());
   }
-  *u = UndEdges{S, M, bits, t_key, t_sorted, t_flag, t_pos};
+  *u = UndEdges{S, M, bits, t_key, t_sorted, t_flag, t_pos, t_rp, t_ci, t_val};
   return SH_OK;
 }
 
@@ -3331,6 +3334,165 @@ int sh_color(sh_engine *e, sh_color_graph *g, sh_vec *color, sh_vec *prio, int32
   *rounds = it;
   *complete = done ? 1 : 0;
   if (coloured) *coloured = (int64_t)g->h_ctl->coloured;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- minimum spanning forest by Boruvka rounds on an edge list (msf.hip.h) ---------------------------------------------
+// The GraphHandle base serves run_batches (control block, pinned copy, events); its list fields stay empty: the search
+// walks a flat list of edge ids and needs no adjacency lists.  d_ctl: MSF_CTL_BYTES, followed by the WlParts of msf_link
+// and those of the jumps.
+struct sh_msf_graph : GraphHandle<MsfCtl> {
+  uint32_t *d_p = nullptr, *d_to = nullptr, *d_wk = nullptr;
+  uint64_t *d_best = nullptr;   // (after the last round: top, one word per vertex)
+  int32_t *d_eu = nullptr, *d_ev = nullptr;
+  MsfLists lists = {};
+  WlPart *d_jpart = nullptr;
+};
+static_assert(sizeof(MsfCtl) <= MSF_CTL_BYTES, "the control block is accounted as MSF_CTL_BYTES (sh_msf_graph_footprint)");
+static_assert(sizeof(WlPart) * MSF_MAX_BLOCKS == MSF_PART_BYTES, "one WlPart per workgroup");
+static_assert(sizeof(MsfCtl::rec) / sizeof(MsfRec) == MSF_BATCH, "one record per round of a batch");
+// sh_msf_graph_footprint: p, to (4 bytes per row), best (8); eu, ev, wk and two work lists (4 bytes per edge each)
+static_assert(MSF_CTL_BYTES + 2 * MSF_PART_BYTES == 33792, "the header states 16 * rows + 20 * edges + 33792");
+static constexpr const char *MSF_CREATE = "sh_msf_graph_create";
+
+extern "C" {
+
+int sh_msf_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_msf_graph **out) {
+  return create_graph_handle<sh_msf_graph>(e, MSF_CREATE, rows, nnz, row_ptr, col_idx, val, out, [&](sh_msf_graph *g) -> int {
+    int rc;
+    g->rows = rows; g->nnz = nnz;
+    DevArrays &own = g->dev;
+    DevArrays build;   // (what build_und_edges left: the arrays as given, the sorted keys, their run heads and the scan of those)
+    uint32_t *t_deg = nullptr;   // (build_und_edges counts the degrees; the forest has no use for them)
+    HIP_TRY(e, build.alloc(&t_deg, rows * 4));
+    HIP_TRY(e, hipMemsetAsync(t_deg, 0, (size_t)std::max<int64_t>(rows, 1) * 4, e->stream));
+    UndEdges u;
+    if ((rc = build_und_edges(e, build, rows, nnz, row_ptr, col_idx, val, t_deg, &u)))
+      return rc;
+    const int64_t M = u.M;
+    if (2 * M > 0x7FFFFF00ll)
+      return fail(e, SH_EINVAL, "%s: twice the %lld edges must be at most 2^31 - 256", MSF_CREATE, (long long)M);
+    g->edges = M;
+    HIP_TRY(e, own.alloc(&g->d_p, rows * 4));
+    HIP_TRY(e, own.alloc(&g->d_to, rows * 4));
+    HIP_TRY(e, own.alloc(&g->d_best, rows * 8));
+    HIP_TRY(e, own.alloc(&g->d_eu, M * 4));
+    HIP_TRY(e, own.alloc(&g->d_ev, M * 4));
+    HIP_TRY(e, own.alloc(&g->d_wk, M * 4));
+    for (int i = 0; i < 2; i++)
+      HIP_TRY(e, own.alloc(&g->lists.list[i], M * 4));   // an edge joins a work list once per round (msf.hip.h, invariant 1)
+    if (M > 0) {
+      const dim3 blk(WL_BS);
+      const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
+      hipLaunchKernelGGL(wl_edge_ends, grid_for(u.S), blk, 0, e->stream, u.sorted, u.head, u.pos, u.S, u.bits, g->d_eu, g->d_ev);
+      HIP_TRY(e, hipGetLastError());
+      HIP_TRY(e, hipMemsetAsync(g->d_wk, 0xFF, (size_t)M * 4, e->stream));
+      hipLaunchKernelGGL(msf_weights, grid_for(nnz), blk, 0, e->stream, u.rp, u.ci, u.val, nnz, (int32_t)rows, g->d_eu, g->d_ev, M, g->d_wk);
+      HIP_TRY(e, hipGetLastError());
+    }
+    if ((rc = open_control(e, g, MSF_CTL_BYTES, MSF_CTL_BYTES + 2 * MSF_PART_BYTES)))
+      return rc;
+    g->d_jpart = (WlPart *)((char *)g->d_ctl + MSF_CTL_BYTES + MSF_PART_BYTES);
+    HIP_TRY(e, hipStreamSynchronize(e->stream));   // (the kernels above read `build`)
+    return SH_OK;
+  });
+}
+
+int sh_msf_graph_free(sh_engine *e, sh_msf_graph *g) { return free_handle(e, g); }
+
+int sh_msf_graph_footprint(const sh_msf_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
+
+int sh_msf_graph_edges(const sh_msf_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
+
+int sh_msf(sh_engine *e, sh_msf_graph *g, sh_vec *in_msf, sh_vec *comp, sh_vec *edge_u, sh_vec *edge_v, sh_vec *weight,
+           int32_t max_rounds, int64_t *tree_edges, int64_t *components, int32_t *rounds, int32_t *complete,
+           int64_t *walked_per_round, int64_t *kept_per_round, int64_t *hooks_per_round, int64_t *jumps_per_round,
+           uint64_t *ns_per_round, uint64_t *total_ns) {
+  // what the scalar alone decides comes first: no handle is needed to be told
+  if (max_rounds < 1)
+    return fail(e, SH_EINVAL, "sh_msf: max_rounds = %d, must be at least 1", (int)max_rounds);
+  if (!e || !g || !in_msf || !tree_edges || !components || !rounds || !complete)
+    return fail(e, SH_EINVAL, "sh_msf: NULL argument (engine, graph, in_msf, tree_edges, components, rounds or complete)");
+  const int64_t rows = g->rows, M = g->edges;
+  const struct { const sh_vec *v; const char *name; } vecs[] = {{in_msf, "in_msf"}, {edge_u, "edge_u"}, {edge_v, "edge_v"}, {weight, "weight"}};
+  for (const auto &x : vecs)
+    if (x.v && x.v->n < M)
+      return fail(e, SH_ESHAPE, "sh_msf: %s is shorter than the graph's %lld edges", x.name, (long long)M);
+  if (comp && comp->n < rows)
+    return fail(e, SH_ESHAPE, "sh_msf: comp is shorter than the graph's %lld rows", (long long)rows);
+  *tree_edges = 0; *components = 0; *rounds = 0; *complete = 1;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, MSF_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
+  const MsfEdges E{(int32_t)M, g->d_eu, g->d_ev, g->d_wk};
+  uint32_t *p = g->d_p;
+  int32_t *chosen = (int32_t *)in_msf->d;
+  uint64_t total = 0, ns = 0;
+  // every vertex a tree of its own, list 0 holds every edge
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, MSF_CTL_BYTES, e->stream));
+  if (edge_u && M > 0) HIP_TRY(e, hipMemcpyAsync(edge_u->d, g->d_eu, (size_t)M * 4, hipMemcpyDeviceToDevice, e->stream));
+  if (edge_v && M > 0) HIP_TRY(e, hipMemcpyAsync(edge_v->d, g->d_ev, (size_t)M * 4, hipMemcpyDeviceToDevice, e->stream));
+  hipLaunchKernelGGL(msf_init, grid, block, 0, e->stream, g->d_ctl, (int32_t)rows, E, p, g->d_best, g->lists.list[0], chosen,
+                     weight ? (uint32_t *)weight->d : nullptr);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  int32_t it = 0;
+  bool done = false;
+  // the launches of a round: each returns at once unless the control block says the round is its turn (and, behind the
+  // find, unless it kept an edge; for a jumping launch after the first, unless the one before it changed a pointer)
+  const auto enqueue = [&](int s, int k) {
+    hipLaunchKernelGGL(msf_find, grid, block, 0, e->stream, g->d_ctl, s, E, p, g->d_best, g->lists);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(msf_pick, grid, block, 0, e->stream, g->d_ctl, s, (int32_t)rows, E, p, g->d_best, g->d_to, chosen);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(msf_link, grid, block, 0, e->stream, g->d_ctl, s, (int32_t)rows, p, g->d_best, g->d_to, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    for (int i = 0; i < MSF_SWEEPS; i++) {
+      hipLaunchKernelGGL(msf_jump, grid, block, 0, e->stream, g->d_ctl, s, i, (int32_t)rows, p, g->d_jpart);
+      HIP_TRY(e, hipGetLastError());
+    }
+    hipLaunchKernelGGL(msf_close, dim3(1), block, 0, e->stream, g->d_ctl, k, s, nblocks, g->d_part, g->d_jpart);
+    HIP_TRY(e, hipGetLastError());
+    return (int)SH_OK;
+  };
+  const auto take = [&](int s, const MsfRec &rc, uint64_t round_ns) {
+    if (walked_per_round) walked_per_round[s] = (int64_t)rc.walked;
+    if (kept_per_round) kept_per_round[s] = (int64_t)rc.kept;
+    if (hooks_per_round) hooks_per_round[s] = (int64_t)rc.hooks;
+    if (jumps_per_round) jumps_per_round[s] = (int64_t)rc.jumps;
+    if (ns_per_round) ns_per_round[s] = round_ns;
+  };
+  const int rc = run_batches(e, "sh_msf: round", g, max_rounds, &it, &done, &total, enqueue, take);
+  if (rc)
+    return rc;
+  // the largest index of every tree (best's memory holds nothing now), the labels (or -1 everywhere) and the roots
+  uint32_t *top = (uint32_t *)g->d_best;
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  if (done) {
+    HIP_TRY(e, hipMemsetAsync(top, 0, (size_t)rows * 4, e->stream));
+    hipLaunchKernelGGL(msf_top, grid, block, 0, e->stream, (int32_t)rows, p, top);
+    HIP_TRY(e, hipGetLastError());
+  }
+  hipLaunchKernelGGL(msf_label, grid, block, 0, e->stream, g->d_ctl, (int32_t)rows, done ? 1 : 0, p, top, comp ? (int32_t *)comp->d : nullptr);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(g->h_ctl, g->d_ctl, sizeof(MsfCtl), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+  total += ns;
+  *components = (int64_t)g->h_ctl->components;
+  *tree_edges = rows - *components;
+  *rounds = it;
+  *complete = done ? 1 : 0;
   if (total_ns)
     *total_ns = total;
   return SH_OK;

@@ -534,6 +534,31 @@ class Engine:
         return (colors.value, n, bool(complete.value), coloured.value, sizes[:n].copy(), edges[:n].copy(), per[:n].copy(),
                 total.value)
 
+    # ---- minimum spanning forest: in_msf[e] = 1 for the edges of the one forest that is lightest under KEY(e)
+    def msf_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.spanning_forest needs (msf.MsfGraph), from the CSR arrays of a square matrix whose float32
+        values are the weights."""
+        from .msf import MsfGraph   # (msf.py imports this module)
+        return self._graph(MsfGraph, row_ptr, col_idx, val)
+
+    def spanning_forest(self, G, in_msf, comp=None, edge_u=None, edge_v=None, weight=None, max_rounds=33):
+        """-> (tree_edges, components, rounds, complete, walked, kept, hooks, jumps, ns, total_ns); per round: the length
+        of the edge list at its start, the edges that still joined two trees, the roots hooked, pointers changed by the
+        jumps, device ns.  in_msf: an int32 vector of >= M = G.edges elements; edge_u, edge_v, weight: None or one more
+        each; comp: None or an int32 vector of >= rows elements.  max_rounds = 33 can never cut a run short (a run has
+        at most floor(log2(rows)) + 1 rounds)."""
+        tree_edges, components = C.c_int64(), C.c_int64()
+        rounds, complete, total = C.c_int32(), C.c_int32(), C.c_uint64()
+        cap = max(int(max_rounds), 1)
+        (walked, kept, hooks, jumps, per), ptrs = _outs(cap, np.int64, np.int64, np.int64, np.int64, np.uint64)
+        h = lambda v: None if v is None else v.h   # noqa: E731
+        self._chk(abi.load().sh_msf(self.h, G.h, in_msf.h, h(comp), h(edge_u), h(edge_v), h(weight), max_rounds,
+                                    C.byref(tree_edges), C.byref(components), C.byref(rounds), C.byref(complete), *ptrs,
+                                    C.byref(total)))
+        n = rounds.value
+        return (tree_edges.value, components.value, n, bool(complete.value), walked[:n].copy(), kept[:n].copy(),
+                hooks[:n].copy(), jumps[:n].copy(), per[:n].copy(), total.value)
+
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
         dt = elem_dtype(semiring)

@@ -64,6 +64,18 @@ int sh_greedy_colors(int64_t rows, int64_t nnz, const int32_t *row_ptr, const in
                      int32_t order, uint32_t seed, const int32_t *prio, int32_t *color, int32_t *depth, int32_t *colors,
                      int64_t *edges);
 
+/* The minimum spanning forest of the simple undirected graph under a square CSR matrix, its float32 values as weights
+ * (clean, sort the keys, Kruskal's loop with a union-find; single-threaded): the gold for sh_msf.  Entry (r, c) counts
+ * when 0 <= c < rows, c != r and its 32 value bits are not all zero.  Edge e is the e-th smallest pair u < v.  Weights are
+ * compared by k(b) = b ^ 0xFFFFFFFF if the sign bit of the bits b is set, else b ^ 0x80000000; the weight of an edge is the
+ * smallest, by k, over all counting entries (u, v) and (v, u); KEY(e) = k(weight[e]) << 32 | e, and the forest is what
+ * Kruskal's algorithm returns when it takes the edges in ascending KEY.  edge_u, edge_v, weight (the 32 bits of the chosen
+ * entry) and in_msf (1 or 0) hold nnz words each, of which *edges are written; comp[v] (rows words) becomes the largest
+ * index of v's component; *components (may be NULL) the number of components.  Return 0, -1 bad argument. */
+int sh_msf_edges(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                 int32_t *edge_u, int32_t *edge_v, uint32_t *weight, int32_t *in_msf, int32_t *comp, int64_t *edges,
+                 int64_t *components);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

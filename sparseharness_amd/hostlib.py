@@ -2,8 +2,8 @@
 loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
 host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp), sh_tri
-(host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp), sh_truss (host/src/truss_numbers.cpp) and sh_color
-(host/src/greedy_colors.cpp)."""
+(host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp), sh_truss (host/src/truss_numbers.cpp), sh_color
+(host/src/greedy_colors.cpp) and sh_msf (host/src/msf_edges.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -37,6 +37,7 @@ SIGNATURES = {
     "sh_core_numbers": (C.c_int, _csr + [_vp, _vp, C.POINTER(_i64)]),
     "sh_truss_numbers": (C.c_int, _csr + [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sh_greedy_colors": (C.c_int, _csr + [C.c_int32, C.c_uint32, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(_i64)]),
+    "sh_msf_edges": (C.c_int, _csr + [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sh_mm_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]),
     "sh_mm_load_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]),
     "sh_host_csr_release": (None, [C.POINTER(_HostCsr)]),
@@ -171,6 +172,22 @@ def greedy_colors(row_ptr, col_idx, val, order=0, seed=0, prio=None):
     _gold("sh_greedy_colors", row_ptr, col_idx, val, int(order), int(seed) & 0xFFFFFFFF, None if prio is None else _p(prio),
           _p(color), _p(depth), C.byref(colors), None)
     return color, colors.value, depth
+
+
+def msf_edges(row_ptr, col_idx, val):
+    """-> (edge_u, edge_v, weight, in_msf, comp, M, components): for edge e of the simple undirected graph under the
+    entries -- the e-th smallest pair (u, v) with u < v -- its ends (int32), the 32 bits of its weight (uint32: the
+    smallest entry of the edge under the total order of the bit patterns) and whether it is in the minimum spanning
+    forest under KEY(e) = k(weight[e]) << 32 | e (int32, 1 or 0); comp[v] (int32) = the largest vertex index of v's
+    component (Engine.spanning_forest's outputs), M = the number of edges, by a single-threaded Kruskal with a union-find
+    on the host.  Entry (r, c) counts when 0 <= c < rows, c != r and its 32 value bits are not all zero."""
+    n = len(row_ptr) - 1
+    cap = max(len(col_idx), 1)   # (M <= nnz)
+    eu, ev, msf = (np.empty(cap, np.int32) for _ in range(3))
+    w, comp = np.empty(cap, np.uint32), np.empty(max(n, 1), np.int32)
+    m, k = C.c_int64(), C.c_int64()
+    _gold("sh_msf_edges", row_ptr, col_idx, val, _p(eu), _p(ev), _p(w), _p(msf), _p(comp), C.byref(m), C.byref(k))
+    return eu[:m.value].copy(), ev[:m.value].copy(), w[:m.value].copy(), msf[:m.value].copy(), comp[:n].copy(), m.value, k.value
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
