@@ -184,6 +184,28 @@ extern "C" int sh_debug_emulate_plan(int64_t rows, int64_t cols, int64_t nnz, co
   if (semiring == 3) return emulate<HMaxMin>(H, rows, cols, (const uint32_t *)x, (uint32_t *)y, stats);
   return -2;
 }
+// sh_debug_emulate_plan for a device with n_cus CUs, and the phase-1 work items the host builder cut for it: items gets
+// up to cap_items of them in launch order, 8 words each (TileChunk: tile, s, e, hs, pdelta, ob0, 0, 0; fillers have
+// s == e).  x and y may both be NULL: the plan is then only built.  Returns the number of items, or the emulator's
+// negative code (-1: the builder refused, -2: no such semiring).
+extern "C" int64_t sh_debug_plan_items(int64_t rows, int64_t cols, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                                       const void *val, const sh_plan_options *opt_p, int n_cus, int semiring, const void *x, void *y,
+                                       int64_t *stats, int32_t *items, int64_t cap_items) {
+  sh_plan_options opt;
+  if (opt_p) opt = *opt_p; else sh_plan_options_default(&opt);
+  TiledHost H;
+  if (!build_tiled_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, n_cus, H)) return -1;
+  static_assert(sizeof(TileChunk) == 32, "8 words per work item");
+  if (items) memcpy(items, H.chunks.data(), (size_t)std::min<int64_t>(cap_items, (int64_t)H.chunks.size()) * sizeof(TileChunk));
+  if (x && y) {
+    int rc = -2;
+    if (semiring == 0) rc = emulate<HPlusTimes>(H, rows, cols, (const uint32_t *)x, (uint32_t *)y, stats);
+    if (semiring == 2) rc = emulate<HOrAnd>(H, rows, cols, (const uint32_t *)x, (uint32_t *)y, stats);
+    if (semiring == 3) rc = emulate<HMaxMin>(H, rows, cols, (const uint32_t *)x, (uint32_t *)y, stats);
+    if (rc != 0) return rc;
+  }
+  return (int64_t)H.chunks.size();
+}
 // How the host builder codes the values of a matrix (CPU tests: which phase-1 instantiation a value set selects):
 // *code_bits = 0 raw words, else 4 / 8 / 16; *distinct = the dictionary's words in use.  0, or -1: the builder refused.
 extern "C" int sh_debug_plan_coding(int64_t rows, int64_t cols, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,

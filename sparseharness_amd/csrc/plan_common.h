@@ -179,6 +179,75 @@ static inline void decide_value_coding(std::vector<uint32_t> &words, bool overfl
   }
 }
 
+// Modelled time of one phase-1 work item, ns: P1_COST_ENTRY per stream entry read, P1_COST_PRODUCT per product written
+// to P (light items only), P1_COST_ITEM per item: 3.5 us until the x tile is staged and 1.5 us between the end of a
+// workgroup and the start of the next one on its CU.  Fitted to the item timeline of the headline matrix (four-bit
+// value codes; profiles/p1_timeline_plain_lists.json); only their ratios matter to the schedule.
+constexpr double P1_COST_ENTRY = 0.163, P1_COST_PRODUCT = 0.040, P1_COST_ITEM = 5000.0;
+static inline double item_cost(const TileChunk &ch, double products_per_entry) {
+  const double n = (double)(ch.e - ch.s);
+  return P1_COST_ENTRY * n + (ch.hs > ch.s ? P1_COST_PRODUCT * products_per_entry * n : 0.0) + P1_COST_ITEM;
+}
+// When the last of `workers` CUs is done with the list, each taking the next item as soon as it is free.
+static inline double list_makespan(const std::vector<TileChunk> &list, int workers, double products_per_entry) {
+  std::vector<double> free_at((size_t)workers, 0.0);   // a min-heap
+  auto later = [](double a, double b) { return a > b; };
+  for (const TileChunk &ch : list) {
+    std::pop_heap(free_at.begin(), free_at.end(), later);
+    free_at.back() += item_cost(ch, products_per_entry);
+    std::push_heap(free_at.begin(), free_at.end(), later);
+  }
+  return *std::max_element(free_at.begin(), free_at.end());
+}
+// One XCD's list of work items (cut_work_items): its last heavy items re-cut finer and moved to the end, longest
+// first, where the model says the list then ends sooner; else the list stays as it is.
+static inline void close_tail(std::vector<TileChunk> &list, int workers, int64_t chunk, double products_per_entry) {
+  const int64_t wave = 64 * HSTRIP;
+  std::vector<size_t> heavy_at;   // positions of the heavy items, last first
+  for (size_t i = list.size(); i-- > 0;)
+    if (list[i].hs <= list[i].s && list[i].s < list[i].e) heavy_at.push_back(i);
+  if (heavy_at.empty() || workers < 2) return;
+  double best = list_makespan(list, workers, products_per_entry);
+  std::vector<TileChunk> best_list;
+  const int held_back[] = {workers / 4, workers / 2, 3 * workers / 4, workers, 3 * workers / 2, 2 * workers, 3 * workers};
+  for (int hb : held_back) {
+    const size_t n_held = std::min<size_t>((size_t)std::max(hb, 1), heavy_at.size());
+    // how they are cut: all in halves, thirds or quarters of an item; or the first ranges in halves and the last
+    // third, half or two thirds of the held-back entries in quarters (the finest items then end the list)
+    for (int mode = 0; mode < 6; mode++) {
+      auto small_for = [&](int parts) { return std::max<int64_t>(wave, (chunk / parts) & ~(wave - 1)); };
+      std::vector<char> held(list.size(), 0);
+      for (size_t k = 0; k < n_held; k++) held[heavy_at[k]] = 1;
+      std::vector<TileChunk> body, ranges, tail;
+      for (size_t i = 0; i < list.size(); i++) {
+        if (!held[i]) { body.push_back(list[i]); continue; }
+        // neighbouring items of one heavy run are one range again
+        if (!ranges.empty() && ranges.back().tile == list[i].tile && ranges.back().e == list[i].s) ranges.back().e = list[i].e;
+        else ranges.push_back(list[i]);
+      }
+      int64_t held_entries = 0, seen = 0;
+      for (const TileChunk &r : ranges) held_entries += (int64_t)r.e - r.s;
+      for (const TileChunk &r : ranges) {   // equal cuts, whole waves of strips from the range's (hence the run's) start
+        const int64_t small = mode < 3 ? small_for(2 + mode) : small_for(6 * seen >= (7 - mode) * held_entries ? 4 : 2);
+        seen += (int64_t)r.e - r.s;
+        const int64_t len = (int64_t)r.e - r.s, pieces = (len + small - 1) / small;
+        const int64_t cut = std::min<int64_t>(small, ((len + pieces - 1) / pieces + wave - 1) & ~(wave - 1));
+        for (int64_t s0 = r.s; s0 < r.e; s0 += cut) {
+          TileChunk ch = r;
+          ch.s = (int32_t)s0;
+          ch.e = (int32_t)std::min<int64_t>(s0 + cut, r.e);
+          tail.push_back(ch);
+        }
+      }
+      std::stable_sort(tail.begin(), tail.end(), [](const TileChunk &a, const TileChunk &b) { return a.e - a.s > b.e - b.s; });
+      body.insert(body.end(), tail.begin(), tail.end());
+      const double t = list_makespan(body, workers, products_per_entry);
+      if (t < best * (1.0 - 1e-9)) { best = t; best_list.swap(body); }
+    }
+  }
+  if (!best_list.empty()) list.swap(best_list);
+}
+
 // Phase-1 work items from the per-tile run tables (run_start / run_len: the tile's light run in the stream, in entries;
 // heavy_start / hrel: its heavy run; ob0[t]: the tile's first block in obase[]).  Fills H.chunks.
 static inline void cut_work_items(const int CT, const std::vector<int64_t> &run_start, const std::vector<int64_t> &run_len,
@@ -273,6 +342,22 @@ static inline void cut_work_items(const int CT, const std::vector<int64_t> &run_
   for (int t = 0; t < CT; t++) {
     cut_run(t, run_start[(size_t)t], run_len[(size_t)t], false);
     cut_run(t, heavy_start[(size_t)t], hrel[(size_t)t], true);
+  }
+  // The end of each XCD's list.  An XCD's workgroups take its list in order, one per CU, so with ~6 equal items per CU
+  // the launch ends with a round in which a few CUs work and the others wait.  What is free to move is the heavy items:
+  // a heavy run may be cut at any multiple of 64 strips (the partial slots are fixed by the stream position) and writes
+  // no P, and the order of a list is speed only.  So the last heavy items of the list are held back, cut into items of
+  // 1/2 .. 1/4 of the normal size and handed out behind everything else, longest first; how many are held back and how
+  // finely they are cut is what minimises the makespan of greedy list scheduling of the modelled item costs on the
+  // XCD's CUs (close_tail, a few thousand items).  The body of the list, every light item, ob0 and the XCD of every
+  // tile stay as they are.  opt.chunk > 0 (a forced item size) and SH_P1_TAIL=0 keep the plain lists.
+  {
+    const char *tail_env = getenv("SH_P1_TAIL");
+    if (opt.chunk <= 0 && xcd_order && !(tail_env && tail_env[0] == '0')) {
+      const int workers = std::max(1, n_cus / 8);
+      const double products_per_entry = H.light_len > 0 ? (double)H.p_len / (double)H.light_len : 0.0;
+      for (auto &list : per_xcd) close_tail(list, workers, chunk, products_per_entry);
+    }
   }
   // per-XCD lists interleaved so that position p holds a chunk of XCD p % 8 (empty fillers where a list is short)
   {

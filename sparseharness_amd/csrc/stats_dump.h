@@ -40,6 +40,20 @@ static void stats_after_tiled(sh_engine *e, int n_bins, int n_chunks) {
     std::vector<uint64_t> hs((size_t)nch * 5);
     (void)hipStreamSynchronize(e->stream);
     (void)hipMemcpy(hs.data(), g_p1_stats_buf, hs.size() * 8, hipMemcpyDeviceToHost);
+    // SH_STATS_P1_FILE=path: the records themselves, one line per work item of this launch (the file holds the last
+    // launch; tools/p1_timeline.py turns it into the per-XCD summary).  Block b runs on XCD b % 8.
+    if (const char *path = getenv("SH_STATS_P1_FILE")) {
+      if (FILE *f = fopen(path, "w")) {
+        fprintf(f, "block,kind,entries,start,staged,end\n");
+        for (int i = 0; i < nch; i++) {
+          const uint64_t *S = &hs[(size_t)i * 5];
+          if (S[1] == 0) continue;   // a filler
+          fprintf(f, "%d,%d,%llu,%llu,%llu,%llu\n", i, (int)S[0], (unsigned long long)S[1], (unsigned long long)S[2],
+                  (unsigned long long)S[3], (unsigned long long)S[4]);
+        }
+        fclose(f);
+      }
+    }
     for (int kind = 0; kind < 2; kind++) {
       double n = 0, ent = 0, stage = 0, total = 0;
       uint64_t t0 = ~0ull, t1 = 0;
