@@ -1372,6 +1372,125 @@ int sh_msf(sh_engine *e, sh_msf_graph *g, sh_vec *in_msf, sh_vec *comp, sh_vec *
            int64_t *walked_per_round, int64_t *kept_per_round, int64_t *hooks_per_round, int64_t *jumps_per_round,
            uint64_t *ns_per_round, uint64_t *total_ns);
 
+/* ---- greedy weighted matching by rounds of locally dominant edges on an edge list -------------------------------------
+ * (the reference has no counterpart.  sh_msf answers "which edges form the cheapest skeleton" of a symmetric matrix;
+ * this answers the question asked next: which unknowns are coupled most strongly and should be merged in pairs when the
+ * matrix is coarsened -- pairwise aggregation in algebraic multigrid, heavy-edge coarsening in partitioners, pairing
+ * pivots.  Class 0 of sh_color is an independent set of vertices, not of edges.)
+ *
+ * The graph and the edge weights are sh_msf's, unchanged: the matrix is square; entry j of row r storing column c with
+ * 0 <= c < rows counts when its 32 value bits are not all zero; the graph is the SIMPLE UNDIRECTED graph under those
+ * entries.  Self-loops, stored zeros and columns outside the matrix change nothing.  Edge e, 0 <= e < M, is the e-th
+ * smallest pair u < v.  Weights are float32 compared by k(b) = b ^ 0xFFFFFFFF if the sign bit is set, else
+ * b ^ 0x80000000; the weight of edge {u, v} is the smallest, by k, over all counting entries (u, v) and (v, u), parallel
+ * entries included.  NaN and infinities have their place in the order.  Nothing is refused.  A stored +0.0 is no edge.
+ *      The order of a call.  Two scalars fix it: heavy is 0 or 1, seed any uint32.
+ *        MKEY(e) = hi(e) << 32 | lo(e)
+ *        hi = k(weight[e]) for heavy == 0 (lightest first), hi = ~k(weight[e]) for heavy == 1 (heaviest first: the
+ *        Python default, what coarsening wants);
+ *        lo = e when seed == 0, lo = mix32(e ^ seed) otherwise, mix32 being sh_color's bijection of the 32-bit words.
+ *      Both forms of lo are bijections of e, so no two keys are equal, and the result is unique: the greedy matching,
+ *      what a serial loop returns when it takes the edges in ascending MKEY and keeps an edge when both its ends are
+ *      still free.  It is maximal, and under heavy == 1 with non-negative weights its weight is at least half the
+ *      maximum weight of a matching (the 1/2-approximation of Avis 1983).  A key may be all ones only for seed != 0 (for
+ *      seed == 0, e < 2^31), on the one edge with mix32(e ^ seed) == 0xFFFFFFFF when its weight is the last of the
+ *      order; that is harmless (csrc/match.hip.h says why) and nothing is masked.
+ *      mate[v]     = the partner of v, or -1 (int32).  rows elements are overwritten, no more.
+ *      in_match[e] = 1 or 0 (int32; optional).  M elements are overwritten, no more.
+ *      edge_u, edge_v, weight (optional): as in sh_msf.
+ *      *pairs      = the number of matched edges = the number of v with mate[v] > v.
+ *      Every comparison is ==.  The result does not depend on the schedule or the run.
+ *
+ *      Schedule (csrc/match.hip.h; the locally dominant edges of Preis 1999, Hoepman 2004 and Manne and Bisseling 2007).
+ *      There is no compare-and-swap, no retry, and no lane waits for another.  State on the device: best[v] one 64-bit
+ *      word per vertex, eu[M], ev[M], wk[M] the ends and k(weight) of every edge, two work lists of M edge ids; mate is
+ *      the caller's vector.  The work item is an edge of a flat list, one lane per edge.  A round is one fixed set of
+ *      four launches enqueued ahead of the host in batches (8, 16, 32, 32, ...), each of which returns at once unless the
+ *      control block on the device gives it work.  Round r walks its list; walked_r is the list's length.
+ *      bid: best[.] = MAX for every free vertex with a listed edge was written by an earlier launch.  An edge with a
+ *      matched end is dropped for good.  Every other edge is kept: it is appended to the next list with a wave-aggregated
+ *      push -- an edge enters a list once per round, so M places cannot overflow -- and MKEY(e) goes into best[eu[e]] and
+ *      best[ev[e]] with the pre-checked 64-bit atomic minimum of sh_msf (one global_atomic_umin_x2).  kept_r edges go on.
+ *      take: walks the next list.  Edge e is matched when best[eu[e]] == MKEY(e) && best[ev[e]] == MKEY(e): it is the
+ *      smallest key among the kept edges at both its ends (locally dominant).  The edge tests itself, so nothing inverts
+ *      mix32.  It stores mate[eu] = ev, mate[ev] = eu and in_match[e] = 1; two matched edges share no end.  take reads
+ *      best and writes mate, bid reads mate and writes best: neither launch reads what it writes itself.  matched_r
+ *      edges are matched.
+ *      clear: best = MAX at both ends of every kept edge (concurrent stores store the same value).  A vertex whose edges
+ *      were all dropped is never bid for again.
+ *      close: one workgroup sums the workgroups' counts, records the round and swaps the lists.  The run ends at the first
+ *      round with kept_r == 0; that round is counted, and take and clear return at once in it.
+ *      Why that is right, by induction over the rounds.  Suppose an edge (u, w) died at u before (u, v) was dominant.  It
+ *      died because w was matched through some (w, x).  That edge was dominant while (u, w) was still kept, so its key is
+ *      smaller: greedy reached (w, x) first and, by induction, took it.  So greedy never takes (u, w), every edge at u or
+ *      v with a key below MKEY(u, v) is of that kind, and both u and v are free when greedy reaches (u, v): greedy takes
+ *      it.  A dropped edge has a matched end, so greedy does not take it.
+ *      Determinism: bid sees one state, so *rounds, walked_per_round, kept_per_round, matched_per_round, mate and
+ *      in_match are functions of the input, heavy and seed alone.  Only the order inside a list and the times may differ
+ *      from run to run.
+ *      Rounds: every round with kept_r > 0 matches at least one edge (the smallest kept key of all is dominant), and a
+ *      pair takes two vertices, so rounds <= floor(rows / 2) + 1.  The bound is attained on a path whose keys ascend
+ *      along it.  The Python default max_rounds = 4096 is a cap on the device time, not a bound.  After a run cut short
+ *      (*complete == 0) mate and in_match hold the pairs found so far, every one of which belongs to the greedy
+ *      matching: a valid matching, not a maximal one.  The handle is good for another call.
+ *      Worst cases: a path, or any graph, with equal weights and seed == 0 has keys that ascend with the edge id and gets
+ *      one pair per round in places; that is what seed is for, and why the Python default is seed = 1.  A hub sends every
+ *      kept edge to one best word: the pre-check keeps the atomics to the falling prefix minima, but the loads meet on
+ *      one line.  Every round costs its four launches however short its list is.
+ *
+ *      Measured on an MI355X (DESIGN.md "6n Greedy matching"; tools/match_bench.py, one process per matrix, sh_match
+ *        under heavy 0 / 1 and seed 0 / 1 and the host gold alternating, 5 rounds, device time against the wall time of
+ *        hostlib.greedy_matching in the same process; drawn weights: one float32 in [0, 1) per stored entry), median
+ *        (min-max) in ms for heavy = 1, seed = 1:
+ *        the 2048 x 2048 grid (4 194 304 rows, 8 384 512 edges), drawn weights: 3.75 (3.74-3.75), 8 rounds, 18.8 M edges
+ *        walked, 1 901 973 pairs (host gold 1229); its rounds cost 1622, 1576, 350, 80, 23, 16, 14 and 13 us for lists of
+ *        8.38, 8.38, 1.69 and 0.30 M edges and less.  The same grid with unit weights: 3.75 (3.75-3.75), 8 rounds, 18.8 M
+ *        edges walked, 1 901 716 pairs (host gold 1184); with seed = 0, measured once: 4165 ms, 3072 rounds, 12 884 M edges
+ *        walked, 2 097 152 pairs (host gold 690) -- 6.0 times the host, and the reason for the default seed.  R-MAT-18
+ *        (262 144 rows, 3 805 085 edges), drawn weights: 1.71 (1.68-1.75), 11 rounds, 8.8 M edges walked, 39 623 pairs
+ *        (host gold 486).  A star of 70 001 leaves (one best word wanted by every edge): 0.34 (0.33-0.38), 2 rounds, its
+ *        matching round 312 us, the empty round behind it 13 us (host gold 3.68).  heavy = 0 and, on drawn weights,
+ *        seed = 0 cost the same within 5 % (profiles/match_*.json).  The handle is built in 0.05 to 0.06 s.
+ *        Rule: with seed != 0, or with weights that differ, a call is 0.003 to 0.004 of the host's sort-and-take loop on
+ *        graphs of 4 to 8 million edges and 0.09 of it on the star; the device lost on none of those.  With equal weights
+ *        and seed = 0 it lost by a factor of 6 on the grid: do not call it that way.  A round costs at least its four
+ *        launches (13 us), so on graphs of a few hundred edges the host is expected to win; where exactly, R-MAT-18 with
+ *        unit weights and graphs above 10^7 edges are unmeasured.
+ *
+ * sh_match_graph_create: the handle is made from the host CSR arrays alone (no sh_csr), by the builder of
+ * sh_msf_graph_create (the same temporaries and bounds: 2M <= 2^31 - 256).  The handle holds on the device: best[rows]
+ * (64-bit), eu[M], ev[M], wk[M], two work lists of M places each and a control block with one count per workgroup; no
+ * adjacency lists.  rows == 0 gives a valid handle.  Freeing NULL is SH_OK.
+ * sh_match_graph_footprint: device bytes held =
+ *     8 * rows + 20 * edges + 17408.
+ * sh_match_graph_edges: M.
+ *
+ * sh_match: mate: an int32 vector of >= rows elements.  in_match, edge_u, edge_v, weight: NULL, or vectors of >= M
+ * elements each.  heavy: 0 or 1.  seed: any.  max_rounds >= 1 bounds the rounds.  The per-round arrays (capacity
+ * max_rounds; each may be NULL): walked_per_round, kept_per_round, matched_per_round, ns_per_round device time.
+ * *total_ns (may be NULL) is the device time of the start and all rounds (hipEvent) as elsewhere.  One handle serves any
+ * number of calls, one at a time; heavy and seed may differ from call to call.  rows == 0 gives SH_OK with zeros and
+ * *complete = 1.
+ * SH_EINVAL: max_rounds < 1, heavy outside {0, 1} (the scalars are checked first); NULL arguments (engine, graph, mate,
+ * pairs, rounds, complete, out, the arrays), rows < 0, nnz < 0.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a
+ * row_ptr that decreases; mate shorter than rows; in_match, edge_u, edge_v or weight shorter than M.  All are reported
+ * before any device work, with the buffers untouched.
+ * NOT covered: maximum-cardinality or maximum-weight matching (this is the greedy 1/2-approximation), bipartite
+ * row-column matching (the graph here is the symmetric one on the rows), the aggregate map of a coarsening (one numpy
+ * line: np.minimum(v, mate) where mate >= 0, else v), continuing a cut-short run (a new call starts over), the multi-GPU
+ * driver, the C++ harness apps.
+ */
+typedef struct sh_match_graph sh_match_graph;
+int sh_match_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                          const void *val, sh_match_graph **out);
+int sh_match_graph_free(sh_engine *e, sh_match_graph *g);
+int sh_match_graph_footprint(const sh_match_graph *g, uint64_t *device_bytes);
+int sh_match_graph_edges(const sh_match_graph *g, int64_t *edges);          /* M */
+int sh_match(sh_engine *e, sh_match_graph *g, sh_vec *mate, sh_vec *in_match, sh_vec *edge_u, sh_vec *edge_v, sh_vec *weight,
+             int32_t heavy, uint32_t seed, int32_t max_rounds, int64_t *pairs, int32_t *rounds, int32_t *complete,
+             int64_t *walked_per_round, int64_t *kept_per_round, int64_t *matched_per_round, uint64_t *ns_per_round,
+             uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,12 +11,13 @@ per-vertex counts, and tri_finish, tri.hip.h), or one of the core-number kernels
 core_close, core.hip.h), or one of the truss kernels (truss_init / truss_support / truss_total / truss_min / truss_open /
 truss_peel / truss_close, truss.hip.h), or one of the colouring kernels (gcol_init / gcol_count / gcol_ready / gcol_assign /
 gcol_close, color.hip.h; the prefix is their own because scc.hip.h speaks of colouring too), or one of the spanning-forest
-kernels (msf_weights / msf_init / msf_find / msf_pick / msf_link / msf_jump / msf_close / msf_top / msf_label, msf.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+kernels (msf_weights / msf_init / msf_find / msf_pick / msf_link / msf_jump / msf_close / msf_top / msf_label, msf.hip.h), or one of the matching
+kernels (match_init / match_bid / match_take / match_clear / match_close, match.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core, seen_truss, seen_gcol, seen_msf = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
+bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core, seen_truss, seen_gcol, seen_msf, seen_match = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
 BFS_KERNELS = ("bfs_init", "bfs_topdown", "bfs_bottomup", "bfs_queue_from_bitmap", "bfs_decide", "bfs_parents")
 SSSP_KERNELS = ("sssp_init", "sssp_relax", "sssp_split", "sssp_decide", "sssp_preds")
 SCC_KERNELS = ("scc_init", "scc_trim", "scc_pick", "scc_seed", "scc_propagate", "scc_claim", "scc_label", "scc_decide")
@@ -24,6 +25,7 @@ TRI_KERNELS = ("tri_count_light", "tri_count_heavy", "tri_finish")
 CORE_KERNELS = ("core_init", "core_min", "core_open", "core_peel", "core_close")
 TRUSS_KERNELS = ("truss_init", "truss_support", "truss_total", "truss_min", "truss_open", "truss_peel", "truss_close")
 GCOL_KERNELS = ("gcol_init", "gcol_count", "gcol_ready", "gcol_assign", "gcol_close")
+MATCH_KERNELS = ("match_init", "match_bid", "match_take", "match_clear", "match_close")
 MSF_KERNELS = ("msf_weights", "msf_init", "msf_find", "msf_pick", "msf_link", "msf_jump", "msf_close", "msf_top", "msf_label")
 WCC_KERNELS = ("wcc_init", "wcc_sample", "wcc_compact", "wcc_full", "wcc_jump", "wcc_decide", "wcc_label")
 for blk in text.split("remark: Function Name: ")[1:]:
@@ -40,9 +42,12 @@ for blk in text.split("remark: Function Name: ")[1:]:
     truss = any(k in name for k in TRUSS_KERNELS)
     gcol = any(k in name for k in GCOL_KERNELS)
     msf = any(k in name for k in MSF_KERNELS)
-    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core and not truss and not gcol and not msf:
+    match = any(k in name for k in MATCH_KERNELS)
+    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core and not truss and not gcol and not msf and not match:
         continue
-    if msf:
+    if match:
+        seen_match.add(name)
+    elif msf:
         seen_msf.add(name)
     elif gcol:
         seen_gcol.add(name)
@@ -122,7 +127,10 @@ if len(seen_gcol) != len(GCOL_KERNELS):
 # the nine kernels of sh_msf, under the limits of the BFS kernels
 if len(seen_msf) != len(MSF_KERNELS):
     sys.exit(f"expected {len(MSF_KERNELS)} spanning-forest kernels in the remarks, found {len(seen_msf)}: {sorted(seen_msf)}")
+# the five kernels of sh_match, under the limits of the BFS kernels
+if len(seen_match) != len(MATCH_KERNELS):
+    sys.exit(f"expected {len(MATCH_KERNELS)} matching kernels in the remarks, found {len(seen_match)}: {sorted(seen_match)}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle, {len(seen_core)} core-number, {len(seen_truss)} truss, {len(seen_gcol)} colouring and {len(seen_msf)} spanning-forest kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle, {len(seen_core)} core-number, {len(seen_truss)} truss, {len(seen_gcol)} colouring, {len(seen_msf)} spanning-forest and {len(seen_match)} matching kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

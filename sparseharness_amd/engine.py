@@ -559,6 +559,31 @@ class Engine:
         return (tree_edges.value, components.value, n, bool(complete.value), walked[:n].copy(), kept[:n].copy(),
                 hooks[:n].copy(), jumps[:n].copy(), per[:n].copy(), total.value)
 
+    # ---- greedy weighted matching: mate[v] = the partner of v in the matching a serial loop over ascending MKEY gives
+    def match_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.matching needs (match.MatchGraph), from the CSR arrays of a square matrix whose float32
+        values are the weights."""
+        from .match import MatchGraph   # (match.py imports this module)
+        return self._graph(MatchGraph, row_ptr, col_idx, val)
+
+    def matching(self, G, mate, heavy=1, seed=1, in_match=None, edge_u=None, edge_v=None, weight=None, max_rounds=4096):
+        """-> (pairs, rounds, complete, walked, kept, matched, ns, total_ns); per round: the length of the edge list at
+        its start, the edges whose ends were both free, the edges matched, device ns.  mate: an int32 vector of >= rows
+        elements; in_match, edge_u, edge_v, weight: None or vectors of >= M = G.edges elements.  heavy = 1: the heaviest
+        edges first; seed != 0 breaks ties by mix32(e ^ seed), seed = 0 by edge id (on equal weights that costs one round
+        per pair in places).  A run has at most rows // 2 + 1 rounds; one cut short leaves a valid matching that is not
+        maximal."""
+        pairs, rounds, complete, total = C.c_int64(), C.c_int32(), C.c_int32(), C.c_uint64()
+        cap = max(int(max_rounds), 1)
+        (walked, kept, matched, per), ptrs = _outs(cap, np.int64, np.int64, np.int64, np.uint64)
+        h = lambda v: None if v is None else v.h   # noqa: E731
+        self._chk(abi.load().sh_match(self.h, G.h, mate.h, h(in_match), h(edge_u), h(edge_v), h(weight), heavy,
+                                      int(seed) & 0xFFFFFFFF, max_rounds, C.byref(pairs), C.byref(rounds), C.byref(complete),
+                                      *ptrs, C.byref(total)))
+        n = rounds.value
+        return (pairs.value, n, bool(complete.value), walked[:n].copy(), kept[:n].copy(), matched[:n].copy(), per[:n].copy(),
+                total.value)
+
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
         dt = elem_dtype(semiring)

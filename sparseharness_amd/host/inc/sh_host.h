@@ -76,6 +76,17 @@ int sh_msf_edges(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_
                  int32_t *edge_u, int32_t *edge_v, uint32_t *weight, int32_t *in_msf, int32_t *comp, int64_t *edges,
                  int64_t *components);
 
+/* The greedy weighted matching of the simple undirected graph under a square CSR matrix, its float32 values as weights
+ * (clean, sort the edges by MKEY, take them in that order and keep an edge when both its ends are still free;
+ * single-threaded): the gold for sh_match.  The edge rule, the edges and their weights are sh_msf_edges'.  MKEY(e) =
+ * hi << 32 | lo with hi = k(weight[e]) for heavy == 0 (lightest first) and ~k(weight[e]) for heavy == 1 (heaviest first),
+ * lo = e for seed == 0 and mix32(e ^ seed) otherwise (sh_color's mix32).  edge_u, edge_v, weight and in_match (1 or 0)
+ * hold nnz words each, of which *edges are written; mate[v] (rows words) becomes the partner of v or -1; *pairs (may be
+ * NULL) the number of matched edges.  Return 0, -1 bad argument (heavy outside {0, 1} included). */
+int sh_greedy_matching(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                       int32_t heavy, uint32_t seed, int32_t *edge_u, int32_t *edge_v, uint32_t *weight, int32_t *in_match,
+                       int32_t *mate, int64_t *edges, int64_t *pairs);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

@@ -14,13 +14,9 @@
 #include <vector>
 
 #include "sh_host.h"
+#include "und_edges.h"
 
-static uint32_t mix32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352du;
-  x ^= x >> 15; x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
+using sh_host::mix32;
 
 extern "C" int sh_greedy_colors(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                                 int32_t order, uint32_t seed, const int32_t *prio, int32_t *color, int32_t *depth,

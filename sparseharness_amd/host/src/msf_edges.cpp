@@ -12,9 +12,7 @@
 #include <vector>
 
 #include "sh_host.h"
-
-static uint32_t order_key(uint32_t b) { return (b & 0x80000000u) ? ~b : (b ^ 0x80000000u); }
-static uint32_t order_bits(uint32_t k) { return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k; }
+#include "und_edges.h"
 
 extern "C" int sh_msf_edges(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                             int32_t *edge_u, int32_t *edge_v, uint32_t *weight, int32_t *in_msf, int32_t *comp,
@@ -22,32 +20,13 @@ extern "C" int sh_msf_edges(int64_t rows, int64_t nnz, const int32_t *row_ptr, c
   if (rows < 0 || nnz < 0 || !row_ptr || !edges_out || (nnz > 0 && (!col_idx || !val || !edge_u || !edge_v || !weight || !in_msf)) ||
       (rows > 0 && !comp))
     return -1;
-  const uint32_t *bits = (const uint32_t *)val;
-  // clean: every entry that counts, as ((smaller, larger), k(value)); sorted, the first of a run is the edge with its
-  // smallest key
-  struct Entry { uint64_t pair; uint32_t k; };
-  std::vector<Entry> entries;
-  entries.reserve((size_t)nnz);
-  for (int64_t r = 0; r < rows; r++)
-    for (int32_t j = row_ptr[r]; j < row_ptr[r + 1]; j++) {
-      const int32_t c = col_idx[j];
-      if (c < 0 || (int64_t)c >= rows || bits[j] == 0u || (int64_t)c == r) continue;
-      const uint64_t lo = (uint64_t)std::min<int64_t>(r, c), hi = (uint64_t)std::max<int64_t>(r, c);
-      entries.push_back(Entry{(lo << 32) | hi, order_key(bits[j])});
-    }
-  std::sort(entries.begin(), entries.end(),
-            [](const Entry &a, const Entry &b) { return a.pair != b.pair ? a.pair < b.pair : a.k < b.k; });
-  int64_t M = 0;
-  std::vector<uint64_t> keys;
-  keys.reserve(entries.size());
-  for (size_t i = 0; i < entries.size(); i++) {
-    if (i > 0 && entries[i].pair == entries[i - 1].pair) continue;
-    edge_u[M] = (int32_t)(entries[i].pair >> 32);
-    edge_v[M] = (int32_t)(entries[i].pair & 0xFFFFFFFFull);
-    weight[M] = order_bits(entries[i].k);
-    in_msf[M] = 0;
-    keys.push_back(((uint64_t)entries[i].k << 32) | (uint64_t)M);
-    M++;
+  // clean (und_edges.h): the edges, their ends, weights and k(weight)
+  std::vector<uint32_t> wk;
+  const int64_t M = sh_host::weighted_edges(rows, nnz, row_ptr, col_idx, (const uint32_t *)val, edge_u, edge_v, weight, wk);
+  std::vector<uint64_t> keys((size_t)M);
+  for (int64_t e = 0; e < M; e++) {
+    in_msf[e] = 0;
+    keys[e] = ((uint64_t)wk[e] << 32) | (uint64_t)e;
   }
   *edges_out = M;
   std::sort(keys.begin(), keys.end());

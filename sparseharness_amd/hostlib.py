@@ -3,7 +3,7 @@ loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
 host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp), sh_tri
 (host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp), sh_truss (host/src/truss_numbers.cpp), sh_color
-(host/src/greedy_colors.cpp) and sh_msf (host/src/msf_edges.cpp)."""
+(host/src/greedy_colors.cpp), sh_msf (host/src/msf_edges.cpp) and sh_match (host/src/greedy_matching.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -38,6 +38,7 @@ SIGNATURES = {
     "sh_truss_numbers": (C.c_int, _csr + [_vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sh_greedy_colors": (C.c_int, _csr + [C.c_int32, C.c_uint32, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(_i64)]),
     "sh_msf_edges": (C.c_int, _csr + [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sh_greedy_matching": (C.c_int, _csr + [C.c_int32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sh_mm_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]),
     "sh_mm_load_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]),
     "sh_host_csr_release": (None, [C.POINTER(_HostCsr)]),
@@ -188,6 +189,22 @@ def msf_edges(row_ptr, col_idx, val):
     m, k = C.c_int64(), C.c_int64()
     _gold("sh_msf_edges", row_ptr, col_idx, val, _p(eu), _p(ev), _p(w), _p(msf), _p(comp), C.byref(m), C.byref(k))
     return eu[:m.value].copy(), ev[:m.value].copy(), w[:m.value].copy(), msf[:m.value].copy(), comp[:n].copy(), m.value, k.value
+
+
+def greedy_matching(row_ptr, col_idx, val, heavy=1, seed=1):
+    """-> (edge_u, edge_v, weight, in_match, mate, M, pairs): the edges of the simple undirected graph under the entries
+    as msf_edges gives them, whether edge e is matched (int32, 1 or 0) and mate[v] (int32) = the partner of v or -1
+    (Engine.matching's outputs), by a single-threaded loop on the host that takes the edges in ascending MKEY and keeps
+    an edge when both its ends are still free.  MKEY(e) = hi << 32 | lo with hi = k(weight[e]) for heavy == 0 and its
+    complement for heavy == 1, lo = e for seed == 0 and mix32(e ^ seed) otherwise."""
+    n = len(row_ptr) - 1
+    cap = max(len(col_idx), 1)   # (M <= nnz)
+    eu, ev, chosen = (np.empty(cap, np.int32) for _ in range(3))
+    w, mate = np.empty(cap, np.uint32), np.empty(max(n, 1), np.int32)
+    m, k = C.c_int64(), C.c_int64()
+    _gold("sh_greedy_matching", row_ptr, col_idx, val, int(heavy), int(seed) & 0xFFFFFFFF, _p(eu), _p(ev), _p(w), _p(chosen),
+          _p(mate), C.byref(m), C.byref(k))
+    return eu[:m.value].copy(), ev[:m.value].copy(), w[:m.value].copy(), chosen[:m.value].copy(), mate[:n].copy(), m.value, k.value
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
