@@ -1491,6 +1491,109 @@ int sh_match(sh_engine *e, sh_match_graph *g, sh_vec *mate, sh_vec *in_match, sh
              int64_t *walked_per_round, int64_t *kept_per_round, int64_t *matched_per_round, uint64_t *ns_per_round,
              uint64_t *total_ns);
 
+/* ---- reverse Cuthill-McKee ordering in level-synchronous steps ----------------------------------------------------------
+ * (the reference has no counterpart.  After sh_color, sh_msf and sh_match this is the fourth question a user asks of a
+ * sparse matrix before solving with it: how to renumber it so that its entries stand near the diagonal -- a smaller
+ * bandwidth and profile for a banded or skyline factorisation, and columns that stay close for the x gather of SpMV.)
+ *
+ * The graph is sh_core's and sh_color's: the matrix is square (rows x rows); entry j of row r storing column c with
+ * 0 <= c < rows counts when its 32 value bits are not all zero; the graph is the SIMPLE UNDIRECTED graph under those
+ * entries.  Self-loops, parallel entries, stored zeros, the direction of an entry and columns outside the matrix change
+ * nothing.  deg[v] is the degree; "smaller" means the smaller pair (deg, index).
+ *      The definition (a serial loop; host/src/rcm_order.cpp is it, word for word).  Walk the vertices in ascending
+ *      (deg, index).  For every vertex v without a position yet:
+ *        1. The root, by George and Liu with a cap.  r = v.  With sweeps == 0 that is all.  Otherwise a breadth-first
+ *           search from r gives its eccentricity e and its last level; then at most `sweeps` times: x = the smallest
+ *           vertex of the last level; if x == r stop; the search from x gives e'; if e' > e take r = x, e = e' and that
+ *           search's last level and go on, otherwise stop and keep r.
+ *        2. Cuthill-McKee from r: r takes the next position; the vertices are then taken in position order, and each
+ *           one's neighbours without a position are appended in ascending (deg, index).
+ *      With reverse == 1 position k becomes rows - 1 - k.
+ *      perm[k]   = the vertex at new position k (int32; scipy's convention: A[perm][:, perm] is the reordered matrix).
+ *      pos[v]    = the new position of v, the inverse of perm (int32; optional).
+ *      level[v]  = the level of v in the search from its component's final root (int32; optional).
+ *      Vertices without an edge come first in the walk; each is its own component and takes no step.
+ *      *components = the components numbered.  *sweeps_run = the searches run to find roots (the one from v included).
+ *      *bandwidth_before / _after = max |p(u) - p(v)| over the edges, *profile_before / _after = the sum over v of
+ *      p(v) - min(p(v), min over the neighbours u of p(u)), p being the identity and the new position; exact, 64-bit.
+ *      A STEP is one level of one search: a search of eccentricity e takes e + 1 steps, and its last step finds nothing.
+ *      kind_per_step is 0 for a level of a root search and 1 for a level of the numbering, size_per_step the level's
+ *      width, edges_per_step the sum of its list lengths.  A run takes at most (sweeps + 2) * rows steps.  With the
+ *      ties fixed as above the answer is unique: every comparison is ==, the records included.
+ *
+ *      Schedule (csrc/rcm.hip.h).  The handle sorts the vertices once by deg << 32 | index and builds the symmetric lists
+ *      over those LABELS, so the smaller (deg, index) is the smaller label and every list stands in child order.  The
+ *      numbering runs level by level: the level occupies positions [a, b) of the order array; a vertex w of the next
+ *      level belongs to the smallest position of [a, b) adjacent to it (atomicMin(owner[w], i)); every position counts
+ *      the entries of its list that it owns; a prefix sum over the counts -- per workgroup over a contiguous chunk, the
+ *      workgroups' totals scanned by each -- gives position i's children their places b + offset + k in list order.  That
+ *      is the serial order: the serial loop appends w when it reaches the first position that has w in its list.  The
+ *      order array is its own queue and nothing is sorted per level.  A level of a root search is unordered: a stamp per
+ *      vertex holds the generation of the search that reached it (generations count down, so claiming is an atomic
+ *      minimum and nothing is cleared between searches), the queue is the free part of the order array, and the smallest
+ *      label of the new level is an atomic minimum.  A step is one fixed set of five launches enqueued ahead of the host
+ *      in batches (8, 16, 32, 32, ...), each of which returns at once unless the control block gives it work; the last is
+ *      one workgroup that records the step and chooses the next: the next level, a search from x, the numbering from r,
+ *      the next component (a cursor over the labels) or the end.  Lists of up to 8 entries are walked by a lane, up to
+ *      2048 by a wave (ranked by a ballot prefix), longer ones by the workgroup in chunks of 256.  Every exchange between
+ *      workgroups crosses a launch boundary; there is no compare-and-swap, no spin and no flag.
+ *      Worst cases: a step costs its five launches however narrow its level is, so a long thin graph (a path, a grid:
+ *      4095 levels per search on 2048 x 2048) pays per level, and a matrix with thousands of small components pays several
+ *      steps for each.
+ *
+ *      Measured on an MI355X (DESIGN.md "6o Reverse Cuthill-McKee"; tools/rcm_bench.py, one process per matrix, sweeps
+ *        0 / 2 / 8 and the host gold alternating, 5 rounds, device time against the wall time of hostlib.rcm_order in the
+ *        same process), median (min-max) in ms for sweeps = 8: the 2048 x 2048 grid (4 194 304 rows, 8 384 512 edges):
+ *        280.5 (267.7-282.7), 12 285 steps, 2 searches, bandwidth 2048 -> 2048 (host gold 1135); the same grid with its
+ *        vertices shuffled: 338.5 (308.7-341.8), bandwidth 4 191 905 -> 2048 (2733); R-MAT-18 (262 144 rows, 3 805 085
+ *        edges): 18.54 (18.02-18.71), 338 steps, 103 searches, 146 419 (581); synth:scircuit (170 998 rows, 958 718
+ *        edges): 3.63 (3.59-3.65), 35 steps, 131 287 (121).  sweeps = 0 costs 111.6, 127.2, 7.24 and 0.90 ms.  A step
+ *        costs 19 to 29 us on the grid however narrow its level is.  The handle is built in 0.05 to 0.06 s.  sh_spmv on
+ *        A[perm][:, perm] against A, both under the default plan, us per call: 47.2 against 52.6 on the grid, 47.3
+ *        against 58.1 on the shuffled grid, 25.1 against 31.3 on R-MAT-18, 12.9 against 13.5 on synth:scircuit.
+ *        Rule: a call is 0.03 of the host's serial loop on the two power-law matrices and 0.12 to 0.25 of it on the
+ *        grids; the device lost on none of the four.  Graphs below 10^5 rows, matrices with thousands of small
+ *        components that have edges, and matrices whose x does not fit in L2 are unmeasured.
+ *
+ * sh_rcm_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  The handle holds on the device:
+ * adj_ptr[rows + 1], adj_col[2M] (the symmetric lists over the labels, every list strictly ascending), S[rows] (label ->
+ * vertex), order, posl, levl, stamp, owner and cnt (`rows` words each) and a control block with a count per workgroup.
+ * rows == 0 gives a valid handle.  Freeing NULL is SH_OK.  The build runs on the device, once: while it runs it needs
+ * what sh_core_graph_create needs and 24 bytes per row for the degrees, the sort keys and the inverse of S; all of it is
+ * released before the call returns.  nnz is bounded as for the other handles, and 2M by 2^31 - 256.
+ * sh_rcm_graph_footprint: device bytes held =
+ *     4 * (rows + 1) + 28 * rows + 8 * edges + 50176.
+ * sh_rcm_graph_edges: M.  sh_rcm_graph_max_degree: the largest degree (the length of the longest list).
+ *
+ * sh_rcm: perm: an int32 vector of >= rows elements; pos, level: NULL, or such vectors; `rows` elements of each are
+ * overwritten, no more.  sweeps in [0, 64] (the Python binding's default: 8).  reverse: 0 or 1 (default 1).
+ * max_steps >= 1 bounds the steps; (sweeps + 2) * rows + 1 can never cut a run short.  The per-step arrays (capacity
+ * max_steps; each may be NULL): kind_per_step, size_per_step, edges_per_step, ns_per_step device time.  *total_ns (may be
+ * NULL) is the device time of the start, all steps and the closing launch (hipEvent) as elsewhere.  A run cut short
+ * returns *complete = 0: the numbered part of perm is as the full run would give it, the rest of perm is -1, pos and
+ * level of the vertices without a position are -1, and *bandwidth_after and *profile_after are -1.  The handle is good
+ * for another call; one handle serves any number of calls, one at a time.  rows == 0 gives SH_OK with zeros and
+ * *complete = 1.
+ * SH_EINVAL: sweeps outside [0, 64], reverse outside {0, 1}, max_steps < 1 (the scalars are checked first); NULL arguments
+ * (engine, graph, perm, components, sweeps_run, steps, complete, the bandwidths and profiles, out, the arrays), rows < 0,
+ * nnz < 0.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases; perm, pos or level shorter than
+ * rows.  All are reported before any device work, with the buffers untouched.
+ * NOT covered: orderings other than RCM (Sloan, nested dissection, minimum degree), running small components
+ * concurrently, permuting an uploaded sh_csr on the device, the multi-GPU driver, the C++ harness apps.
+ */
+typedef struct sh_rcm_graph sh_rcm_graph;
+int sh_rcm_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_rcm_graph **out);
+int sh_rcm_graph_free(sh_engine *e, sh_rcm_graph *g);
+int sh_rcm_graph_footprint(const sh_rcm_graph *g, uint64_t *device_bytes);
+int sh_rcm_graph_edges(const sh_rcm_graph *g, int64_t *edges);          /* M */
+int sh_rcm_graph_max_degree(const sh_rcm_graph *g, int64_t *entries);
+int sh_rcm(sh_engine *e, sh_rcm_graph *g, sh_vec *perm, sh_vec *pos, sh_vec *level, int32_t sweeps, int32_t reverse,
+           int32_t max_steps, int32_t *components, int32_t *sweeps_run, int32_t *steps, int32_t *complete,
+           int64_t *bandwidth_before, int64_t *bandwidth_after, int64_t *profile_before, int64_t *profile_after,
+           int32_t *kind_per_step, int64_t *size_per_step, int64_t *edges_per_step, uint64_t *ns_per_step,
+           uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,14 @@ SIGNATURES = {
     "sh_match_graph_edges": (_int, [_vp, C.POINTER(_i64)]),
     "sh_match": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, C.c_uint32, _i32, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32),
                         C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "sh_rcm_graph_create": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _pp]),
+    "sh_rcm_graph_free": (_int, [_vp, _vp]),
+    "sh_rcm_graph_footprint": (_int, [_vp, C.POINTER(_u64)]),
+    "sh_rcm_graph_edges": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_rcm_graph_max_degree": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_rcm": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                      C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64),
+                      C.POINTER(_i64), C.POINTER(_u64), C.POINTER(_u64)]),
 }
 
 _lib = None

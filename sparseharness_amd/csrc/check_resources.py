@@ -12,12 +12,13 @@ core_close, core.hip.h), or one of the truss kernels (truss_init / truss_support
 truss_peel / truss_close, truss.hip.h), or one of the colouring kernels (gcol_init / gcol_count / gcol_ready / gcol_assign /
 gcol_close, color.hip.h; the prefix is their own because scc.hip.h speaks of colouring too), or one of the spanning-forest
 kernels (msf_weights / msf_init / msf_find / msf_pick / msf_link / msf_jump / msf_close / msf_top / msf_label, msf.hip.h), or one of the matching
-kernels (match_init / match_bid / match_take / match_clear / match_close, match.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+kernels (match_init / match_bid / match_take / match_clear / match_close, match.hip.h), or one of the ordering kernels (rcm_init /
+rcm_begin / rcm_sweep / rcm_claim / rcm_count / rcm_place / rcm_close / rcm_finish / rcm_total, rcm.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core, seen_truss, seen_gcol, seen_msf, seen_match = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
+bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core, seen_truss, seen_gcol, seen_msf, seen_match, seen_rcm = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
 BFS_KERNELS = ("bfs_init", "bfs_topdown", "bfs_bottomup", "bfs_queue_from_bitmap", "bfs_decide", "bfs_parents")
 SSSP_KERNELS = ("sssp_init", "sssp_relax", "sssp_split", "sssp_decide", "sssp_preds")
 SCC_KERNELS = ("scc_init", "scc_trim", "scc_pick", "scc_seed", "scc_propagate", "scc_claim", "scc_label", "scc_decide")
@@ -26,6 +27,7 @@ CORE_KERNELS = ("core_init", "core_min", "core_open", "core_peel", "core_close")
 TRUSS_KERNELS = ("truss_init", "truss_support", "truss_total", "truss_min", "truss_open", "truss_peel", "truss_close")
 GCOL_KERNELS = ("gcol_init", "gcol_count", "gcol_ready", "gcol_assign", "gcol_close")
 MATCH_KERNELS = ("match_init", "match_bid", "match_take", "match_clear", "match_close")
+RCM_KERNELS = ("rcm_init", "rcm_begin", "rcm_sweep", "rcm_claim", "rcm_count", "rcm_place", "rcm_close", "rcm_finish", "rcm_total")
 MSF_KERNELS = ("msf_weights", "msf_init", "msf_find", "msf_pick", "msf_link", "msf_jump", "msf_close", "msf_top", "msf_label")
 WCC_KERNELS = ("wcc_init", "wcc_sample", "wcc_compact", "wcc_full", "wcc_jump", "wcc_decide", "wcc_label")
 for blk in text.split("remark: Function Name: ")[1:]:
@@ -43,9 +45,12 @@ for blk in text.split("remark: Function Name: ")[1:]:
     gcol = any(k in name for k in GCOL_KERNELS)
     msf = any(k in name for k in MSF_KERNELS)
     match = any(k in name for k in MATCH_KERNELS)
-    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core and not truss and not gcol and not msf and not match:
+    rcm = any(k in name for k in RCM_KERNELS)
+    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core and not truss and not gcol and not msf and not match and not rcm:
         continue
-    if match:
+    if rcm:
+        seen_rcm.add(name)
+    elif match:
         seen_match.add(name)
     elif msf:
         seen_msf.add(name)
@@ -130,7 +135,10 @@ if len(seen_msf) != len(MSF_KERNELS):
 # the five kernels of sh_match, under the limits of the BFS kernels
 if len(seen_match) != len(MATCH_KERNELS):
     sys.exit(f"expected {len(MATCH_KERNELS)} matching kernels in the remarks, found {len(seen_match)}: {sorted(seen_match)}")
+# the nine kernels of sh_rcm, under the limits of the BFS kernels
+if len(seen_rcm) != len(RCM_KERNELS):
+    sys.exit(f"expected {len(RCM_KERNELS)} ordering kernels in the remarks, found {len(seen_rcm)}: {sorted(seen_rcm)}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle, {len(seen_core)} core-number, {len(seen_truss)} truss, {len(seen_gcol)} colouring, {len(seen_msf)} spanning-forest and {len(seen_match)} matching kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle, {len(seen_core)} core-number, {len(seen_truss)} truss, {len(seen_gcol)} colouring, {len(seen_msf)} spanning-forest, {len(seen_match)} matching and {len(seen_rcm)} ordering kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

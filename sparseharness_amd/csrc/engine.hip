@@ -21,6 +21,7 @@
 #include "color.hip.h"
 #include "msf.hip.h"
 #include "match.hip.h"
+#include "rcm.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 #include "dev_arrays.h"
@@ -1969,7 +1970,7 @@ static int create_graph_handle(sh_engine *e, const char *fn, int64_t rows, int64
   return SH_OK;
 }
 
-// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core, sh_truss, sh_color, sh_msf and sh_match: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core, sh_truss, sh_color, sh_msf, sh_match and sh_rcm: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
 // next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
 // enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
 // step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
@@ -3622,6 +3623,204 @@ int sh_match(sh_engine *e, sh_match_graph *g, sh_vec *mate, sh_vec *in_match, sh
   *pairs = found;
   *rounds = it;
   *complete = done ? 1 : 0;
+  if (total_ns)
+    *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- reverse Cuthill-McKee ordering in level-synchronous steps (rcm.hip.h) ----------------------------------------------
+// The GraphHandle base serves run_batches.  The symmetric lists stand over the LABELS (the vertices sorted by (deg, index))
+// in d_in_ptr / d_in_col; d_S maps a label back to its vertex.  d_ctl: RCM_CTL_BYTES, followed by the WlParts of a step
+// and the RcmFins of the closing launch.
+struct sh_rcm_graph : GraphHandle<RcmCtl> {
+  int64_t max_degree = 0, zeros = 0;   // the longest list; the vertices without an edge (labels 0 .. zeros - 1)
+  int32_t *d_S = nullptr;
+  RcmState st = {};
+  RcmFin *d_fin = nullptr;
+};
+static_assert(sizeof(RcmCtl) <= RCM_CTL_BYTES, "the control block is accounted as RCM_CTL_BYTES (sh_rcm_graph_footprint)");
+static_assert(sizeof(WlPart) * RCM_MAX_BLOCKS == RCM_PART_BYTES, "one WlPart per workgroup");
+static_assert(sizeof(RcmFin) * RCM_MAX_BLOCKS == RCM_FIN_BYTES, "one RcmFin per workgroup");
+static_assert(sizeof(RcmCtl::rec) / sizeof(RcmRec) == RCM_BATCH, "one record per step of a batch");
+// sh_rcm_graph_footprint: ptr; S, order, posl, levl, stamp, owner and cnt (4 bytes per row each); col (8 bytes per edge)
+static_assert(RCM_CTL_BYTES + RCM_PART_BYTES + RCM_FIN_BYTES == 50176, "the header states 4 * (rows + 1) + 28 * rows + 8 * edges + 50176");
+static constexpr const char *RCM_CREATE = "sh_rcm_graph_create";
+
+// The lists of an RCM handle from host CSR arrays: the edges of the simple graph and the degrees (build_und_edges), the
+// vertices sorted by deg << 32 | index (S and its inverse), every edge as two keys over the labels, sorted, the list
+// starts taken from them (build_symmetric_lists' second half, over labels).  Returns with the stream synchronised.
+static int build_label_lists(sh_engine *e, sh_rcm_graph *g, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                             const void *val) {
+  g->rows = rows; g->nnz = nnz;
+  DevArrays &own = g->dev;
+  DevArrays scratch;   // what the build needs while it runs
+  HIP_TRY(e, own.alloc(&g->d_in_ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_S, rows * 4));
+  HIP_TRY(e, hipMemsetAsync(g->d_in_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  uint32_t *t_deg = nullptr, *t_inv = nullptr, *t_two = nullptr;   // t_two: the labels without an edge, the longest list
+  uint64_t *t_vkey = nullptr, *t_vsorted = nullptr;
+  HIP_TRY(e, scratch.alloc(&t_deg, rows * 4));
+  HIP_TRY(e, scratch.alloc(&t_inv, rows * 4));
+  HIP_TRY(e, scratch.alloc(&t_vkey, rows * 8));
+  HIP_TRY(e, scratch.alloc(&t_vsorted, rows * 8));
+  HIP_TRY(e, scratch.alloc(&t_two, 8));
+  HIP_TRY(e, hipMemsetAsync(t_deg, 0, (size_t)std::max<int64_t>(rows, 1) * 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(t_two, 0, 8, e->stream));
+  UndEdges u;
+  const int rc = build_und_edges(e, scratch, rows, nnz, row_ptr, col_idx, val, t_deg, &u);
+  if (rc)
+    return rc;
+  const int64_t S = u.S, M = u.M, E = 2 * M;
+  if (E > 0x7FFFFF00ll)
+    return fail(e, SH_EINVAL, "%s: the lists hold %lld entries (twice the %lld edges), must be at most 2^31 - 256", RCM_CREATE,
+                (long long)E, (long long)M);
+  g->edges = M;
+  HIP_TRY(e, own.alloc(&g->d_in_col, E * 4));
+  const dim3 blk(WL_BS);
+  const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
+  if (rows > 0) {
+    hipLaunchKernelGGL(rcm_vertex_keys, grid_for(rows), blk, 0, e->stream, t_deg, rows, t_vkey);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_keys_u64(e->stream, t_vkey, t_vsorted, rows, 64));
+    hipLaunchKernelGGL(rcm_labels, grid_for(rows), blk, 0, e->stream, t_vsorted, rows, g->d_S, t_inv, t_two);
+    HIP_TRY(e, hipGetLastError());
+  }
+  if (M > 0) {
+    uint64_t *t_key = nullptr, *t_sorted = nullptr;
+    HIP_TRY(e, scratch.alloc(&t_key, E * 8));
+    HIP_TRY(e, scratch.alloc(&t_sorted, E * 8));
+    hipLaunchKernelGGL(rcm_both_ways, grid_for(S), blk, 0, e->stream, u.sorted, u.head, u.pos, S, u.bits, t_inv, t_key);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_keys_u64(e->stream, t_key, t_sorted, E, 2 * u.bits));
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(E, rows + 1)), blk, 0, e->stream, t_sorted, E, rows, u.bits, g->d_in_ptr, g->d_in_col);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(wl_max_len, dim3((unsigned)std::max(1, std::min(e->n_cus * 4, RCM_MAX_BLOCKS))), blk, 0, e->stream, g->d_in_ptr, rows,
+                       t_two + 1);
+    HIP_TRY(e, hipGetLastError());
+  }
+  uint32_t two[2] = {0, 0};
+  HIP_TRY(e, hipMemcpyAsync(two, t_two, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  g->zeros = (int64_t)two[0];
+  g->max_degree = (int64_t)two[1];
+  return SH_OK;
+}
+
+extern "C" {
+
+int sh_rcm_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                        const void *val, sh_rcm_graph **out) {
+  return create_graph_handle<sh_rcm_graph>(e, RCM_CREATE, rows, nnz, row_ptr, col_idx, val, out, [&](sh_rcm_graph *g) -> int {
+    int rc;
+    if ((rc = build_label_lists(e, g, rows, nnz, row_ptr, col_idx, val)))
+      return rc;
+    HIP_TRY(e, g->dev.alloc(&g->st.order, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->st.posl, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->st.levl, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->st.stamp, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->st.owner, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->st.cnt, rows * 4));
+    if ((rc = open_control(e, g, RCM_CTL_BYTES, RCM_CTL_BYTES + RCM_PART_BYTES + RCM_FIN_BYTES)))
+      return rc;
+    g->d_fin = (RcmFin *)((char *)g->d_ctl + RCM_CTL_BYTES + RCM_PART_BYTES);
+    return SH_OK;
+  });
+}
+
+int sh_rcm_graph_free(sh_engine *e, sh_rcm_graph *g) { return free_handle(e, g); }
+
+int sh_rcm_graph_footprint(const sh_rcm_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
+
+int sh_rcm_graph_edges(const sh_rcm_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
+
+int sh_rcm_graph_max_degree(const sh_rcm_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->max_degree); }
+
+int sh_rcm(sh_engine *e, sh_rcm_graph *g, sh_vec *perm, sh_vec *pos, sh_vec *level, int32_t sweeps, int32_t reverse, int32_t max_steps,
+           int32_t *components, int32_t *sweeps_run, int32_t *steps, int32_t *complete,
+           int64_t *bandwidth_before, int64_t *bandwidth_after, int64_t *profile_before, int64_t *profile_after,
+           int32_t *kind_per_step, int64_t *size_per_step, int64_t *edges_per_step, uint64_t *ns_per_step, uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (sweeps < 0 || sweeps > RCM_MAX_SWEEPS)
+    return fail(e, SH_EINVAL, "sh_rcm: sweeps = %d, must be in [0, %d]", (int)sweeps, RCM_MAX_SWEEPS);
+  if (reverse != 0 && reverse != 1)
+    return fail(e, SH_EINVAL, "sh_rcm: reverse = %d, must be 0 (Cuthill-McKee) or 1 (reversed)", (int)reverse);
+  if (max_steps < 1)
+    return fail(e, SH_EINVAL, "sh_rcm: max_steps = %d, must be at least 1", (int)max_steps);
+  if (!e || !g || !perm || !components || !sweeps_run || !steps || !complete || !bandwidth_before || !bandwidth_after ||
+      !profile_before || !profile_after)
+    return fail(e, SH_EINVAL, "sh_rcm: NULL argument (engine, graph, perm, components, sweeps_run, steps, complete, or a bandwidth or profile)");
+  const int64_t rows = g->rows;
+  const struct { const sh_vec *v; const char *name; } vecs[] = {{perm, "perm"}, {pos, "pos"}, {level, "level"}};
+  for (const auto &x : vecs)
+    if (x.v && x.v->n < rows)
+      return fail(e, SH_ESHAPE, "sh_rcm: %s is shorter than the graph's %lld rows", x.name, (long long)rows);
+  *components = 0; *sweeps_run = 0; *steps = 0; *complete = 1;
+  *bandwidth_before = 0; *bandwidth_after = 0; *profile_before = 0; *profile_after = 0;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, RCM_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
+  const RcmGraph G{(int32_t)rows, g->d_in_ptr, g->d_in_col};
+  const RcmState &St = g->st;
+  uint64_t total = 0;
+  // the vertices without an edge take the first positions; the walk stands at the first vertex that has one
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, RCM_CTL_BYTES, e->stream));
+  hipLaunchKernelGGL(rcm_init, grid, block, 0, e->stream, G, St, (uint32_t)g->zeros);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(rcm_begin, dim3(1), block, 0, e->stream, g->d_ctl, (int32_t)rows, St, (uint32_t)g->zeros, sweeps);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  int32_t it = 0;
+  bool done = false;
+  // the launches of a step: each returns at once unless the control block says the step is its turn and of its kind
+  const auto enqueue = [&](int s, int k) {
+    hipLaunchKernelGGL(rcm_sweep, grid, block, 0, e->stream, g->d_ctl, s, G, St, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(rcm_claim, grid, block, 0, e->stream, g->d_ctl, s, G, St);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(rcm_count, grid, block, 0, e->stream, g->d_ctl, s, G, St, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(rcm_place, grid, block, 0, e->stream, g->d_ctl, s, G, St, g->d_part);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(rcm_close, dim3(1), block, 0, e->stream, g->d_ctl, k, s, (int32_t)rows, nblocks, g->d_part, St);
+    HIP_TRY(e, hipGetLastError());
+    return (int)SH_OK;
+  };
+  const auto take = [&](int s, const RcmRec &rc, uint64_t step_ns) {
+    if (kind_per_step) kind_per_step[s] = rc.kind;
+    if (size_per_step) size_per_step[s] = (int64_t)rc.size;
+    if (edges_per_step) edges_per_step[s] = (int64_t)rc.edges;
+    if (ns_per_step) ns_per_step[s] = step_ns;
+  };
+  const int rc = run_batches(e, "sh_rcm: step", g, max_steps, &it, &done, &total, enqueue, take);
+  if (rc)
+    return rc;
+  // the closing launch: perm, pos and level through S; bandwidth and profile before and after
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  hipLaunchKernelGGL(rcm_finish, grid, block, 0, e->stream, g->d_ctl, G, St, g->d_S, reverse, (int32_t *)perm->d,
+                     pos ? (int32_t *)pos->d : nullptr, level ? (int32_t *)level->d : nullptr, g->d_fin);
+  HIP_TRY(e, hipGetLastError());
+  hipLaunchKernelGGL(rcm_total, dim3(1), block, 0, e->stream, g->d_ctl, nblocks, g->d_fin);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(g->h_ctl, g->d_ctl, sizeof(RcmCtl), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  uint64_t ns = 0;
+  HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+  total += ns;
+  *components = g->h_ctl->components;
+  *sweeps_run = g->h_ctl->sweeps_run;
+  *steps = it;
+  *complete = done ? 1 : 0;
+  *bandwidth_before = g->h_ctl->bw[0];
+  *profile_before = g->h_ctl->prof[0];
+  *bandwidth_after = done ? g->h_ctl->bw[1] : -1;
+  *profile_after = done ? g->h_ctl->prof[1] : -1;
   if (total_ns)
     *total_ns = total;
   return SH_OK;

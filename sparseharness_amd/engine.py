@@ -584,6 +584,34 @@ class Engine:
         return (pairs.value, n, bool(complete.value), walked[:n].copy(), kept[:n].copy(), matched[:n].copy(), per[:n].copy(),
                 total.value)
 
+    # ---- reverse Cuthill-McKee: perm[k] = the vertex at new position k, in the order a serial loop with fixed ties gives
+    def rcm_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.rcm_order needs (rcm.RcmGraph), from the CSR arrays of a square matrix."""
+        from .rcm import RcmGraph   # (rcm.py imports this module)
+        return self._graph(RcmGraph, row_ptr, col_idx, val)
+
+    def rcm_order(self, G, perm, pos=None, level=None, sweeps=8, reverse=1, max_steps=None):
+        """-> (components, sweeps_run, steps, complete, bandwidth_before, bandwidth_after, profile_before, profile_after,
+        kinds, sizes, edges, ns, total_ns); per step (one level of one breadth-first search): 0 for a root search and 1
+        for the numbering, the level's width, the sum of its list lengths, device ns.  perm: an int32 vector of >= rows
+        elements (A[perm][:, perm] is the reordered matrix); pos, level: None or such vectors.  sweeps: the searches
+        George and Liu's root finder may add to the first one, 0 for the first vertex of the walk as the root;
+        reverse = 0 gives the Cuthill-McKee order itself.  max_steps = None: min((sweeps + 2) * rows + 1, 2^20); a run
+        cut short has complete = False, -1 in the rest of perm and -1 for both values after."""
+        if max_steps is None:
+            max_steps = min((int(sweeps) + 2) * G.n + 1, 1 << 20)
+        components, sweeps_run, steps, complete, total = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+        bw0, bw1, prof0, prof1 = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        cap = max(int(max_steps), 1)
+        (kinds, sizes, edges, per), ptrs = _outs(cap, np.int32, np.int64, np.int64, np.uint64)
+        h = lambda v: None if v is None else v.h   # noqa: E731
+        self._chk(abi.load().sh_rcm(self.h, G.h, perm.h, h(pos), h(level), sweeps, reverse, max_steps, C.byref(components),
+                                    C.byref(sweeps_run), C.byref(steps), C.byref(complete), C.byref(bw0), C.byref(bw1),
+                                    C.byref(prof0), C.byref(prof1), *ptrs, C.byref(total)))
+        n = steps.value
+        return (components.value, sweeps_run.value, n, bool(complete.value), bw0.value, bw1.value, prof0.value, prof1.value,
+                kinds[:n].copy(), sizes[:n].copy(), edges[:n].copy(), per[:n].copy(), total.value)
+
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
         dt = elem_dtype(semiring)

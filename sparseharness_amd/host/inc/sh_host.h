@@ -87,6 +87,23 @@ int sh_greedy_matching(int64_t rows, int64_t nnz, const int32_t *row_ptr, const 
                        int32_t heavy, uint32_t seed, int32_t *edge_u, int32_t *edge_v, uint32_t *weight, int32_t *in_match,
                        int32_t *mate, int64_t *edges, int64_t *pairs);
 
+/* The reverse Cuthill-McKee ordering of the simple undirected graph under a square CSR pattern (clean, sort every list by
+ * (deg, index), walk the vertices in ascending (deg, index), pick each component's root by George and Liu's searches with
+ * a cap of `sweeps` beyond the first, number it from the root with one queue; single-threaded): the gold for sh_rcm, and
+ * its definition.  Entry (r, c) counts when 0 <= c < rows, c != r and its 32 value bits are not all zero, in either
+ * direction, once.  sweeps in [0, 64] (0: the first vertex of the walk is the root); reverse in {0, 1} (1: position k
+ * becomes rows - 1 - k).  perm[k] (rows words) becomes the vertex at new position k; pos[v] and level[v] (rows words each;
+ * may be NULL) its inverse and the level of v from its component's root; bandwidth[0], [1] and profile[0], [1] (may be
+ * NULL) max |p(u) - p(v)| over the edges and the sum of p(v) - min(p(v), min over the neighbours) under the identity and
+ * under the new order; *components, *searches (the searches run to find roots) and *edges may be NULL.  A step is one
+ * level of one search, a search from a vertex with an edge only: kind[s] (0 a root search, 1 the numbering), size[s] (the
+ * level's width) and looked[s] (the sum of its list lengths) are written for s < steps_cap (each may be NULL), *steps (may
+ * be NULL) becomes the number of steps.  Return 0, -1 bad argument. */
+int sh_rcm_order(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                 int32_t sweeps, int32_t reverse, int32_t *perm, int32_t *pos, int32_t *level, int64_t *bandwidth,
+                 int64_t *profile, int32_t *components, int32_t *searches, int64_t *edges, int64_t steps_cap, int32_t *kind,
+                 int64_t *size, int64_t *looked, int64_t *steps);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

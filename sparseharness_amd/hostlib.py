@@ -3,7 +3,7 @@ loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
 host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp), sh_tri
 (host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp), sh_truss (host/src/truss_numbers.cpp), sh_color
-(host/src/greedy_colors.cpp), sh_msf (host/src/msf_edges.cpp) and sh_match (host/src/greedy_matching.cpp)."""
+(host/src/greedy_colors.cpp), sh_msf (host/src/msf_edges.cpp), sh_match (host/src/greedy_matching.cpp) and sh_rcm (host/src/rcm_order.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -39,6 +39,8 @@ SIGNATURES = {
     "sh_greedy_colors": (C.c_int, _csr + [C.c_int32, C.c_uint32, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(_i64)]),
     "sh_msf_edges": (C.c_int, _csr + [_vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sh_greedy_matching": (C.c_int, _csr + [C.c_int32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sh_rcm_order": (C.c_int, _csr + [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                      C.POINTER(_i64), _i64, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sh_mm_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]),
     "sh_mm_load_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]),
     "sh_host_csr_release": (None, [C.POINTER(_HostCsr)]),
@@ -205,6 +207,31 @@ def greedy_matching(row_ptr, col_idx, val, heavy=1, seed=1):
     _gold("sh_greedy_matching", row_ptr, col_idx, val, int(heavy), int(seed) & 0xFFFFFFFF, _p(eu), _p(ev), _p(w), _p(chosen),
           _p(mate), C.byref(m), C.byref(k))
     return eu[:m.value].copy(), ev[:m.value].copy(), w[:m.value].copy(), chosen[:m.value].copy(), mate[:n].copy(), m.value, k.value
+
+
+def rcm_order(row_ptr, col_idx, val, sweeps=8, reverse=1, records=False):
+    """-> (perm, pos, level, bandwidth_before, bandwidth_after, profile_before, profile_after, components, searches), and
+    with records (kinds, sizes, edges) behind them -- per step, i.e. per level of every search from a vertex with an
+    edge: 0 for a root search and 1 for the numbering, the level's width, the sum of its list lengths --:
+    perm[k] (int32) = the vertex at new position k under the reverse Cuthill-McKee ordering of the simple undirected
+    graph under the entries (Engine.rcm_order's perm; A[perm][:, perm] is the reordered matrix), pos its inverse,
+    level[v] the level of v from its component's root, bandwidth and profile under the identity and under the new order,
+    the components and the searches run to find roots, by the serial definition on the host: the vertices walked in
+    ascending (deg, index), each component's root by George and Liu's searches (at most `sweeps` beyond the first; 0: the
+    first vertex of the walk), the numbering with one queue and every list in ascending (deg, index).  Entry (r, c)
+    counts when 0 <= c < rows, c != r and its 32 value bits are not all zero."""
+    n = len(row_ptr) - 1
+    perm, pos, level = (np.empty(max(n, 1), np.int32) for _ in range(3))
+    bw, prof = np.zeros(2, np.int64), np.zeros(2, np.int64)
+    comps, searches = C.c_int32(), C.c_int32()
+    cap = (int(sweeps) + 2) * n + 1 if records else 0   # (a run has at most (sweeps + 2) * rows steps)
+    kinds, sizes, edges, steps = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int64), _i64()
+    _gold("sh_rcm_order", row_ptr, col_idx, val, int(sweeps), int(reverse), _p(perm), _p(pos), _p(level), _p(bw), _p(prof),
+          C.byref(comps), C.byref(searches), None, cap, _p(kinds), _p(sizes), _p(edges), C.byref(steps))
+    out = (perm[:n].copy(), pos[:n].copy(), level[:n].copy(), int(bw[0]), int(bw[1]), int(prof[0]), int(prof[1]), comps.value,
+           searches.value)
+    k = steps.value
+    return out + (kinds[:k].copy(), sizes[:k].copy(), edges[:k].copy()) if records else out
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
