@@ -7,13 +7,14 @@
 //   - a word that is used as an index (a vertex or edge id of a queue or work list) gets index_word, which the caller
 //     chooses as a VALID id whose consumption would change the answer; a piece record gets {index_word, 0}, the first
 //     piece of that vertex's list;
-//   - arrays built once (d_in_*, d_out_*, weights, d_rpieces, d_deg, d_eid, d_eu, d_ev, the forward lists and the
-//     control block of sh_tri_graph) are not touched.
+//   - arrays built once (d_in_*, d_out_*, weights, d_rpieces, d_deg, d_eid, d_eu, d_ev, d_wk, d_S, the forward lists and
+//     the control block of sh_tri_graph) are not touched.
 // So a call that consumes a poisoned word gives a wrong answer, not a wild access.  index_word is checked against the
-// handle (rows; edges for sh_truss_graph) before anything is filled.
+// handle (rows; edges for sh_truss_graph; min(rows, edges) for sh_msf_graph and sh_match_graph, whose parent words hold
+// vertices and whose work lists hold edges) before anything is filled.
 // kind: 0 sh_frontier, 1 sh_bfs_graph, 2 sh_sssp_graph, 3 sh_scc_graph, 4 sh_wcc_graph, 5 sh_tri_graph, 6 sh_core_graph,
-// 7 sh_truss_graph (the order of the header).  What is left out of a handle, and why, is listed case by case below and in
-// DESIGN.md "Graph and worklist hygiene".
+// 7 sh_truss_graph, 8 sh_color_graph, 9 sh_msf_graph, 10 sh_match_graph, 11 sh_rcm_graph (the order of the header).
+// What is left out of a handle, and why, is listed case by case below and in DESIGN.md "Graph and worklist hygiene".
 // sizes[0..SH_DEBUG_GRAPH_SIZES): the bytes filled per array, in the order of the `fill` calls below; the rest 0.
 #pragma once
 
@@ -136,6 +137,64 @@ extern "C" int sh_debug_poison_graph(sh_engine *e, int kind, void *handle, uint3
       fill(g->d_sup, data_word);
       fill(g->d_stamp, data_word);
       for (int i = 0; i < 2; i++) fill(g->lists.list[i], index_word);
+      break;
+    }
+    case 8: {
+      // d_deg and the symmetric lists (d_in_ptr, d_in_col) are built once.  d_wait is zeroed for every row by gcol_init,
+      // the WlParts are written by every workgroup of gcol_assign before gcol_close sums them, and a work list is read
+      // up to the counts of the control block only, which sh_color zeroes.
+      sh_color_graph *g = (sh_color_graph *)handle;
+      if ((int64_t)index_word >= g->rows) return SH_EINVAL;
+      dev = &g->dev;
+      fill(g->d_ctl, data_word);   // ColorCtl and the WlParts
+      fill(g->d_wait, data_word);
+      for (int i = 0; i < 2; i++) fill(g->lists.list[i], index_word);   // vertices
+      break;
+    }
+    case 9: {
+      // d_eu, d_ev and d_wk are built once.  msf_init writes p, best and list 0 whole; to[r] is written by msf_pick for
+      // exactly the roots whose word msf_link reads; the WlParts of msf_link and of the jumps (d_jpart, behind them in
+      // d_ctl's allocation) are written by every workgroup of a round before msf_close sums them.  p and to hold vertex
+      // ids and the lists edge ids: index_word has to be valid as both.
+      sh_msf_graph *g = (sh_msf_graph *)handle;
+      if ((int64_t)index_word >= std::min(g->rows, g->edges)) return SH_EINVAL;
+      dev = &g->dev;
+      fill(g->d_ctl, data_word);    // MsfCtl, the WlParts of msf_link and those of the jumps (d_jpart)
+      fill(g->d_best, data_word);   // (64-bit words: data_word twice; 0 is a key below every bid)
+      fill(g->d_p, index_word);     // vertices: msf_find, msf_pick and msf_jump index by it
+      fill(g->d_to, index_word);    // vertices: msf_link stores it into p
+      for (int i = 0; i < 2; i++) fill(g->lists.list[i], index_word);   // edges
+      break;
+    }
+    case 10: {
+      // d_eu, d_ev and d_wk are built once (build_weighted_edges, as for sh_msf_graph); mate is the caller's vector.
+      // match_init writes best and list 0 whole, match_bid fills the other list up to the count match_take and
+      // match_clear read, and every workgroup of match_take writes its WlPart before match_close sums them.  The handle
+      // has no array of vertex ids; index_word is checked as for sh_msf_graph all the same, so that one word serves both.
+      sh_match_graph *g = (sh_match_graph *)handle;
+      if ((int64_t)index_word >= std::min(g->rows, g->edges)) return SH_EINVAL;
+      dev = &g->dev;
+      fill(g->d_ctl, data_word);    // MatchCtl and the WlParts
+      fill(g->d_best, data_word);   // (64-bit words: data_word twice; 0 is a key below every bid)
+      for (int i = 0; i < 2; i++) fill(g->lists.list[i], index_word);   // edges
+      break;
+    }
+    case 11: {
+      // d_S, d_in_ptr and d_in_col (the lists over the labels) are built once.  rcm_init writes posl, levl, stamp and
+      // owner whole in every call; cnt[i] is written by rcm_count for the positions rcm_place reads; order is read in
+      // [a, b) and below `done` only, which the call wrote; the WlParts are written by every workgroup of rcm_sweep or
+      // rcm_count before they are read, the RcmFins (d_fin, behind them in d_ctl's allocation) by rcm_finish before
+      // rcm_total.  Only order is used as an index (labels); posl, levl, stamp, owner and cnt are compared or stored.
+      sh_rcm_graph *g = (sh_rcm_graph *)handle;
+      if ((int64_t)index_word >= g->rows) return SH_EINVAL;
+      dev = &g->dev;
+      fill(g->d_ctl, data_word);   // RcmCtl, the WlParts and the RcmFins (d_fin)
+      fill(g->st.order, index_word);
+      fill(g->st.posl, data_word);
+      fill(g->st.levl, data_word);
+      fill(g->st.stamp, data_word);
+      fill(g->st.owner, data_word);
+      fill(g->st.cnt, data_word);
       break;
     }
     default:

@@ -1,7 +1,8 @@
 """Inputs and references for the graph-hygiene tests: what a graph or worklist call may read is its operands and its
 handle, what it may write is `rows` (`edges`) elements of its outputs.  CPU only: numpy, the references the suite already
-pins (small_graphs_ref for the unions; oracle_bfs, sssp_ref, scc_ref, wcc_ref, tri_ref, core_ref, truss_ref for the wheel;
-the C oracle's iterate for sh_iterate_frontier); nothing here touches the engine.  Not a test and not a conftest.
+pins (small_graphs_ref for the unions, and rcm_ref.levels for sh_rcm, which has no tensor form; oracle_bfs, sssp_ref,
+scc_ref, wcc_ref, tri_ref, core_ref, truss_ref, color_ref, msf_ref, match_ref, rcm_ref for the wheel; the C oracle's iterate
+for sh_iterate_frontier); nothing here touches the engine.  Not a test and not a conftest.
 tests/test_graph_hygiene_cpu.py asserts on these references that a word written one element too far, left unwritten or read
 from a guard would show; tests/test_graph_hygiene_gpu.py runs the engine on them.
 
@@ -20,14 +21,20 @@ per workgroup, pieces of 2048 / 4096 list entries):
 
 Guard words of the inputs mean something if they are read: 1 behind x0 of sh_bfs_levels (a source), 0x00000000 behind x0
 of sh_sssp (a source at distance 0, and what fresh memory holds), hygiene_shapes.POISON[sr] around x, y0 and scratch of
-sh_iterate_frontier.  Outputs are prefilled with 0xDEADBEEF and sit between guards of it."""
+sh_iterate_frontier, 0x7FFFFFFF around prio of sh_color (a priority above every vertex's).  sh_msf and sh_match read
+weights: small_graphs_ref.weights on the unions (asymmetric pairs, ties, -1.5, -0.0, +inf, a NaN, one stored +0.0), rim
+1 and spokes 0.5 on the wheel.  Outputs are prefilled with 0xDEADBEEF and sit between guards of it."""
 import functools
 
 import numpy as np
 
 import bfs_ref
+import color_ref
 import core_ref
 import hygiene_shapes as HS
+import match_ref
+import msf_ref
+import rcm_ref
 import scc_ref
 import small_graphs_ref as R
 import sssp_ref
@@ -53,6 +60,12 @@ WHEEL_RIM_SOURCE = 1000
 NAMES = UNION_NAMES + ("wheel",)
 FRONTIER_NAMES = ("u5x51-blocks", "wheel")   # the shapes sh_iterate_frontier runs on
 DELTA, FRONTIER_CAP = 1e-4, 64
+# the settings sh_color, sh_match and sh_rcm run under here.  Order 0 and the prio vector put the wheel's hub last, so
+# that its colour, the last word before the guard, is 2 at least; order 2 puts it first.
+COLOR_SETTINGS = ((0, 0, False), (2, 1, False), (1, 1, True))   # (order, seed, prio)
+MATCH_SETTINGS = ((1, 1), (0, 0))                               # (heavy, seed)
+RCM_SETTINGS = ((8, 1), (0, 0))                                 # (sweeps, reverse)
+PRIO_GUARD = 0x7FFFFFFF   # around prio: a priority above every vertex's, so that a guard read as a priority shows
 
 
 def frozen(d):
@@ -73,8 +86,10 @@ class Start:
 
 class Shape:
     """rp / ci / val: the pattern as bfs, sssp and scc get it (val: the weights of sssp; bfs and scc get ones);
-    rp1 / ci1: as wcc, tri, core and truss get it (the undirected shapes stored one way).  want[entry point]: dict of the
-    expected vectors and scalars; starts: the source sets."""
+    rp1 / ci1: as wcc, tri, core, truss, color and rcm get it (the undirected shapes stored one way); rp / ci / wval: as
+    msf and match get it (the unions: small_graphs_ref.weights; the wheel: val), Mw its edges (a stored +0.0 is no entry);
+    prio: the priority vector of sh_color.  want[entry point]: dict of the expected vectors and scalars -- for color, match
+    and rcm one dict per setting; cut (the wheel): the same after max_rounds = 1 / max_steps = 1; starts: the source sets."""
 
 
 def _components(comp):
@@ -109,9 +124,67 @@ def union(window, numbering):
                   core=dict(core=R.scatter(c_["core"], numbering).astype(np.int32), deg=deg, degeneracy=c_["degeneracy"]),
                   truss=dict(truss=k["truss"], support=k["support"], edge_u=k["edge_u"], edge_v=k["edge_v"],
                              max_truss=k["max_truss"], triangles=k["triangles"], edges=k["M"]))
-    for d_ in s.want.values():
-        frozen(d_)
+    wv, prio = R.weights(graphs, n), R.prio_of(graphs, n)
+    s.wval, s.prio = np.ascontiguousarray(wv[g, r, c]), R.scatter(prio, numbering).astype(np.int32)
+    f = R.msf(A, wv, numbering)
+    s.Mw = f["M"]
+    edge = lambda d: dict(edge_u=d["edge_u"], edge_v=d["edge_v"], weight=d["weight"])   # noqa: E731
+    s.want["msf"] = dict(in_msf=f["in_msf"], comp=R.to_global(f["comp"], numbering).astype(np.int32), tree_edges=f["tree_edges"],
+                         components=f["components"], **edge(f))
+    s.want["color"], s.want["match"], s.want["rcm"] = {}, {}, {}
+    for order, seed, with_prio in COLOR_SETTINGS:
+        c = R.coloring(A, R.color_keys(A, numbering, order, seed, prio if with_prio else None))
+        s.want["color"][(order, seed, with_prio)] = dict(color=R.scatter(c["color"], numbering).astype(np.int32), colors=c["colors"],
+                                                         rounds=int(c["depth"].max()) + 1)
+    for heavy, seed in MATCH_SETTINGS:
+        m = R.matching(A, wv, numbering, heavy, seed)
+        s.want["match"][(heavy, seed)] = dict(mate=R.to_global(m["mate"], numbering).astype(np.int32), in_match=m["in_match"],
+                                              pairs=m["pairs"], **edge(m))
+    for sweeps, reverse in RCM_SETTINGS:
+        s.want["rcm"][(sweeps, reverse)] = _rcm(s, sweeps, reverse)
+    _freeze_all(s.want)
     return s
+
+
+RCM_SCALARS = ("components", "sweeps_run", "steps", "complete", "bandwidth_before", "bandwidth_after", "profile_before", "profile_after")
+
+
+def _rcm(s, sweeps, reverse, max_steps=None):
+    """rcm_ref.levels on the shape as one matrix: sh_rcm has no tensor form, and the walk in (deg, index) orders the
+    components of a union."""
+    w = rcm_ref.levels(s.rows, s.rp1, s.ci1, np.ones(len(s.ci1), np.float32), sweeps=sweeps, reverse=reverse, max_steps=max_steps)
+    return {k: w[k] for k in ("perm", "pos", "level", "kind", "size", "edges") + RCM_SCALARS}
+
+
+def _freeze_all(want):
+    for d_ in want.values():
+        frozen(d_)
+        for inner in d_.values():
+            if isinstance(inner, dict):
+                frozen(inner)
+
+
+def _four_on_the_wheel(s, max_rounds=None):
+    """color_ref, msf_ref, match_ref and rcm_ref on the wheel; max_rounds = 1: what a run cut short after one round (one
+    step) leaves, by the references' own max_rounds / max_steps forms."""
+    n, ones1 = s.rows, np.ones(len(s.ci1), np.float32)
+    want = dict(color={}, match={}, rcm={})
+    for order, seed, with_prio in COLOR_SETTINGS:
+        c = color_ref.schedule(n, s.rp1, s.ci1, ones1, order=order, seed=seed, prio=s.prio if with_prio else None, max_rounds=max_rounds)
+        want["color"][(order, seed, with_prio)] = dict(color=c["color"], colors=c["colors"], rounds=c["rounds"], complete=c["complete"],
+                                                       coloured=c["coloured"])
+    f = msf_ref.schedule(n, s.rp, s.ci, s.wval, **({} if max_rounds is None else dict(max_rounds=max_rounds)))
+    want["msf"] = dict(in_msf=f["in_msf"], comp=f["comp"], edge_u=f["eu"], edge_v=f["ev"], weight=f["weight"], tree_edges=f["tree_edges"],
+                       components=f["components"], complete=f["complete"])
+    for heavy, seed in MATCH_SETTINGS:
+        m = match_ref.rounds(n, f["eu"], f["ev"], match_ref.mkeys(msf_ref.order_key(f["weight"]), heavy, seed),
+                             **({} if max_rounds is None else dict(max_rounds=max_rounds)))
+        want["match"][(heavy, seed)] = dict(mate=m["mate"], in_match=m["in_match"], pairs=m["pairs"], complete=m["complete"],
+                                            edge_u=f["eu"], edge_v=f["ev"], weight=f["weight"])
+    for sweeps, reverse in RCM_SETTINGS:
+        want["rcm"][(sweeps, reverse)] = _rcm(s, sweeps, reverse, max_steps=max_rounds)
+    _freeze_all(want)
+    return want, f["M"]
 
 
 def wheel():
@@ -145,8 +218,14 @@ def wheel():
                   core=dict(core=c_["core"], deg=c_["deg"], degeneracy=c_["degeneracy"]),
                   truss=dict(truss=k["truss"], support=k["support"], edge_u=k["edge_u"], edge_v=k["edge_v"],
                              max_truss=k["max_truss"], triangles=k["triangles"], edges=k["M"]))
-    for d_ in s.want.values():
-        frozen(d_)
+    s.wval = s.val
+    s.prio = (np.arange(n) % 3).astype(np.int32)
+    s.prio[hub] = -1   # the hub last
+    four, s.Mw = _four_on_the_wheel(s)
+    s.want.update(four)
+    s.cut, _ = _four_on_the_wheel(s, max_rounds=1)
+    assert s.Mw == WHEEL_M
+    _freeze_all(s.want)
     return s
 
 

@@ -4,7 +4,7 @@ share.  Not a test and not a conftest.
 A `Guarded` operand is an sh_vec_wrap view into a larger allocation of its own, GUARD words of a chosen guard on either
 side, starting at a chosen word offset behind a 256-byte boundary; `read` brings the whole allocation back and asserts
 that no guard word changed.  `Dev` is one engine of one library through the C ABI.  After a HIP call that failed (`Dev.ok`
-saw SH_EHIP) nothing more is started on the device by any module that uses the `_not_halted` fixture: `_halt` says why."""
+saw SH_EHIP, or `call` an EngineError with that code) nothing more is started on the device by any module that uses the `_not_halted` fixture: `_halt` says why."""
 import ctypes as C
 
 import numpy as np
@@ -31,6 +31,17 @@ def same_bits(got, want, what):
     bad = np.nonzero(got != want)[0]
     assert len(bad) == 0, (f"{what}: {len(bad)} of {len(want)} words differ, first at {bad[:6].tolist()}: got "
                            f"{[hex(v) for v in got[bad[:6]]]} want {[hex(v) for v in want[bad[:6]]]}")
+
+
+def call(fn, *args, **kw):
+    """fn(...) of the Python binding; a failed HIP call ends the GPU work of the calling module (_halt)."""
+    from sparseharness_amd.engine import EngineError
+    try:
+        return fn(*args, **kw)
+    except EngineError as err:
+        if err.code == abi.SH_EHIP:
+            _halt.append(str(err))
+        raise
 
 
 class Dev:

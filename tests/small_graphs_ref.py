@@ -2,7 +2,9 @@
 point written from the definitions in include/sparseharness_hip.h as numpy over (G, n, n) tensors.  Not a test, not a
 conftest: tests/test_small_graphs_ref.py pins what is here against the project's other references and scipy,
 tests/test_small_graphs_gpu.py compares the engine with it.  Nothing here calls scc_ref, wcc_ref, tri_ref, core_ref,
-truss_ref, sssp_ref or oracle_bfs, and no line is shared with the product.
+truss_ref, sssp_ref, color_ref, msf_ref, match_ref, rcm_ref or oracle_bfs, and no line is shared with the product.
+sh_rcm alone has no tensor form here: its walk in (deg, index) order runs over the whole union, so its tests take
+rcm_ref.serial and rcm_ref.levels on the union as one matrix.
 
 Conventions.  A[g, r, c] is true when row r of graph g stores column c: in the header's words the edge c -> r.  A "local"
 answer is a (G, n) array that speaks of the vertices 0 .. n - 1 of each graph on its own (a parent, a label: a local
@@ -13,7 +15,9 @@ index or -1); to_global() turns it into what the engine must return for the unio
              round cross workgroups.
 
 Both keep the local order inside a graph (u < v locally iff globally), so every "smallest" and "largest" rule of the
-header gives the same local answer under either.
+header gives the same local answer under either.  Not so the ties that hash an id: orders 1 and 2 of sh_color compare
+mix32(v ^ seed) of the union's vertex index, sh_match with seed != 0 mix32(e ^ seed) of the union's edge id, so there
+the order inside a graph differs between the two numberings, and the references take the union's ids.
 """
 import numpy as np
 
@@ -260,6 +264,20 @@ def core(A):
     return dict(core=number, degeneracy=int(number.max()))
 
 
+def edges(A, numbering):
+    """The union's edge list in the header's order: edge e is the e-th smallest pair u < v of union indices.  -> dict(
+    edge_u, edge_v (int32, per edge), graph, lu, lv (the graph and the local ends lu < lv of every edge), M)."""
+    S = simple(A)
+    G, n, _ = S.shape
+    g, u, v = np.nonzero(S & np.triu(np.ones((n, n), bool), 1)[None])
+    ids = vertex_ids(G, n, numbering)
+    gu, gv = ids[g, u], ids[g, v]
+    order = np.lexsort((gv, gu))
+    g, u, v, gu, gv = g[order], u[order], v[order], gu[order], gv[order]
+    assert (gu < gv).all()
+    return dict(edge_u=gu.astype(np.int32), edge_v=gv.astype(np.int32), graph=g, lu=u, lv=v, M=len(g))
+
+
 def truss(A, numbering):
     """support = (S @ S) * S; peel k = 3 .. n + 1, each to its fixed point: truss[e] = the last k whose peel e survived,
     2 for an edge that survived none.  -> dict(truss, support, edge_u, edge_v (per edge of the union in the header's
@@ -279,17 +297,208 @@ def truss(A, numbering):
             E &= ~drop
         number[E] = k
     assert not E.any()   # K_n has truss n: nothing survives the peel of n + 1
-    g, u, v = np.nonzero(S & np.triu(np.ones((n, n), bool), 1)[None])
-    ids = vertex_ids(G, n, numbering)
-    gu, gv = ids[g, u], ids[g, v]
-    order = np.lexsort((gv, gu))
-    g, u, v, gu, gv = g[order], u[order], v[order], gu[order], gv[order]
-    assert (gu < gv).all()
+    e = edges(S, numbering)
+    g, u, v, gu, gv = e["graph"], e["lu"], e["lv"], e["edge_u"], e["edge_v"]
     total = int(support.sum())
     assert total % 6 == 0   # every triangle is counted at its three edges, each seen from both ends
     return dict(truss=number[g, u, v].astype(np.int32), support=support[g, u, v].astype(np.int32),
-                edge_u=gu.astype(np.int32), edge_v=gv.astype(np.int32), graph=g, lu=u, lv=v,
+                edge_u=gu, edge_v=gv, graph=g, lu=u, lv=v,
                 max_truss=int(number.max()), triangles=total // 6, M=len(g))
+
+
+# ------------------------------------------------------------------ greedy colouring in a fixed order
+def mix32(x):
+    """x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 on uint32 words (uint64 in numpy)."""
+    m = np.uint64(0xFFFFFFFF)
+    x = np.asarray(x).astype(np.uint64) & m
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x7FEB352D)) & m
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x846CA68B)) & m
+    return x ^ (x >> np.uint64(16))
+
+
+def color_keys(A, numbering, order, seed, prio=None, tie="header", ids="global"):
+    """(G, n) int64: vertex v precedes u exactly when key[v] > key[u].  The primary is prio ((G, n)) when given, the
+    degree for order 2, else 0; the tie is built from the UNION's index of the vertex: the smaller index first for order
+    0, the larger mix32(v ^ seed) first for orders 1 and 2.  tie = "larger" (the larger index first, under order 0) and
+    ids = "local" (the tie from the local index) are broken on purpose (tests/test_small_graphs_ref.py)."""
+    assert order in (0, 1, 2)
+    G, n, _ = A.shape
+    v = vertex_ids(G, n, numbering) if ids == "global" else np.tile(np.arange(n, dtype=np.int64), (G, 1))
+    primary = np.asarray(prio, np.int64) if prio is not None else (simple(A).sum(axis=2).astype(np.int64) if order == 2 else np.zeros((G, n), np.int64))
+    if order == 0:
+        low = v if tie == "larger" else (1 << 32) - 1 - v
+    else:
+        low = mix32(v ^ (int(seed) & 0xFFFFFFFF)).astype(np.int64)
+    return primary * (1 << 32) + low
+
+
+def prio_of(G, n):
+    """(G, n) int32: a priority vector with ties inside a graph (so that the order below it still decides), a negative
+    value, and another pattern from graph to graph."""
+    g, v = np.arange(G, dtype=np.int64)[:, None], np.arange(n, dtype=np.int64)[None, :]
+    return ((v * 3 + g) % 4 - 1).astype(np.int32)
+
+
+def coloring(A, key):
+    """n steps per graph: the uncoloured vertex of the largest key takes the smallest colour that none of its coloured
+    neighbours holds.  -> dict(color (G, n) local, colors, depth (G, n): the longest chain of preceding neighbours that
+    ends in the vertex, counted from 0)."""
+    S = simple(A)
+    G, n, _ = S.shape
+    key = np.asarray(key, np.int64)
+    color, depth = np.full((G, n), -1, np.int64), np.zeros((G, n), np.int64)
+    rows = np.arange(G)
+    for _ in range(n):
+        v = np.where(color < 0, key, np.iinfo(np.int64).min).argmax(axis=1)
+        assert (color[rows, v] < 0).all()
+        before = S[rows, v, :] & (color >= 0)                                 # (G, n): the coloured neighbours
+        held = (before[:, :, None] & (color[:, :, None] == np.arange(n + 1)[None, None, :])).any(axis=1)
+        color[rows, v] = held.argmin(axis=1)                                  # (n neighbours cannot hold n + 1 colours)
+        depth[rows, v] = np.where(before.any(axis=1), np.where(before, depth, -1).max(axis=1) + 1, 0)
+    return dict(color=color, colors=int(color.max()) + 1, depth=depth)
+
+
+# ------------------------------------------------------------------ weights by bit pattern: forest and matching
+_ONE, _TWO, _HALF, _THREE = 0x3F800000, 0x40000000, 0x3F000000, 0x40400000
+_NEG, _MZERO, _PZERO, _INF, _NAN = 0xBFC00000, 0x80000000, 0x00000000, 0x7F800000, 0x7FC00001   # -1.5, -0.0, +0.0, +inf, a NaN
+# the 32 bits stored at position (r, c) of the base table: most pairs asymmetric ((0, 1): 2 and 1), many pairs of equal
+# weight (1 and 0.5 throughout), -1.5 at (0, 3) and (4, 2), -0.0 at (2, 3), +inf at (0, 4) and on both sides of (4, 5), a
+# NaN at (1, 5), and ONE stored +0.0 at (1, 2): no entry by the graph rule, so {1, 2} is an edge only through (2, 1)
+WBITS = np.array([[_ONE,  _TWO,   _ONE,   _NEG,   _INF,  _HALF],
+                  [_ONE,  _THREE, _PZERO, _TWO,   _ONE,  _NAN],
+                  [_TWO,  _HALF,  _ONE,   _MZERO, _TWO,  _ONE],
+                  [_ONE,  _TWO,   _ONE,   _HALF,  _HALF, _TWO],
+                  [_HALF, _ONE,   _NEG,   _TWO,   _ONE,  _INF],
+                  [_TWO,  _ONE,   _ONE,   _HALF,  _INF,  _ONE]], np.uint32)
+
+
+def order_key(b):
+    """k(b) of the header on uint32 bits: b ^ 0xFFFFFFFF if the sign bit is set, else b ^ 0x80000000."""
+    b = np.asarray(b, np.uint32)
+    return np.where(b >> np.uint32(31) != 0, b ^ np.uint32(0xFFFFFFFF), b ^ np.uint32(0x80000000)).astype(np.uint32)
+
+
+def weights(G, n):
+    """(G, n, n) float32, the value stored at every position: graph g reads WBITS rotated by g % 6 along both axes (so
+    that the 3 and 4 vertices of a small graph meet every special value in some graph), with the sign bit of every value
+    flipped in every fifth graph (the order of the weights turns round; +0.0 becomes -0.0, which counts, and -0.0
+    becomes the stored zero).  Only bits are moved: no arithmetic touches the NaN."""
+    assert n <= len(WBITS)
+    g = np.arange(G)[:, None, None]
+    r, c = np.arange(n)[None, :, None], np.arange(n)[None, None, :]
+    b = WBITS[(r + g) % 6, (c + g) % 6]
+    b = np.where(g % 5 == 0, b ^ np.uint32(0x80000000), b).astype(np.uint32)
+    return np.ascontiguousarray(b).view(np.float32)
+
+
+def edge_weights(A, val, numbering, entry="smallest", zero_counts=False):
+    """The weighted graph of sh_msf and sh_match: an entry counts when it is stored and its 32 bits are not all zero; the
+    weight of a pair is the smallest counting entry of its two positions by k.  -> edges() of the counting pattern, with
+    k (uint32 per edge) and weight (the 32 bits of the chosen entry).  entry = "first" (the entry met first in the
+    row-major order of the matrix, that of the smaller row) and zero_counts are broken on purpose."""
+    b = bits(val).reshape(np.asarray(val).shape)
+    counts = A & ((b != 0) | zero_counts)
+    e = edges(counts, numbering)
+    g, u, v = e["graph"], e["lu"], e["lv"]
+    top = np.uint64(1) << np.uint64(32)   # (above every k: a position that does not count)
+    ku = np.where(counts[g, u, v], order_key(b[g, u, v]).astype(np.uint64), top)   # the entry in the smaller row
+    kv = np.where(counts[g, v, u], order_key(b[g, v, u]).astype(np.uint64), top)
+    use_u = (ku <= kv) if entry == "smallest" else counts[g, u, v]
+    e["k"] = np.where(use_u, ku, kv).astype(np.uint32)
+    e["weight"] = np.where(use_u, b[g, u, v], b[g, v, u]).astype(np.uint32)
+    return e
+
+
+def _ranks(graph, key):
+    """The rank of every edge among the edges of its graph in ascending key, and the largest number of edges of a graph."""
+    order = np.lexsort((key, graph))
+    start = np.concatenate([[0], np.cumsum(np.bincount(graph))])[graph[order]] if len(graph) else np.zeros(0, np.int64)
+    rank = np.empty(len(graph), np.int64)
+    rank[order] = np.arange(len(graph)) - start
+    return rank, (int(rank.max()) + 1 if len(graph) else 0)
+
+
+def msf(A, val, numbering, tie="header", **broken):
+    """Kruskal in every graph at once: the edges in ascending KEY(e) = k(weight[e]) << 32 | e, e the union's edge id; step
+    j takes the j-th edge of every graph and keeps it when its ends carry different labels.  A label is the largest index
+    of the component so far.  -> dict(in_msf (per edge), comp (G, n) local, tree_edges, components, k, weight and the
+    fields of edges()).  tie = "larger" (KEY's low word ~e) and **broken (edge_weights) are wrong on purpose."""
+    G, n, _ = A.shape
+    e = edge_weights(A, val, numbering, **broken)
+    ids = np.arange(e["M"], dtype=np.uint64)
+    key = (e["k"].astype(np.uint64) << np.uint64(32)) | (ids if tie == "header" else np.uint64(0xFFFFFFFF) - ids)
+    rank, most = _ranks(e["graph"], key)
+    label = np.tile(np.arange(n, dtype=np.int64), (G, 1))
+    in_msf = np.zeros(e["M"], np.int32)
+    for j in range(most):
+        at = np.flatnonzero(rank == j)
+        g = e["graph"][at]
+        a, b = label[g, e["lu"][at]], label[g, e["lv"][at]]
+        take = a != b
+        in_msf[at[take]] = 1
+        g, a, b = g[take], a[take], b[take]
+        rows = label[g]
+        label[g] = np.where((rows == a[:, None]) | (rows == b[:, None]), np.maximum(a, b)[:, None], rows)
+    components = int((label == np.arange(n)[None, :]).sum())
+    e.update(in_msf=in_msf, comp=label, tree_edges=G * n - components, components=components)
+    assert e["tree_edges"] == int(in_msf.sum())
+    return e
+
+
+def matching(A, val, numbering, heavy, seed, tie="header", ids="global", **broken):
+    """The greedy matching in every graph at once: the edges in ascending MKEY = hi << 32 | lo, hi = k(weight) or its
+    complement (heavy), lo = e or mix32(e ^ seed) (seed != 0) on the union's edge id e; an edge is kept when both its ends
+    are free.  -> dict(mate (G, n) local, in_match (per edge), pairs, and the fields of edge_weights()).  tie = "larger"
+    (lo = ~e under seed 0) and ids = "local" (lo from the edge's rank inside its graph) are wrong on purpose."""
+    assert heavy in (0, 1)
+    G, n, _ = A.shape
+    e = edge_weights(A, val, numbering, **broken)
+    eid = np.arange(e["M"], dtype=np.uint64)
+    if ids == "local":
+        eid = _ranks(e["graph"], eid)[0].astype(np.uint64)
+    seed = int(seed) & 0xFFFFFFFF
+    lo = mix32(eid ^ np.uint64(seed)) if seed else (eid if tie == "header" else np.uint64(0xFFFFFFFF) - eid)
+    hi = (e["k"] ^ np.uint32(0xFFFFFFFF) if heavy else e["k"]).astype(np.uint64)
+    rank, most = _ranks(e["graph"], (hi << np.uint64(32)) | lo)
+    mate = np.full((G, n), -1, np.int64)
+    in_match = np.zeros(e["M"], np.int32)
+    for j in range(most):
+        at = np.flatnonzero(rank == j)
+        g, u, v = e["graph"][at], e["lu"][at], e["lv"][at]
+        take = (mate[g, u] < 0) & (mate[g, v] < 0)
+        in_match[at[take]] = 1
+        mate[g[take], u[take]], mate[g[take], v[take]] = v[take], u[take]
+    e.update(mate=mate, in_match=in_match, pairs=int(in_match.sum()))
+    return e
+
+
+# ------------------------------------------------------------------ what the GPU file runs, and what the CPU file pins
+UNIONS = (("digraphs", 3), ("digraphs", 4), ("undirected", 4), ("undirected", 5), ("undirected", 6))
+COLOR_SETTINGS = tuple((order, seed, False) for order in (0, 1, 2) for seed in (0, 1)) + ((1, 1, True),)   # (order, seed, prio)
+MATCH_SETTINGS = ((0, 0), (0, 1), (1, 0), (1, 1))                                                          # (heavy, seed)
+RCM_UNIONS = (("undirected", 4), ("undirected", 5), ("digraphs", 3))
+RCM_SETTINGS = ((0, 0), (0, 1), (8, 0), (8, 1))                                                            # (sweeps, reverse)
+
+
+def graphs_of(kind, n):
+    return all_digraphs(n) if kind == "digraphs" else all_undirected(n)
+
+
+def storings(kind, A):
+    """name -> mask of the entries written, for the weighted entry points: the digraphs as they are; the undirected
+    graphs one way (halves) and both ways, where the smaller of two entries decides."""
+    return {"as it is": None} if kind == "digraphs" else {"one way": halves(A), "both ways": None}
+
+
+def color_schedule(A, depth):
+    """(rounds, sizes, edges) of a complete sh_color run from the chain depths: round r's list is the vertices of depth r,
+    its edges the sum of their degrees."""
+    deg = simple(A).sum(axis=2)
+    rounds = int(depth.max()) + 1
+    return (rounds, np.bincount(depth.ravel(), minlength=rounds).astype(np.int64),
+            np.bincount(depth.ravel(), weights=deg.ravel(), minlength=rounds).astype(np.int64))
 
 
 # ------------------------------------------------------------------ telling a failure as a small graph

@@ -4,8 +4,10 @@ catch: asserted on the references alone, no engine.
 (a) the first and the last element of every expected output vector differ from 0xDEADBEEF, the prefill: an element the
     call left unwritten at either end shows;
 (b) per entry point, in one shape at least, the last element is not what the call's own initialisation leaves (level and
-    pred -1, dist FLT_MAX or 0, tri 0, core 0, truss 2, support 0, comp[v] = v): a kernel that stops one element short
-    after a correct initialisation shows;
+    pred -1, dist FLT_MAX or 0, tri 0, core 0, truss 2, support 0, comp[v] = v, color -1 or 0, mate -1, in_msf and
+    in_match 0, perm and pos -1): a kernel that stops one element short after a correct initialisation shows.  comp is
+    looked at in its first element: the last vertex is the largest of its component whatever the graph.  Every shape has an
+    unmatched vertex, a tree edge and an edge outside the forest;
 (c) every BFS and SSSP case on a union is two levels deep at least and leaves a vertex unreached, and turning an unreached
     vertex into a source changes the answer: a guard word read as a source shows.  The wheel is connected, so it has no
     unreached vertex; from a rim vertex it is two levels deep, from the hub one level by construction (every vertex is the
@@ -32,6 +34,12 @@ def outputs(s):
                         ("truss", ("truss", "support", "edge_u", "edge_v"))):
         for name in names:
             yield what, name, s.want[what][name]
+    for name in ("in_msf", "comp", "edge_u", "edge_v", "weight"):
+        yield "msf", name, s.want["msf"][name]
+    for what, names in (("color", ("color",)), ("match", ("mate", "in_match", "edge_u", "edge_v", "weight")), ("rcm", ("perm", "pos", "level"))):
+        for setting, want in s.want[what].items():
+            for name in names:
+                yield what, name, want[name]
 
 
 def words(a):
@@ -43,6 +51,8 @@ def test_a_word_left_unwritten_at_either_end_shows(name):   # (a)
     s = S.shape(name)
     for what, vec_name, vec in outputs(s):
         want_len = {"tri": s.rows, "truss": s.M, "support": s.M, "edge_u": s.M, "edge_v": s.M}.get(vec_name, s.rows)
+        if what in ("msf", "match") and vec_name not in ("comp", "mate"):
+            want_len = s.Mw   # the edges of the weighted graph: a stored +0.0 is no entry
         assert len(vec) == want_len > 0, (what, vec_name, len(vec))
         w = words(vec)   # (a uint64 count is two words)
         assert w[0] != DEAD32 and w[-1] != DEAD32 and (vec.dtype != np.uint64 or (w[1] != DEAD32 and w[-2] != DEAD32)), (what, vec_name)
@@ -60,7 +70,17 @@ def test_the_last_element_is_not_what_an_initialisation_leaves():   # (b)
         seen |= {k for k, ok in (("tri", w["tri"]["tri"][-1] > 0), ("core", w["core"]["core"][-1] >= 1),
                                  ("truss", w["truss"]["truss"][-1] >= 3), ("support", w["truss"]["support"][-1] >= 1),
                                  ("scc", w["scc"]["comp"][0] != 0), ("wcc", w["wcc"]["comp"][0] != 0)) if ok}
-    assert seen == {"level", "parent", "dist", "pred", "tri", "core", "truss", "support", "scc", "wcc"}, seen
+        seen |= {k for k, ok in (("in_msf", w["msf"]["in_msf"][-1] != 0), ("msf comp", w["msf"]["comp"][0] != 0)) if ok}
+        for want in w["color"].values():
+            seen |= {"color"} if want["color"][-1] >= 1 else set()
+        for want in w["match"].values():
+            seen |= {k for k, ok in (("mate", want["mate"][-1] != -1), ("in_match", want["in_match"][-1] != 0)) if ok}
+            assert (want["mate"] == -1).any(), (name, "no unmatched vertex")
+        for want in w["rcm"].values():
+            seen |= {k for k in ("perm", "pos") if want[k][-1] != -1}
+        assert (w["msf"]["in_msf"] == 1).any() and (w["msf"]["in_msf"] == 0).any(), (name, "a tree edge and an edge outside the forest")
+    assert seen == {"level", "parent", "dist", "pred", "tri", "core", "truss", "support", "scc", "wcc", "in_msf", "msf comp", "color",
+                    "mate", "in_match", "perm", "pos"}, seen
     # the wheel alone has them all: the hub's element is the last word before the guard, the hub's edge the last edge id
     s = S.shape("wheel")
     rim = s.starts[0]
@@ -69,6 +89,26 @@ def test_the_last_element_is_not_what_an_initialisation_leaves():   # (b)
     assert s.want["tri"]["tri"][-1] == S.WHEEL_N - 1 and s.want["core"]["core"][-1] == 3 and s.want["truss"]["truss"][-1] == 3
     assert s.want["truss"]["support"][-1] == 2 and (s.want["truss"]["edge_u"][-1], s.want["truss"]["edge_v"][-1]) == (S.WHEEL_N - 2, S.WHEEL_N - 1)
     assert (s.want["scc"]["comp"] == S.WHEEL_N - 1).all() and (s.want["wcc"]["comp"] == S.WHEEL_N - 1).all()
+    # the hub is joined to a cycle, which takes two colours at least: coloured last (order 0: the largest index; prio:
+    # the smallest priority) its colour is >= 2.  Every spoke (0.5) is lighter than every rim edge (1): the forest is the
+    # spokes, the last edge id among them.  Lightest first by edge id, the first spoke 0 - hub is matched: mate[hub] = 0.
+    hub = S.WHEEL_N - 1
+    assert s.want["color"][(0, 0, False)]["color"][hub] >= 2 and s.want["color"][(1, 1, True)]["color"][hub] >= 2
+    assert s.want["color"][(2, 1, False)]["color"][hub] == 0 and s.prio[hub] == s.prio.min() == -1
+    f = s.want["msf"]
+    assert f["in_msf"][-1] == 1 and np.array_equal(f["in_msf"] == 1, f["edge_v"] == hub) and (f["comp"] == hub).all()
+    assert f["tree_edges"] == S.WHEEL_N - 1 and f["components"] == 1 and (f["edge_u"][-1], f["edge_v"][-1]) == (hub - 1, hub)
+    assert s.want["match"][(0, 0)]["mate"][hub] == 0 and s.want["match"][(0, 0)]["mate"][0] == hub
+    for setting, want in s.want["match"].items():
+        assert (want["mate"] == -1).sum() % 2 == 1   # 4131 vertices: one at least stays alone
+    for want in s.want["rcm"].values():
+        assert sorted(want["perm"].tolist()) == list(range(S.WHEEL_N)) and want["complete"] and want["components"] == 1
+    # a run cut short (one round, one step) has something left to do, and says so in the vectors
+    cut = s.cut
+    assert all(not c["complete"] and (c["color"] == -1).any() and (c["color"] >= 0).any() for c in cut["color"].values())
+    assert not cut["msf"]["complete"] and (cut["msf"]["comp"] == -1).all() and cut["msf"]["in_msf"].any()
+    assert all(not m["complete"] and m["pairs"] >= 1 and m["pairs"] < s.want["match"][k]["pairs"] for k, m in cut["match"].items())
+    assert all(not r["complete"] and r["steps"] == 1 and (r["perm"] == -1).any() and r["bandwidth_after"] == -1 for r in cut["rcm"].values())
 
 
 @pytest.mark.parametrize("name", S.UNION_NAMES)

@@ -4,18 +4,22 @@ words against the references of tests/graph_hygiene_shapes.py (tests/test_graph_
 make a word written too far, left unwritten or read from a guard visible).
 
 Tier 1, the production library.  Every vector operand of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_tri, sh_core,
-sh_truss and sh_iterate_frontier is a view (sh_vec_wrap) between 256 guard words on either side, read back whole after
-the call.  A call with operands o_0 .. o_j runs four times on one handle; in run k operand o_i starts (i + k) % 4 words
-behind a 256-byte boundary.  Each run is made with views of exactly the required length and again with 3 elements more,
-which must still hold what they held.  Outputs are prefilled with 0xDEADBEEF between guards of it; the guards of an input
-mean something if they are read (a source for the searches, the semiring's poison for the iteration).  Asserted per
+sh_truss, sh_color, sh_msf, sh_match, sh_rcm and sh_iterate_frontier is a view (sh_vec_wrap) between 256 guard words on
+either side, read back whole after the call.  A call with operands o_0 .. o_j runs four times on one handle; in run k
+operand o_i starts (i + k) % 4 words behind a 256-byte boundary.  Each run is made with views of exactly the required
+length and again with 3 elements more, which must still hold what they held.  Outputs are prefilled with 0xDEADBEEF
+between guards of it; the guards of an input mean something if they are read (a source for the searches, the semiring's
+poison for the iteration, a priority above every vertex's around prio of sh_color).  Asserted per
 call: every output vector and every scalar or record that does not depend on the setting equals the reference, no guard
 word changed, every input is bit for bit what was uploaded.  A run cut short (max_levels / max_rounds / max_steps /
-max_iters = 1, on the wheel) leaves guards and tail alone as well, and sh_sssp leaves `pred` untouched.
+max_iters = 1, on the wheel) leaves guards and tail alone as well, and sh_sssp leaves `pred` untouched; sh_color, sh_msf,
+sh_match and sh_rcm then leave what the header says (-1 for a vertex without a colour, a component, a mate or a position,
+the tree edges and pairs of the first round), compared with the max_rounds / max_steps forms of their references.  The
+header states no alignment rule for the operands of these four: the rotation through all four word offsets pins that.
 The small operations -- sh_vec_fill, sh_vec_copy, sh_bits_from_column, sh_bits_to_column -- on views of odd lengths at
 every word offset: neither has an alignment rule, and the test pins that.
 
-Tier 2, the tools library: the same guarded calls of all eight with every per-call array of the handle poisoned before
+Tier 2, the tools library: the same guarded calls of all twelve with every per-call array of the handle poisoned before
 each call (sh_debug_poison_graph, csrc/debug_graph_tools.h)."""
 import contextlib
 import ctypes as C
@@ -28,7 +32,7 @@ import bfs_ref
 import graph_hygiene_shapes as S
 import hygiene_shapes as HS
 import small_graphs_ref as R
-from guarded import DEAD, Dev, _halt, _not_halted, same_bits   # noqa: F401 (the fixture is used by being here)
+from guarded import DEAD, Dev, _not_halted, call, same_bits   # noqa: F401 (the fixture is used by being here)
 from sparseharness_amd import abi
 from sparseharness_amd.engine import Engine, EngineError
 from test_plan_limits_gpu import Tools
@@ -54,16 +58,6 @@ def using(lib):
         abi._lib = old
 
 
-def call(fn, *args, **kw):
-    """fn(...) of the Python binding; a failed HIP call ends the module's GPU work (guarded._halt)."""
-    try:
-        return fn(*args, **kw)
-    except EngineError as err:
-        if err.code == abi.SH_EHIP:
-            _halt.append(str(err))
-        raise
-
-
 class Ctx:
     """One library, one engine on it, and the handles of every shape, made at first use and kept until the module is done."""
 
@@ -81,10 +75,13 @@ class Ctx:
             with using(self.lib):
                 h = dict(bfs=eng.bfs_graph(s.rp, s.ci, ones), sssp=eng.sssp_graph(s.rp, s.ci, s.val), scc=eng.scc_graph(s.rp, s.ci, ones),
                          wcc=eng.wcc_graph(s.rp1, s.ci1, ones1), core=eng.core_graph(s.rp1, s.ci1, ones1),
-                         truss=eng.truss_graph(s.rp1, s.ci1, ones1))
+                         truss=eng.truss_graph(s.rp1, s.ci1, ones1), color=call(eng.color_graph, s.rp1, s.ci1, ones1),
+                         rcm=call(eng.rcm_graph, s.rp1, s.ci1, ones1), msf=call(eng.msf_graph, s.rp, s.ci, s.wval),
+                         match=call(eng.match_graph, s.rp, s.ci, s.wval))
                 for order in ORDERS:
                     h[("tri", order)] = eng.tri_graph(s.rp1, s.ci1, ones1, order=order)
-                assert h["truss"].edges == h["core"].edges == h[("tri", 0)].edges == s.M
+                assert h["truss"].edges == h["core"].edges == h[("tri", 0)].edges == h["color"].edges == h["rcm"].edges == s.M
+                assert h["msf"].edges == h["match"].edges == s.Mw
             self.made[name] = h
         return self.made[name]
 
@@ -335,6 +332,92 @@ def truss(c, name, with_optional, k, extra, before=None, max_rounds=None):
         free(*vecs)
 
 
+def color(c, name, setting, k, extra, before=None, max_rounds=None):
+    """prio, where the setting has one, is a guarded input: its guards and tail hold a priority above every vertex's."""
+    s, (order, seed, with_prio) = S.shape(name), setting
+    want = (s.want if max_rounds is None else s.cut)["color"][setting]
+    what = f"sh_color {name} (order, seed, prio) {setting} run {k} extra {extra} max_rounds {max_rounds}"
+    cv = c.out(s.rows, k, extra)
+    pv = c.inp(s.prio, k + 1, S.PRIO_GUARD, extra) if with_prio else None
+    try:
+        if before:
+            before("color", c.handles(name)["color"], what)
+        with using(c.lib):
+            res = call(c.eng.greedy_colors, c.handles(name)["color"], cv, pv, order=order, seed=seed, max_rounds=max_rounds)
+        colors, rounds, complete, coloured = res[:4]
+        written(cv, want["color"], what + ": color")   # (a run cut short leaves -1 for every vertex without a colour)
+        assert (colors, rounds, complete) == (want["colors"], want["rounds"], max_rounds is None), (what, colors, rounds, complete)
+        assert coloured == int((want["color"] >= 0).sum()), (what, coloured)
+        if with_prio:
+            unchanged(pv, what + ": prio")
+    finally:
+        free(cv, pv)
+
+
+MSF_VECTORS = ("in_msf", "comp", "edge_u", "edge_v", "weight")
+MATCH_VECTORS = ("mate", "in_match", "edge_u", "edge_v", "weight")
+RCM_VECTORS = ("perm", "pos", "level")
+
+
+def msf(c, name, with_optional, k, extra, before=None, max_rounds=33):
+    s = S.shape(name)
+    want = (s.want if max_rounds == 33 else s.cut)["msf"]
+    what = f"sh_msf {name} optional vectors {with_optional} run {k} extra {extra} max_rounds {max_rounds}"
+    G = c.handles(name)["msf"]
+    vecs = [c.out(s.rows if nm == "comp" else s.Mw, k + i, extra) if (i == 0 or with_optional) else None for i, nm in enumerate(MSF_VECTORS)]
+    try:
+        if before:
+            before("msf", G, what)
+        with using(c.lib):
+            res = call(c.eng.spanning_forest, G, *vecs, max_rounds=max_rounds)
+        for nm, v in zip(MSF_VECTORS, vecs):   # (cut short: the tree edges of the rounds run, comp -1 everywhere)
+            if v is not None:
+                written(v, want[nm], f"{what}: {nm}")
+        assert res[:2] == (want["tree_edges"], want["components"]) and res[3] == (max_rounds == 33), (what, res[:4])
+    finally:
+        free(*vecs)
+
+
+def match(c, name, setting, with_optional, k, extra, before=None, max_rounds=MAX_ROUNDS):
+    s = S.shape(name)
+    want = (s.want if max_rounds == MAX_ROUNDS else s.cut)["match"][setting]
+    what = f"sh_match {name} (heavy, seed) {setting} optional vectors {with_optional} run {k} extra {extra} max_rounds {max_rounds}"
+    G = c.handles(name)["match"]
+    vecs = [c.out(s.rows if nm == "mate" else s.Mw, k + i, extra) if (i == 0 or with_optional) else None for i, nm in enumerate(MATCH_VECTORS)]
+    try:
+        if before:
+            before("match", G, what)
+        with using(c.lib):
+            res = call(c.eng.matching, G, vecs[0], setting[0], setting[1], *vecs[1:], max_rounds=max_rounds)
+        for nm, v in zip(MATCH_VECTORS, vecs):   # (cut short: the pairs of the rounds run, -1 for everybody else)
+            if v is not None:
+                written(v, want[nm], f"{what}: {nm}")
+        assert (res[0], res[2]) == (want["pairs"], max_rounds == MAX_ROUNDS), (what, res[:3])
+    finally:
+        free(*vecs)
+
+
+def rcm(c, name, setting, with_optional, k, extra, before=None, max_steps=None):
+    s = S.shape(name)
+    want = (s.want if max_steps is None else s.cut)["rcm"][setting]
+    what = f"sh_rcm {name} (sweeps, reverse) {setting} optional vectors {with_optional} run {k} extra {extra} max_steps {max_steps}"
+    G = c.handles(name)["rcm"]
+    vecs = [c.out(s.rows, k + i, extra) if (i == 0 or with_optional) else None for i in range(3)]
+    try:
+        if before:
+            before("rcm", G, what)
+        with using(c.lib):
+            res = call(c.eng.rcm_order, G, *vecs, sweeps=setting[0], reverse=setting[1], max_steps=max_steps)
+        for nm, v in zip(RCM_VECTORS, vecs):   # (cut short: -1 in the rest of perm, and for a vertex without a position)
+            if v is not None:
+                written(v, want[nm], f"{what}: {nm}")
+        assert res[:8] == tuple(want[f] for f in S.RCM_SCALARS), (what, res[:8])
+        for f, got in zip(("kind", "size", "edges"), res[8:11]):
+            assert np.array_equal(got, want[f]), (what, f)
+    finally:
+        free(*vecs)
+
+
 def frontier(c, name, sr, plan, share, k, extra, before=None, max_iters=S.FRONTIER_CAP):
     s = S.shape(name)
     va, x0, want, launches, converged = S.frontier_case(name, sr)
@@ -440,6 +523,40 @@ def test_truss_between_guards(prod, name):
             truss(prod, name, with_optional, k, extra)
 
 
+@pytest.mark.parametrize("name", S.NAMES)
+def test_color_between_guards(prod, name):
+    for setting in S.COLOR_SETTINGS:   # (with and without prio, the optional operand)
+        for k, extra in runs():
+            color(prod, name, setting, k, extra)
+
+
+@pytest.mark.parametrize("name", S.NAMES)
+def test_msf_between_guards(prod, name):
+    for with_optional in (True, False):
+        for k, extra in runs():
+            msf(prod, name, with_optional, k, extra)
+
+
+@pytest.mark.parametrize("name", S.NAMES)
+def test_match_between_guards(prod, name):
+    for setting in S.MATCH_SETTINGS:
+        for with_optional in (True, False):
+            for k, extra in runs():
+                match(prod, name, setting, with_optional, k, extra)
+
+
+@pytest.mark.parametrize("name", S.NAMES)
+def test_rcm_between_guards(prod, name):
+    """u5x1023 has 1398 components with edges, and sh_rcm pays per step: 10 824 steps a call at sweeps = 8, 3608 at 0.
+    Its eight runs of four calls took 4.5 s on an MI355X, so there two runs stand for the eight: offset 1 at the exact
+    length and offset 3 with 3 elements more.  Every other shape keeps all eight."""
+    some = [(1, 0), (3, S.EXTRA)] if name.startswith("u5x1023") else runs()
+    for setting in S.RCM_SETTINGS:
+        for with_optional in (True, False):
+            for k, extra in some:
+                rcm(prod, name, setting, with_optional, k, extra)
+
+
 @pytest.mark.parametrize("sr", S.FRONTIER_SEMIRINGS, ids=HS.SR_NAME.get)
 @pytest.mark.parametrize("name", S.FRONTIER_NAMES)
 def test_iterate_frontier_between_guards(prod, name, sr):
@@ -461,6 +578,13 @@ def test_a_run_cut_short_stays_inside_its_vectors(prod):
         components(prod, "wheel", "wcc", 0, k, S.EXTRA, cap=1)
         core(prod, "wheel", 0, True, k, S.EXTRA, max_rounds=1)
         truss(prod, "wheel", True, k, S.EXTRA, max_rounds=1)
+        for setting in S.COLOR_SETTINGS:
+            color(prod, "wheel", setting, k, S.EXTRA, max_rounds=1)
+        msf(prod, "wheel", True, k, S.EXTRA, max_rounds=1)
+        for setting in S.MATCH_SETTINGS:
+            match(prod, "wheel", setting, True, k, S.EXTRA, max_rounds=1)
+        for setting in S.RCM_SETTINGS:
+            rcm(prod, "wheel", setting, True, k, S.EXTRA, max_steps=1)
         for sr in S.FRONTIER_SEMIRINGS:
             frontier(prod, "wheel", sr, 1, 1.0, k, S.EXTRA, max_iters=1)
 
@@ -515,7 +639,7 @@ def test_bits_columns_on_views(prod, words, n):
 # after writing it: data words with 0xFFFFFFFF or 0, queues and work lists with a valid vertex or edge id whose
 # consumption would change the answer, piece lists with the first piece of that vertex (DESIGN.md "Graph and worklist
 # hygiene" lists the arrays and the ones left out).
-KIND = {"frontier": 0, "bfs": 1, "sssp": 2, "scc": 3, "wcc": 4, "tri": 5, "core": 6, "truss": 7}
+KIND = {"frontier": 0, "bfs": 1, "sssp": 2, "scc": 3, "wcc": 4, "tri": 5, "core": 6, "truss": 7, "color": 8, "msf": 9, "match": 10, "rcm": 11}
 N_SIZES = 12
 TIER2_NAMES = ("u5x51-strided", "wheel")
 ONES, ZERO = 0xFFFFFFFF, 0x00000000
@@ -545,7 +669,11 @@ def owned_bytes(kind, s, edges):
             "sssp": [2048 + 16384 + 4096, arr(r), arr(r), arr(r), arr(r), arr(r), pieces, pieces],
             "tri": [2 * 16384],
             "core": [2048 + 2 * 16384, arr(r), arr(r), arr(r), arr(8 * (2 * s.M // 1024 + 1)), arr(8 * (2 * s.M // 1024 + 1))],
-            "truss": [2048 + 3 * 16384, arr(m), arr(m), arr(m), arr(m)]}[kind]
+            "truss": [2048 + 3 * 16384, arr(m), arr(m), arr(m), arr(m)],
+            "color": [1024 + 16384, arr(r), arr(r), arr(r)],
+            "msf": [1024 + 2 * 16384, arr(2 * r), arr(r), arr(r), arr(4 * edges), arr(4 * edges)],
+            "match": [1024 + 16384, arr(2 * r), arr(4 * edges), arr(4 * edges)],
+            "rcm": [1024 + 16384 + 32768] + [arr(r)] * 6}[kind]
 
 
 def index_word(kind, s):
@@ -561,7 +689,18 @@ def index_word(kind, s):
         return int(np.flatnonzero(level == -1)[-1]) if (level == -1).any() else int(np.flatnonzero(level == 2)[-1])
     if kind == "truss":
         return int(np.argmax(s.want["truss"]["truss"]))
-    return int(np.argmax(s.want["core"]["core"]))
+    if kind in ("msf", "match"):
+        # one word for two id spaces, so below min(rows, edges).  sh_msf: as a vertex one that is not the largest of its
+        # component (a parent word taken for the call's own hangs a tree under it: comp differs), as an edge one outside
+        # the forest (taken from a stale list and chosen, in_msf differs).  sh_match: an edge outside the matching under
+        # every setting run here.
+        lim = min(s.rows, s.Mw)
+        if kind == "msf":
+            ok = (s.want["msf"]["in_msf"][:lim] == 0) & (s.want["msf"]["comp"][:lim] != np.arange(lim))
+        else:
+            ok = np.all([w["in_match"][:lim] == 0 for w in s.want["match"].values()], axis=0)
+        return int(np.flatnonzero(ok)[-1])
+    return int(np.argmax(s.want["core"]["core"]))   # sh_core, and sh_color and sh_rcm: coloured or numbered twice, out of turn
 
 
 def poisoner(c, name, data_word):
@@ -571,6 +710,7 @@ def poisoner(c, name, data_word):
         c.dev.ok(c.lib.sh_debug_poison_graph(c.dev.h, KIND[kind], G.h, data_word, index_word(kind, s), sizes))
         with using(c.lib):
             want = owned_bytes(kind, s, len(s.ci) if kind == "frontier" else G.edges)
+            assert kind not in ("msf", "match") or G.edges == s.Mw
         if (name, kind) not in _printed:
             _printed.add((name, kind))
             print(f"{what}: bytes poisoned {list(sizes)}")
@@ -622,6 +762,32 @@ def test_wcc_on_a_poisoned_handle(tools, name):
         components(tools, name, "wcc", SAMPLES[(i // 2) % 2], i, S.EXTRA * (i % 2), before=poisoner(tools, name, word))
 
 
+@pytest.mark.parametrize("name", TIER2_NAMES)
+def test_color_on_a_poisoned_handle(tools, name):
+    for i, word in enumerate((ONES, ZERO, ONES, ZERO, ONES, ZERO)):
+        color(tools, name, S.COLOR_SETTINGS[i % 3], i, S.EXTRA * (i % 2), before=poisoner(tools, name, word))
+
+
+@pytest.mark.parametrize("name", TIER2_NAMES)
+def test_msf_on_a_poisoned_handle(tools, name):
+    """(ZERO: every best word is a key below every bid of the call, should one survive msf_init)"""
+    for i, word in enumerate((ONES, ZERO, ONES, ZERO)):
+        msf(tools, name, i < 2, i, S.EXTRA * (i % 2), before=poisoner(tools, name, word))
+
+
+@pytest.mark.parametrize("name", TIER2_NAMES)
+def test_match_on_a_poisoned_handle(tools, name):
+    for i, word in enumerate((ONES, ZERO, ONES, ZERO)):
+        match(tools, name, S.MATCH_SETTINGS[(i // 2) % 2], i % 2 == 0, i, S.EXTRA * (i % 2), before=poisoner(tools, name, word))
+
+
+@pytest.mark.parametrize("name", TIER2_NAMES)
+def test_rcm_on_a_poisoned_handle(tools, name):
+    """(ZERO: every stamp and owner is the smallest word, what an atomic minimum can never lower)"""
+    for i, word in enumerate((ONES, ZERO, ONES, ZERO)):
+        rcm(tools, name, S.RCM_SETTINGS[(i // 2) % 2], i % 2 == 0, i, S.EXTRA * (i % 2), before=poisoner(tools, name, word))
+
+
 @pytest.mark.parametrize("sr", S.FRONTIER_SEMIRINGS, ids=HS.SR_NAME.get)
 @pytest.mark.parametrize("name", TIER2_NAMES)
 def test_iterate_frontier_on_a_poisoned_handle(tools, name, sr):
@@ -637,6 +803,8 @@ def test_the_poison_hook_refuses_an_id_outside_the_handle(tools):
     h = tools.handles("wheel")
     F = tools.frontier("wheel", HS.OA, 1)[1]
     for kind, G, bad in (("frontier", F, s.rows), ("bfs", h["bfs"], s.rows), ("sssp", h["sssp"], s.rows), ("scc", h["scc"], s.rows),
-                         ("wcc", h["wcc"], s.rows), ("core", h["core"], s.rows), ("truss", h["truss"], s.M)):
+                         ("wcc", h["wcc"], s.rows), ("core", h["core"], s.rows), ("truss", h["truss"], s.M),
+                         ("color", h["color"], s.rows), ("msf", h["msf"], min(s.rows, s.Mw)), ("match", h["match"], min(s.rows, s.Mw)),
+                         ("rcm", h["rcm"], s.rows)):
         assert tools.lib.sh_debug_poison_graph(tools.dev.h, KIND[kind], G.h, ONES, bad, sizes) == abi.SH_EINVAL, kind
-    assert tools.lib.sh_debug_poison_graph(tools.dev.h, 8, h["bfs"].h, ONES, 0, sizes) == abi.SH_EINVAL
+    assert tools.lib.sh_debug_poison_graph(tools.dev.h, 12, h["bfs"].h, ONES, 0, sizes) == abi.SH_EINVAL

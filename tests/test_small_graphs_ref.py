@@ -2,11 +2,20 @@
 oracle_bfs, sssp_ref on the union of all 65 536 digraphs on 4 vertices; tri_ref, core_ref, truss_ref on the union of all
 32 768 graphs on 6 vertices) and against scipy.sparse.csgraph on the 3-vertex digraphs; that the unions are what they
 claim; that they tell a wrong tie-break from a right one (the discrimination counts of DESIGN.md 4, "Exhaustive small
-graphs"); and that the two numberings give the same local answers.  Every comparison is ==."""
+graphs"); and that the two numberings give the same local answers.  The references of the four newer entry points:
+coloring against color_ref.first_fit (and color_ref.schedule for the records), msf against msf_ref.kruskal on
+msf_ref.edges, matching against match_ref.greedy and certify, on every union of the GPU file under both numberings and
+every setting it runs, and graph by graph on the digraphs on 3 and 4 and the graphs on 4 and 5 vertices; rcm_ref.levels
+against rcm_ref.serial with the step counts the GPU file pays; and each of five rules broken on purpose changes an
+output on some union under each numbering.  Every comparison is ==."""
 import numpy as np
 import pytest
 
+import color_ref
 import core_ref
+import match_ref
+import msf_ref
+import rcm_ref
 import scc_ref
 import small_graphs_ref as R
 import sssp_ref
@@ -244,6 +253,172 @@ def test_the_unions_tell_a_wrong_tie_break_from_a_right_one():
 
 
 RECORDED = (15_345, 57_946, 34_647, 80_448, 36_765, 56_994)   # the figures of DESIGN.md, so that a change of the inputs shows
+
+
+# ------------------------------------------------------------------ 3b. colour, forest, matching, ordering
+BY_GRAPH = (("digraphs", 3), ("digraphs", 4), ("undirected", 4), ("undirected", 5))   # the unions of graphs of up to 5 vertices: also graph by graph
+
+
+def weighted_case(kind, n, numbering, stored_name):
+    """-> (A, val (G, n, n), csr = (N, rp, ci, va)): a union with the weights of R.weights as one matrix."""
+    key = ("w", kind, n, numbering, stored_name)
+    if key not in _cases:
+        A = R.graphs_of(kind, n)
+        val = R.weights(len(A), n)
+        stored = R.storings(kind, A)[stored_name]
+        rp, ci, (g, r, c) = R.union(A, numbering, stored)
+        _cases[key] = (A if stored is None else A & stored, val, (len(A) * n, rp, ci, np.ascontiguousarray(val[g, r, c])))
+    return _cases[key]
+
+
+def single(A, g, val=None):
+    """Graph g alone as CSR arrays (values: ones, or val[g] at the stored positions)."""
+    n = A.shape[1]
+    r, c = np.nonzero(A[g])
+    rp = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=n))]).astype(np.int32)
+    va = np.ones(len(c), np.float32) if val is None else np.ascontiguousarray(val[g][r, c])
+    return n, rp, c.astype(np.int32), va
+
+
+def test_the_weights_are_what_they_claim():
+    b = R.WBITS
+    off = ~np.eye(6, dtype=bool)
+    assert (b != b.T)[off].sum() >= 20 and (b == b.T)[off].any()           # asymmetric pairs, and one that is not
+    k = R.order_key(b)
+    low = np.minimum(k, k.T)[np.triu(off)]
+    assert len(np.unique(low)) < len(low)                                   # equal weights on different pairs
+    for word in (0xBFC00000, 0x80000000, 0x7F800000, 0x7FC00001):           # -1.5, -0.0, +inf, a NaN
+        assert (b[off] == word).any(), hex(word)
+    assert (b == 0)[off].sum() == 1 and b[1, 2] == 0 and b[2, 1] != 0       # one stored +0.0, its opposite counts
+    assert np.isnan(b.view(np.float32)[1, 5]) and np.isposinf(b.view(np.float32)[0, 4])
+    # k is the header's order: -NaN < -inf < -1.5 < -0.0 < +0.0 < 0.5 < +inf < +NaN
+    line = np.array([0xFFC00001, 0xFF800000, 0xBFC00000, 0x80000000, 0, 0x3F000000, 0x7F800000, 0x7FC00001], np.uint32)
+    assert (np.diff(R.order_key(line).astype(np.int64)) > 0).all()
+    for n in (3, 4, 5, 6):   # every special value reaches every size in some graph, bit for bit; every fifth graph negated
+        val = R.bits(R.weights(30, n)).reshape(30, n, n)
+        for word in (0, 0x80000000, 0xBFC00000, 0x3FC00000, 0x7F800000, 0xFF800000, 0x7FC00001, 0xFFC00001):
+            assert (val[:, ~np.eye(n, dtype=bool)] == word).any(), (n, hex(word))
+        assert np.array_equal(val[0], b[:n, :n] ^ np.uint32(0x80000000)) and np.array_equal(val[1], np.roll(b, -1, (0, 1))[:n, :n])
+    assert np.array_equal(R.mix32(np.arange(1000) ^ 7).astype(np.uint32), color_ref.mix32(np.arange(1000) ^ 7))
+    assert np.array_equal(R.order_key(b), msf_ref.order_key(b))
+
+
+@pytest.mark.parametrize("numbering", R.NUMBERINGS)
+@pytest.mark.parametrize("kind,n", R.UNIONS, ids=lambda v: str(v))
+def test_colouring_equals_the_serial_first_fit(kind, n, numbering):
+    """Every setting the GPU file runs, the union as one matrix through color_ref.first_fit; the records the GPU file takes
+    from the chain depths (R.color_schedule) against color_ref.schedule, on every union at every setting; on the unions
+    of graphs of up to 5 vertices (BY_GRAPH) graph by graph as well, each graph a matrix of its own, under both
+    numberings and the settings whose tie does not need the union's index (order 0, with and without prio)."""
+    c = digraphs(n, numbering) if kind == "digraphs" else undirected(n, numbering)
+    A = c.A
+    prio = R.prio_of(c.G, n)
+    for order, seed, with_prio in R.COLOR_SETTINGS + ((0, 0, True),):
+        mine = R.coloring(A, R.color_keys(A, numbering, order, seed, prio if with_prio else None))
+        pv = R.scatter(prio, numbering) if with_prio else None
+        color, colors, depth = color_ref.first_fit(*c.csr(), order=order, seed=seed, prio=pv)
+        what = (kind, n, numbering, order, seed, with_prio)
+        assert np.array_equal(color, R.scatter(mine["color"], numbering)) and colors == mine["colors"], what
+        assert np.array_equal(depth, R.scatter(mine["depth"], numbering)), what
+        s = color_ref.schedule(*c.csr(), order=order, seed=seed, prio=pv)
+        rounds, sizes, edges = R.color_schedule(A, mine["depth"])
+        assert s["complete"] and s["rounds"] == rounds and np.array_equal(s["size"], sizes) and np.array_equal(s["edges"], edges), what
+        assert np.array_equal(s["color"], color)
+        if (kind, n) in BY_GRAPH:
+            if order == 0:
+                for g in range(c.G):
+                    alone = color_ref.first_fit(*single(A, g), order=0, prio=prio[g] if with_prio else None)
+                    assert np.array_equal(alone[0], mine["color"][g]) and np.array_equal(alone[2], mine["depth"][g]), (what, g)
+
+
+@pytest.mark.parametrize("numbering", R.NUMBERINGS)
+@pytest.mark.parametrize("kind,n", R.UNIONS, ids=lambda v: str(v))
+def test_forest_and_matching_equal_the_serial_loops(kind, n, numbering):
+    """msf_ref.kruskal on msf_ref.edges, match_ref.greedy and certify under every (heavy, seed) of the GPU file, the union
+    as one matrix under every storing; graph by graph on the unions of graphs of up to 5 vertices (BY_GRAPH), under both
+    numberings (seed 0: the tie by the edge id keeps its local order; mix32 of a union's edge id has no counterpart in a
+    graph alone)."""
+    A0 = R.graphs_of(kind, n)
+    for stored_name in R.storings(kind, A0):
+        A, val, csr = weighted_case(kind, n, numbering, stored_name)
+        N = csr[0]
+        eu, ev, weight, k = msf_ref.edges(*csr)
+        f = R.msf(A, val, numbering)
+        what = (kind, n, numbering, stored_name)
+        assert np.array_equal(eu, f["edge_u"]) and np.array_equal(ev, f["edge_v"]), what
+        assert np.array_equal(weight, f["weight"]) and np.array_equal(k, f["k"]), what
+        in_msf = msf_ref.kruskal(N, eu, ev, k)
+        assert np.array_equal(in_msf, f["in_msf"]), what
+        assert np.array_equal(msf_ref.labels(N, eu, ev, in_msf), R.to_global(f["comp"], numbering)), what
+        assert np.array_equal(f["comp"], R.wcc(A & (R.bits(val).reshape(val.shape) != 0))), what
+        for heavy, seed in R.MATCH_SETTINGS:
+            m = R.matching(A, val, numbering, heavy, seed)
+            keys = match_ref.mkeys(k, heavy, seed)
+            mate, chosen = match_ref.greedy(N, eu, ev, keys)
+            assert np.array_equal(mate, R.to_global(m["mate"], numbering)) and np.array_equal(chosen, m["in_match"]), (what, heavy, seed)
+            assert match_ref.certify(mate, eu, ev, keys) == "" and m["pairs"] == int((mate > np.arange(N)).sum())
+        if (kind, n) in BY_GRAPH:
+            zero = {h: R.matching(A, val, numbering, h, 0) for h in (0, 1)}
+            by_graph = np.argsort(f["graph"], kind="stable")   # the edges of a graph, in ascending edge id
+            start = np.concatenate([[0], np.cumsum(np.bincount(f["graph"], minlength=len(A)))])
+            for g in range(len(A)):
+                one = single(A, g, val)
+                mine = by_graph[start[g]:start[g + 1]]
+                eu1, ev1, w1, k1 = msf_ref.edges(*one)
+                assert np.array_equal(eu1, f["lu"][mine]) and np.array_equal(ev1, f["lv"][mine]) and np.array_equal(w1, f["weight"][mine]), (what, g)
+                assert np.array_equal(msf_ref.kruskal(n, eu1, ev1, k1), f["in_msf"][mine]), (what, g)
+                for h in (0, 1):
+                    mate, chosen = match_ref.greedy(n, eu1, ev1, match_ref.mkeys(k1, h, 0))
+                    assert np.array_equal(mate, zero[h]["mate"][g]) and np.array_equal(chosen, zero[h]["in_match"][mine]), (what, g, h)
+
+
+def test_the_rcm_step_counts_of_the_unions():
+    """sh_rcm has no tensor form: the GPU file takes rcm_ref.levels on the union as one matrix.  Here: it equals the
+    serial definition there, and the steps the GPU file pays at sweeps = 8 are the ones it was planned with."""
+    steps = {}
+    for kind, n in R.RCM_UNIONS:
+        c = digraphs(n) if kind == "digraphs" else undirected(n)
+        lv, se = rcm_ref.levels(*c.csr(), sweeps=8, reverse=1), rcm_ref.serial(*c.csr(), sweeps=8, reverse=1)
+        for f in ("perm", "pos", "level"):
+            assert np.array_equal(lv[f], se[f]), (kind, n, f)
+        steps[(kind, n)] = (lv["components"], lv["steps"])
+        assert lv["steps"] <= 20_000
+    assert steps == {("undirected", 4): (98, 579), ("digraphs", 3): (600, 3_672), ("undirected", 5): (1_398, 10_824)}, steps
+
+
+@pytest.mark.parametrize("numbering", R.NUMBERINGS)
+def test_the_unions_tell_a_broken_rule_of_the_four_from_the_right_one(numbering):
+    """Each rule broken on purpose changes an output on some union under this numbering (the count of differing
+    elements is printed per rule and union)."""
+    counts = {}
+    for kind, n in R.UNIONS:
+        A0 = R.graphs_of(kind, n)
+        G = len(A0)
+        d = {}
+        right = R.coloring(A0, R.color_keys(A0, numbering, 0, 0))["color"]
+        d["colour: ties by the larger id"] = int((R.coloring(A0, R.color_keys(A0, numbering, 0, 0, tie="larger"))["color"] != right).sum())
+        right = R.coloring(A0, R.color_keys(A0, numbering, 1, 1))["color"]
+        d["colour: mix32 of the local id"] = int((R.coloring(A0, R.color_keys(A0, numbering, 1, 1, ids="local"))["color"] != right).sum())
+        for stored_name in R.storings(kind, A0):
+            A, val, _ = weighted_case(kind, n, numbering, stored_name)
+            f = R.msf(A, val, numbering)
+            m = {hs: R.matching(A, val, numbering, *hs) for hs in R.MATCH_SETTINGS}
+
+            def differs(a, b, names):
+                return int(a["M"] != b["M"]) or sum(int((a[x] != b[x]).sum()) for x in names)
+            add = lambda name, v: d.__setitem__(name, d.get(name, 0) + v)   # noqa: E731
+            add("forest: ties by the larger id", differs(R.msf(A, val, numbering, tie="larger"), f, ("in_msf",)))
+            add("matching: ties by the larger id", differs(R.matching(A, val, numbering, 0, 0, tie="larger"), m[(0, 0)], ("mate",)))
+            add("forest: the first entry", differs(R.msf(A, val, numbering, entry="first"), f, ("in_msf", "weight")))
+            add("matching: the first entry", differs(R.matching(A, val, numbering, 1, 1, entry="first"), m[(1, 1)], ("mate",)))
+            add("forest: +0.0 counted", differs(R.msf(A, val, numbering, zero_counts=True), f, ("in_msf", "comp")))
+            add("matching: +0.0 counted", differs(R.matching(A, val, numbering, 1, 1, zero_counts=True), m[(1, 1)], ("mate",)))
+            add("matching: heavy ignored", differs(m[(0, 1)], m[(1, 1)], ("mate",)))
+            add("matching: mix32 of the local id", differs(R.matching(A, val, numbering, 1, 1, ids="local"), m[(1, 1)], ("mate",)))
+        counts[(kind, n)] = d
+        print(f"{kind}{n}-{numbering}: {d}")
+    for rule in next(iter(counts.values())):
+        assert any(d[rule] > 0 for d in counts.values()), (rule, numbering)
 
 
 # ------------------------------------------------------------------ 4. a failure is told as a small graph
