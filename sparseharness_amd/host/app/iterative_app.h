@@ -13,8 +13,10 @@
 // cycles and no diagonal, TODO.md:7-8).
 #pragma once
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <numeric>
+#include <string>
 
 #include "common.h"
 #include "csv_utils.h"
@@ -126,6 +128,26 @@ private:
   std::vector<SemiRingType> _final_host;
 };
 
+// SH_DUMP_FINAL=<dir>: after each run of the run file, the app's result vector -- the final vector of the last trial
+// (spmv_harness: the output of the last trial), one element per matrix row -- is written as raw 4-byte elements to
+// <dir>/<matrix_name>.<app>.bin, <app> being the program's name without "_harness".  Unset: nothing is written.
+// The tests compare that file element by element; SH_RESULT only carries sums.
+inline void dump_final_vector(const char *argv0, const std::string &matrix_name, const void *data, std::size_t elements) {
+  const char *dir = std::getenv("SH_DUMP_FINAL");
+  if (!dir || !dir[0])
+    return;
+  std::string app(argv0);
+  app = app.substr(app.find_last_of('/') == std::string::npos ? 0 : app.find_last_of('/') + 1);
+  if (app.size() > 8 && app.compare(app.size() - 8, 8, "_harness") == 0)
+    app.resize(app.size() - 8);
+  const std::string path = std::string(dir) + "/" + matrix_name + "." + app + ".bin";
+  FILE *f = std::fopen(path.c_str(), "wb");
+  if (!f || std::fwrite(data, 4, elements, f) != elements || std::fclose(f) != 0) {
+    LOG_ERROR("SH_DUMP_FINAL: cannot write ", path);
+    std::exit(-1);
+  }
+}
+
 inline bool env_host_loop() {
   const char *e = std::getenv("SH_HOST_LOOP");
   return e && e[0] == '1';
@@ -168,6 +190,7 @@ template <typename App> int iterative_main(int argc, char *argv[]) {
     auto fin = harness.finalVector();
     std::cout << "SH_RESULT iterations=" << harness.lastIterations() << " converged=" << harness.lastConverged()
               << " " << App::summarise(fin) << "\n";
+    dump_final_vector(argv[0], matrix_name, fin.data(), std::min<std::size_t>(fin.size(), (std::size_t)matrix.height()));
   }
   return 0;
 }

@@ -12,6 +12,7 @@
 #include "csds_timer.h"
 #include "csv_utils.h"
 #include "harness.h"
+#include "iterative_app.h"
 #include "kernel_config.h"
 #include "kernel_utils.h"
 #include "options.h"
@@ -46,6 +47,9 @@ public:
     runtimes.push_back(SqlStat(median_time, STATISTIC_VALUE, run.global1, run.local1, MEDIAN_RESULT));
     return runtimes;
   }
+
+  // y of the last trial, as read back for the compare against the gold
+  const std::vector<char> &lastOutput() const { return _mem_manager._output_host_buffer; }
 
 private:
   SqlStat executeRun(Run run, unsigned int, std::vector<float> &gold) override {
@@ -109,6 +113,8 @@ int main(int argc, char *argv[]) {
     const double bytes = 8.0 * nnz + 4.0 * (matrix.height() + 1) + 4.0 * matrix.width() + 4.0 * matrix.height();
     std::cout << "SH_PERF median_ms=" << ms << " gflops=" << 2.0 * nnz / (ms * 1e6) << " algorithmic_GBps="
               << bytes / (ms * 1e6) << "\n";
+    dump_final_vector(argv[0], matrix_name, harness.lastOutput().data(),
+                      std::min<std::size_t>(harness.lastOutput().size() / 4, (std::size_t)matrix.height()));
   }
   return 0;
 }

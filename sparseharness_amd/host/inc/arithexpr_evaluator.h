@@ -4,7 +4,8 @@
 // v_MWidthC_1 / v_MHeight_2 / v_VLength_3 and evaluates through the 38 kLoC
 // exprtk header; the expressions Lift emits only use + - * / and parentheses
 // over integers, so a 40-line recursive-descent evaluator is enough.
-// Unparseable strings (e.g. "?", quirk A-13) evaluate to 0.
+// Unparseable strings (e.g. "?", quirk A-13) evaluate to 0, and so does a
+// result outside `int` (NaN included).
 #pragma once
 #include <cctype>
 #include <string>
@@ -15,7 +16,8 @@ public:
     Evaluator ev(expr.c_str(), v_MWidthC_1, v_MHeight_2, v_VLength_3);
     double v = ev.sum();
     ev.ws();
-    return (ev.ok && *ev.p == '\0') ? (int)v : 0;
+    // (int)v is undefined outside int: such a size (4*MHeight*MWidthC at 10 M rows, say) reads as 0, like "?"
+    return (ev.ok && *ev.p == '\0' && v > -2147483649.0 && v < 2147483648.0) ? (int)v : 0;
   }
 
 private:

@@ -25,6 +25,22 @@ inline std::size_t read_size_t(const csv_token &tok) {
   return v;
 }
 
+// Strict reading of one field: decimal digits with blanks (or a CR) around them and nothing else.
+inline bool parse_size_t(const csv_token &tok, std::size_t &v) {
+  std::size_t a = 0, b = tok.size();
+  while (a < b && (tok[a] == ' ' || tok[a] == '\t')) ++a;
+  while (b > a && (tok[b - 1] == ' ' || tok[b - 1] == '\t' || tok[b - 1] == '\r')) --b;
+  if (a == b || b - a > 19)
+    return false;
+  v = 0;
+  for (; a < b; ++a) {
+    if (tok[a] < '0' || tok[a] > '9')
+      return false;
+    v = v * 10 + (std::size_t)(tok[a] - '0');
+  }
+  return true;
+}
+
 inline std::vector<csv_line> load_csv(const std::string &filename) {
   std::vector<csv_line> lines;
   std::ifstream in(filename);

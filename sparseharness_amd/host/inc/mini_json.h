@@ -67,7 +67,15 @@ private:
         case 'f': out += '\f'; break;
         case 'u': {
           if (end - p < 5) fail("bad \\u escape");
-          append_utf8(out, (unsigned)std::stoul(std::string(p + 1, p + 5), nullptr, 16));
+          unsigned cp = 0;
+          for (int i = 1; i <= 4; i++) {
+            const char c = p[i];
+            if (c >= '0' && c <= '9') cp = cp * 16 + (unsigned)(c - '0');
+            else if (c >= 'a' && c <= 'f') cp = cp * 16 + (unsigned)(c - 'a' + 10);
+            else if (c >= 'A' && c <= 'F') cp = cp * 16 + (unsigned)(c - 'A' + 10);
+            else fail("bad \\u escape");
+          }
+          append_utf8(out, cp);
           p += 4;
           break;
         }
@@ -82,9 +90,19 @@ private:
     ++p;
     return out;
   }
+  // value() recurses once per nesting level: the kernel config schema nests four deep, 64 is refused
+  static constexpr int MAX_DEPTH = 64;
+  int depth = 0;
+  struct Nested {
+    int &d;
+    explicit Nested(int &depth) : d(depth) { ++d; }
+    ~Nested() { --d; }
+  };
   Value value() {
     ws();
     if (p >= end) fail("unexpected end");
+    Nested level(depth);
+    if (depth > MAX_DEPTH) fail("nested too deeply");
     Value v;
     if (*p == '{') {
       v.kind = Value::Object;

@@ -7,6 +7,22 @@
 //     entries are mirrored right behind their original;
 //   * values are narrowed through `int` (src/sparse_matrix.cpp:107) unless
 //     truncation is switched off (SH_NO_TRUNCATE=1 or set_truncate(false)).
+// Invariant after a successful load (from a file or from the binary cache):
+// row_ptr has height() + 1 non-decreasing entries from 0 to storedNonZeros(),
+// and every col_idx lies in [0, width()).  A file that cannot be loaded so is
+// refused with one line on stderr and exit(-1): an index outside 1..M / 1..N
+// (in either field, mirrored copies included), negative numbers or more
+// entries than 32-bit row offsets hold on the size line, a symmetric banner
+// on a rectangular matrix, a body that ends before the promised entries, and
+// a token that is no number.  Entries beyond the promised count are ignored.
+// Comment lines ('%' as the first non-blank character, any length) and blank
+// lines ahead of the size line are skipped; a comment between entries is
+// refused as a token that is no number (the reference's fscanf loop stalls on
+// it and indexes row -1).
+// Rectangular files are loaded, not refused: under the transposed layout an
+// M x N file gives height() == N rows of width() == M, so every legal J has
+// a row and every legal I a column.  (The apps still stop at "Matrix is not
+// square"; for a square file nothing differs from the reference.)
 // What is native: rows are held as CSR (row_ptr / col_idx / val), not as a
 // vector of vectors of pairs, and cl_encode() emits that CSR as the device
 // layout instead of padded ELLPACK / RSA byte buffers.

@@ -217,9 +217,14 @@ template <typename T> bool SparseMatrix<T>::load_from_cache(const std::string &f
   FILE *f = std::fopen(cp.c_str(), "rb");
   if (!f) return false;
   CacheHeader h;
-  bool ok = std::fread(&h, sizeof h, 1, f) == 1 && std::memcmp(h.magic, CACHE_MAGIC, 8) == 0 &&
-            h.elem_is_int == (int)std::is_integral<T>::value && h.truncated == (int)truncate() && h.src_size == size &&
-            h.src_mtime_ns == mtime && h.rows >= 0 && h.nnz >= 0;
+  struct stat cst;
+  bool ok = ::fstat(::fileno(f), &cst) == 0 && std::fread(&h, sizeof h, 1, f) == 1 &&
+            std::memcmp(h.magic, CACHE_MAGIC, 8) == 0 && h.elem_is_int == (int)std::is_integral<T>::value &&
+            h.truncated == (int)truncate() && h.src_size == size && h.src_mtime_ns == mtime && h.rows >= 0 &&
+            h.rows < INT32_MAX && h.cols >= 0 && h.nnz >= 0 && h.nnz <= INT32_MAX;
+  // the header is only believed once the file is exactly as long as it says: nothing is sized from a damaged
+  // header (at most 8 + 16 GiB would be asked for otherwise), and a short or overlong file is a damaged one
+  ok = ok && (int64_t)cst.st_size == (int64_t)sizeof h + 4 * ((int64_t)h.rows + 1) + 8 * h.nnz;
   if (ok) {
     row_ptr_.resize((std::size_t)h.rows + 1);
     col_idx_.resize((std::size_t)h.nnz);
@@ -228,6 +233,17 @@ template <typename T> bool SparseMatrix<T>::load_from_cache(const std::string &f
          std::fread(col_idx_.data(), 4, col_idx_.size(), f) == col_idx_.size() &&
          std::fread(val_.data(), 4, val_.size(), f) == val_.size() && row_ptr_[0] == 0 &&
          row_ptr_[(std::size_t)h.rows] == h.nnz;
+    // the loader's invariant (sparse_matrix.h) holds for cached rows too
+    for (std::size_t r = 0; ok && r < (std::size_t)h.rows; r++)
+      ok = row_ptr_[r] <= row_ptr_[r + 1];
+    int bad = 0;
+    if (ok) {
+      const uint32_t width = (uint32_t)h.cols;
+#pragma omp parallel for reduction(| : bad)
+      for (int64_t k = 0; k < h.nnz; k++)
+        bad |= (uint32_t)col_idx_[(std::size_t)k] >= width;
+    }
+    ok = ok && !bad;
   }
   std::fclose(f);
   if (!ok) {
@@ -367,23 +383,44 @@ template <typename T> void SparseMatrix<T>::load_from_file(const std::string &fi
     std::cerr << "Cannot process this matrix type. Typecode: " << b.typecode << ENDL;
     std::exit(-1);
   }
-  // size line: first non-comment line (reference: src/mmio.cpp:174-199)
+  // Every refusal is one line on stderr and exit(-1), the loader's convention for a file it cannot open.
+  auto refuse = [&](const std::string &why) {
+    std::cerr << "Bad matrix file " << filename << ": " << why << ENDL;
+    std::exit(-1);
+  };
+  // size line: first line that is neither a comment nor blank (reference: src/mmio.cpp:174-199).  A comment is a
+  // line whose first non-blank character is '%', of any length: the reference's reader takes '%' in the first
+  // column only and cuts lines at 1024 characters, and spins for ever on what it then finds.
   std::string line;
-  do {
-    if (sc.p >= sc.end) {
-      std::cerr << "Cannot read matrix sizes and number of non-zeros" << ENDL;
-      return;
-    }
+  for (;;) {
+    if (sc.p >= sc.end)
+      refuse("the file ended early, before the size line");
     line = sc.next_line();
-  } while (!line.empty() && line[0] == '%');
-  if (std::sscanf(line.c_str(), "%d %d %d", &rows, &cols, &nonz) != 3) {
-    if (!(sc.next_int(rows) && sc.next_int(cols) && sc.next_int(nonz))) {
-      std::cerr << "Cannot read matrix sizes and number of non-zeros" << ENDL;
-      rows = cols = nonz = 0;
-      return;
-    }
+    const std::size_t a = line.find_first_not_of(" \t\r\v\f");
+    if (a != std::string::npos && line[a] != '%')
+      break;
   }
-  std::cerr << "Rows " << rows << " cols " << cols << " non-zeros " << nonz << ENDL;
+  int M = 0, N = 0;
+  if (std::sscanf(line.c_str(), "%d %d %d", &M, &N, &nonz) != 3) {
+    if (!(sc.next_int(M) && sc.next_int(N) && sc.next_int(nonz)))
+      refuse("cannot read matrix sizes and number of non-zeros");
+  }
+  std::cerr << "Rows " << M << " cols " << N << " non-zeros " << nonz << ENDL;
+  if (M < 0 || N < 0 || nonz < 0)
+    refuse("negative number on the size line (" + std::to_string(M) + " " + std::to_string(N) + " " + std::to_string(nonz) + ")");
+  if (b.symmetric && M != N)
+    refuse("symmetric banner on a rectangular " + std::to_string(M) + " x " + std::to_string(N) + " matrix");
+  if ((int64_t)nonz * (b.symmetric ? 2 : 1) > (int64_t)INT32_MAX)
+    refuse("too many non-zeros for 32-bit row offsets (" + std::to_string(nonz) + (b.symmetric ? ", mirrored)" : ")"));
+  // an entry takes at least "1 1\n" (pattern) or "1 1 1\n": a size line that promises more than the body can hold
+  // is refused here, before anything is sized by it
+  if ((uint64_t)nonz * (b.pattern ? 4u : 6u) > (uint64_t)(sc.end - sc.p) + 1)
+    refuse("the file ended early: the size line promises " + std::to_string(nonz) + " entries, the body has " +
+           std::to_string(sc.end - sc.p) + " bytes");
+  // transposed layout (quirk A-1): file column J is the row, file row I the column, so an M x N file gives N rows
+  // of width M.  (The reference sizes the rows by M and overruns them when N > M.)
+  rows = N;
+  cols = M;
 
   const bool trunc = truncate();
   std::vector<int32_t> ei, ej;
@@ -391,7 +428,7 @@ template <typename T> void SparseMatrix<T>::load_from_file(const std::string &fi
   const std::size_t cap = (std::size_t)nonz * (b.symmetric ? 2 : 1);
   ei.reserve(cap); ej.reserve(cap); ev.reserve(cap);
   auto emit = [&](int I, int J, double v) {
-    --I; --J;
+    I = (int)((unsigned)I - 1u); J = (int)((unsigned)J - 1u);   // (wraps for INT_MIN; the bounds check refuses it)
     const T tv = tuple_value<T>(v);
     ei.push_back(I); ej.push_back(J); ev.push_back(tv);
     if (b.symmetric && I != J) {
@@ -444,7 +481,7 @@ template <typename T> void SparseMatrix<T>::load_from_file(const std::string &fi
           ++ls.p;
         }
         if (!pt.ok) break;
-        pt.I.push_back(I - 1); pt.J.push_back(J - 1); pt.V.push_back(tuple_value<T>(v));
+        pt.I.push_back((int)((unsigned)I - 1u)); pt.J.push_back((int)((unsigned)J - 1u)); pt.V.push_back(tuple_value<T>(v));
         pt.out += (b.symmetric && I != J) ? 2 : 1;
       }
     }
@@ -469,24 +506,40 @@ template <typename T> void SparseMatrix<T>::load_from_file(const std::string &fi
     LOG_DEBUG("parallel MatrixMarket parse on ", nthreads, " threads: ", parsed ? "ok" : "fell back to the sequential scanner");
   }
   if (!parsed) {
+    // Entries beyond `nonz` are ignored, as the reference's loop ignores them.  A token that is missing or is
+    // no number is refused: fscanf leaves such a token where it is and hands out index 0 for it and for every
+    // entry after it.
     for (int k = 0; k < nonz; k++) {
       int I = 0, J = 0;
       double v = 1.0;
-      sc.next_int(I);
-      sc.next_int(J);
-      if (!b.pattern)
-        sc.next_double(v);
+      const bool read = sc.next_int(I) && sc.next_int(J) && (b.pattern || sc.next_double(v)) &&
+                        (sc.p >= sc.end || Scanner::ws(*sc.p));
+      if (!read) {
+        sc.skip_ws();
+        if (sc.p >= sc.end)
+          refuse("the file ended early: entry " + std::to_string(k + 1) + " of " + std::to_string(nonz) + " is missing or cut short");
+        const char *q = sc.p;
+        while (q < sc.end && q - sc.p < 24 && !Scanner::ws(*q)) ++q;
+        refuse("entry " + std::to_string(k + 1) + ": token \"" + std::string(sc.p, q) + "\" was not read as a number");
+      }
       emit(I, J, v);
     }
   }
   // counting sort by row (= file column J), stable => file order inside a row
   start_timer(calculate_ellpack, sparse_matrix);
   row_ptr_.assign((std::size_t)rows + 1, 0);
+  // Both indices are checked inside the two passes of the sort, each where its array is read anyway: J (the row)
+  // here, before it indexes anything, I (the column) in the scatter pass below.
+  auto refuse_index = [&](std::size_t k, bool first) {
+    refuse("stored entry " + std::to_string(k) + (b.symmetric ? " (mirrored copies counted)" : "") + " has " +
+           (first ? "first index (row) " + std::to_string((int64_t)ei[k] + 1) + " outside 1.." + std::to_string(M)
+                  : "second index (column) " + std::to_string((int64_t)ej[k] + 1) + " outside 1.." + std::to_string(N)) +
+           " of the " + std::to_string(M) + " x " + std::to_string(N) + " matrix");
+  };
+  const uint32_t urows = (uint32_t)rows, ucols = (uint32_t)cols;
   for (std::size_t k = 0; k < ej.size(); k++) {
-    if (ej[k] < 0 || ej[k] >= rows) {
-      std::cerr << "Matrix entry " << k << " has column " << ej[k] + 1 << " outside the matrix" << ENDL;
-      std::exit(-1);
-    }
+    if ((uint32_t)ej[k] >= urows)
+      refuse_index(k, false);
     row_ptr_[(std::size_t)ej[k] + 1]++;
   }
   for (int r = 0; r < rows; r++) {
@@ -496,11 +549,17 @@ template <typename T> void SparseMatrix<T>::load_from_file(const std::string &fi
   col_idx_.resize(ej.size());
   val_.resize(ej.size());
   std::vector<int32_t> cursor(row_ptr_.begin(), row_ptr_.end() - 1);
+  bool outside = false;
   for (std::size_t k = 0; k < ej.size(); k++) {
     const int32_t pos = cursor[(std::size_t)ej[k]]++;
     col_idx_[(std::size_t)pos] = ei[k];
+    outside |= (uint32_t)ei[k] >= ucols;
     val_[(std::size_t)pos] = narrow(ev[k], trunc);
   }
+  if (outside)
+    for (std::size_t k = 0; k < ei.size(); k++)
+      if ((uint32_t)ei[k] >= ucols)
+        refuse_index(k, true);
   if (keep_flag()) {
     raw_val_.resize(ej.size());
     file_order_.resize(ej.size());

@@ -22,8 +22,13 @@ def run_app(app, matrix, kernel, env_extra=None, *extra, runfile=None):
     return subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
 
 
-def test_spmv_app_reports_correct(matrix_name):
-    r = run_app("spmv_harness", matrix_name, "spmv.json")
+def dumped(folder, matrix, app):
+    """The vector the app left under SH_DUMP_FINAL=<folder> (host/app/iterative_app.h), as its 32-bit words."""
+    return np.fromfile(os.path.join(str(folder), f"{matrix}.{app}.bin"), np.uint32)
+
+
+def test_spmv_app_reports_correct(matrix_name, tmp_path):
+    r = run_app("spmv_harness", matrix_name, "spmv.json", {"SH_DUMP_FINAL": str(tmp_path)})
     assert r.returncode == 0, r.stderr[-800:]
     sql = [l for l in r.stdout.splitlines() if l.startswith("INSERT INTO table_name")]
     assert len(sql) == 1
@@ -33,6 +38,8 @@ def test_spmv_app_reports_correct(matrix_name):
                      % matrix_name, sql[0])
     assert 'PROFILING_DATUM("hipLaunchKernel", "harness"' in r.stdout
     assert "SH_PERF median_ms=" in r.stdout
+    # and y itself, every row, is the reference's gold bit for bit
+    np.testing.assert_array_equal(dumped(tmp_path, matrix_name, "spmv"), golden(matrix_name)["gold_x1"].view(np.uint32))
 
 
 def test_spmv_app_chunked_config_pads_height():
@@ -44,9 +51,9 @@ def test_spmv_app_chunked_config_pads_height():
 
 @pytest.mark.parametrize("app,kernel,tag", [("sssp_harness", "sssp.json", "sssp"), ("bfs_harness", "bfs.json", "bfs")])
 @pytest.mark.parametrize("host_loop", ["0", "1"])
-def test_iterative_apps_match_reference(matrix_name, app, kernel, tag, host_loop):
+def test_iterative_apps_match_reference(matrix_name, app, kernel, tag, host_loop, tmp_path):
     g = golden(matrix_name)
-    r = run_app(app, matrix_name, kernel, {"SH_HOST_LOOP": host_loop}, "-x", "2000")
+    r = run_app(app, matrix_name, kernel, {"SH_HOST_LOOP": host_loop, "SH_DUMP_FINAL": str(tmp_path)}, "-x", "2000")
     assert r.returncode == 0, r.stderr[-800:]
     res = [l for l in r.stdout.splitlines() if l.startswith("SH_RESULT")][0]
     iters, conv = int(g[tag + "_meta"][0]), int(g[tag + "_meta"][1])
@@ -61,29 +68,33 @@ def test_iterative_apps_match_reference(matrix_name, app, kernel, tag, host_loop
     sql = [l for l in r.stdout.splitlines() if l.startswith("INSERT INTO table_name")]
     assert len(sql) == 3                                    # one INSERT per trial
     assert sql[0].count("RAW_RESULT") == iters and "MULTI_ITERATION_SUM" in sql[0] and "MEDIAN_RESULT" in sql[0]
+    # the whole final vector, vertex by vertex (the sums above do not see two distances swapped)
+    np.testing.assert_array_equal(dumped(tmp_path, matrix_name, tag), fin.view(np.uint32))
 
 
 @pytest.mark.parametrize("host_loop", ["0", "1"])
 @pytest.mark.parametrize("name", ["matrix2", "matrix3", "matrix4"])   # see tests/test_oracle.py PR_OK
-def test_pagerank_app_matches_reference(name, host_loop):
+def test_pagerank_app_matches_reference(name, host_loop, tmp_path):
     g = golden(name)
-    r = run_app("pr_harness", name, "pr.json", {"SH_HOST_LOOP": host_loop}, "-x", "2000")
+    r = run_app("pr_harness", name, "pr.json", {"SH_HOST_LOOP": host_loop, "SH_DUMP_FINAL": str(tmp_path)}, "-x", "2000")
     assert r.returncode == 0, r.stderr[-800:]
     res = [l for l in r.stdout.splitlines() if l.startswith("SH_RESULT")][0]
     assert f"iterations={int(g['pr_meta'][0])} converged={int(g['pr_meta'][1])}" in res
     fin = g["pr_final"]
     assert float(res.split("rank_sum=")[1].split()[0]) == pytest.approx(float(fin.astype(np.float64).sum()), rel=1e-6)
+    np.testing.assert_array_equal(dumped(tmp_path, name, "pr"), fin.view(np.uint32))      # every rank, bit for bit
 
 
 @pytest.mark.parametrize("host_loop", ["0", "1"])
-def test_scc_app_matches_reference(matrix_name, host_loop):
+def test_scc_app_matches_reference(matrix_name, host_loop, tmp_path):
     g = golden(matrix_name)
-    r = run_app("scc_harness", matrix_name, "scc.json", {"SH_HOST_LOOP": host_loop}, "-x", "2000")
+    r = run_app("scc_harness", matrix_name, "scc.json", {"SH_HOST_LOOP": host_loop, "SH_DUMP_FINAL": str(tmp_path)}, "-x", "2000")
     assert r.returncode == 0, r.stderr[-800:]
     res = [l for l in r.stdout.splitlines() if l.startswith("SH_RESULT")][0]
     fin = g["scc_final"]
     assert f"iterations={int(g['scc_meta'][0])} converged={int(g['scc_meta'][1])}" in res
     assert f"labels={len(set(fin.tolist()))} label_sum={int(fin.astype(np.int64).sum())}" in res
+    np.testing.assert_array_equal(dumped(tmp_path, matrix_name, "scc"), fin.view(np.uint32))   # every label
 
 
 def test_experiment_sweep_end_to_end(tmp_path):
@@ -271,12 +282,31 @@ def test_bfs_app_at_config4_size_on_the_layout_it_picks_itself():
 
 
 @pytest.mark.parametrize("host_loop", ["0", "1"])
-def test_bfs_app_on_the_bit_blocked_layout(matrix_name, host_loop):
+def test_bfs_app_on_the_bit_blocked_layout(matrix_name, host_loop, tmp_path):
     """bfs_harness with the matrix uploaded in the bit-blocked (or,and) layout only (what the harness does by itself for
     large matrices; forced here on the reference's example matrices): same launches, same final vector."""
     g = golden(matrix_name)
-    r = run_app("bfs_harness", matrix_name, "bfs.json", {"SH_HOST_LOOP": host_loop, "SH_OR_AND_BITS": "2"}, "-x", "2000")
+    r = run_app("bfs_harness", matrix_name, "bfs.json", {"SH_HOST_LOOP": host_loop, "SH_OR_AND_BITS": "2", "SH_DUMP_FINAL": str(tmp_path)},
+                "-x", "2000")
     assert r.returncode == 0, r.stderr[-800:]
     res = [l for l in r.stdout.splitlines() if l.startswith("SH_RESULT")][0]
     assert f"iterations={int(g['bfs_meta'][0])} converged={int(g['bfs_meta'][1])}" in res
     assert res.endswith(f"set={int((g['bfs_final'] != 0).sum())}")
+    np.testing.assert_array_equal(dumped(tmp_path, matrix_name, "bfs"), g["bfs_final"].view(np.uint32))
+
+
+@pytest.mark.parametrize("app,kernel,tag", [("sssp_harness", "sssp.json", "sssp"), ("scc_harness", "scc.json", "scc")])
+@pytest.mark.parametrize("host_loop", ["0", "1"])
+def test_second_run_of_a_run_file_starts_from_the_initial_vectors(app, kernel, tag, host_loop, tmp_path):
+    """resetInputs (host/app/iterative_app.h): with a two-line run file and three trials, the second run starts from
+    x0 / y0 again, so the vector it leaves -- the dump is written after every run -- is the one a single run leaves,
+    and both runs report the same result line."""
+    g = golden("matrix4")
+    rf = tmp_path / "two_runs.csv"
+    rf.write_text("1280,1,1,256,1,1\n2560,1,1,128,1,1\n")
+    r = run_app(app, "matrix4", kernel, {"SH_HOST_LOOP": host_loop, "SH_DUMP_FINAL": str(tmp_path)}, "-x", "2000", runfile=str(rf))
+    assert r.returncode == 0, r.stderr[-800:]
+    res = [l for l in r.stdout.splitlines() if l.startswith("SH_RESULT")]
+    assert len(res) == 2 and res[0] == res[1]
+    assert f"iterations={int(g[tag + '_meta'][0])} converged={int(g[tag + '_meta'][1])}" in res[1]
+    np.testing.assert_array_equal(dumped(tmp_path, "matrix4", tag), g[tag + "_final"].view(np.uint32))

@@ -261,6 +261,17 @@ def test_binary_csr_cache_roundtrip_and_invalidation(tmp_path, monkeypatch):
     # truncated cache file -> parse again
     p.write_bytes(p.read_bytes()[:100])
     np.testing.assert_array_equal(H.mm_load(str(src))[5], fresh[5])
+    # a header that asks for 2^40 entries or 2^31 - 1 rows, a file of another length than its header says, a row_ptr
+    # that decreases, a column outside the matrix: each is told from the file's own length and contents (nothing is
+    # sized from the header before the length agrees with it), parsed again, and the cache rewritten
+    from host_ingest_child import damaged_caches
+    valid = p.read_bytes()
+    for what, blob in damaged_caches(valid).items():
+        p.write_bytes(blob)
+        again = H.mm_load(str(src))
+        for a, b in zip(fresh, again):
+            np.testing.assert_array_equal(np.asarray(a), np.asarray(b), err_msg=what)
+        assert p.read_bytes() == valid, what
     # PageRank (needs file order) never goes through the cache
     pr = H.mm_load(mtx("matrix3"), normalise=H.NORM_PAGERANK)
     assert pr[0] == 20
