@@ -226,12 +226,10 @@ __global__ __launch_bounds__(WL_BS) void bfs_decide(BfsCtl *ctl, int k, int L, i
   if (L >= 0)
     for (int64_t i = (int64_t)blockIdx.x * WL_BS + threadIdx.x; i < words; i += (int64_t)gridDim.x * WL_BS) bm[i] = 0u;
   if (blockIdx.x != 0) return;
-  __shared__ int32_t s_go, s_mode;
-  if (threadIdx.x == 0) { s_go = (L < 0 || ctl->step == L) ? 1 : 0; s_mode = ctl->mode; }
-  __syncthreads();
-  if (!s_go) return;
-  uint32_t a = 0, b = 0;
-  if (!wl_sum_parts(part, nparts, &a, &b)) return;
+  if (!wl_from_thread0(L < 0 || ctl->step == L)) return;
+  const WlPart sums = wl_sum_parts(part, nparts);
+  if (threadIdx.x != 0) return;
+  const uint32_t a = sums.a, b = sums.b;
   if (L < 0) {
     const uint32_t nsrc = ctl->qcount[0];
     ctl->nsrc = nsrc; ctl->fsize = nsrc;
@@ -241,7 +239,7 @@ __global__ __launch_bounds__(WL_BS) void bfs_decide(BfsCtl *ctl, int k, int L, i
     ctl->have_queue = 1;
     return;
   }
-  const int p = L & 1, mode = s_mode;
+  const int p = L & 1, mode = ctl->mode;   // (this thread alone stores it, below)
   const uint32_t found = mode == 0 ? ctl->qcount[p ^ 1] : a;
   const uint32_t edges = mode == 0 ? a : b;
   const int done = found == 0 ? 1 : 0;

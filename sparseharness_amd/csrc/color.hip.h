@@ -121,13 +121,6 @@ __device__ __forceinline__ uint64_t gcol_key(const ColorOrder &O, int32_t v) {
   const uint32_t lo = O.order == 0 ? ~(uint32_t)v : gcol_mix32((uint32_t)v ^ O.seed);
   return ((uint64_t)hi << 32) | lo;
 }
-__device__ __forceinline__ int32_t gcol_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// What one wave wrote to its own LDS words is there for all its lanes from here on.
-__device__ __forceinline__ void gcol_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // v joins a work list: at the front, or at the far end when its list is of the workgroup class.  (Any control flow.)
 __device__ __forceinline__ void gcol_push(ColorCtl *ctl, int q, uint32_t *__restrict__ list, int32_t rows, int32_t v, int32_t len) {
   if (len > GCOL_PIECE) list[(int64_t)rows - 1 - (int64_t)wl_append_here(&ctl->nl[q])] = (uint32_t)v;
@@ -218,7 +211,6 @@ __device__ __forceinline__ uint32_t gcol_walk(const ColorGraph &G, const uint32_
                                               Taken taken, Give give) {
   __shared__ uint32_t s_wave[WL_BS / 64][GCOL_WAVE_WORDS];
   __shared__ uint32_t s_win[GCOL_WINDOW / 32];
-  __shared__ uint32_t s_min[WL_BS / 64];
   const int lane = wl_lane(), wv = (int)(threadIdx.x >> 6);
   uint32_t looked = 0;
   for (int64_t base = wl_wave() * 64; base < n; base += wl_waves() * 64) {
@@ -243,12 +235,12 @@ __device__ __forceinline__ uint32_t gcol_walk(const ColorGraph &G, const uint32_
       const int words = lb / 32 + 1;   // colours 0 .. lb
       uint32_t *bm = s_wave[wv];
       for (int w = lane; w < words; w += 64) bm[w] = 0u;
-      gcol_wave_sync();
+      wl_wave_sync();
       for (int32_t j = lane; j < lb; j += 64) {
         const int32_t c = taken(G.col[sb + j], true);
         if (c >= 0 && c <= lb) (void)__hip_atomic_fetch_or(&bm[c >> 5], 1u << (c & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
-      gcol_wave_sync();
+      wl_wave_sync();
       uint32_t best = 0xFFFFFFFFu;
       for (int w = lane; w < words; w += 64) {
         const uint32_t free_bits = ~bm[w];
@@ -256,7 +248,7 @@ __device__ __forceinline__ uint32_t gcol_walk(const ColorGraph &G, const uint32_
       }
       best = wl_wave_min(best);   // (lb entries mark at most lb of the lb + 1 colours the words hold)
       if (lane == 0) give(vb, (int32_t)best);
-      gcol_wave_sync();           // (the bitmap is read before the next list clears it)
+      wl_wave_sync();           // (the bitmap is read before the next list clears it)
     }
   }
   for (int64_t h = blockIdx.x; h < nl; h += gridDim.x) {   // a long list: the whole workgroup, a window of colours per walk
@@ -277,12 +269,8 @@ __device__ __forceinline__ uint32_t gcol_walk(const ColorGraph &G, const uint32_
         const uint32_t free_bits = ~s_win[w];
         if (free_bits) best = min(best, (uint32_t)(w * 32 + __ffs((int)free_bits) - 1));
       }
-      best = wl_wave_min(best);
-      if (lane == 0) s_min[wv] = best;
-      __syncthreads();
-      best = s_min[0];
-      for (int w = 1; w < WL_BS / 64; w++) best = min(best, s_min[w]);
-      __syncthreads();   // (s_min and the bitmap are read before the next walk or list writes them)
+      best = wl_block_fold<WlMin>(best);
+      __syncthreads();   // (the bitmap is read before the next walk or list writes it)
       if (best != 0xFFFFFFFFu) {   // (the same word in every thread)
         if (threadIdx.x == 0) give(v, lo + (int32_t)best);
         break;
@@ -290,20 +278,6 @@ __device__ __forceinline__ uint32_t gcol_walk(const ColorGraph &G, const uint32_
     }
   }
   return looked;
-}
-
-// The workgroup's sum of a and its largest b -> its WlPart (convergent control flow only; wl_block_part with a maximum).
-__device__ __forceinline__ void gcol_block_part(WlPart *__restrict__ part, uint32_t a, uint32_t b) {
-  __shared__ uint32_t s_a[WL_BS / 64], s_b[WL_BS / 64];
-  a = wl_wave_sum(a);
-  for (int o = 32; o > 0; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o));
-  if (wl_lane() == 0) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t ta = 0, tb = 0;
-    for (int w = 0; w < WL_BS / 64; w++) { ta += s_a[w]; tb = max(tb, s_b[w]); }
-    part[blockIdx.x] = WlPart{ta, tb, 0u, 0u};
-  }
 }
 
 // Round s: colours the work list's vertices and takes one from the word of every neighbour they precede.
@@ -315,7 +289,7 @@ __global__ __launch_bounds__(WL_BS) void gcol_assign(ColorCtl *ctl, int s, Color
   uint32_t most = 0;   // the largest colour this lane gave, plus 1
   const uint32_t looked = gcol_walk(G, L.list[p], (int64_t)ctl->n[p], (int64_t)ctl->nl[p], window,
       [&](int32_t u, bool first) {
-        const int32_t c = gcol_load(&color[u]);   // (not written in this launch: u is in another round's list)
+        const int32_t c = wl_load(&color[u]);   // (not written in this launch: u is in another round's list)
         if (c < 0 && first && __hip_atomic_fetch_add(&wait[u], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1)
           gcol_push(ctl, q, next, G.rows, u, G.ptr[u + 1] - G.ptr[u]);   // this lane owns u
         return c;
@@ -324,24 +298,16 @@ __global__ __launch_bounds__(WL_BS) void gcol_assign(ColorCtl *ctl, int s, Color
         color[v] = c;
         most = max(most, (uint32_t)c + 1u);
       });
-  gcol_block_part(part, looked, most);
+  wl_block_part<WlMax>(part, looked, most);
 }
 
 // Closes round s (slot r of the batch).  One workgroup folds the WlParts (no atomics on one word) and its first lane
 // records the round and decides.
 __global__ __launch_bounds__(WL_BS) void gcol_close(ColorCtl *ctl, int r, int s, int32_t rows, int nparts, const WlPart *__restrict__ part) {
-  __shared__ int32_t s_go;
-  __shared__ uint32_t s_a[WL_BS], s_b[WL_BS];
-  if (threadIdx.x == 0) s_go = ctl->step == s ? 1 : 0;
-  __syncthreads();
-  if (!s_go) return;
-  uint32_t ta = 0, tb = 0;
-  for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) { ta += part[i].a; tb = max(tb, part[i].b); }
-  s_a[threadIdx.x] = ta; s_b[threadIdx.x] = tb;
-  __syncthreads();
+  if (!wl_from_thread0(ctl->step == s)) return;
+  const WlPart sums = wl_sum_parts<WlMax>(part, nparts);
   if (threadIdx.x != 0) return;
-  uint32_t looked = 0, most = 0;
-  for (int i = 0; i < WL_BS; i++) { looked += s_a[i]; most = max(most, s_b[i]); }
+  const uint32_t looked = sums.a, most = sums.b;
   const int p = ctl->p;
   const uint32_t size = ctl->n[p] + ctl->nl[p];
   ctl->rec[r] = ColorRec{1, size, looked, 0u};

@@ -132,18 +132,6 @@ __global__ __launch_bounds__(WL_BS) void core_init(CoreCtl *ctl, int32_t rows, i
   if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->remaining = (uint32_t)rows; ctl->chase = chase; ctl->opening = 1; }
 }
 
-// The smallest of the workgroup's words -> every thread (convergent control flow only).
-__device__ __forceinline__ uint32_t core_block_min(uint32_t v) {
-  __shared__ uint32_t s_m[WL_BS / 64];
-  v = wl_wave_min(v);
-  __syncthreads();   // (a second call in one kernel: the words of the first have been read)
-  if (wl_lane() == 0) s_m[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = s_m[0];
-  for (int w = 1; w < WL_BS / 64; w++) v = min(v, s_m[w]);
-  return v;
-}
-
 // Opening round s, first pass: the smallest remaining degree among the unsettled, per workgroup.
 __global__ __launch_bounds__(WL_BS) void core_min(const CoreCtl *ctl, int s, int32_t rows, const int32_t *__restrict__ cur,
                                                    const int32_t *__restrict__ core, WlPart *__restrict__ mins) {
@@ -151,7 +139,7 @@ __global__ __launch_bounds__(WL_BS) void core_min(const CoreCtl *ctl, int s, int
   uint32_t best = CORE_NONE;
   for (int64_t v = (int64_t)blockIdx.x * WL_BS + threadIdx.x; v < rows; v += (int64_t)gridDim.x * WL_BS)
     if (core[v] < 0) best = min(best, (uint32_t)cur[v]);
-  best = core_block_min(best);
+  best = wl_block_fold<WlMin>(best);
   if (threadIdx.x == 0) mins[blockIdx.x] = WlPart{best, 0u, 0u, 0u};
 }
 
@@ -161,7 +149,7 @@ __global__ __launch_bounds__(WL_BS) void core_open(CoreCtl *ctl, int s, CoreGrap
   if (ctl->step != s || !ctl->opening) return;
   uint32_t m = CORE_NONE;
   for (int i = (int)threadIdx.x; i < (int)gridDim.x; i += WL_BS) m = min(m, mins[i].a);
-  const int32_t k = (int32_t)core_block_min(m);
+  const int32_t k = (int32_t)wl_block_fold<WlMin>(m);
   const int p = ctl->p;
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl->k = k;   // (no workgroup of this launch reads it)
   uint32_t *__restrict__ list = L.list[p];
@@ -194,7 +182,7 @@ __global__ __launch_bounds__(WL_BS) void core_peel(CoreCtl *ctl, int s, CoreGrap
   };
   const auto hit = [&](int32_t j) {
     const int32_t u = G.col[j];
-    if (__hip_atomic_load(&cur[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= k) return;   // settled, listed or owned
+    if (wl_load(&cur[u]) <= k) return;   // settled, listed or owned
     const int32_t old = __hip_atomic_fetch_add(&cur[u], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (old == k + 1) {   // this lane owns u
       const int32_t len = G.ptr[u + 1] - G.ptr[u];
@@ -223,12 +211,10 @@ __global__ __launch_bounds__(WL_BS) void core_peel(CoreCtl *ctl, int s, CoreGrap
 // Closes round s (slot r of the batch).  One workgroup sums the WlParts (no atomics on one word) and its first lane
 // records the round and decides.
 __global__ __launch_bounds__(WL_BS) void core_close(CoreCtl *ctl, int r, int s, int nparts, const WlPart *__restrict__ part) {
-  __shared__ int32_t s_go;
-  if (threadIdx.x == 0) s_go = ctl->step == s ? 1 : 0;
-  __syncthreads();
-  if (!s_go) return;
-  uint32_t looked = 0, chased = 0;
-  if (!wl_sum_parts(part, nparts, &looked, &chased)) return;
+  if (!wl_from_thread0(ctl->step == s)) return;
+  const WlPart sums = wl_sum_parts(part, nparts);
+  if (threadIdx.x != 0) return;
+  const uint32_t looked = sums.a, chased = sums.b;
   const int p = ctl->p;
   const uint32_t size = ctl->n[p];
   ctl->rec[r] = CoreRec{1, ctl->k, size, chased, looked};

@@ -181,21 +181,11 @@ __global__ __launch_bounds__(WL_BS) void match_clear(const MatchCtl *ctl, int s,
 // Closes round s (slot k of the batch).  One workgroup sums the WlParts (no atomics on one word) and its first lane
 // records the round, swaps the lists and decides.
 __global__ __launch_bounds__(WL_BS) void match_close(MatchCtl *ctl, int k, int s, int nparts, const WlPart *__restrict__ part) {
-  __shared__ int32_t s_go;
-  __shared__ uint32_t s_a[WL_BS];
-  if (threadIdx.x == 0) s_go = ctl->step == s ? 1 : 0;
-  __syncthreads();
-  if (!s_go) return;
+  if (!wl_from_thread0(ctl->step == s)) return;
   const int pl = ctl->p, q = pl ^ 1;
   const uint32_t kept = ctl->n[q];
-  uint32_t ta = 0;   // (the parts are this round's only if take ran)
-  if (kept)
-    for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) ta += part[i].a;
-  s_a[threadIdx.x] = ta;
-  __syncthreads();
+  const uint32_t matched = wl_sum_parts(part, kept ? nparts : 0).a;   // (the parts are this round's only if take ran)
   if (threadIdx.x != 0) return;
-  uint32_t matched = 0;
-  for (int i = 0; i < WL_BS; i++) matched += s_a[i];
   ctl->rec[k] = MatchRec{1, ctl->n[pl], kept, matched};
   ctl->n[pl] = 0u;
   ctl->p = q;

@@ -205,52 +205,26 @@ __global__ __launch_bounds__(WL_BS) void msf_link(const MsfCtl *ctl, int s, int3
   wl_block_part(part, hooks, 0u);
 }
 
-// Jumping launch i of round s, over all vertices: p[v] = p[p[v]] until p[v] is a root as this lane sees it, MSF_JUMPS
-// times at most.  p[v] is written by the lane of v alone; what it reads of others is a pointer they hold now or held
-// before, an ancestor either way, and every jump gains at least one hop of the forest the launch started from.
+// Jumping launch i of round s, over all vertices: wl_jump, MSF_JUMPS jumps per vertex at most.  Every jump gains at
+// least one hop of the forest the launch started from.
 __global__ __launch_bounds__(WL_BS) void msf_jump(MsfCtl *ctl, int s, int i, int32_t rows, uint32_t *p, WlPart *__restrict__ jpart) {
   if (ctl->step != s || ctl->n[ctl->p ^ 1] == 0u || (i > 0 && !ctl->moved[i - 1])) return;
-  uint32_t moved = 0;
-  for (int64_t v = (int64_t)blockIdx.x * WL_BS + threadIdx.x; v < rows; v += (int64_t)gridDim.x * WL_BS) {
-    uint32_t q = p[v];
-    for (int h = 0; h < MSF_JUMPS; h++) {
-      const uint32_t up = p[q];
-      if (up == q) break;
-      p[v] = q = up;
-      moved++;
-    }
-  }
-  __shared__ uint32_t s_m[WL_BS / 64];
-  moved = wl_wave_sum(moved);
-  if (wl_lane() == 0) s_m[threadIdx.x >> 6] = moved;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < WL_BS / 64; w++) t += s_m[w];
-    jpart[blockIdx.x].a = i == 0 ? t : jpart[blockIdx.x].a + t;   // (this thread alone, launch after launch)
-    if (t) ctl->moved[i] = 1u;                                  // (whoever stores it stores the same word)
-  }
+  wl_jump(i, MSF_JUMPS, rows, p, jpart, ctl->moved);
 }
 
 // Closes round s (slot k of the batch).  One workgroup sums the WlParts (no atomics on one word) and its first lane
 // records the round, swaps the lists and decides.
 __global__ __launch_bounds__(WL_BS) void msf_close(MsfCtl *ctl, int k, int s, int nparts, const WlPart *__restrict__ part,
                                                    const WlPart *__restrict__ jpart) {
-  __shared__ int32_t s_go;
-  __shared__ uint32_t s_a[WL_BS], s_b[WL_BS];
-  if (threadIdx.x == 0) s_go = ctl->step == s ? 1 : 0;
-  __syncthreads();
-  if (!s_go) return;
+  if (!wl_from_thread0(ctl->step == s)) return;
   const int pl = ctl->p, q = pl ^ 1;
   const uint32_t kept = ctl->n[q];
-  uint32_t ta = 0, tb = 0;   // hooks, pointers changed (the parts are this round's only if its launches ran)
+  uint32_t hooks = 0, jumps = 0;   // hooks, pointers changed (the parts are this round's only if its launches ran)
   if (kept)
-    for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) { ta += part[i].a; tb += jpart[i].a; }
-  s_a[threadIdx.x] = ta; s_b[threadIdx.x] = tb;
-  __syncthreads();
+    for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) { hooks += part[i].a; jumps += jpart[i].a; }
+  hooks = wl_block_fold<WlSum>(hooks);
+  jumps = wl_block_fold<WlSum>(jumps);
   if (threadIdx.x != 0) return;
-  uint32_t hooks = 0, jumps = 0;
-  for (int i = 0; i < WL_BS; i++) { hooks += s_a[i]; jumps += s_b[i]; }
   ctl->rec[k] = MsfRec{1, ctl->n[pl], kept, hooks, jumps, 0u};
   ctl->n[pl] = 0u;
   ctl->p = q;
@@ -285,15 +259,8 @@ __global__ __launch_bounds__(WL_BS) void msf_label(MsfCtl *ctl, int32_t rows, in
     if (comp) comp[v] = complete ? (int32_t)top[up] : -1;
     roots += up == (uint32_t)v ? 1u : 0u;
   }
-  __shared__ uint32_t s_r[WL_BS / 64];
-  roots = wl_wave_sum(roots);
-  if (wl_lane() == 0) s_r[threadIdx.x >> 6] = roots;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < WL_BS / 64; w++) t += s_r[w];
-    if (t) wl_add(&ctl->components, t);   // (one add per workgroup)
-  }
+  roots = wl_block_fold<WlSum>(roots);
+  if (threadIdx.x == 0 && roots) wl_add(&ctl->components, roots);   // (one add per workgroup)
 }
 
 } // namespace sh

@@ -137,8 +137,6 @@ __global__ __launch_bounds__(WL_BS) void rcm_both_ways(const uint64_t *__restric
 }
 
 // ---- the walk -----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rcm_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // One tile: thread t of the workgroup brings a list (s, len; `valid`) with two carried words, key and base.  Every entry
 // w of the list is asked pred(key, w) ONCE, and every chosen entry gets emit(key, base, w, rank), rank = the chosen
 // entries of its list before it.  -> for the thread that brought the list, the chosen entries of it.
@@ -306,7 +304,7 @@ __global__ __launch_bounds__(WL_BS) void rcm_sweep(RcmCtl *ctl, int s, RcmGraph 
     looked += (uint32_t)len;
     (void)rcm_tile(G.col, valid, 0u, 0u, st, len,
         [&](uint32_t, uint32_t w) {   // (an older generation is a larger word; the one lane that reads it owns w)
-          return rcm_load(&St.stamp[w]) != gen && __hip_atomic_fetch_min(&St.stamp[w], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != gen;
+          return wl_load(&St.stamp[w]) != gen && __hip_atomic_fetch_min(&St.stamp[w], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != gen;
         },
         [&](uint32_t, uint32_t, uint32_t w, uint32_t) {
           St.order[wl_append_here(&ctl->tail)] = w;
@@ -331,7 +329,7 @@ __global__ __launch_bounds__(WL_BS) void rcm_claim(const RcmCtl *ctl, int s, Rcm
     (void)rcm_tile(G.col, valid, (uint32_t)i, 0u, st, len,
         [&](uint32_t, uint32_t w) { return St.posl[w] < 0; },   // (posl is not written in this launch)
         [&](uint32_t key, uint32_t, uint32_t w, uint32_t) {
-          if (rcm_load(&St.owner[w]) > key) (void)__hip_atomic_fetch_min(&St.owner[w], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (wl_load(&St.owner[w]) > key) (void)__hip_atomic_fetch_min(&St.owner[w], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         });
   }
 }
@@ -396,12 +394,12 @@ __global__ __launch_bounds__(WL_BS) void rcm_place(const RcmCtl *ctl, int s, Rcm
 
 // Closes step s (slot r of the batch).  One workgroup folds the WlParts and its first thread records the step and decides.
 __global__ __launch_bounds__(WL_BS) void rcm_close(RcmCtl *ctl, int r, int s, int32_t rows, int nparts, const WlPart *__restrict__ part, RcmState St) {
-  __shared__ int32_t s_go, s_next;
-  if (threadIdx.x == 0) { s_go = ctl->step == s ? 1 : 0; s_next = 0; }
-  __syncthreads();
-  if (!s_go) return;
-  uint32_t children = 0, looked = 0;
-  if (wl_sum_parts(part, nparts, &children, &looked)) {
+  __shared__ int32_t s_next;   // thread 0's verdict, across the barrier below: the component is numbered, look for the next
+  if (!wl_from_thread0(ctl->step == s)) return;
+  const WlPart sums = wl_sum_parts(part, nparts);
+  if (threadIdx.x == 0) {
+    const uint32_t children = sums.a, looked = sums.b;
+    s_next = 0;
     const int kind = ctl->kind;
     const uint32_t b = ctl->b;
     ctl->rec[r] = RcmRec{1, kind, b - ctl->a, looked};
@@ -441,8 +439,6 @@ __global__ __launch_bounds__(WL_BS) void rcm_close(RcmCtl *ctl, int r, int s, in
 __global__ __launch_bounds__(WL_BS) void rcm_finish(const RcmCtl *ctl, RcmGraph G, RcmState St, const int32_t *__restrict__ S, int32_t reverse,
                                                      int32_t *__restrict__ perm, int32_t *__restrict__ pos, int32_t *__restrict__ level,
                                                      RcmFin *__restrict__ fin) {
-  __shared__ uint32_t s_bw[2][WL_BS / 64];
-  __shared__ uint64_t s_prof[2][WL_BS / 64];
   const int lane = wl_lane();
   const int64_t rows = G.rows, done = (int64_t)ctl->done;
   const auto placed = [&](int32_t p) { return p < 0 ? -1 : reverse ? (int32_t)(rows - 1 - p) : p; };
@@ -483,39 +479,24 @@ __global__ __launch_bounds__(WL_BS) void rcm_finish(const RcmCtl *ctl, RcmGraph 
         um = min(um, u); qm = min(qm, q);
         bw0 = max(bw0, (uint32_t)abs(vb - u)); bw1 = max(bw1, (uint32_t)abs(pb - q));
       }
-      for (int o = 32; o > 0; o >>= 1) { um = min(um, __shfl_xor(um, o)); qm = min(qm, __shfl_xor(qm, o)); }
+      um = wl_wave_fold<WlMin>(um); qm = wl_wave_fold<WlMin>(qm);
       if (lane == src) { vmin = um; pmin = qm; }
     }
     if (on) { prof0 += (uint64_t)(v - vmin); prof1 += (uint64_t)(p - pmin); }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    bw0 = max(bw0, (uint32_t)__shfl_xor((int)bw0, o)); bw1 = max(bw1, (uint32_t)__shfl_xor((int)bw1, o));
-    prof0 += (uint64_t)__shfl_xor((unsigned long long)prof0, o); prof1 += (uint64_t)__shfl_xor((unsigned long long)prof1, o);
-  }
-  if (lane == 0) { const int w = (int)(threadIdx.x >> 6); s_bw[0][w] = bw0; s_bw[1][w] = bw1; s_prof[0][w] = prof0; s_prof[1][w] = prof1; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    RcmFin f = {};
-    for (int w = 0; w < WL_BS / 64; w++)
-      for (int k = 0; k < 2; k++) { f.bw[k] = max(f.bw[k], s_bw[k][w]); f.prof[k] += s_prof[k][w]; }
-    fin[blockIdx.x] = f;
-  }
+  // (four folds one after the other, left to right, each with its pair of barriers: once per call, so it does not matter)
+  const RcmFin f{{wl_block_fold<WlMax>(bw0), wl_block_fold<WlMax>(bw1)}, {wl_block_fold<WlSum>(prof0), wl_block_fold<WlSum>(prof1)}, 0ull};
+  if (threadIdx.x == 0) fin[blockIdx.x] = f;
 }
 // One workgroup folds the RcmFins into the control block.
 __global__ __launch_bounds__(WL_BS) void rcm_total(RcmCtl *ctl, int nparts, const RcmFin *__restrict__ fin) {
-  __shared__ uint32_t s_bw[2][WL_BS];
-  __shared__ uint64_t s_prof[2][WL_BS];
   RcmFin f = {};
   for (int i = (int)threadIdx.x; i < nparts; i += WL_BS)
     for (int k = 0; k < 2; k++) { f.bw[k] = max(f.bw[k], fin[i].bw[k]); f.prof[k] += fin[i].prof[k]; }
-  for (int k = 0; k < 2; k++) { s_bw[k][threadIdx.x] = f.bw[k]; s_prof[k][threadIdx.x] = f.prof[k]; }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  for (int k = 0; k < 2; k++) {
-    uint32_t bw = 0;
-    uint64_t prof = 0;
-    for (int i = 0; i < WL_BS; i++) { bw = max(bw, s_bw[k][i]); prof += s_prof[k][i]; }
-    ctl->bw[k] = (int64_t)bw; ctl->prof[k] = (int64_t)prof;
+  for (int k = 0; k < 2; k++) {   // (four folds one after the other, as in rcm_finish)
+    const uint32_t bw = wl_block_fold<WlMax>(f.bw[k]);
+    const uint64_t prof = wl_block_fold<WlSum>(f.prof[k]);
+    if (threadIdx.x == 0) { ctl->bw[k] = (int64_t)bw; ctl->prof[k] = (int64_t)prof; }
   }
 }
 

@@ -95,9 +95,6 @@ struct SccLists {   // the handle's work lists, as a kernel argument
   __device__ WlPiece *ip(int i) const { return i ? ip1 : ip0; }
 };
 
-__device__ __forceinline__ uint32_t scc_umax(uint32_t *p, uint32_t v) {
-  return __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ bool scc_cas(int32_t *p, int32_t expect, int32_t v) {
   return __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -107,27 +104,14 @@ __device__ __forceinline__ void scc_file(SccCtl *ctl, const SccGraph &G, const S
   wl_push_pieces<SCC_PIECE>(&ctl->nop[q], v, (uint32_t)(G.out_ptr[v + 1] - G.out_ptr[v]), L.op(q));
   wl_push_pieces<SCC_PIECE>(&ctl->nip[q], v, (uint32_t)(G.in_ptr[v + 1] - G.in_ptr[v]), L.ip(q));
 }
-// The workgroup's sums and maximum -> its WlPart (convergent control flow only).
-__device__ __forceinline__ void scc_block_part(WlPart *__restrict__ part, uint32_t a, uint32_t b, uint32_t c) {
-  __shared__ uint32_t s_a[WL_BS / 64], s_b[WL_BS / 64], s_c[WL_BS / 64];
-  a = wl_wave_sum(a);
-  b = wl_wave_sum(b);
-  for (int o = 32; o > 0; o >>= 1) c = max(c, (uint32_t)__shfl_xor((int)c, o));
-  if (wl_lane() == 0) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; s_c[threadIdx.x >> 6] = c; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t ta = 0, tb = 0, tc = 0;
-    for (int w = 0; w < WL_BS / 64; w++) { ta += s_a[w]; tb += s_b[w]; tc = max(tc, s_c[w]); }
-    part[blockIdx.x] = WlPart{ta, tb, tc, 0u};
-  }
-}
 
 // Is pivot candidate a (product, vertex; v < 0: none) better than b?  The larger product, ties to the larger index.
 __device__ __forceinline__ bool scc_better(uint64_t pa, int32_t va, uint64_t pb, int32_t vb) {
   return va >= 0 && (vb < 0 || pa > pb || (pa == pb && va > vb));
 }
 // The workgroup's best pivot candidate -> every thread (convergent control flow only): shuffles inside a wave, one
-// shared word pair per wave.
+// shared word pair per wave.  It stays beside wl_block_fold: that folds one word, this an arg-max over a pair whose two
+// halves must travel together.  One call per kernel (its words have no barrier ahead of them).
 __device__ __forceinline__ void scc_block_best(uint64_t *best, int32_t *bv) {
   __shared__ uint64_t s_prod[WL_BS / 64];
   __shared__ int32_t s_v[WL_BS / 64];
@@ -205,7 +189,7 @@ __global__ __launch_bounds__(WL_BS) void scc_trim(SccCtl *ctl, int s, int phase,
     if (sweep == 0) return;
     const uint32_t tag = (uint32_t)s + 1u;
     const auto file = [&](int32_t r) {
-      if (comp[r] == -1 && scc_umax(&stamp[r], tag) < tag) L.cand[wl_append_here(&ctl->ncand)] = (uint32_t)r;
+      if (comp[r] == -1 && wl_umax(&stamp[r], tag) < tag) L.cand[wl_append_here(&ctl->ncand)] = (uint32_t)r;
     };
     const auto none = [](int32_t, bool) { return 0u; };
     const int64_t n = ctl->n[p];
@@ -233,7 +217,7 @@ __global__ __launch_bounds__(WL_BS) void scc_trim(SccCtl *ctl, int s, int phase,
       settled++;
     }
   }
-  scc_block_part(part, looked, settled, 0u);   // (thread 0 alone read the phase-0 word, and it alone replaces it)
+  wl_block_part(part, looked, settled);   // (thread 0 alone read the phase-0 word, and it alone replaces it)
 }
 
 // The pivot round's candidate of every workgroup: the live vertex with the largest (in-list length) x (out-list length)
@@ -295,10 +279,10 @@ __global__ __launch_bounds__(WL_BS) void scc_propagate(SccCtl *ctl, int s, SccGr
       [&](int32_t j, uint32_t c) {
         const int32_t r = G.out_row[j];
         if (comp[r] != -1 || colour[r] >= c) return;   // (a stale colour is a smaller one: this never skips a raise)
-        if (scc_umax(&colour[r], c) < c && scc_umax(&stamp[r], tag) < tag)
+        if (wl_umax(&colour[r], c) < c && wl_umax(&stamp[r], tag) < tag)
           scc_file(ctl, G, L, q, wl_append_here(&ctl->n[q]), (uint32_t)r);
       });
-  scc_block_part(part, looked, 0u, 0u);
+  wl_block_part(part, looked, 0u);
 }
 
 // A claim sweep.  Sweep 0 claims the roots; later sweeps walk the in-lists of what the sweep before claimed.
@@ -340,7 +324,7 @@ __global__ __launch_bounds__(WL_BS) void scc_claim(SccCtl *ctl, int s, SccGraph 
           top = max(top, (uint32_t)c + 1u);
         });
   }
-  scc_block_part(part, looked, claimed, top);
+  wl_block_part<WlSum, WlMax>(part, looked, claimed, top);
 }
 
 // Closes the pivot round: what it claimed (live, colour 2) gets the largest claimed index as its label.
@@ -351,7 +335,7 @@ __global__ __launch_bounds__(WL_BS) void scc_label(const SccCtl *ctl, int s, int
   uint32_t n = 0;
   for (int64_t v = (int64_t)blockIdx.x * WL_BS + threadIdx.x; v < rows; v += (int64_t)gridDim.x * WL_BS)
     if (comp[v] == -1 && colour[v] == 2u) { comp[v] = label; n++; }
-  scc_block_part(part, 0u, n, 0u);
+  wl_block_part(part, 0u, n);
 }
 
 // What follows a round that left live vertices behind: a trim round after a pivot or colouring round (when the caller
@@ -368,11 +352,7 @@ __device__ __forceinline__ void scc_next_round(SccCtl *ctl, bool after_trim) {
 // they retire about 6 ns apart, see frontier_detect) and its first lane moves the state machine.
 __global__ __launch_bounds__(WL_BS) void scc_decide(SccCtl *ctl, int k, int s, int nparts, const WlPart *__restrict__ part, int32_t rows,
                                                      int32_t trim, int32_t pivot) {
-  __shared__ int32_t s_go;
-  __shared__ uint32_t s_a[WL_BS / 64], s_b[WL_BS / 64], s_c[WL_BS / 64];
-  if (threadIdx.x == 0) s_go = (s < 0 || ctl->step == s) ? 1 : 0;
-  __syncthreads();
-  if (!s_go) return;
+  if (!wl_from_thread0(s < 0 || ctl->step == s)) return;
   if (s < 0) {
     if (threadIdx.x != 0) return;
     ctl->rows = (uint32_t)rows; ctl->opt_trim = trim; ctl->opt_pivot = pivot;
@@ -380,15 +360,9 @@ __global__ __launch_bounds__(WL_BS) void scc_decide(SccCtl *ctl, int k, int s, i
     ctl->step = 0;
     return;
   }
-  uint32_t a = 0, b = 0, c = 0;
-  for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) { a += part[i].a; b += part[i].b; c = max(c, part[i].c); }
-  a = wl_wave_sum(a);
-  b = wl_wave_sum(b);
-  for (int o = 32; o > 0; o >>= 1) c = max(c, (uint32_t)__shfl_xor((int)c, o));
-  if (wl_lane() == 0) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; s_c[threadIdx.x >> 6] = c; }
-  __syncthreads();
+  const WlPart sums = wl_sum_parts<WlSum, WlMax>(part, nparts);
   if (threadIdx.x != 0) return;
-  for (int w = 1; w < WL_BS / 64; w++) { a += s_a[w]; b += s_b[w]; c = max(c, s_c[w]); }
+  const uint32_t a = sums.a, b = sums.b, c = sums.c;
   const int ph = ctl->phase, p = ctl->cur, kind = ctl->kind;
   uint32_t settled = 0, edges = 0;
   bool round_end = false;

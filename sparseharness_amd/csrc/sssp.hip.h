@@ -66,12 +66,6 @@ struct SsspCtl {
   SsspRec rec[SSSP_BATCH];
 };
 
-__device__ __forceinline__ uint32_t sssp_umin(uint32_t *p, uint32_t v) {
-  return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t sssp_umax(uint32_t *p, uint32_t v) {
-  return __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // d0 = min(|x0|, FLT_MAX): what the first launch of sh_iterate makes of an infinite start
 __device__ __forceinline__ uint32_t sssp_start_bits(uint32_t x) { return min(x & 0x7FFFFFFFu, SSSP_FLT_MAX); }
 
@@ -80,7 +74,9 @@ struct SsspKeep {   // wl_edge_flag: an entry is an edge when |a| is finite (and
 };
 
 // ---- building the handle (once): what worklist.hip.h does not have
-// sum[b] = the sum of the weights workgroup b strides over, in double (the host adds the partials: the default delta)
+// sum[b] = the sum of the weights workgroup b strides over, in double (the host adds the partials: the default delta).
+// Not wl_block_fold, and its tree is not to be touched: doubles added in another order differ in their last bits, and
+// with them the default delta and the round counts that depend on it.
 __global__ __launch_bounds__(WL_BS) void sssp_weight_sum(const uint32_t *__restrict__ w, int64_t edges, double *__restrict__ sum) {
   __shared__ double s_sum[WL_BS];
   double acc = 0.0;
@@ -123,14 +119,8 @@ __device__ __forceinline__ void sssp_split_min(const SsspCtl *ctl, const uint32_
     const uint32_t v = far[i];
     if (stamp[v] == SSSP_FAR) m = min(m, dist[v]);
   }
-  m = wl_wave_min(m);
-  __shared__ uint32_t s_m[WL_BS / 64];
-  if (wl_lane() == 0) s_m[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < WL_BS / 64; w++) m = min(m, s_m[w]);
-    pmin[blockIdx.x] = m;
-  }
+  m = wl_block_fold<WlMin>(m);
+  if (threadIdx.x == 0) pmin[blockIdx.x] = m;
 }
 
 // The end of the bucket that holds distance m, as the bits of the smallest float that is not below it.  It is above m
@@ -153,14 +143,9 @@ __device__ __forceinline__ void sssp_split_move(SsspCtl *ctl, int R, int nparts,
                                                 const int32_t *__restrict__ out_ptr, uint32_t *__restrict__ far0,
                                                 uint32_t *__restrict__ far1, uint32_t *__restrict__ near,
                                                 WlPiece *__restrict__ pl) {
-  __shared__ uint32_t s_m[WL_BS / 64];
   uint32_t m = 0xFFFFFFFFu;
   for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) m = min(m, pmin[i]);
-  m = wl_wave_min(m);
-  if (wl_lane() == 0) s_m[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = s_m[0];
-  for (int w = 1; w < WL_BS / 64; w++) m = min(m, s_m[w]);
+  m = wl_block_fold<WlMin>(m);
   const uint32_t thr = m == 0xFFFFFFFFu ? ctl->thr : sssp_bucket_end(m, delta);
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl->thr_new = thr;   // (read by sssp_relax and sssp_decide, not in this launch)
   const int f = ctl->fsel, p = R & 1, lane = wl_lane();
@@ -203,14 +188,14 @@ __device__ __forceinline__ uint32_t sssp_try(SsspCtl *ctl, int q, int f, int32_t
                                              uint32_t *__restrict__ near_next, WlPiece *__restrict__ pl_next,
                                              uint32_t *__restrict__ far) {
   if (nd >= dist[r]) return 0;   // (a stale word is a larger one: dist only falls, so this never skips an improvement)
-  const uint32_t old = sssp_umin(&dist[r], nd);
+  const uint32_t old = wl_umin(&dist[r], nd);
   if (old <= nd) return 0;
   if (nd < thr) {
-    if (sssp_umax(&stamp[r], tag) < tag) {
+    if (wl_umax(&stamp[r], tag) < tag) {
       near_next[wl_append_here(&ctl->ncount[q])] = (uint32_t)r;
       wl_push_pieces<SSSP_OUT_PIECE>(&ctl->npieces[q], (uint32_t)r, (uint32_t)(out_ptr[r + 1] - out_ptr[r]), pl_next);
     }
-  } else if (sssp_umax(&stamp[r], SSSP_FAR) == 0u) {
+  } else if (wl_umax(&stamp[r], SSSP_FAR) == 0u) {
     far[wl_append_here(&ctl->fcount[f])] = (uint32_t)r;
   }
   return old == SSSP_FLT_MAX ? 1u : 0u;
@@ -243,10 +228,7 @@ __global__ __launch_bounds__(WL_BS) void sssp_relax(SsspCtl *ctl, int R, uint32_
 // Closes round R (slot k of the batch); R = -1 closes sssp_init.  One workgroup sums the WlParts (no atomics on one
 // word: they retire about 6 ns apart, see frontier_detect) and its first lane turns the page.
 __global__ __launch_bounds__(WL_BS) void sssp_decide(SsspCtl *ctl, int k, int R, int nparts, const WlPart *__restrict__ part) {
-  __shared__ int32_t s_go;
-  if (threadIdx.x == 0) s_go = (R < 0 || ctl->round == R) ? 1 : 0;
-  __syncthreads();
-  if (!s_go) return;
+  if (!wl_from_thread0(R < 0 || ctl->round == R)) return;
   if (R < 0) {
     if (threadIdx.x != 0) return;
     const uint32_t nsrc = ctl->fcount[0];
@@ -257,8 +239,9 @@ __global__ __launch_bounds__(WL_BS) void sssp_decide(SsspCtl *ctl, int k, int R,
     ctl->need_split = nsrc == 0 ? 0 : 1;
     return;
   }
-  uint32_t a = 0, b = 0;
-  if (!wl_sum_parts(part, nparts, &a, &b)) return;
+  const WlPart sums = wl_sum_parts(part, nparts);
+  if (threadIdx.x != 0) return;
+  const uint32_t a = sums.a, b = sums.b;
   const int p = R & 1, split = ctl->need_split;
   if (split) {   // the far list the split consumed is empty now; its survivors and this round's arrivals are in the other
     ctl->fcount[ctl->fsel] = 0;

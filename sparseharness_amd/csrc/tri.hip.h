@@ -77,24 +77,6 @@ __device__ __forceinline__ bool tri_find(P s, uint32_t n, int32_t c, uint32_t *l
   *looked += seen;
   return hit;
 }
-// The workgroup's two sums -> thread 0, and only for it the answer is true (convergent control flow only).
-__device__ __forceinline__ bool tri_block_sums(uint64_t *hits, uint64_t *probes) {
-  __shared__ uint64_t s_h[WL_BS], s_p[WL_BS];
-  s_h[threadIdx.x] = *hits; s_p[threadIdx.x] = *probes;
-  __syncthreads();
-  for (int o = WL_BS / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { s_h[threadIdx.x] += s_h[threadIdx.x + o]; s_p[threadIdx.x] += s_p[threadIdx.x + o]; }
-    __syncthreads();
-  }
-  *hits = s_h[0]; *probes = s_p[0];
-  return threadIdx.x == 0;
-}
-// The lanes of a wave meet, and what they stored to the wave's LDS before is what they load after.
-__device__ __forceinline__ void tri_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // The wave streams N+(b) = col[sb, sb + lb) and bisects every entry into the n staged entries of s -> the hits, the
 // same number in every lane.
@@ -156,7 +138,7 @@ __global__ __launch_bounds__(WL_BS) void tri_count_light(TriGraph G, uint64_t *t
       m &= m - 1;
       const int32_t sa = __shfl(s, src), na = __shfl(n, src);
       for (int32_t i = lane; i < na; i += 64) mine[i] = col[sa + i];
-      tri_wave_sync();
+      wl_wave_sync();
       uint32_t looked = 0;
       uint64_t ha = 0;
       for (int32_t i = 0; i < na; i++) {
@@ -166,7 +148,7 @@ __global__ __launch_bounds__(WL_BS) void tri_count_light(TriGraph G, uint64_t *t
         if (PER_VERTEX && hb && lane == 0) tri_add(tri, b, hb);
         ha += hb;
       }
-      tri_wave_sync();   // (before the next list overwrites the staged one)
+      wl_wave_sync();   // (before the next list overwrites the staged one)
       probes += looked;
       if (lane == 0) {
         if (PER_VERTEX && ha) tri_add(tri, (int32_t)(base + src), ha);
@@ -174,7 +156,9 @@ __global__ __launch_bounds__(WL_BS) void tri_count_light(TriGraph G, uint64_t *t
       }
     }
   }
-  if (tri_block_sums(&hits, &probes)) part[blockIdx.x] = TriPart{hits, probes};
+  hits = wl_block_fold<WlSum>(hits);
+  probes = wl_block_fold<WlSum>(probes);
+  if (threadIdx.x == 0) part[blockIdx.x] = TriPart{hits, probes};
 }
 
 // The workgroup class.  The rows are dealt to the workgroups in runs of TRI_DEAL (neighbouring hubs go to different
@@ -224,14 +208,18 @@ __global__ __launch_bounds__(WL_BS) void tri_count_heavy(TriGraph G, uint64_t *t
     }
     __syncthreads();   // (s_todo and s_ntodo are done with)
   }
-  if (tri_block_sums(&hits, &probes)) part[blockIdx.x] = TriPart{hits, probes};
+  hits = wl_block_fold<WlSum>(hits);
+  probes = wl_block_fold<WlSum>(probes);
+  if (threadIdx.x == 0) part[blockIdx.x] = TriPart{hits, probes};
 }
 
 // Closes the call: one workgroup sums the TriParts of the two counting launches.
 __global__ __launch_bounds__(WL_BS) void tri_finish(TriCtl *ctl, int nparts, const TriPart *__restrict__ part) {
   uint64_t hits = 0, probes = 0;
   for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) { hits += part[i].hits; probes += part[i].probes; }
-  if (tri_block_sums(&hits, &probes)) { ctl->triangles = hits; ctl->probes = probes; }
+  hits = wl_block_fold<WlSum>(hits);
+  probes = wl_block_fold<WlSum>(probes);
+  if (threadIdx.x == 0) { ctl->triangles = hits; ctl->probes = probes; }
 }
 
 } // namespace sh

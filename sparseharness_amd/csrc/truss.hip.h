@@ -85,7 +85,7 @@
 // hubs costs its shorter list, bisected entry by entry into the longer, in the support pass and once more in the round
 // in which it is current, by one workgroup.  A clique of n vertices costs n^3 / 2 bisections in the support pass.
 #pragma once
-#include "core.hip.h"
+#include "worklist.hip.h"
 
 namespace sh {
 
@@ -95,6 +95,7 @@ constexpr int TRUSS_BATCH = 32;            // rounds enqueued ahead of the host 
 constexpr int TRUSS_MAX_BLOCKS = 1024;     // workgroups of a launch at most
 constexpr int TRUSS_CTL_BYTES = 2048;      // device bytes set aside for TrussCtl
 constexpr int TRUSS_PART_BYTES = 16 * TRUSS_MAX_BLOCKS;
+constexpr uint32_t TRUSS_NONE = 0xFFFFFFFFu;   // no unsettled edge seen (a support is below 2^31)
 
 struct TrussRec {   // what round k of a batch did (read back by the host once per batch)
   int32_t ran, k;
@@ -116,7 +117,7 @@ struct TrussCtl {
   TrussRec rec[TRUSS_BATCH];
 };
 // Per workgroup: truss_support: a = its sum of supports; truss_peel: a = its sum of min(deg u, deg v).  (truss_min's
-// words are WlParts: a = the smallest remaining support among the workgroup's unsettled edges, CORE_NONE if none.)
+// words are WlParts: a = the smallest remaining support among the workgroup's unsettled edges, TRUSS_NONE if none.)
 struct TrussPart { uint64_t a, pad; };
 
 struct TrussGraph {   // the handle's lists and edges, as a kernel argument
@@ -124,8 +125,6 @@ struct TrussGraph {   // the handle's lists and edges, as a kernel argument
   const int32_t *ptr, *col, *eid, *eu, *ev;
 };
 struct TrussLists { uint32_t *list[2]; };   // M places each
-
-__device__ __forceinline__ int32_t truss_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // Edge e as a work item: a = the end with the shorter list (u on a tie), b the other, [sa, sa + la) a's list.
 struct TrussItem { int32_t a, b, sa, la; };
@@ -143,36 +142,6 @@ __device__ __forceinline__ int32_t truss_find(const TrussGraph &G, int32_t b, in
     if (G.col[mid] < w) lo = mid + 1; else hi = mid;
   }
   return (lo < end && G.col[lo] == w) ? lo : -1;
-}
-__device__ __forceinline__ uint64_t truss_wave_sum64(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
-  return v;
-}
-// The workgroup's sum -> its TrussPart (convergent control flow only).
-__device__ __forceinline__ void truss_block_part(TrussPart *__restrict__ part, uint64_t a) {
-  __shared__ uint64_t s_a[WL_BS / 64];
-  a = truss_wave_sum64(a);
-  if (wl_lane() == 0) s_a[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t t = 0;
-    for (int w = 0; w < WL_BS / 64; w++) t += s_a[w];
-    part[blockIdx.x] = TrussPart{t, 0ull};
-  }
-}
-// The sum of a launch's TrussParts, by one workgroup (convergent control flow only): thread 0 gets it, and only for it
-// the answer is true.
-__device__ __forceinline__ bool truss_sum_parts(const TrussPart *__restrict__ part, int nparts, uint64_t *a) {
-  __shared__ uint64_t s_t[WL_BS];
-  uint64_t t = 0;
-  for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) t += part[i].a;
-  s_t[threadIdx.x] = t;
-  __syncthreads();
-  if (threadIdx.x != 0) return false;
-  t = 0;
-  for (int i = 0; i < WL_BS; i++) t += s_t[i];
-  *a = t;
-  return true;
 }
 
 // The walk: items [0, n) through item(i) (an edge id, or -1 for a place that holds none; an item whose shorter list is
@@ -250,12 +219,15 @@ __global__ __launch_bounds__(WL_BS) void truss_support(const TrussCtl *ctl, Trus
                if (!shared) sup[e] = (int32_t)cnt;
                else if (cnt) (void)__hip_atomic_fetch_add(&sup[e], (int32_t)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
              });
-  truss_block_part(part, total);
+  total = wl_block_fold<WlSum>(total);
+  if (threadIdx.x == 0) part[blockIdx.x] = TrussPart{total, 0ull};
 }
 
 __global__ __launch_bounds__(WL_BS) void truss_total(TrussCtl *ctl, int nparts, const TrussPart *__restrict__ part) {
   uint64_t hits = 0;
-  if (truss_sum_parts(part, nparts, &hits)) ctl->hits = hits;
+  for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) hits += part[i].a;
+  hits = wl_block_fold<WlSum>(hits);
+  if (threadIdx.x == 0) ctl->hits = hits;
 }
 
 // Opening round `step`, first pass: the smallest remaining support among the unsettled (with an empty list: those of
@@ -263,10 +235,10 @@ __global__ __launch_bounds__(WL_BS) void truss_total(TrussCtl *ctl, int nparts, 
 __global__ __launch_bounds__(WL_BS) void truss_min(const TrussCtl *ctl, int step, int32_t edges, const int32_t *__restrict__ sup,
                                                     const int32_t *__restrict__ stamp, WlPart *__restrict__ mins) {
   if (ctl->step != step || !ctl->opening) return;
-  uint32_t best = CORE_NONE;
+  uint32_t best = TRUSS_NONE;
   for (int64_t e = (int64_t)blockIdx.x * WL_BS + threadIdx.x; e < edges; e += (int64_t)gridDim.x * WL_BS)
     if (stamp[e] == 0) best = min(best, (uint32_t)sup[e]);
-  best = core_block_min(best);
+  best = wl_block_fold<WlMin>(best);
   if (threadIdx.x == 0) mins[blockIdx.x] = WlPart{best, 0u, 0u, 0u};
 }
 
@@ -274,9 +246,9 @@ __global__ __launch_bounds__(WL_BS) void truss_min(const TrussCtl *ctl, int step
 __global__ __launch_bounds__(WL_BS) void truss_open(TrussCtl *ctl, int step, TrussGraph G, const int32_t *__restrict__ sup,
                                                      int32_t *__restrict__ stamp, const WlPart *__restrict__ mins, TrussLists L) {
   if (ctl->step != step || !ctl->opening) return;
-  uint32_t m = CORE_NONE;
+  uint32_t m = TRUSS_NONE;
   for (int i = (int)threadIdx.x; i < (int)gridDim.x; i += WL_BS) m = min(m, mins[i].a);
-  const int32_t s = (int32_t)core_block_min(m);
+  const int32_t s = (int32_t)wl_block_fold<WlMin>(m);
   const int p = ctl->p;
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl->s = s;   // (no workgroup of this launch reads it)
   uint32_t *__restrict__ list = L.list[p];
@@ -307,7 +279,7 @@ __global__ __launch_bounds__(WL_BS) void truss_peel(TrussCtl *ctl, int step, Tru
   uint32_t *__restrict__ nfar = next + (G.edges - 1);
   uint64_t walked = 0;
   const auto dec = [&](int32_t x) {
-    if (truss_load(&sup[x]) <= s) return;   // listed or owned
+    if (wl_load(&sup[x]) <= s) return;   // listed or owned
     const int32_t old = __hip_atomic_fetch_add(&sup[x], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (old == s + 1) {   // this lane owns x
       __hip_atomic_store(&stamp[x], r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -321,12 +293,12 @@ __global__ __launch_bounds__(WL_BS) void truss_peel(TrussCtl *ctl, int step, Tru
              [&](int32_t e, int32_t la) { truss[e] = s + 2; walked += (uint64_t)la; },
              [&](int32_t e, int32_t b, int32_t j) {
                const int32_t e1 = G.eid[j];
-               const int32_t st1 = truss_load(&stamp[e1]);
+               const int32_t st1 = wl_load(&stamp[e1]);
                if (st1 > 0 && st1 < r) return 0u;   // gone (no bisection for it)
                const int32_t j2 = truss_find(G, b, G.col[j]);
                if (j2 < 0) return 0u;
                const int32_t e2 = G.eid[j2];
-               const int32_t st2 = truss_load(&stamp[e2]);
+               const int32_t st2 = wl_load(&stamp[e2]);
                if (st2 > 0 && st2 < r) return 0u;
                const bool c1 = st1 == r, c2 = st2 == r;
                if (!c1 && (!c2 || e < e2)) dec(e1);
@@ -334,18 +306,18 @@ __global__ __launch_bounds__(WL_BS) void truss_peel(TrussCtl *ctl, int step, Tru
                return 0u;
              },
              [](int32_t, uint32_t, bool) {});
-  truss_block_part(part, walked);
+  walked = wl_block_fold<WlSum>(walked);
+  if (threadIdx.x == 0) part[blockIdx.x] = TrussPart{walked, 0ull};
 }
 
 // Closes round `step` (slot r of the batch).  One workgroup sums the TrussParts (no atomics on one word) and its first
 // lane records the round and decides.
 __global__ __launch_bounds__(WL_BS) void truss_close(TrussCtl *ctl, int r, int step, int nparts, const TrussPart *__restrict__ part) {
-  __shared__ int32_t s_go;
-  if (threadIdx.x == 0) s_go = ctl->step == step ? 1 : 0;
-  __syncthreads();
-  if (!s_go) return;
+  if (!wl_from_thread0(ctl->step == step)) return;
   uint64_t walked = 0;
-  if (!truss_sum_parts(part, nparts, &walked)) return;
+  for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) walked += part[i].a;
+  walked = wl_block_fold<WlSum>(walked);
+  if (threadIdx.x != 0) return;
   const int p = ctl->p;
   const uint32_t size = ctl->n[p] + ctl->nl[p];
   ctl->rec[r] = TrussRec{1, ctl->s + 2, size, 0u, walked};

@@ -107,21 +107,6 @@ __device__ __forceinline__ int wcc_hook(uint32_t *p, uint32_t u, uint32_t w) {
   return a == b ? 0 : 2;
 }
 
-// The workgroup's three sums -> its WlPart (convergent control flow only).
-__device__ __forceinline__ void wcc_block_part(WlPart *__restrict__ part, uint32_t a, uint32_t b, uint32_t c) {
-  __shared__ uint32_t s_a[WL_BS / 64], s_b[WL_BS / 64], s_c[WL_BS / 64];
-  a = wl_wave_sum(a);
-  b = wl_wave_sum(b);
-  c = wl_wave_sum(c);
-  if (wl_lane() == 0) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; s_c[threadIdx.x >> 6] = c; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t ta = 0, tb = 0, tc = 0;
-    for (int w = 0; w < WL_BS / 64; w++) { ta += s_a[w]; tb += s_b[w]; tc += s_c[w]; }
-    part[blockIdx.x] = WlPart{ta, tb, tc, 0u};
-  }
-}
-
 // p[v] = v for every row; the caller's setting into the control block (which the host has zeroed: step = 0)
 __global__ __launch_bounds__(WL_BS) void wcc_init(WccCtl *ctl, int32_t rows, int32_t sample, uint32_t *__restrict__ p) {
   for (int64_t v = (int64_t)blockIdx.x * WL_BS + threadIdx.x; v < rows; v += (int64_t)gridDim.x * WL_BS) p[v] = (uint32_t)v;
@@ -138,7 +123,7 @@ __global__ __launch_bounds__(WL_BS) void wcc_sample(const WccCtl *ctl, int s, Wc
     const int r = wcc_hook(p, (uint32_t)G.in_col[b + s], (uint32_t)v);
     looked++; hooks += r == 1; open += r != 0;
   }
-  wcc_block_part(part, looked, hooks, open);
+  wl_block_part<WlSum, WlSum>(part, looked, hooks, open);
 }
 
 // L = the most frequent parent among the WCC_PICKS vertices i * rows / WCC_PICKS, ties to the larger index -> every
@@ -147,7 +132,6 @@ __global__ __launch_bounds__(WL_BS) void wcc_sample(const WccCtl *ctl, int s, Wc
 __device__ __forceinline__ uint32_t wcc_pick(const uint32_t *__restrict__ p, int32_t rows) {
   constexpr int SLOTS = 2 * WCC_PICKS;
   __shared__ uint32_t s_key[SLOTS], s_cnt[SLOTS];
-  __shared__ uint32_t s_best_n[WL_BS / 64], s_best_v[WL_BS / 64];
   for (int i = (int)threadIdx.x; i < SLOTS; i += WL_BS) { s_key[i] = WCC_NONE; s_cnt[i] = 0u; }
   __syncthreads();
   for (int i = (int)threadIdx.x; i < WCC_PICKS; i += WL_BS) {
@@ -160,20 +144,10 @@ __device__ __forceinline__ uint32_t wcc_pick(const uint32_t *__restrict__ p, int
     }
   }
   __syncthreads();
-  uint32_t bn = 0, bv = 0;   // (the count, the vertex): the larger count, ties to the larger vertex
-  const auto better = [](uint32_t n, uint32_t v, uint32_t bn, uint32_t bv) { return n > bn || (n == bn && v > bv); };
+  uint64_t best = 0;   // count << 32 | vertex: the larger count, ties to the larger vertex, is the larger word
   for (int i = (int)threadIdx.x; i < SLOTS; i += WL_BS)
-    if (s_key[i] != WCC_NONE && better(s_cnt[i], s_key[i], bn, bv)) { bn = s_cnt[i]; bv = s_key[i]; }
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t on = (uint32_t)__shfl_xor((int)bn, o), ov = (uint32_t)__shfl_xor((int)bv, o);
-    if (better(on, ov, bn, bv)) { bn = on; bv = ov; }
-  }
-  if (wl_lane() == 0) { s_best_n[threadIdx.x >> 6] = bn; s_best_v[threadIdx.x >> 6] = bv; }
-  __syncthreads();
-  bn = s_best_n[0]; bv = s_best_v[0];
-  for (int w = 1; w < WL_BS / 64; w++)
-    if (better(s_best_n[w], s_best_v[w], bn, bv)) { bn = s_best_n[w]; bv = s_best_v[w]; }
-  return bv;
+    if (s_key[i] != WCC_NONE) best = max(best, ((uint64_t)s_cnt[i] << 32) | (uint64_t)s_key[i]);
+  return (uint32_t)wl_block_fold<WlMax>(best);
 }
 
 // Round `sample`, before its walk: the pick (every workgroup by itself: it waits for nobody) and the work list.
@@ -207,55 +181,24 @@ __global__ __launch_bounds__(WL_BS) void wcc_full(const WccCtl *ctl, int s, WccG
                                                     [&](int32_t j, uint32_t v) { tally(wcc_hook(p, (uint32_t)G.in_col[j], v)); });
   looked += wl_expand<WCC_SHORT, WCC_PIECE>(list, n, opieces, ctl->nop, G.out_ptr, self,
                                             [&](int32_t j, uint32_t v) { tally(wcc_hook(p, v, (uint32_t)G.out_row[j])); });
-  wcc_block_part(part, looked, hooks, open);
+  wl_block_part<WlSum, WlSum>(part, looked, hooks, open);
 }
 
-// Jumping launch i of round s, over all rows: p[v] = p[p[v]] until p[v] is a root as this lane sees it, WCC_JUMPS times
-// at most.  No hook runs beside it, so p[v] is written by the lane of v alone; what it reads of others is a pointer
-// they hold now or held before, an ancestor either way.
+// Jumping launch i of round s, over all rows: wl_jump, WCC_JUMPS jumps per vertex at most.
 __global__ __launch_bounds__(WL_BS) void wcc_jump(WccCtl *ctl, int s, int i, int32_t rows, uint32_t *p, WlPart *__restrict__ jpart) {
   if (ctl->step != s || (i > 0 && !ctl->moved[i - 1])) return;
-  uint32_t moved = 0;
-  for (int64_t v = (int64_t)blockIdx.x * WL_BS + threadIdx.x; v < rows; v += (int64_t)gridDim.x * WL_BS) {
-    uint32_t q = p[v];
-    for (int h = 0; h < WCC_JUMPS; h++) {
-      const uint32_t up = p[q];
-      if (up == q) break;
-      p[v] = q = up;
-      moved++;
-    }
-  }
-  __shared__ uint32_t s_m[WL_BS / 64];
-  moved = wl_wave_sum(moved);
-  if (wl_lane() == 0) s_m[threadIdx.x >> 6] = moved;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < WL_BS / 64; w++) t += s_m[w];
-    jpart[blockIdx.x].a = i == 0 ? t : jpart[blockIdx.x].a + t;   // (this thread alone, launch after launch)
-    if (t) ctl->moved[i] = 1u;                                  // (whoever stores it stores the same word)
-  }
+  wl_jump(i, WCC_JUMPS, rows, p, jpart, ctl->moved);
 }
 
 // Closes round s (slot k of the batch).  One workgroup sums the WlParts (no atomics on one word: they retire about 6 ns
 // apart, see frontier_detect) and its first lane records the round and decides.
 __global__ __launch_bounds__(WL_BS) void wcc_decide(WccCtl *ctl, int k, int s, int nparts, const WlPart *__restrict__ part,
                                                      const WlPart *__restrict__ jpart) {
-  __shared__ int32_t s_go;
-  __shared__ uint32_t s_sum[4][WL_BS / 64];
-  if (threadIdx.x == 0) s_go = ctl->step == s ? 1 : 0;
-  __syncthreads();
-  if (!s_go) return;
+  if (!wl_from_thread0(ctl->step == s)) return;
   uint32_t t[4] = {0u, 0u, 0u, 0u};   // entries looked at, hooks, entries left unsettled, pointers changed
   for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) { t[0] += part[i].a; t[1] += part[i].b; t[2] += part[i].c; t[3] += jpart[i].a; }
-  for (int f = 0; f < 4; f++) {
-    t[f] = wl_wave_sum(t[f]);
-    if (wl_lane() == 0) s_sum[f][threadIdx.x >> 6] = t[f];
-  }
-  __syncthreads();
+  for (int f = 0; f < 4; f++) t[f] = wl_block_fold<WlSum>(t[f]);
   if (threadIdx.x != 0) return;
-  for (int f = 0; f < 4; f++)
-    for (int w = 1; w < WL_BS / 64; w++) t[f] += s_sum[f][w];
   const bool full = s >= ctl->sample;
   if (s == ctl->sample) ctl->skipped = ctl->rows - ctl->n;
   ctl->rec[k] = WccRec{1, full ? WCC_KIND_FULL : WCC_KIND_SAMPLE, t[1], t[3], t[0]};
@@ -274,15 +217,8 @@ __global__ __launch_bounds__(WL_BS) void wcc_label(WccCtl *ctl, int32_t rows, in
     comp[v] = complete ? (int32_t)up : -1;
     roots += (complete && up == (uint32_t)v) ? 1u : 0u;
   }
-  __shared__ uint32_t s_r[WL_BS / 64];
-  roots = wl_wave_sum(roots);
-  if (wl_lane() == 0) s_r[threadIdx.x >> 6] = roots;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < WL_BS / 64; w++) t += s_r[w];
-    if (t) wl_add(&ctl->components, t);   // (one add per workgroup)
-  }
+  roots = wl_block_fold<WlSum>(roots);
+  if (threadIdx.x == 0 && roots) wl_add(&ctl->components, roots);   // (one add per workgroup)
 }
 
 } // namespace sh

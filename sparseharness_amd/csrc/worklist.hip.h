@@ -1,5 +1,13 @@
 // worklist.hip.h -- what the worklist algorithms share (frontier.hip.h, bfs.hip.h, sssp.hip.h, ..., core.hip.h, truss.hip.h): list cursors, the cutting
-// of long lists into pieces, per-workgroup sums, the two traversal skeletons and the kernels that build a graph handle.
+// of long lists into pieces, the folds (over a wave, over a workgroup, over a launch's per-workgroup parts), the gate of a
+// closing kernel, the jump pass, the two traversal skeletons and the kernels that build a graph handle.
+//
+// Folds: wl_wave_fold<OP> and wl_block_fold<OP> with OP one of WlSum, WlMin, WlMax, on 32- and 64-bit unsigned words;
+// wl_block_part writes a workgroup's WlPart and wl_sum_parts folds a launch's.  An algorithm writes no fold of its own:
+// a part of another layout (TrussPart, TriPart, RcmFin) or two part arrays at once are a strided loop of the kernel's
+// and wl_block_fold per word.  What is not a fold stays with its kernel: scans and rankings (rcm_block_scan, rcm_tile,
+// frontier_detect), the arg-max over a pair that fits no word (scc_block_best), a semiring-typed wave reduction
+// (fr_wave_reduce) and the double sum of sssp_weight_sum, whose order of additions is part of its result.
 //
 // Work distribution: every kernel runs a fixed grid whose waves stride over a device-side list length (the host does
 // not know it).  A wave takes 64 list entries at a time: lists of up to SHORT entries one lane each, longer ones the
@@ -13,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 namespace sh {
 
@@ -50,13 +59,59 @@ __device__ __forceinline__ uint32_t wl_append_here(uint32_t *cursor) {
   if (lane == __ffsll((unsigned long long)here) - 1) first = wl_add(cursor, (uint32_t)__popcll(here));
   return (uint32_t)__builtin_amdgcn_readfirstlane((int)first) + (uint32_t)__popcll(here & ((1ull << lane) - 1ull));
 }
-__device__ __forceinline__ uint32_t wl_wave_sum(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+// Relaxed agent-scope one-liners: a load that goes to the L2, where the atomics meet, and the two unsigned atomics that
+// only ever move a word one way (-> the word as it was).
+template <class T>
+__device__ __forceinline__ T wl_load(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ uint32_t wl_umin(uint32_t *p, uint32_t v) {
+  return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ uint32_t wl_umax(uint32_t *p, uint32_t v) {
+  return __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The lanes of a wave meet, and what they stored to the wave's LDS words before is what they load after.
+__device__ __forceinline__ void wl_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- folds.  The operations are associative and commutative on integers: no result depends on who folds first.
+struct WlSum { template <class T> __device__ static T of(T a, T b) { return a + b; } };
+struct WlMin { template <class T> __device__ static T of(T a, T b) { return min(a, b); } };
+struct WlMax { template <class T> __device__ static T of(T a, T b) { return max(a, b); } };
+// The wave's word -> every lane (wave-uniform control flow only).
+template <class OP, class T>
+__device__ __forceinline__ T wl_wave_fold(T v) {
+  for (int o = 32; o > 0; o >>= 1) v = OP::of(v, (T)__shfl_xor(v, o));
   return v;
 }
-__device__ __forceinline__ uint32_t wl_wave_min(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+__device__ __forceinline__ uint32_t wl_wave_sum(uint32_t v) { return wl_wave_fold<WlSum>(v); }
+__device__ __forceinline__ uint32_t wl_wave_min(uint32_t v) { return wl_wave_fold<WlMin>(v); }
+// The workgroup's word -> EVERY thread: shuffles inside a wave, one LDS word per wave.  CONVERGENT CONTROL FLOW ONLY:
+// every thread of the workgroup calls it, all of them together (it holds barriers).  A kernel may call it as often as it
+// likes: the array below is one array however often this is inlined, so the first barrier keeps a call from writing
+// the words that a thread is still reading for the call before.
+template <class OP, class T>
+__device__ __forceinline__ T wl_block_fold(T v) {
+  __shared__ T s_w[WL_BS / 64];
+  v = wl_wave_fold<OP>(v);
+  __syncthreads();
+  if (wl_lane() == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = s_w[0];
+  for (int w = 1; w < WL_BS / 64; w++) v = OP::of(v, s_w[w]);
   return v;
+}
+// A word of thread 0 -> every thread of the workgroup (one LDS word, one barrier; convergent control flow only, and once
+// per kernel: nothing keeps a second call from overwriting the word under a late reader).  THE GATE OF A CLOSING KERNEL,
+// `if (!wl_from_thread0(ctl->step == s)) return;`, needs it: thread 0 stores the next step further down, so a wave that
+// read the step for itself, late, could leave before a barrier at which its siblings wait.
+__device__ __forceinline__ uint32_t wl_from_thread0(uint32_t v) {
+  __shared__ uint32_t s_v;
+  if (threadIdx.x == 0) s_v = v;
+  __syncthreads();
+  return s_v;
 }
 // The pieces of a list of `len` entries join piece list `list` (nothing when it is no longer than PIECE).  A piece list
 // over lists that hold E entries in all needs E / (PIECE / 2) + 1 places: sum of ceil(len / PIECE) over len > PIECE.
@@ -68,32 +123,72 @@ __device__ __forceinline__ void wl_push_pieces(uint32_t *cursor, uint32_t id, ui
     for (uint32_t j = 0; j < np; j++) list[b + j] = WlPiece{id, j * PIECE};
   }
 }
-// The workgroup's sums -> its WlPart (convergent control flow only).
-__device__ __forceinline__ void wl_block_part(WlPart *__restrict__ part, uint32_t a, uint32_t b) {
-  __shared__ uint32_t s_a[WL_BS / 64], s_b[WL_BS / 64];
-  a = wl_wave_sum(a);
-  b = wl_wave_sum(b);
-  if (wl_lane() == 0) { s_a[threadIdx.x >> 6] = a; s_b[threadIdx.x >> 6] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t ta = 0, tb = 0;
-    for (int w = 0; w < WL_BS / 64; w++) { ta += s_a[w]; tb += s_b[w]; }
-    part[blockIdx.x] = WlPart{ta, tb, 0u, 0u};
+// The workgroup's WlPart -> EVERY thread: a is summed, b folded by OPB and c by OPC (WlSum or WlMax: 0 is the neutral
+// word of either; WlNone: the part has no c, the word stays 0).  CONVERGENT CONTROL FLOW ONLY, and ONE barrier for all
+// the words, none ahead of them: parts are written by every traversal launch and folded once per round, and a
+// round-heavy run is bound by just these latencies.  So, unlike wl_block_fold and like wl_from_thread0, ONCE PER KERNEL
+// (the words are its own, not wl_block_fold's): a kernel has one part to write, a closing kernel one array of them to
+// fold -- wl_block_part and wl_sum_parts are its only callers, and a kernel calls one of them on one path.
+struct WlNone {};
+template <class OPB, class OPC>
+__device__ __forceinline__ WlPart wl_block_fold_part(uint32_t a, uint32_t b, uint32_t c) {
+  constexpr bool HAS_C = !std::is_same<OPC, WlNone>::value;
+  __shared__ uint32_t s_w[HAS_C ? 3 : 2][WL_BS / 64];
+  const int wv = (int)(threadIdx.x >> 6);
+  a = wl_wave_fold<WlSum>(a);
+  b = wl_wave_fold<OPB>(b);
+  if constexpr (HAS_C) c = wl_wave_fold<OPC>(c);
+  if (wl_lane() == 0) {
+    s_w[0][wv] = a; s_w[1][wv] = b;
+    if constexpr (HAS_C) s_w[2][wv] = c;
   }
-}
-// The sums of a launch's WlParts, by one workgroup (convergent control flow only): thread 0 gets them, and only for it
-// the answer is true.
-__device__ __forceinline__ bool wl_sum_parts(const WlPart *__restrict__ part, int nparts, uint32_t *a, uint32_t *b) {
-  __shared__ uint32_t s_a[WL_BS], s_b[WL_BS];
-  uint32_t ta = 0, tb = 0;
-  for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) { ta += part[i].a; tb += part[i].b; }
-  s_a[threadIdx.x] = ta; s_b[threadIdx.x] = tb;
   __syncthreads();
-  if (threadIdx.x != 0) return false;
-  ta = 0; tb = 0;
-  for (int i = 0; i < WL_BS; i++) { ta += s_a[i]; tb += s_b[i]; }
-  *a = ta; *b = tb;
-  return true;
+  WlPart t{s_w[0][0], s_w[1][0], 0u, 0u};
+  if constexpr (HAS_C) t.c = s_w[2][0];
+  for (int w = 1; w < WL_BS / 64; w++) {
+    t.a += s_w[0][w]; t.b = OPB::of(t.b, s_w[1][w]);
+    if constexpr (HAS_C) t.c = OPC::of(t.c, s_w[2][w]);
+  }
+  return t;
+}
+// The workgroup's words -> its WlPart (once per kernel: it has one part).
+template <class OPB = WlSum, class OPC = WlNone>
+__device__ __forceinline__ void wl_block_part(WlPart *__restrict__ part, uint32_t a, uint32_t b, uint32_t c = 0u) {
+  const WlPart t = wl_block_fold_part<OPB, OPC>(a, b, c);
+  if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+// A launch's WlParts folded the same way, by one workgroup -> every thread (once per kernel).
+template <class OPB = WlSum, class OPC = WlNone>
+__device__ __forceinline__ WlPart wl_sum_parts(const WlPart *__restrict__ part, int nparts) {
+  uint32_t a = 0, b = 0, c = 0;
+  for (int i = (int)threadIdx.x; i < nparts; i += WL_BS) {
+    a += part[i].a; b = OPB::of(b, part[i].b);
+    if constexpr (!std::is_same<OPC, WlNone>::value) c = OPC::of(c, part[i].c);
+  }
+  return wl_block_fold_part<OPB, OPC>(a, b, c);
+}
+
+// The jump pass of a parent forest whose pointers only go towards the root (wcc.hip.h, msf.hip.h), launch i of a
+// round's sweeps, over all rows: p[v] = p[p[v]] until p[v] is a root as this lane sees it, `jumps` times at most.  No
+// hook runs beside it, so p[v] is written by the lane of v alone; what it reads of others is a pointer they hold now
+// or held before, an ancestor either way.  The pointers the workgroup changed are added to jpart[].a (launch 0 of the
+// round stores), and moved[i] says whether anybody changed one (wl_block_fold's contract).
+__device__ __forceinline__ void wl_jump(int i, int jumps, int32_t rows, uint32_t *p, WlPart *__restrict__ jpart, uint32_t *moved_flags) {
+  uint32_t moved = 0;
+  for (int64_t v = (int64_t)blockIdx.x * WL_BS + threadIdx.x; v < rows; v += (int64_t)gridDim.x * WL_BS) {
+    uint32_t q = p[v];
+    for (int h = 0; h < jumps; h++) {
+      const uint32_t up = p[q];
+      if (up == q) break;
+      p[v] = q = up;
+      moved++;
+    }
+  }
+  moved = wl_block_fold<WlSum>(moved);
+  if (threadIdx.x == 0) {
+    jpart[blockIdx.x].a = i == 0 ? moved : jpart[blockIdx.x].a + moved;   // (this thread alone, launch after launch)
+    if (moved) moved_flags[i] = 1u;                                        // (whoever stores it stores the same word)
+  }
 }
 
 // The push traversal: for every v of list[0, n) the entries [ptr[v], ptr[v + 1]), lists above PIECE entries through
@@ -360,7 +455,7 @@ __global__ __launch_bounds__(WL_BS) void wl_max_len(const int32_t *__restrict__ 
   uint32_t best = 0;
   for (int64_t r = (int64_t)blockIdx.x * WL_BS + threadIdx.x; r < rows; r += (int64_t)gridDim.x * WL_BS)
     best = max(best, (uint32_t)(ptr[r + 1] - ptr[r]));
-  for (int o = 32; o > 0; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o));
+  best = wl_wave_fold<WlMax>(best);
   if (wl_lane() == 0 && best) (void)__hip_atomic_fetch_max(out, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 

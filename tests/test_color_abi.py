@@ -128,8 +128,13 @@ def test_resource_check_and_kernel_file():
                    "A LIST OF `rows` PLACES CANNOT OVERFLOW", "NO KERNEL EVER WAITS", "EVERY LOOP IS BOUNDED",
                    "NO RESTORE IS NEEDED", "ONLY THE FIRST WALK DECREMENTS", "Hasenplaugh"):
         assert phrase in code, phrase
-    for k in KERNELS + ("gcol_walk", "gcol_block_part", "gcol_mix32", "0x7feb352du", "0x846ca68bu"):
+    for k in KERNELS + ("gcol_walk", "gcol_mix32", "0x7feb352du", "0x846ca68bu"):
         assert k in code, k
+    # the sum and the largest colour go through the shared folds, and the header defines no workgroup fold of its own
+    for k in ("wl_block_part<WlMax>(part, looked, most)", "wl_sum_parts<WlMax>(part, nparts)", "wl_block_fold<WlMin>(best)"):
+        assert k in code, k
+    assert "__shfl_xor" not in code and "_block_part(WlPart" not in code
+    assert not re.search(r"__shared__[^;]*\[WL_BS(?: / 64)?\](?!\[)", code)   # (per-wave bitmaps are [WL_BS / 64][words])
     assert "asm" not in code.replace("amdgcn", "")   # plain C++ and builtins only
     assert "compare_exchange" not in code and "atomicCAS" not in code   # one decrement per preceding neighbour: no retry loop
     assert "wl_expand" not in code.split("#pragma once")[1]   # a sibling traversal, as truss_walk

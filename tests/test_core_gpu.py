@@ -115,8 +115,8 @@ def run(eng, mat, chase, with_deg=True, max_rounds=None, G=None):
             G.free()
 
 
-def check(eng, name, chase, mat=None):
-    w = want(name)
+def check(eng, name, chase, mat=None, w=None):
+    w = want(name) if w is None else w
     mat = matrix(name) if mat is None else mat
     n = mat[0]
     got = run(eng, mat, chase)

@@ -90,11 +90,11 @@ def matrix(name):
     return _cache[name]
 
 
-def want(name, heavy, seed, max_rounds=1 << 30):
+def want(name, heavy, seed, max_rounds=1 << 30, mat=None):
     """The reference's answer and records, computed once per pattern and order and left unchanged."""
     key = (name, heavy, seed, max_rounds)
     if key not in _want:
-        n, eu, ev, weight, keys = M.case(matrix(name), heavy, seed)
+        n, eu, ev, weight, keys = M.case(matrix(name) if mat is None else mat, heavy, seed)
         r = M.rounds(n, eu, ev, keys, max_rounds=max_rounds)
         r.update(eu=eu, ev=ev, weight=weight, keys=keys, M=len(eu))
         if r["complete"]:

@@ -127,9 +127,18 @@ def test_resource_check_and_kernel_file():
     for phrase in ("LABEL SPACE", "THE LEVEL FORM IS THE SERIAL FORM", "EVERY VERTEX GETS ONE POSITION", "NO KERNEL EVER WAITS",
                    "EVERY LOOP IS BOUNDED", "Cuthill, McKee", "George, Liu", "Worst cases"):
         assert phrase in " ".join(code.replace("//", " ").split()), phrase   # (a phrase may run over a comment's line break)
-    for k in KERNELS + ("struct RcmCtl", "RcmRec rec[RCM_BATCH]", "wl_append_here", "wl_block_part", "wl_sum_parts"):
+    for k in KERNELS + ("struct RcmCtl", "RcmRec rec[RCM_BATCH]", "wl_append_here"):
         assert k in code, k
     body = code.split("#pragma once")[1]
+    # the parts and the closing sums go through the shared folds, and the header defines no workgroup fold of its own:
+    # what is left of shuffles and per-wave words ranks entries (rcm_tile, rcm_block_scan), it folds nothing
+    for k in ("wl_block_part(part, 0u, looked)", "wl_block_part(part, total, looked)", "wl_sum_parts(part, nparts)",
+              "wl_block_fold<WlMax>(bw0)", "wl_block_fold<WlSum>(prof0)", "wl_block_fold<WlMax>(f.bw[k])",
+              "wl_block_fold<WlSum>(f.prof[k])"):
+        assert k in body, k
+    assert "__shfl_xor" not in body and "_block_part(WlPart" not in body and "_sum_parts(const" not in body
+    words = re.findall(r"__shared__[^;]*\[WL_BS(?: / 64)?\](?!\[)[^;]*;", body)
+    assert len(words) == 2 and "s_wcnt[WL_BS / 64]" in words[0] and "s_w[WL_BS / 64]" in words[1], words
     assert "asm" not in body.replace("amdgcn", "")   # plain C++ and builtins only
     assert "compare_exchange" not in body and "atomicCAS" not in body   # no compare-and-swap, no retry
     assert "while (true)" not in body and "for (;;)" not in body        # no spin

@@ -81,16 +81,19 @@ def run(eng, G, n, trim=1, pivot=1, cap=1 << 20):
 # ------------------------------------------------------------------ 1. every matrix, every setting
 @pytest.mark.parametrize("name", NAMES)
 def test_components_and_rounds_under_every_setting(eng, name):
-    n, rp, ci, va = matrix(name)
     if name == "edges":
-        P.assert_edge_lengths(rp, ci)
-    ref = want(name)
+        P.assert_edge_lengths(*matrix(name)[1:3])
+    components_and_rounds_under_every_setting(eng, name, matrix(name), want(name), lambda trim, pivot: sched(name, trim, pivot))
+
+
+def components_and_rounds_under_every_setting(eng, name, mat, ref, sched_of):
+    n, rp, ci, va = mat
     G = eng.scc_graph(rp, ci, va)
     assert G.edges == len(S.edges_of(n, rp, ci, va)[0])
     for trim, pivot in SETTINGS:
         comp, (components, settled, trimmed, rounds, steps, complete, kinds, sizes, steps_per, edges, ns, total) = \
             run(eng, G, n, trim, pivot)
-        _, w_kinds, w_sizes = sched(name, trim, pivot)
+        _, w_kinds, w_sizes = sched_of(trim, pivot)
         print(f"{name} trim={trim} pivot={pivot}: components {components} trimmed {trimmed} rounds {rounds} steps {steps} "
               f"kinds {kinds[:8].tolist()} sizes {sizes[:8].tolist()} total_ns {total}")
         np.testing.assert_array_equal(comp, ref, err_msg=f"{name} trim={trim} pivot={pivot}")

@@ -81,10 +81,10 @@ def matrix(name):
     return _cache[name]
 
 
-def reference(name, x0):
+def reference(name, x0, mat=None):
     key = (name, x0.tobytes())
     if key not in _refs:
-        n, rp, ci, va = matrix(name)
+        n, rp, ci, va = matrix(name) if mat is None else mat
         _refs[key] = S.sssp(rp, ci, va, x0)
     return _refs[key]
 
@@ -114,8 +114,8 @@ def run(eng, G, x0, delta=-1.0, with_pred=True, cap=1 << 20):
     return dist, pred, res
 
 
-def check(name, x0, dist, pred, res, what=""):
-    want_dist, want_pred, want_reached, outdeg_sum = reference(name, x0)
+def check(name, x0, dist, pred, res, what="", mat=None):
+    want_dist, want_pred, want_reached, outdeg_sum = reference(name, x0, mat)
     rounds, buckets, reached, complete, relaxed, sizes, edges, per, total = res
     print(f"{name} {what}: rounds {rounds} buckets {buckets} reached {reached} relaxed {relaxed} (out-degrees of the reached: "
           f"{outdeg_sum}) total_ns {total}")

@@ -94,8 +94,8 @@ def run(eng, mat, order, per_vertex=True, with_deg=True):
         G.free()
 
 
-def check(eng, name, order, mat=None):
-    wt, wd, wm = want(name)
+def check(eng, name, order, mat=None, w=None):
+    wt, wd, wm = want(name) if w is None else w
     tri, deg, total, probes, edges, longest = run(eng, matrix(name) if mat is None else mat, order)
     assert np.array_equal(tri, wt) and np.array_equal(deg, wd)
     assert edges == wm and 3 * total == int(wt.sum())

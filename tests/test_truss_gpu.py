@@ -123,8 +123,8 @@ def same(got, w, records=True):
             assert np.array_equal(got[f], w[f]), f
 
 
-def check(eng, name, mat=None):
-    w = want(name)
+def check(eng, name, mat=None, w=None):
+    w = want(name) if w is None else w
     mat = matrix(name) if mat is None else mat
     n = mat[0]
     got = run(eng, mat)

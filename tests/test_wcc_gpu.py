@@ -83,10 +83,10 @@ def run(eng, G, n, sample=2, cap=1 << 20):
     return comp, res
 
 
-def check(eng, name, samples=SAMPLES):
+def check(eng, name, samples=SAMPLES, mat=None, ref=None):
     """comp == the reference under every sample, and what the counts must satisfy; -> the results by sample."""
-    n, rp, ci, va = matrix(name)
-    ref = want(name)
+    n, rp, ci, va = matrix(name) if mat is None else mat
+    ref = want(name) if ref is None else ref
     largest = int(np.bincount(ref).max())
     G = eng.wcc_graph(rp, ci, va)
     assert G.edges == len(S.edges_of(n, rp, ci, va)[0])
