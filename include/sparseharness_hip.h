@@ -1594,6 +1594,111 @@ int sh_rcm(sh_engine *e, sh_rcm_graph *g, sh_vec *perm, sh_vec *pos, sh_vec *lev
            int32_t *kind_per_step, int64_t *size_per_step, int64_t *edges_per_step, uint64_t *ns_per_step,
            uint64_t *total_ns);
 
+/* ---- betweenness centrality by Brandes' two sweeps, in float64 -------------------------------------------------------------
+ * (the reference has no counterpart.  Of the six kernels a graph library is measured by -- BFS, SSSP, PageRank, connected
+ * components, triangle counting, betweenness centrality -- this is the last one: which vertices the shortest paths run
+ * through.  Brandes, "A faster algorithm for betweenness centrality", J. Math. Sociol. 2001.)
+ *
+ * The edge rule is sh_bfs_levels's: the matrix is square (rows x rows); an edge c -> r exists when row r stores column c
+ * with 0 <= c < rows and a value whose 32 bits are not all zero.  The graph is the SIMPLE DIRECTED graph under those
+ * entries: parallel entries are one edge and self-loops are none (a shortest-path count must not see a stored duplicate
+ * as a second path); stored zeros and columns outside the matrix are legal and are no edges.
+ *      For a source s:
+ *      level_s(v) = the BFS distance from s, -1 if unreached.
+ *      sigma_s(v) = the number of shortest s -> v paths: sigma_s(s) = 1, 0 if v is unreached, else the sum over the
+ *                   edges u -> v with level(u) == level(v) - 1 of sigma_s(u).
+ *      delta_s(v) = the sum over the edges v -> w with level(w) == level(v) + 1 of (sigma(v) / sigma(w)) * (1 + delta(w)).
+ *      bc[v]      = the sum over the sources, in the order given, of delta_s(v) for v != s.
+ *      Endpoints are not counted and nothing is normalised: on a symmetric pattern every unordered pair counts twice, and
+ *      halving is the caller's line.  A source may occur twice and then counts twice.
+ *
+ *      Arithmetic.  sigma, delta and bc are IEEE float64.  sigma is exact while it stays below 2^53, rounded above, and
+ *      +inf above the float64 range, after which that source's delta is whatever IEEE gives (inf / inf is a NaN, whose
+ *      sign and payload IEEE leaves open).  Nothing is refused: sigma_max_per_source returns the largest sigma of every
+ *      source, so the caller sees which case holds.  THE ORDER OF EVERY ADDITION IS PART OF THE RESULT, and it is fixed
+ *      here, once, as a function of the list alone -- its entries in ascending neighbour index and its length:
+ *        SUM(list): entry j of the list contributes the term t[j], +0.0 where the entry does not take part (a neighbour
+ *        on another level).  The list is cut into pieces of 2048 entries, the last one shorter.  Inside a piece there are
+ *        64 strided partials, partial[l] = (((+0.0 + t[l]) + t[l + 64]) + t[l + 128]) + ..., folded by a fixed butterfly:
+ *        for o = 32, 16, 8, 4, 2, 1: partial[l] = partial[l] + partial[l ^ o] for all l at once; the piece's sum is
+ *        partial[0].  The piece sums are added left to right, starting from +0.0.  The empty list sums to +0.0.
+ *      Every term is non-negative, so padding with +0.0 is exact, and a list of up to 8 entries sums to
+ *      ((t0 + t4) + (t2 + t6)) + ((t1 + t5) + (t3 + t7)).  sigma_s(v) = SUM over v's in-list, delta_s(v) = SUM over v's
+ *      out-list with the term (sigma(v) / sigma(w)) * (1 + delta(w)) -- one correctly rounded division, one addition, one
+ *      multiplication, no fused multiply-add --, and bc[v] = bc[v] + delta_s(v), source after source, for the vertices v
+ *      of the levels 1 .. depth - 1 (the others have delta +0.0 or are the source).  With that every comparison is ==:
+ *      tests/bc_ref.py restates SUM in numpy and host/src/bc_scores.cpp in C++.
+ *
+ *      Why the result is schedule-free: one owner per value.  sigma[w] is computed by the one lane or wave that pulls
+ *      over w's in-list, delta[v] and bc[v] by the one that pulls over v's out-list, from values that launches which
+ *      ended before have written.  There are no float atomics.  The queue order decides who computes a value, never from
+ *      what or in which order, so no value depends on the queue order, the grid, the batch size or the run; the same
+ *      SUM serves a lane (up to 8 entries), a wave (up to a piece) and a wave over several pieces.
+ *
+ *      Schedule (csrc/bc.hip.h).  The handle holds the surviving entries as 64-bit keys, sorted and deduplicated as
+ *      sh_tri_graph_create does, as in-lists and out-lists, both strictly ascending; per vertex a level word, sigma and
+ *      delta; one order array that is its own queue, with the start of every level kept on the device.  Forward, one step
+ *      per level, enqueued ahead of the host in batches (8, 16, 32, 32, ...) of gated launches: bc_expand pushes the
+ *      out-lists of the level (atomicMin on the unsigned level word claims w, and the one lane that saw it unreached
+ *      appends it: no compare-and-swap; out-lists above 2048 entries are pushed in pieces), bc_count pulls sigma for the
+ *      new segment, bc_close (one workgroup) records the step and opens the next.  A sweep of depth d takes d + 1 steps;
+ *      its last step finds nothing.  Backward, the host knows the depth and enqueues one ungated launch per level
+ *      depth - 1 ... 1 (level 0 is the source alone); bc_delta pulls delta and adds it into bc.
+ *      Worst cases: a path pays three launches forward and one backward per level and source, however narrow the level;
+ *      a hub's list is pulled by one wave alone, 64 entries at a time; sigma overflows on grids (C(n, n / 2) leaves
+ *      float64 near n = 1030).
+ *
+ *      Measured on an MI355X (DESIGN.md "6p Betweenness centrality"; tools/bc_bench.py, one process per matrix, 4 drawn
+ *        sources, sh_bc, as many sh_bfs_levels calls from the same sources -- the forward sweep's floor -- and the host
+ *        gold alternating, 5 rounds, device time against the wall time of hostlib.bc_scores), median (min-max) in ms for
+ *        the four sources: synth:scircuit (170 998 rows, 958 733 edges): 7.00 (6.98-7.07), 90 steps, 0.044 of the
+ *        host's 159.4, 2.98 times the four sh_bfs_levels calls (2.35); R-MAT-18 (262 144 rows, 3 939 181 edges, longest
+ *        list 15 918): 14.06 (13.98-14.15), 27 steps, 0.028 of the host's 509.9, 19.3 times the four sh_bfs_levels calls
+ *        (0.73: bottom-up levels with an early exit, which a path count cannot use); the 512 x 512 grid (262 144 rows,
+ *        1 046 528 edges, depths 662 to 1011, sigma up to 5.5e302): 75.71 (75.68-76.04), 3277 steps, 1.11 times the
+ *        host's 68.2 -- the device loses --, 1.12 times the four sh_bfs_levels calls (67.73).  The handle is built in
+ *        0.05 s.  More than four sources, graphs below 10^5 rows and graphs whose sigma overflows are unmeasured.
+ *        bench.py as parent, new, parent, new on one box: 0.38800, 0.38838, 0.38970, 0.38893 ms per step.
+ *
+ * sh_bc_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  rows == 0 gives a valid handle.
+ * Freeing NULL is SH_OK.  The build runs on the device, once; while it runs it needs the arrays as given, two words per
+ * entry and 16 bytes per surviving entry plus 8 per edge for the keys, all released before the call returns.
+ * sh_bc_graph_footprint: device bytes held =
+ *     12 * (rows + 1) + 24 * rows + 8 * edges + 16 * (edges / 1024 + 1) + 17408.
+ * (in_ptr, out_ptr and the level starts; level, order, sigma, delta; in_col and out_col; two piece lists; the control
+ * block with a count per workgroup.)  sh_bc_graph_edges: the simple directed edges.  sh_bc_graph_max_list: the longest
+ * in- or out-list.
+ *
+ * sh_bc: sources: a host array of n_sources int32 vertex indices; n_sources == 0 is legal and launches no kernel (with
+ * accumulate == 0 bc is still set to +0.0, the sum over no sources).  bc: an sh_vec of >= 2 * rows four-byte elements,
+ * 8-byte aligned, read as `rows` little-endian float64 (sh_tri's convention); 2 * rows elements are written, no more.
+ * accumulate == 0: bc starts from +0.0; accumulate == 1: the scores are added to what bc holds, so a caller may cut its
+ * sources into several calls and get the bits of one call.  sigma (optional, the format of bc) and level (optional,
+ * int32, >= rows elements) give the last source's values; without sources they are left alone.  *steps (may be NULL) =
+ * the forward steps of all sources.  The per-source arrays are host arrays of n_sources entries, each may be NULL:
+ * depth_per_source (int32, the last level that holds a vertex), reached_per_source (int64, the source included),
+ * sigma_max_per_source (double), edges_per_source (int64: the out-list entries walked forward, an exact count),
+ * ns_per_source and *total_ns device time (hipEvent) as elsewhere.  One handle serves any number of calls, one at a time.
+ * rows == 0 gives SH_OK.
+ * SH_EINVAL: accumulate outside {0, 1}, n_sources < 0 (the scalars are checked first); NULL arguments (engine, graph, bc,
+ * sources when n_sources > 0, out, the arrays); a source outside [0, rows); bc or sigma not aligned to 8 bytes; bc, sigma
+ * and level overlapping one another; rows < 0, nnz < 0.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr
+ * that decreases; bc or sigma shorter than 2 * rows, level shorter than rows.  All are reported before any device work,
+ * with the buffers untouched.
+ * NOT covered: several sources per matrix read, weighted shortest paths, edge betweenness, normalisation, the multi-GPU
+ * driver, the C++ harness apps.
+ */
+typedef struct sh_bc_graph sh_bc_graph;
+int sh_bc_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                       const void *val, sh_bc_graph **out);
+int sh_bc_graph_free(sh_engine *e, sh_bc_graph *g);
+int sh_bc_graph_footprint(const sh_bc_graph *g, uint64_t *device_bytes);
+int sh_bc_graph_edges(const sh_bc_graph *g, int64_t *edges);
+int sh_bc_graph_max_list(const sh_bc_graph *g, int64_t *entries);
+int sh_bc(sh_engine *e, sh_bc_graph *g, const int32_t *sources, int32_t n_sources, sh_vec *bc, int32_t accumulate,
+          sh_vec *sigma, sh_vec *level, int64_t *steps, int32_t *depth_per_source, int64_t *reached_per_source,
+          double *sigma_max_per_source, int64_t *edges_per_source, uint64_t *ns_per_source, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,13 @@ SIGNATURES = {
     "sh_rcm": (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
                       C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64),
                       C.POINTER(_i64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "sh_bc_graph_create": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _pp]),
+    "sh_bc_graph_free": (_int, [_vp, _vp]),
+    "sh_bc_graph_footprint": (_int, [_vp, C.POINTER(_u64)]),
+    "sh_bc_graph_edges": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_bc_graph_max_list": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_bc": (_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64),
+                     C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(_u64), C.POINTER(_u64)]),
 }
 
 _lib = None

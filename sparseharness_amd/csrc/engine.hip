@@ -22,6 +22,7 @@
 #include "msf.hip.h"
 #include "match.hip.h"
 #include "rcm.hip.h"
+#include "bc.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 #include "dev_arrays.h"
@@ -1970,7 +1971,7 @@ static int create_graph_handle(sh_engine *e, const char *fn, int64_t rows, int64
   return SH_OK;
 }
 
-// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core, sh_truss, sh_color, sh_msf, sh_match and sh_rcm: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core, sh_truss, sh_color, sh_msf, sh_match, sh_rcm and sh_bc: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
 // next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
 // enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
 // step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
@@ -3823,6 +3824,230 @@ int sh_rcm(sh_engine *e, sh_rcm_graph *g, sh_vec *perm, sh_vec *pos, sh_vec *lev
   *profile_after = done ? g->h_ctl->prof[1] : -1;
   if (total_ns)
     *total_ns = total;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- betweenness centrality by Brandes' two sweeps, in float64 (bc.hip.h) ------------------------------------------------
+// The GraphHandle base serves run_batches.  d_in_ptr / d_in_col and d_out_ptr / d_out_row hold the simple directed graph
+// by target and by source, every list strictly ascending (d_in_w, d_out_w and the static row pieces stay NULL).
+// d_ctl: BC_CTL_BYTES, followed by the WlParts of bc_expand.
+struct sh_bc_graph : GraphHandle<BcCtl> {
+  int64_t max_list = 0;   // the longest in- or out-list
+  BcState st = {};
+};
+static_assert(sizeof(BcCtl) <= BC_CTL_BYTES, "the control block is accounted as BC_CTL_BYTES (sh_bc_graph_footprint)");
+static_assert(sizeof(WlPart) * BC_MAX_BLOCKS == BC_PART_BYTES, "one WlPart per workgroup");
+static_assert(sizeof(BcCtl::rec) / sizeof(BcRec) == BC_BATCH, "one record per step of a batch");
+// sh_bc_graph_footprint: in_ptr, out_ptr and lstart; level and order (4 bytes per row each), sigma and delta (8 each);
+// in_col and out_col (4 bytes per edge each); two piece lists of edges / (BC_PIECE / 2) + 1 places of 8 bytes
+static_assert(BC_CTL_BYTES + BC_PART_BYTES == 17408 && BC_PIECE / 2 == 1024 && sizeof(WlPiece) == 8,
+              "the header states 12 * (rows + 1) + 24 * rows + 8 * edges + 16 * (edges / 1024 + 1) + 17408");
+static constexpr const char *BC_CREATE = "sh_bc_graph_create";
+
+// The lists of a BC handle from host CSR arrays: the entries that count and are no self-loops (wl_und_flag) become keys
+// (r << bits | c), sorted; the first key of every run is an edge of the simple directed graph (sh_tri_graph_create's
+// clean-up, without folding the two directions); the in-lists are read off the sorted keys, the out-lists off the
+// flipped keys, sorted again.  Returns with the stream synchronised: the host arrays are done with.
+static int build_directed_lists(sh_engine *e, sh_bc_graph *g, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                                const void *val) {
+  g->rows = rows; g->nnz = nnz;
+  DevArrays &own = g->dev;
+  DevArrays tmp;
+  HIP_TRY(e, own.alloc(&g->d_in_ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_out_ptr, (rows + 1) * 4));
+  HIP_TRY(e, hipMemsetAsync(g->d_in_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_out_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  int32_t *t_rp = nullptr, *t_ci = nullptr;
+  uint32_t *t_val = nullptr, *t_flag = nullptr, *t_pos = nullptr, *t_max = nullptr;
+  uint64_t *t_key = nullptr, *t_sorted = nullptr, *t_okey = nullptr;
+  int64_t S = 0, M = 0;
+  const int bits = 32 - __builtin_clz((unsigned)std::max<int64_t>(rows - 1, 1));   // (rows <= 2^31 - 256)
+  const dim3 blk(WL_BS);
+  const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
+  HIP_TRY(e, tmp.alloc(&t_max, 4));
+  HIP_TRY(e, hipMemsetAsync(t_max, 0, 4, e->stream));
+  if (rows > 0 && nnz > 0) {
+    HIP_TRY(e, tmp.alloc(&t_rp, (rows + 1) * 4));
+    HIP_TRY(e, tmp.alloc(&t_ci, nnz * 4));
+    HIP_TRY(e, tmp.alloc(&t_val, nnz * 4));
+    HIP_TRY(e, tmp.alloc(&t_flag, (nnz + 1) * 4));
+    HIP_TRY(e, tmp.alloc(&t_pos, (nnz + 1) * 4));
+    HIP_TRY(e, hipMemcpyAsync(t_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(t_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(t_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(wl_und_flag<BfsKeep>), grid_for(nnz + 1), blk, 0, e->stream, t_rp, t_ci, t_val, nnz, (int32_t)rows, t_flag);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_exclusive_sum_u32(e->stream, t_flag, t_pos, nnz + 1));
+    uint32_t n = 0;
+    HIP_TRY(e, hipMemcpy(&n, t_pos + nnz, 4, hipMemcpyDeviceToHost));
+    S = (int64_t)n;
+  }
+  if (S > 0) {
+    HIP_TRY(e, tmp.alloc(&t_key, S * 8));
+    HIP_TRY(e, tmp.alloc(&t_sorted, S * 8));
+    hipLaunchKernelGGL(bc_in_keys, grid_for(nnz), blk, 0, e->stream, t_rp, t_ci, t_flag, t_pos, nnz, (int32_t)rows, bits, t_key);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_keys_u64(e->stream, t_key, t_sorted, S, 2 * bits));
+    // (t_flag and t_pos hold nnz + 1 >= S + 1 words: they serve the run heads and their scan)
+    hipLaunchKernelGGL(wl_run_heads, grid_for(S + 1), blk, 0, e->stream, t_sorted, S, t_flag);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_exclusive_sum_u32(e->stream, t_flag, t_pos, S + 1));
+    uint32_t n = 0;
+    HIP_TRY(e, hipMemcpy(&n, t_pos + S, 4, hipMemcpyDeviceToHost));
+    M = (int64_t)n;
+  }
+  g->edges = M;
+  HIP_TRY(e, own.alloc(&g->d_in_col, M * 4));
+  HIP_TRY(e, own.alloc(&g->d_out_row, M * 4));
+  if (M > 0) {
+    HIP_TRY(e, tmp.alloc(&t_okey, M * 8));
+    // (t_key has been sorted from: its first M <= S words take the edges' keys, in order)
+    hipLaunchKernelGGL(bc_out_keys, grid_for(S), blk, 0, e->stream, t_sorted, t_flag, t_pos, S, bits, t_key, t_okey);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(M, rows + 1)), blk, 0, e->stream, t_key, M, rows, bits, g->d_in_ptr, g->d_in_col);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_keys_u64(e->stream, t_okey, t_sorted, M, 2 * bits));
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(M, rows + 1)), blk, 0, e->stream, t_sorted, M, rows, bits, g->d_out_ptr, g->d_out_row);
+    HIP_TRY(e, hipGetLastError());
+    const dim3 mgrid((unsigned)std::max(1, std::min(e->n_cus * 4, BC_MAX_BLOCKS)));
+    hipLaunchKernelGGL(wl_max_len, mgrid, blk, 0, e->stream, g->d_in_ptr, rows, t_max);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(wl_max_len, mgrid, blk, 0, e->stream, g->d_out_ptr, rows, t_max);
+    HIP_TRY(e, hipGetLastError());
+  }
+  uint32_t longest = 0;
+  HIP_TRY(e, hipMemcpyAsync(&longest, t_max, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  g->max_list = (int64_t)longest;
+  return SH_OK;
+}
+
+extern "C" {
+
+int sh_bc_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                       const void *val, sh_bc_graph **out) {
+  return create_graph_handle<sh_bc_graph>(e, BC_CREATE, rows, nnz, row_ptr, col_idx, val, out, [&](sh_bc_graph *g) -> int {
+    int rc;
+    if ((rc = build_directed_lists(e, g, rows, nnz, row_ptr, col_idx, val)))
+      return rc;
+    const int64_t places = g->edges / (BC_PIECE / 2) + 1;   // see wl_push_pieces
+    HIP_TRY(e, g->dev.alloc(&g->st.level, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->st.order, rows * 4));
+    HIP_TRY(e, g->dev.alloc(&g->st.lstart, (rows + 1) * 4));
+    HIP_TRY(e, g->dev.alloc(&g->st.sigma, rows * 8));
+    HIP_TRY(e, g->dev.alloc(&g->st.delta, rows * 8));
+    HIP_TRY(e, g->dev.alloc(&g->st.pl[0], places * (int64_t)sizeof(WlPiece)));
+    HIP_TRY(e, g->dev.alloc(&g->st.pl[1], places * (int64_t)sizeof(WlPiece)));
+    return open_control(e, g, BC_CTL_BYTES, BC_CTL_BYTES + BC_PART_BYTES);
+  });
+}
+
+int sh_bc_graph_free(sh_engine *e, sh_bc_graph *g) { return free_handle(e, g); }
+
+int sh_bc_graph_footprint(const sh_bc_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
+
+int sh_bc_graph_edges(const sh_bc_graph *g, int64_t *edges) { return HANDLE_GET(g, edges, g->edges); }
+
+int sh_bc_graph_max_list(const sh_bc_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->max_list); }
+
+int sh_bc(sh_engine *e, sh_bc_graph *g, const int32_t *sources, int32_t n_sources, sh_vec *bc, int32_t accumulate, sh_vec *sigma,
+          sh_vec *level, int64_t *steps, int32_t *depth_per_source, int64_t *reached_per_source, double *sigma_max_per_source,
+          int64_t *edges_per_source, uint64_t *ns_per_source, uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (accumulate != 0 && accumulate != 1)
+    return fail(e, SH_EINVAL, "sh_bc: accumulate = %d, must be 0 (bc starts from zero) or 1 (the scores are added to bc)", (int)accumulate);
+  if (n_sources < 0)
+    return fail(e, SH_EINVAL, "sh_bc: n_sources = %d, must be at least 0", (int)n_sources);
+  if (!e || !g || !bc || (n_sources > 0 && !sources))
+    return fail(e, SH_EINVAL, "sh_bc: NULL argument (engine, graph, bc, or sources of a call that has some)");
+  const int64_t rows = g->rows;
+  for (int32_t i = 0; i < n_sources; i++)
+    if (sources[i] < 0 || (int64_t)sources[i] >= rows)
+      return fail(e, SH_EINVAL, "sh_bc: sources[%d] = %d is outside [0, %lld)", (int)i, (int)sources[i], (long long)rows);
+  if (bc->n < 2 * rows)
+    return fail(e, SH_ESHAPE, "sh_bc: bc holds fewer than 2 elements for each of the graph's %lld rows", (long long)rows);
+  if (sigma && sigma->n < 2 * rows)
+    return fail(e, SH_ESHAPE, "sh_bc: sigma holds fewer than 2 elements for each of the graph's %lld rows", (long long)rows);
+  if (level && level->n < rows)
+    return fail(e, SH_ESHAPE, "sh_bc: level is shorter than the graph's %lld rows", (long long)rows);
+  if (((uintptr_t)bc->d & 7u) || (sigma && ((uintptr_t)sigma->d & 7u)))
+    return fail(e, SH_EINVAL, "sh_bc: bc or sigma is not aligned to 8 bytes");
+  {
+    const struct { const sh_vec *v; int64_t bytes; } outs[] = {{bc, rows * 8}, {sigma, rows * 8}, {level, rows * 4}};
+    for (int i = 0; i < 3; i++)
+      for (int j = i + 1; j < 3; j++) {
+        if (!outs[i].v || !outs[j].v || rows == 0) continue;
+        const char *a = (const char *)outs[i].v->d, *b = (const char *)outs[j].v->d;
+        if (a < b + outs[j].bytes && b < a + outs[i].bytes)
+          return fail(e, SH_EINVAL, "sh_bc: bc, sigma and level must not alias one another");
+      }
+  }
+  if (steps) *steps = 0;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const int nblocks = std::max(1, std::min(e->n_cus * 4, BC_MAX_BLOCKS));
+  const dim3 grid((unsigned)nblocks), block(WL_BS);
+  const BcGraph G{(int32_t)rows, g->d_in_ptr, g->d_in_col, g->d_out_ptr, g->d_out_row};
+  const BcState &St = g->st;
+  if (!accumulate) HIP_TRY(e, hipMemsetAsync(bc->d, 0, (size_t)rows * 8, e->stream));
+  uint64_t all = 0;
+  int64_t all_steps = 0;
+  for (int32_t i = 0; i < n_sources; i++) {
+    uint64_t total = 0, ns = 0;
+    int64_t walked = 0;
+    HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+    HIP_TRY(e, hipMemsetAsync(g->d_ctl, 0, BC_CTL_BYTES, e->stream));
+    hipLaunchKernelGGL(bc_init, grid, block, 0, e->stream, g->d_ctl, G, St, sources[i]);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+    // the forward sweep: the launches of a step, each of which returns at once unless the control block says it is its turn
+    const auto enqueue = [&](int s, int k) {
+      hipLaunchKernelGGL(bc_expand, grid, block, 0, e->stream, g->d_ctl, s, G, St, g->d_part);
+      HIP_TRY(e, hipGetLastError());
+      hipLaunchKernelGGL(bc_count, grid, block, 0, e->stream, g->d_ctl, s, G, St);
+      HIP_TRY(e, hipGetLastError());
+      hipLaunchKernelGGL(bc_close, dim3(1), block, 0, e->stream, g->d_ctl, k, s, nblocks, g->d_part, St);
+      HIP_TRY(e, hipGetLastError());
+      return (int)SH_OK;
+    };
+    const auto take = [&](int, const BcRec &rc, uint64_t) { walked += (int64_t)rc.edges; };
+    int32_t it = 0;
+    bool done = false;
+    const int rc = run_batches(e, "sh_bc: step", g, (int32_t)std::min<int64_t>(rows, 0x7FFFFFFF), &it, &done, &total, enqueue, take);
+    if (rc)
+      return rc;
+    if (!done)
+      return fail(e, SH_EHIP, "sh_bc: the forward sweep of source %d did not end within %lld steps", (int)i, (long long)rows);
+    // the backward sweep: the host knows the depth; level 0 is the source alone
+    const int32_t depth = g->h_ctl->depth;
+    HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+    for (int32_t L = depth - 1; L >= 1; L--) {
+      hipLaunchKernelGGL(bc_delta, grid, block, 0, e->stream, (int)L, G, St, (double *)bc->d);
+      HIP_TRY(e, hipGetLastError());
+    }
+    HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+    HIP_TRY(e, hipStreamSynchronize(e->stream));
+    HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+    total += ns;
+    all += total;
+    all_steps += it;
+    if (depth_per_source) depth_per_source[i] = depth;
+    if (reached_per_source) reached_per_source[i] = (int64_t)g->h_ctl->tail;
+    if (sigma_max_per_source) memcpy(&sigma_max_per_source[i], &g->h_ctl->smax, 8);
+    if (edges_per_source) edges_per_source[i] = walked;
+    if (ns_per_source) ns_per_source[i] = total;
+  }
+  if (n_sources > 0) {   // the last source's values
+    if (sigma) HIP_TRY(e, hipMemcpyAsync(sigma->d, St.sigma, (size_t)rows * 8, hipMemcpyDeviceToDevice, e->stream));
+    if (level) HIP_TRY(e, hipMemcpyAsync(level->d, St.level, (size_t)rows * 4, hipMemcpyDeviceToDevice, e->stream));
+  }
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  if (steps) *steps = all_steps;
+  if (total_ns) *total_ns = all;
   return SH_OK;
 }
 

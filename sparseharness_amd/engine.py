@@ -37,7 +37,7 @@ def _csr_args(row_ptr, col_idx, val):
     return row_ptr, col_idx, val
 
 
-_CTYPE_OF = {np.int32: C.c_int32, np.int64: C.c_int64, np.uint64: C.c_uint64}
+_CTYPE_OF = {np.int32: C.c_int32, np.int64: C.c_int64, np.uint64: C.c_uint64, np.float64: C.c_double}
 
 
 def _outs(cap, *dtypes):
@@ -611,6 +611,28 @@ class Engine:
         n = steps.value
         return (components.value, sweeps_run.value, n, bool(complete.value), bw0.value, bw1.value, prof0.value, prof1.value,
                 kinds[:n].copy(), sizes[:n].copy(), edges[:n].copy(), per[:n].copy(), total.value)
+
+    # ---- betweenness centrality: bc[v] = the sum over the sources s != v of delta_s(v), float64, every sum in one fixed order
+    def bc_graph(self, row_ptr, col_idx, val):
+        """The handle Engine.betweenness needs (bc.BcGraph), from the CSR arrays of a square matrix."""
+        from .bc import BcGraph   # (bc.py imports this module)
+        return self._graph(BcGraph, row_ptr, col_idx, val)
+
+    def betweenness(self, G, sources, bc, accumulate=0, sigma=None, level=None):
+        """-> (steps, depths, reached, sigma_max, edges, ns, total_ns); per source: the last level that holds a vertex, the
+        vertices reached (the source included), the largest path count (float64: exact below 2^53, inf once it has
+        overflowed), the out-list entries walked forward, device ns.  sources: int32 vertex indices, taken in the order
+        given.  bc: a vector of >= 2 * rows 4-byte elements (rows float64 scores; download(np.uint32, 2 * rows).view(np.float64) reads them);
+        accumulate = 1 adds to what it holds.  sigma: None or such a vector, level: None or an int32 vector of >= rows
+        elements; both get the last source's values."""
+        sources = np.ascontiguousarray(sources, np.int32)
+        n = len(sources)
+        steps, total = C.c_int64(), C.c_uint64()
+        (depths, reached, smax, edges, per), ptrs = _outs(max(n, 1), np.int32, np.int64, np.float64, np.int64, np.uint64)
+        h = lambda v: None if v is None else v.h   # noqa: E731
+        self._chk(abi.load().sh_bc(self.h, G.h, _ptr(sources) if n else None, n, bc.h, accumulate, h(sigma), h(level),
+                                   C.byref(steps), *ptrs, C.byref(total)))
+        return steps.value, depths[:n].copy(), reached[:n].copy(), smax[:n].copy(), edges[:n].copy(), per[:n].copy(), total.value
 
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):

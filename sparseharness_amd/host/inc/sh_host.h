@@ -104,6 +104,18 @@ int sh_rcm_order(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_
                  int64_t *profile, int32_t *components, int32_t *searches, int64_t *edges, int64_t steps_cap, int32_t *kind,
                  int64_t *size, int64_t *looked, int64_t *steps);
 
+/* Betweenness centrality of the simple directed graph under a square CSR pattern (clean, then Brandes' two sweeps per
+ * source with one queue; single-threaded): the gold for sh_bc.  Entry (r, c) is the edge c -> r when 0 <= c < rows, c != r
+ * and its 32 value bits are not all zero; parallel entries are one edge.  Every sum is float64 in the order that
+ * include/sparseharness_hip.h fixes (SUM), so the results equal sh_bc's bit for bit.  sources[n_sources] are taken in the
+ * order given; accumulate in {0, 1} (1: the scores are added to what bc holds).  bc[v] (rows doubles); sigma[v] (rows
+ * doubles) and level[v] (rows words) of the last source (each may be NULL); per source (each may be NULL): depth (the last
+ * level that holds a vertex), reached (the source included), sigma_max and edges (the out-list entries walked forward).
+ * Return 0, -1 bad argument. */
+int sh_bc_scores(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                 const int32_t *sources, int32_t n_sources, int32_t accumulate, double *bc, double *sigma, int32_t *level,
+                 int32_t *depth, int64_t *reached, double *sigma_max, int64_t *edges);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

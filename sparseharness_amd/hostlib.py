@@ -3,7 +3,7 @@ loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
 host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp), sh_tri
 (host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp), sh_truss (host/src/truss_numbers.cpp), sh_color
-(host/src/greedy_colors.cpp), sh_msf (host/src/msf_edges.cpp), sh_match (host/src/greedy_matching.cpp) and sh_rcm (host/src/rcm_order.cpp)."""
+(host/src/greedy_colors.cpp), sh_msf (host/src/msf_edges.cpp), sh_match (host/src/greedy_matching.cpp), sh_rcm (host/src/rcm_order.cpp) and sh_bc (host/src/bc_scores.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -41,6 +41,7 @@ SIGNATURES = {
     "sh_greedy_matching": (C.c_int, _csr + [C.c_int32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sh_rcm_order": (C.c_int, _csr + [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.POINTER(_i64), _i64, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "sh_bc_scores": (C.c_int, _csr + [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sh_mm_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]),
     "sh_mm_load_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]),
     "sh_host_csr_release": (None, [C.POINTER(_HostCsr)]),
@@ -232,6 +233,27 @@ def rcm_order(row_ptr, col_idx, val, sweeps=8, reverse=1, records=False):
            searches.value)
     k = steps.value
     return out + (kinds[:k].copy(), sizes[:k].copy(), edges[:k].copy()) if records else out
+
+
+def bc_scores(row_ptr, col_idx, val, sources, bc=None):
+    """-> (bc, sigma, level, depths, reached, sigma_max, edges): bc[v] (float64) = the betweenness of v in the simple
+    directed graph under the entries, summed over `sources` in the order given (Engine.betweenness's bc; `bc`: scores to
+    add to, as accumulate = 1), sigma (float64) and level (int32) of the last source, and per source the last level that
+    holds a vertex, the vertices reached, the largest path count and the out-list entries walked forward, by a serial
+    Brandes on the host whose every float64 sum runs in the order include/sparseharness_hip.h fixes: the results are
+    sh_bc's bit for bit.  Entry (r, c) is the edge c -> r when 0 <= c < rows, c != r and its 32 value bits are not all
+    zero."""
+    n = len(row_ptr) - 1
+    sources = np.ascontiguousarray(sources, np.int32)
+    k = len(sources)
+    out = np.zeros(max(n, 1), np.float64) if bc is None else np.array(bc, np.float64)
+    assert len(out) >= n
+    sigma, level = np.zeros(max(n, 1), np.float64), np.full(max(n, 1), -1, np.int32)
+    depths, reached = np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int64)
+    smax, edges = np.zeros(max(k, 1), np.float64), np.zeros(max(k, 1), np.int64)
+    _gold("sh_bc_scores", row_ptr, col_idx, val, _p(sources), k, 0 if bc is None else 1, _p(out), _p(sigma), _p(level),
+          _p(depths), _p(reached), _p(smax), _p(edges))
+    return out[:n], sigma[:n], level[:n], depths[:k], reached[:k], smax[:k], edges[:k]
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
