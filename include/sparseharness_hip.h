@@ -1699,6 +1699,109 @@ int sh_bc(sh_engine *e, sh_bc_graph *g, const int32_t *sources, int32_t n_source
           sh_vec *sigma, sh_vec *level, int64_t *steps, int32_t *depth_per_source, int64_t *reached_per_source,
           double *sigma_max_per_source, int64_t *edges_per_source, uint64_t *ns_per_source, uint64_t *total_ns);
 
+/* ---- sparse triangular solve: x = T^-1 b by level sets, float64, every sum in one fixed order ----------------------
+ * (the reference has no counterpart.  It is the kernel Gauss-Seidel, SSOR and every ILU or IC preconditioner apply: the
+ * engine orders (sh_rcm), colours (sh_color), pairs (sh_match) and multiplies (sh_spmv); this solves.  Level scheduling:
+ * Anderson, Saad, Int. J. High Speed Computing 1989; on GPUs: Naumov, NVIDIA NVR-2011-001.  The spin-waiting
+ * "synchronisation-free" algorithms are out: no kernel here ever waits for another kernel's write.)
+ *
+ * THE DEFINITION IS PART OF THE ABI.  The matrix is square (rows x rows), given as host CSR with float32 values; uplo
+ * selects the triangle (0 lower, 1 upper) and unit == 1 takes the diagonal as one.
+ *      Every stored entry (r, c) with 0 <= c < rows takes part, whatever its value: explicit zeros, NaN and infinities
+ *      are included and nothing is refused.  Entries of the other triangle and columns out of range are ignored; diagonal
+ *      entries are ignored when unit == 1.  Rows need not be sorted.
+ *      LIST(r) = the strictly-triangular entries of row r in ascending (column, position as given); parallel entries stay
+ *                separate terms (a stable radix sort of the keys (r << bits | c) with the value riding along gives this).
+ *      d[r]    = the diagonal entries of r widened to float64 and added left to right, starting from +0.0; a missing
+ *                diagonal is +0.0.
+ *      level[r] = 0 for an empty list, else 1 + the largest level[c] over the list.  order = the rows in ascending
+ *                (level, index); lstart[L] = where level L starts in order.
+ *      x[r]    = (b[r] - S_r) / d[r], or b[r] - S_r when unit == 1, with S_r = SUM over LIST(r) of the terms
+ *                t_j = (double)val_j * x[col_j].  Each product, the subtraction and the division are rounded once: no fused
+ *                multiply-add.  A zero or missing diagonal gives what IEEE gives (inf or NaN); sh_trsv_graph_zero_diag
+ *                and _first_zero say how many rows have d[r] == 0 and which is the first, so the caller sees it.
+ *      SUM is sh_bc's shape: the list is cut into pieces of 2048 entries, the last one shorter; inside a piece 64 strided
+ *      partials, partial[l] = (((+0.0 + t[l]) + t[l + 64]) + t[l + 128]) + ..., folded by the fixed butterfly: for
+ *      o = 32, 16, 8, 4, 2, 1: partial[l] = partial[l] + partial[l ^ o] for all l at once; the piece's sum is partial[0];
+ *      the piece sums are added left to right, starting from +0.0.  The empty list sums to +0.0.  THE TERMS ARE SIGNED: a
+ *      partial starts from +0.0, so it is never -0.0 and padding with +0.0 is exact; a list of up to 8 entries sums to
+ *      ((p0 + p4) + (p2 + p6)) + ((p1 + p5) + (p3 + p7)) with p_k = +0.0 + t_k (not t_k: eight terms of -0.0 sum to +0.0 in
+ *      every tier).  A lane (up to 8 entries), a wave (up to a piece) and a wave over several pieces compute ONE function.
+ *      With that every comparison is ==, a NaN standing where a NaN stands: tests/trsv_ref.py restates the definition in
+ *      numpy and host/src/trsv_solve.cpp in C++.
+ *      float32 callers (sh_spmv works in float32): with f32 == 1, b is read as rows float32 and widened, x is written as
+ *      float32, rounded once on the way out; later rows read the unrounded float64 value (the handle keeps it).  With
+ *      f32 == 0, b and x are rows float64 in 2 * rows four-byte elements, 8-byte aligned (sh_bc's convention).  b and x
+ *      may be the same vector.
+ *
+ *      Schedule (csrc/trsv.hip.h).  sh_trsv_graph_create builds on the device, once: flag and key the entries, one stable
+ *      sort, gather values and diagonals; the flipped lists ("who waits for me") serve the analysis only: gated rounds
+ *      enqueued ahead of the host in batches (8, 16, 32, 32, ...), a waiting count per row, round L settles its work list
+ *      at level L and gives every dependant one atomic decrement per entry, the one lane that sees zero owns the row for
+ *      the next round: no compare-and-swap.  One sort of (level << bits | row) gives order.  The flipped lists, the keys
+ *      and the work lists are released before the call returns; the host keeps lstart (levels + 1 words).
+ *      sh_trsv: one lane per row (64 rows per wave), one owner per x[r], no float atomics.  A wide level is one ungated
+ *      launch (trsv_level: the grid sized by the level's width, at most 1024 workgroups, a grid-stride loop).  A run of
+ *      consecutive THIN levels is one launch of ONE workgroup (trsv_run) with a workgroup barrier between levels: x is
+ *      written and read inside that launch by one workgroup's waves only, by plain stores and loads ordered by the barrier
+ *      at workgroup scope; no agent fence, no flag, no spin.  A run holds at most SH_TRSV_RUN = 1024 levels (a level in a
+ *      run costs a barrier and a chain of dependent loads, a few microseconds, so a launch stays in the low
+ *      milliseconds).  The plan is a host function of lstart, thin and SH_TRSV_RUN alone: a level is thin when it holds at
+ *      most `thin` rows; consecutive thin levels form runs, cut at SH_TRSV_RUN; every other level is a launch of its own.
+ *      thin == 0 gives one launch per level; thin < 0 means the default, 256; thin > 65536 is refused.  x does not depend
+ *      on thin.
+ *      Worst cases: a path (a bidiagonal matrix) has `rows` levels of one row: the analysis pays two launches per level,
+ *      the solve one barrier per level and one launch per 1024 levels, and a host loop wins; a hub row's list is summed
+ *      by one wave alone, 64 entries at a time; the analysis of a matrix with `rows` levels takes `rows` rounds.
+ *
+ *      Measured on an MI355X (DESIGN.md "6q Sparse triangular solve"; tools/trsv_bench.py, one process per matrix, the
+ *        lower triangle with a dominant diagonal, float64, sh_trsv and the host gold alternating, 5 rounds, device time
+ *        against the wall time of hostlib.trsv_solve), median in ms: the 2048 x 2048 grid Laplacian as generated
+ *        (4 194 304 rows, 4095 levels): thin 0: 18.22, 64: 18.03, 256: 17.53, 1024: 22.39, 4096: 46.25; the host 168.5: the
+ *        default is 0.104 of it (a level in a run costs about 3.1 us, a launch of its own 4.45 us).  The same grid
+ *        permuted by sh_color's classes (5 levels): 0.076 for every thin, 0.0004 of the host's 174.8.  R-MAT-18 symmetrised
+ *        (943 levels, longest list 15 839): 30.68 at thin 256, 0.93 of the host's 32.8: a tie.  synth:scircuit (24
+ *        levels): 0.547, 0.069 of the host's 7.90.  The default thin = 256 is the arm that wins on the grid as generated
+ *        and loses nothing on the permuted one.  A sweep of SH_TRSV_RUN and a true path are unmeasured.
+ *        bench.py as parent, new, parent, new on one box: 0.38762, 0.39065, 0.39172, 0.39044 ms per step.
+ *
+ * sh_trsv_graph_create: the handle is made from the host CSR arrays alone (no sh_csr).  rows == 0 gives a valid handle
+ * and a solve that launches nothing.  Freeing NULL is SH_OK.  While the build runs it needs the arrays as given, two words
+ * per entry, about 24 bytes per list entry and 36 per row, all released before the call returns.
+ * sh_trsv_graph_footprint: device bytes held =
+ *     4 * (rows + 1) + 24 * rows + 8 * entries + 4 * (levels + 1) + 17408.
+ * (ptr; d, the float64 x of a float32 call, order and level; col and val; lstart; the analysis' control block with a
+ * count per workgroup.)  sh_trsv_graph_entries: the list entries, the diagonal not counted.  _levels, _max_list (the
+ * longest list), _max_width (the widest level), _zero_diag (rows with d == 0; always 0 when unit), _first_zero (the
+ * smallest such row, -1 if none).  sh_trsv_graph_level: level[r] into an int32 sh_vec of >= rows elements.
+ *
+ * sh_trsv: *launches = the launches of the call, *runs = how many of them were runs, *levels_in_runs = the levels those
+ * held (each may be NULL; they are the plan's, known before anything is launched), *total_ns device time (hipEvent) as
+ * elsewhere.  rows elements (f32) or 2 * rows elements of x are written, no more.  One handle serves any number of
+ * calls, one at a time.
+ * SH_EINVAL: uplo or unit outside {0, 1} (sh_trsv_graph_create), f32 outside {0, 1}, thin > 65536 (the scalars are
+ * checked first); NULL arguments; a float64 b or x not aligned to 8 bytes; b and x overlapping without being the same
+ * vector; rows < 0, nnz < 0.  SH_ESHAPE: row_ptr[0] != 0, row_ptr[rows] != nnz or a row_ptr that decreases; b or x
+ * shorter than rows (f32) or 2 * rows elements; level shorter than rows.  All are reported before any launch, with the
+ * buffers untouched.
+ * NOT covered: several right-hand sides, the transposed solve, factorisation (ILU, IC), the multi-GPU driver, the C++
+ * harness apps.
+ */
+typedef struct sh_trsv_graph sh_trsv_graph;
+int sh_trsv_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                         const void *val, int32_t uplo, int32_t unit, sh_trsv_graph **out);
+int sh_trsv_graph_free(sh_engine *e, sh_trsv_graph *g);
+int sh_trsv_graph_footprint(const sh_trsv_graph *g, uint64_t *device_bytes);
+int sh_trsv_graph_entries(const sh_trsv_graph *g, int64_t *entries);
+int sh_trsv_graph_levels(const sh_trsv_graph *g, int64_t *levels);
+int sh_trsv_graph_max_list(const sh_trsv_graph *g, int64_t *entries);
+int sh_trsv_graph_max_width(const sh_trsv_graph *g, int64_t *rows);
+int sh_trsv_graph_zero_diag(const sh_trsv_graph *g, int64_t *rows);
+int sh_trsv_graph_first_zero(const sh_trsv_graph *g, int64_t *row);
+int sh_trsv_graph_level(sh_engine *e, sh_trsv_graph *g, sh_vec *level);
+int sh_trsv(sh_engine *e, sh_trsv_graph *g, const sh_vec *b, sh_vec *x, int32_t f32, int32_t thin, int64_t *launches,
+            int64_t *runs, int64_t *levels_in_runs, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

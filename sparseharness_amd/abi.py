@@ -175,6 +175,17 @@ SIGNATURES = {
     "sh_bc_graph_max_list": (_int, [_vp, C.POINTER(_i64)]),
     "sh_bc": (_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64),
                      C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "sh_trsv_graph_create": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _pp]),
+    "sh_trsv_graph_free": (_int, [_vp, _vp]),
+    "sh_trsv_graph_footprint": (_int, [_vp, C.POINTER(_u64)]),
+    "sh_trsv_graph_entries": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_trsv_graph_levels": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_trsv_graph_max_list": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_trsv_graph_max_width": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_trsv_graph_zero_diag": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_trsv_graph_first_zero": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_trsv_graph_level": (_int, [_vp, _vp, _vp]),
+    "sh_trsv": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_u64)]),
 }
 
 _lib = None

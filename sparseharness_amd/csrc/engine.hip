@@ -23,6 +23,7 @@
 #include "match.hip.h"
 #include "rcm.hip.h"
 #include "bc.hip.h"
+#include "trsv.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 #include "dev_arrays.h"
@@ -1971,7 +1972,7 @@ static int create_graph_handle(sh_engine *e, const char *fn, int64_t rows, int64
   return SH_OK;
 }
 
-// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core, sh_truss, sh_color, sh_msf, sh_match, sh_rcm and sh_bc: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
+// The loop of sh_bfs_levels, sh_sssp, sh_scc, sh_wcc, sh_core, sh_truss, sh_color, sh_msf, sh_match, sh_rcm, sh_bc and the analysis of sh_trsv_graph_create: batches of gated steps enqueued ahead of the host (the first batch holds 8, the
 // next ones twice as many up to the records the control block has).  Per batch: the records are cleared, enqueue(s, k)
 // enqueues step s as slot k, the control block is copied back, and take(s, rec, ns) gets the record and the time of every
 // step that ran.  The launches between e->ev0 and e->ev1 (the caller's init) are timed from the first batch's readback.
@@ -4048,6 +4049,281 @@ int sh_bc(sh_engine *e, sh_bc_graph *g, const int32_t *sources, int32_t n_source
   HIP_TRY(e, hipStreamSynchronize(e->stream));
   if (steps) *steps = all_steps;
   if (total_ns) *total_ns = all;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- sparse triangular solve by level sets, in float64 (trsv.hip.h) ---------------------------------------------------------
+// The GraphHandle base serves run_batches (the analysis).  d_in_ptr / d_in_col hold the lists (ascending (column,
+// position as given)), d_val their values, d_diag the diagonal; d_order / d_lstart the level sets, d_level the level of
+// every row; d_xw the float64 x of a float32 call.  The flipped lists, the keys and the work lists of the analysis are
+// temporaries of the build.  d_ctl: TRSV_CTL_BYTES, followed by the WlParts of trsv_settle.
+struct sh_trsv_graph : GraphHandle<TrsvCtl> {
+  int32_t uplo = 0, unit = 0;
+  int64_t levels = 0, max_list = 0, max_width = 0, zero_diag = 0, first_zero = -1;
+  float *d_val = nullptr;
+  double *d_diag = nullptr, *d_xw = nullptr;
+  uint32_t *d_order = nullptr, *d_lstart = nullptr;
+  int32_t *d_level = nullptr;
+  std::vector<uint32_t> lstart;   // levels + 1 words: what the plan of a call is made from
+};
+static_assert(sizeof(TrsvCtl) <= TRSV_CTL_BYTES, "the control block is accounted as TRSV_CTL_BYTES (sh_trsv_graph_footprint)");
+static_assert(sizeof(WlPart) * TRSV_MAX_BLOCKS == TRSV_PART_BYTES, "one WlPart per workgroup");
+static_assert(sizeof(TrsvCtl::rec) / sizeof(TrsvRec) == TRSV_BATCH, "one record per round of a batch");
+// sh_trsv_graph_footprint: ptr (4 bytes per row + 1); d and the float64 work vector (8 per row each), order and level (4
+// each); col and val (4 bytes per entry each); lstart (4 per level + 1); the control block and its parts
+static_assert(TRSV_CTL_BYTES + TRSV_PART_BYTES == 17408,
+              "the header states 4 * (rows + 1) + 24 * rows + 8 * entries + 4 * (levels + 1) + 17408");
+static constexpr const char *TRSV_CREATE = "sh_trsv_graph_create";
+
+// One launch of a call's plan: a wide level (n == 0: trsv_level of level L0) or a run (trsv_run of levels L0 ... L0 + n - 1).
+struct TrsvLaunch { int32_t L0, n; };
+// The plan: a host function of lstart, thin and the cap alone.  A level is thin when it holds at most `thin` rows;
+// consecutive thin levels form runs of at most `cap` levels; every other level is a launch of its own.
+static void trsv_plan(const std::vector<uint32_t> &lstart, int64_t thin, int32_t cap, std::vector<TrsvLaunch> &plan) {
+  const int64_t levels = (int64_t)lstart.size() - 1;
+  for (int64_t L = 0; L < levels;) {
+    if ((int64_t)(lstart[L + 1] - lstart[L]) > thin) { plan.push_back({(int32_t)L, 0}); L++; continue; }
+    int64_t n = 0;
+    while (L + n < levels && n < cap && (int64_t)(lstart[L + n + 1] - lstart[L + n]) <= thin) n++;
+    plan.push_back({(int32_t)L, (int32_t)n});
+    L += n;
+  }
+}
+
+// The lists, the diagonal and the level sets of a TRSV handle from host CSR arrays.  Returns with the stream synchronised.
+static int build_trsv(sh_engine *e, sh_trsv_graph *g, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                      const void *val) {
+  g->rows = rows; g->nnz = nnz;
+  DevArrays &own = g->dev;
+  DevArrays tmp;
+  int32_t *t_rp = nullptr, *t_ci = nullptr, *t_out_ptr = nullptr, *t_out_row = nullptr, *t_wait = nullptr;
+  uint32_t *t_val = nullptr, *t_flag = nullptr, *t_pos = nullptr, *t_word = nullptr, *t_max = nullptr, *t_zero = nullptr;
+  uint64_t *t_key = nullptr, *t_sorted = nullptr;
+  int64_t S = 0;
+  const int bits = 32 - __builtin_clz((unsigned)std::max<int64_t>(rows - 1, 1));   // (rows <= 2^31 - 256)
+  const dim3 blk(WL_BS);
+  const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
+  HIP_TRY(e, own.alloc(&g->d_in_ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_diag, rows * 8));
+  HIP_TRY(e, own.alloc(&g->d_xw, rows * 8));
+  HIP_TRY(e, own.alloc(&g->d_order, rows * 4));
+  HIP_TRY(e, own.alloc(&g->d_level, rows * 4));
+  HIP_TRY(e, hipMemsetAsync(g->d_in_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  HIP_TRY(e, tmp.alloc(&t_max, 4));
+  HIP_TRY(e, tmp.alloc(&t_zero, 8));
+  const uint32_t zero0[2] = {0u, 0xFFFFFFFFu};
+  HIP_TRY(e, hipMemsetAsync(t_max, 0, 4, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(t_zero, zero0, 8, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, tmp.alloc(&t_rp, (rows + 1) * 4));
+  HIP_TRY(e, tmp.alloc(&t_out_ptr, (rows + 1) * 4));
+  HIP_TRY(e, hipMemcpyAsync(t_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemsetAsync(t_out_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  if (rows > 0 && nnz > 0) {
+    HIP_TRY(e, tmp.alloc(&t_ci, nnz * 4));
+    HIP_TRY(e, tmp.alloc(&t_val, nnz * 4));
+    HIP_TRY(e, tmp.alloc(&t_flag, (nnz + 1) * 4));
+    HIP_TRY(e, tmp.alloc(&t_pos, (nnz + 1) * 4));
+    HIP_TRY(e, hipMemcpyAsync(t_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(t_val, val, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(trsv_flag, grid_for(nnz + 1), blk, 0, e->stream, t_rp, t_ci, nnz, (int32_t)rows, g->uplo, t_flag);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_exclusive_sum_u32(e->stream, t_flag, t_pos, nnz + 1));
+    uint32_t n = 0;
+    HIP_TRY(e, hipMemcpy(&n, t_pos + nnz, 4, hipMemcpyDeviceToHost));
+    S = (int64_t)n;
+  }
+  if (rows > 0) {   // (a row without entries has d = +0.0 too)
+    if (g->unit) HIP_TRY(e, hipMemsetAsync(g->d_diag, 0, (size_t)rows * 8, e->stream));
+    else {
+      hipLaunchKernelGGL(trsv_diag, grid_for(rows), blk, 0, e->stream, t_rp, t_ci, (const float *)t_val, (int32_t)rows, g->d_diag, t_zero);
+      HIP_TRY(e, hipGetLastError());
+    }
+  }
+  g->edges = S;
+  HIP_TRY(e, own.alloc(&g->d_in_col, S * 4));
+  HIP_TRY(e, own.alloc(&g->d_val, S * 4));
+  HIP_TRY(e, tmp.alloc(&t_out_row, S * 4));
+  if (S > 0) {
+    HIP_TRY(e, tmp.alloc(&t_key, S * 8));
+    HIP_TRY(e, tmp.alloc(&t_sorted, S * 8));
+    HIP_TRY(e, tmp.alloc(&t_word, S * 4));
+    hipLaunchKernelGGL(trsv_keys, grid_for(nnz), blk, 0, e->stream, t_rp, t_ci, t_val, t_flag, t_pos, nnz, (int32_t)rows, bits, t_key, t_word);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_pairs_u64_u32(e->stream, t_key, t_sorted, t_word, (uint32_t *)g->d_val, S, 2 * bits));
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(S, rows + 1)), blk, 0, e->stream, t_sorted, S, rows, bits, g->d_in_ptr, g->d_in_col);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(trsv_flip, grid_for(S), blk, 0, e->stream, t_sorted, S, bits, t_key);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_keys_u64(e->stream, t_key, t_sorted, S, 2 * bits));
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(S, rows + 1)), blk, 0, e->stream, t_sorted, S, rows, bits, t_out_ptr, t_out_row);
+    HIP_TRY(e, hipGetLastError());
+    const dim3 mgrid((unsigned)std::max(1, std::min(e->n_cus * 4, TRSV_MAX_BLOCKS)));
+    hipLaunchKernelGGL(wl_max_len, mgrid, blk, 0, e->stream, g->d_in_ptr, rows, t_max);
+    HIP_TRY(e, hipGetLastError());
+  }
+  int rc;
+  if ((rc = open_control(e, g, TRSV_CTL_BYTES, TRSV_CTL_BYTES + TRSV_PART_BYTES)))
+    return rc;
+  // the analysis: gated rounds, one level each
+  g->lstart.assign(1, 0u);
+  if (rows > 0) {
+    TrsvFlip F{(int32_t)rows, t_out_ptr, t_out_row, nullptr, g->d_level, {nullptr, nullptr}, {nullptr, nullptr}};
+    const int64_t places = S / (TRSV_PIECE / 2) + 1;   // see wl_push_pieces
+    HIP_TRY(e, tmp.alloc(&t_wait, rows * 4));
+    F.wait = t_wait;
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(e, tmp.alloc(&F.list[i], rows * 4));
+      HIP_TRY(e, tmp.alloc(&F.pieces[i], places * (int64_t)sizeof(WlPiece)));
+    }
+    const int nblocks = std::max(1, std::min(e->n_cus * 4, TRSV_MAX_BLOCKS));
+    const dim3 grid((unsigned)nblocks);
+    HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+    hipLaunchKernelGGL(trsv_seed, grid, blk, 0, e->stream, g->d_ctl, (const int32_t *)g->d_in_ptr, F);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+    const auto enqueue = [&](int s, int k) {
+      hipLaunchKernelGGL(trsv_settle, grid, blk, 0, e->stream, g->d_ctl, s, F, g->d_part);
+      HIP_TRY(e, hipGetLastError());
+      hipLaunchKernelGGL(trsv_close, dim3(1), blk, 0, e->stream, g->d_ctl, k, s, nblocks, g->d_part);
+      HIP_TRY(e, hipGetLastError());
+      return (int)SH_OK;
+    };
+    const auto take = [&](int, const TrsvRec &r, uint64_t) {
+      g->lstart.push_back(g->lstart.back() + r.size);
+      g->max_width = std::max<int64_t>(g->max_width, (int64_t)r.size);
+    };
+    int32_t it = 0;
+    bool done = false;
+    uint64_t total = 0;
+    if ((rc = run_batches(e, "sh_trsv_graph_create: round", g, (int32_t)std::min<int64_t>(rows, 0x7FFFFFFF), &it, &done, &total, enqueue, take)))
+      return rc;
+    if (!done || (int64_t)g->lstart.back() != rows)
+      return fail(e, SH_EHIP, "sh_trsv_graph_create: the analysis settled %lld of %lld rows in %d rounds", (long long)g->lstart.back(),
+                  (long long)rows, (int)it);
+    g->levels = it;
+    // order: one sort of (level << bits | row)
+    const int lbits = 32 - __builtin_clz((unsigned)std::max<int64_t>(g->levels - 1, 1));
+    uint64_t *t_lkey = nullptr, *t_lsorted = nullptr;
+    HIP_TRY(e, tmp.alloc(&t_lkey, rows * 8));
+    HIP_TRY(e, tmp.alloc(&t_lsorted, rows * 8));
+    hipLaunchKernelGGL(trsv_rank_keys, grid_for(rows), blk, 0, e->stream, (const int32_t *)g->d_level, (int32_t)rows, bits, t_lkey);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_keys_u64(e->stream, t_lkey, t_lsorted, rows, bits + lbits));
+    hipLaunchKernelGGL(trsv_order, grid_for(rows), blk, 0, e->stream, (const uint64_t *)t_lsorted, (int32_t)rows, bits, g->d_order);
+    HIP_TRY(e, hipGetLastError());
+  }
+  HIP_TRY(e, own.alloc(&g->d_lstart, (g->levels + 1) * 4));
+  HIP_TRY(e, hipMemcpyAsync(g->d_lstart, g->lstart.data(), (size_t)(g->levels + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  uint32_t longest = 0, zero[2] = {0u, 0xFFFFFFFFu};
+  HIP_TRY(e, hipMemcpyAsync(&longest, t_max, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(zero, t_zero, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  g->max_list = (int64_t)longest;
+  g->zero_diag = (int64_t)zero[0];
+  g->first_zero = zero[0] ? (int64_t)zero[1] : -1;
+  return SH_OK;   // (the flipped lists, the keys and the work lists go with tmp)
+}
+
+extern "C" {
+
+int sh_trsv_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                         int32_t uplo, int32_t unit, sh_trsv_graph **out) {
+  if (out) *out = nullptr;
+  // what the scalars alone decide comes first
+  if (uplo != 0 && uplo != 1)
+    return fail(e, SH_EINVAL, "%s: uplo = %d, must be 0 (lower) or 1 (upper)", TRSV_CREATE, (int)uplo);
+  if (unit != 0 && unit != 1)
+    return fail(e, SH_EINVAL, "%s: unit = %d, must be 0 (the diagonal is stored) or 1 (it is one)", TRSV_CREATE, (int)unit);
+  return create_graph_handle<sh_trsv_graph>(e, TRSV_CREATE, rows, nnz, row_ptr, col_idx, val, out, [&](sh_trsv_graph *g) -> int {
+    g->uplo = uplo; g->unit = unit;
+    return build_trsv(e, g, rows, nnz, row_ptr, col_idx, val);
+  });
+}
+
+int sh_trsv_graph_free(sh_engine *e, sh_trsv_graph *g) { return free_handle(e, g); }
+
+int sh_trsv_graph_footprint(const sh_trsv_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
+
+int sh_trsv_graph_entries(const sh_trsv_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->edges); }
+
+int sh_trsv_graph_levels(const sh_trsv_graph *g, int64_t *levels) { return HANDLE_GET(g, levels, g->levels); }
+
+int sh_trsv_graph_max_list(const sh_trsv_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->max_list); }
+
+int sh_trsv_graph_max_width(const sh_trsv_graph *g, int64_t *rows) { return HANDLE_GET(g, rows, g->max_width); }
+
+int sh_trsv_graph_zero_diag(const sh_trsv_graph *g, int64_t *rows) { return HANDLE_GET(g, rows, g->zero_diag); }
+
+int sh_trsv_graph_first_zero(const sh_trsv_graph *g, int64_t *row) { return HANDLE_GET(g, row, g->first_zero); }
+
+int sh_trsv_graph_level(sh_engine *e, sh_trsv_graph *g, sh_vec *level) {
+  if (!e || !g || !level)
+    return fail(e, SH_EINVAL, "sh_trsv_graph_level: NULL argument (engine, graph or level)");
+  if (level->n < g->rows)
+    return fail(e, SH_ESHAPE, "sh_trsv_graph_level: level is shorter than the graph's %lld rows", (long long)g->rows);
+  if (g->rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipMemcpyAsync(level->d, g->d_level, (size_t)g->rows * 4, hipMemcpyDeviceToDevice, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  return SH_OK;
+}
+
+int sh_trsv(sh_engine *e, sh_trsv_graph *g, const sh_vec *b, sh_vec *x, int32_t f32, int32_t thin, int64_t *launches, int64_t *runs,
+            int64_t *levels_in_runs, uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (f32 != 0 && f32 != 1)
+    return fail(e, SH_EINVAL, "sh_trsv: f32 = %d, must be 0 (b and x are float64) or 1 (float32)", (int)f32);
+  if (thin > TRSV_THIN_MAX)
+    return fail(e, SH_EINVAL, "sh_trsv: thin = %d, must be at most %d (negative: the default, %d)", (int)thin, TRSV_THIN_MAX, TRSV_THIN);
+  if (!e || !g || !b || !x)
+    return fail(e, SH_EINVAL, "sh_trsv: NULL argument (engine, graph, b or x)");
+  const int64_t rows = g->rows, per = f32 ? 1 : 2;
+  if (b->n < per * rows)
+    return fail(e, SH_ESHAPE, "sh_trsv: b holds fewer than %d elements for each of the graph's %lld rows", (int)per, (long long)rows);
+  if (x->n < per * rows)
+    return fail(e, SH_ESHAPE, "sh_trsv: x holds fewer than %d elements for each of the graph's %lld rows", (int)per, (long long)rows);
+  if (!f32 && (((uintptr_t)b->d & 7u) || ((uintptr_t)x->d & 7u)))
+    return fail(e, SH_EINVAL, "sh_trsv: b or x is not aligned to 8 bytes");
+  if (rows > 0 && b->d != x->d) {
+    const char *pb = (const char *)b->d, *px = (const char *)x->d;
+    const int64_t bytes = rows * 4 * per;
+    if (pb < px + bytes && px < pb + bytes)
+      return fail(e, SH_EINVAL, "sh_trsv: b and x overlap without being the same vector");
+  }
+  if (thin < 0) thin = TRSV_THIN;
+  std::vector<TrsvLaunch> plan;
+  trsv_plan(g->lstart, thin, TRSV_RUN, plan);
+  int64_t n_runs = 0, in_runs = 0;
+  for (const TrsvLaunch &l : plan) { n_runs += l.n > 0; in_runs += l.n; }
+  if (launches) *launches = (int64_t)plan.size();
+  if (runs) *runs = n_runs;
+  if (levels_in_runs) *levels_in_runs = in_runs;
+  if (total_ns) *total_ns = 0;
+  if (rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  const TrsvLists T{g->d_in_ptr, g->d_in_col, g->d_val, g->d_diag, g->d_order};
+  const TrsvIo Io{b->d, f32 ? g->d_xw : (double *)x->d, f32 ? (float *)x->d : nullptr, f32, g->unit};
+  const dim3 block(WL_BS);
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  for (const TrsvLaunch &l : plan) {
+    if (l.n > 0) {
+      hipLaunchKernelGGL(trsv_run, dim3(1), block, 0, e->stream, l.L0, l.n, (const uint32_t *)g->d_lstart, T, Io);
+    } else {
+      const uint32_t a = g->lstart[l.L0], z = g->lstart[l.L0 + 1];
+      const dim3 grid((unsigned)std::min<int64_t>(((int64_t)(z - a) + WL_BS - 1) / WL_BS, TRSV_MAX_BLOCKS));
+      hipLaunchKernelGGL(trsv_level, grid, block, 0, e->stream, a, z, T, Io);
+    }
+    HIP_TRY(e, hipGetLastError());
+  }
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  uint64_t ns = 0;
+  HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+  if (total_ns) *total_ns = ns;
   return SH_OK;
 }
 

@@ -399,6 +399,10 @@ hipError_t device_exclusive_sum_u32(hipStream_t stream, const uint32_t *in, uint
 // n 64-bit keys sorted ascending by their bits [0, bits) (rocPRIM radix sort, plan_gpu.hip); in and out are different arrays.
 // Waits for the stream.
 hipError_t device_sort_keys_u64(hipStream_t stream, const uint64_t *in, uint64_t *out, int64_t n, int bits);
+// The same with a 32-bit word riding on every key; the sort is STABLE: equal keys keep the order they came in
+// (sh_trsv_graph_create: the parallel entries of a list stay in the order given).  Waits for the stream.
+hipError_t device_sort_pairs_u64_u32(hipStream_t stream, const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout,
+                                     int64_t n, int bits);
 
 // ---- the (or,and) semiring on bits (see bits.hip.h) -----------------------
 struct BitsHost {

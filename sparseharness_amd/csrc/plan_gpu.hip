@@ -1054,6 +1054,19 @@ hipError_t device_sort_keys_u64(hipStream_t stream, const uint64_t *in, uint64_t
   return r;
 }
 
+// The same with a 32-bit word riding on every key (sh_trsv_graph_create: the entries' values).  A radix sort is stable.
+hipError_t device_sort_pairs_u64_u32(hipStream_t stream, const uint64_t *kin, uint64_t *kout, const uint32_t *vin, uint32_t *vout,
+                                     int64_t n, int bits) {
+  if (n <= 0) return hipSuccess;
+  CubTemp tmp;
+  size_t bytes = 0;
+  hipError_t r = sort_pairs((void *)nullptr, bytes, kin, kout, vin, vout, n, 0, bits, stream);
+  if (r == hipSuccess) r = tmp.reserve(bytes);
+  if (r == hipSuccess) r = sort_pairs(tmp.p, bytes, kin, kout, vin, vout, n, 0, bits, stream);
+  if (r == hipSuccess) r = hipStreamSynchronize(stream);   // (the temporary storage dies here)
+  return r;
+}
+
 int build_bits_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t nnz, const int32_t *d_rp, const int32_t *d_ci,
                         const uint32_t *d_val, BitsHost &H, uint32_t **d_ent, std::string &why) {
   H.n_rr = (int32_t)std::max<int64_t>(1, (rows + BITS_BR - 1) / BITS_BR);

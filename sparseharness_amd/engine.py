@@ -634,6 +634,25 @@ class Engine:
                                    C.byref(steps), *ptrs, C.byref(total)))
         return steps.value, depths[:n].copy(), reached[:n].copy(), smax[:n].copy(), edges[:n].copy(), per[:n].copy(), total.value
 
+    # ---- sparse triangular solve: x = T^-1 b by level sets, float64, every sum in one fixed order
+    def trsv_graph(self, row_ptr, col_idx, val, uplo=0, unit=0):
+        """The handle Engine.trsv needs (trsv.TrsvGraph), from the CSR arrays of a square matrix: its lower (uplo = 0) or
+        upper (1) triangle; unit = 1 takes the diagonal as one and ignores stored diagonal entries.  An ILU(0) factor kept
+        in one matrix gives two handles: (uplo=0, unit=1) and (uplo=1, unit=0)."""
+        from .trsv import TrsvGraph   # (trsv.py imports this module)
+        return self._graph(TrsvGraph, row_ptr, col_idx, val, uplo, unit)
+
+    def trsv(self, G, b, x, f32=0, thin=None):
+        """-> (launches, runs, levels_in_runs, total_ns): the launches of the call, how many of them were runs of thin
+        levels inside one workgroup, the levels those held, device ns.  b, x: vectors of >= 2 * rows 4-byte elements
+        (rows float64, 8-byte aligned), or with f32 = 1 of >= rows float32; x may be b.  thin: consecutive levels of at
+        most `thin` rows share a launch (0: one launch per level; None: the default, trsv.TRSV_THIN).  x does not depend
+        on thin."""
+        launches, runs, in_runs, total = C.c_int64(), C.c_int64(), C.c_int64(), C.c_uint64()
+        self._chk(abi.load().sh_trsv(self.h, G.h, b.h, x.h, f32, -1 if thin is None else int(thin), C.byref(launches),
+                                     C.byref(runs), C.byref(in_runs), C.byref(total)))
+        return launches.value, runs.value, in_runs.value, total.value
+
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
         dt = elem_dtype(semiring)

@@ -116,6 +116,21 @@ int sh_bc_scores(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_
                  const int32_t *sources, int32_t n_sources, int32_t accumulate, double *bc, double *sigma, int32_t *level,
                  int32_t *depth, int64_t *reached, double *sigma_max, int64_t *edges);
 
+/* The sparse triangular solve T x = b of a square CSR matrix by plain substitution (single-threaded): the gold for
+ * sh_trsv.  uplo 0 lower / 1 upper, unit 0 / 1 (the diagonal is one and stored diagonal entries are ignored).  Every
+ * stored entry with 0 <= c < rows takes part whatever its value; entries of the other triangle and columns out of range
+ * are ignored; rows need not be sorted and parallel entries are separate terms, in ascending (column, position as
+ * given).  Every sum is float64 in the order that include/sparseharness_hip.h fixes (SUM of signed terms), so x equals
+ * sh_trsv's bit for bit.  f32 0: b and x are rows doubles; 1: rows floats, b widened, x rounded once on the way out (later
+ * rows read the unrounded value).  b and x may be the same array.  level[r] (rows words, may be NULL) = 0 for an empty
+ * list, else 1 + the largest level in the list.  figures (6 words, may be NULL): list entries, levels, the longest list,
+ * the widest level, the rows with d == 0 (0 when unit), the smallest such row or -1.  Return 0, -1 bad argument. */
+int sh_trsv_solve(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val, const void *b,
+                  int32_t uplo, int32_t unit, int32_t f32, void *x, int32_t *level, int64_t *figures);
+/* SUM of n signed float64 terms as sh_trsv defines it.  tier 0: as sh_trsv chooses (one lane up to 8 terms, pieces
+ * beyond); 1: the one-lane formula where n <= 8; 2: the pieces for any n.  The tiers are one function. */
+double sh_trsv_list_sum(const double *t, int64_t n, int32_t tier);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

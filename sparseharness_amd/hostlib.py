@@ -3,7 +3,7 @@ loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
 host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp), sh_tri
 (host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp), sh_truss (host/src/truss_numbers.cpp), sh_color
-(host/src/greedy_colors.cpp), sh_msf (host/src/msf_edges.cpp), sh_match (host/src/greedy_matching.cpp), sh_rcm (host/src/rcm_order.cpp) and sh_bc (host/src/bc_scores.cpp)."""
+(host/src/greedy_colors.cpp), sh_msf (host/src/msf_edges.cpp), sh_match (host/src/greedy_matching.cpp), sh_rcm (host/src/rcm_order.cpp), sh_bc (host/src/bc_scores.cpp) and sh_trsv (host/src/trsv_solve.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -42,6 +42,8 @@ SIGNATURES = {
     "sh_rcm_order": (C.c_int, _csr + [C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.POINTER(_i64), _i64, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sh_bc_scores": (C.c_int, _csr + [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sh_trsv_solve": (C.c_int, _csr + [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "sh_trsv_list_sum": (C.c_double, [_vp, _i64, C.c_int32]),
     "sh_mm_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]),
     "sh_mm_load_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]),
     "sh_host_csr_release": (None, [C.POINTER(_HostCsr)]),
@@ -254,6 +256,30 @@ def bc_scores(row_ptr, col_idx, val, sources, bc=None):
     _gold("sh_bc_scores", row_ptr, col_idx, val, _p(sources), k, 0 if bc is None else 1, _p(out), _p(sigma), _p(level),
           _p(depths), _p(reached), _p(smax), _p(edges))
     return out[:n], sigma[:n], level[:n], depths[:k], reached[:k], smax[:k], edges[:k]
+
+
+def trsv_solve(row_ptr, col_idx, val, b, uplo=0, unit=0, f32=0):
+    """-> (x, level, figures): x (float64, or float32 when f32) = the solution of T x = b for the triangle `uplo` (0 lower,
+    1 upper) of the square matrix, its diagonal taken as one when `unit` (Engine.trsv's x), level[r] (int32) = 0 for an
+    empty list, else 1 + the largest level in r's list, and figures = dict(entries, levels, max_list, max_width,
+    zero_diag, first_zero) (the getters of trsv.TrsvGraph), by plain substitution on the host whose every float64 sum
+    runs in the order include/sparseharness_hip.h fixes: the results are sh_trsv's bit for bit.  Every stored entry with
+    0 <= c < rows takes part whatever its value; parallel entries are separate terms."""
+    n = len(row_ptr) - 1
+    b = np.ascontiguousarray(b, np.float32 if f32 else np.float64)
+    assert len(b) >= n
+    x = np.zeros(max(n, 1), b.dtype)
+    level, fig = np.zeros(max(n, 1), np.int32), np.zeros(6, np.int64)
+    _gold("sh_trsv_solve", row_ptr, col_idx, val, _p(b), int(uplo), int(unit), int(f32), _p(x), _p(level), _p(fig))
+    names = ("entries", "levels", "max_list", "max_width", "zero_diag", "first_zero")
+    return x[:n], level[:n], dict(zip(names, (int(v) for v in fig)))
+
+
+def trsv_list_sum(terms, tier=0):
+    """SUM of signed float64 terms as sh_trsv defines it (tier 0: as sh_trsv chooses; 1: the one-lane formula, at most 8
+    terms; 2: the pieces)."""
+    t = np.ascontiguousarray(terms, np.float64)
+    return float(load().sh_trsv_list_sum(_p(t), len(t), int(tier)))
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
