@@ -21,7 +21,7 @@ template <class SR>
 int emulate(const TiledHost &H, int64_t rows, int64_t cols, const uint32_t *x, uint32_t *y, int64_t *stats) {
   using T = typename SR::T;
   constexpr uint32_t POISON = 0x7FC0DEADu;
-  std::vector<uint32_t> P((size_t)H.p_len + 4, POISON), partial((size_t)H.n_partials + 1, POISON), xs((size_t)TCOLS + 4);
+  std::vector<uint32_t> P((size_t)H.p_len + 4, POISON), partial((size_t)H.n_partials + 1, POISON), xs((size_t)H.tcols + 4);
   const bool coded = !H.vdict.empty();
   auto value_at = [&](int64_t q) -> uint32_t {
     if (!coded) return H.tval[(size_t)q];
@@ -32,14 +32,22 @@ int emulate(const TiledHost &H, int64_t rows, int64_t cols, const uint32_t *x, u
   // ---- phase 1
   for (const TileChunk &ch : H.chunks) {
     if (ch.s >= ch.e) continue;
-    const int64_t c0 = (int64_t)ch.tile * TCOLS;
-    for (int i = 0; i < TCOLS; i++) xs[(size_t)i] = (c0 + i < cols) ? x[c0 + i] : tobits<T>(SR::identity());
-    xs[(size_t)TCOLS] = tobits<T>(SR::identity());
+    const int64_t c0 = (int64_t)ch.tile * H.tcols;
+    for (int i = 0; i < H.tcols; i++) xs[(size_t)i] = (c0 + i < cols) ? x[c0 + i] : tobits<T>(SR::identity());
+    xs[(size_t)H.tcols] = tobits<T>(SR::identity());
+    const uint32_t first_mask = tcol_first_mask(H.tcols);
     auto prod = [&](int64_t q, uint32_t colmask) { return SR::mul(hbits<T>(xs[H.tcol[(size_t)q] & colmask]), hbits<T>(value_at(q))); };
     if (ch.hs > ch.s) {   // light chunk: blocks of 64 groups; a group stores 4 products unless it folds into the one in front
       if (ch.s % 256 || ch.e % 4) return -10;
       const int64_t gs = ch.s / 4, le = ch.e / 4;
-      auto flagged = [&](int64_t g) { return g < le && (H.tcol[(size_t)g * 4] & TCOL_FOLD) != 0; };
+      // the fold flag of group g: bit 15 of its first column code, or (wide layouts) its bit in the mask word of its block
+      const bool wide = H.tcols != TCOLS;
+      if (wide && H.fmask.size() != H.obase.size()) return -14;
+      auto flagged = [&](int64_t g) {
+        if (g >= le) return false;
+        if (!wide) return (H.tcol[(size_t)g * 4] & TCOL_FOLD) != 0;
+        return ((H.fmask[(size_t)ch.ob0 + (size_t)((g - gs) / 64)] >> ((g - gs) % 64)) & 1ull) != 0;
+      };
       for (int64_t blk = 0; gs + blk * 64 < le; blk++) {
         int64_t pos = H.obase[(size_t)ch.ob0 + (size_t)blk];
         for (int64_t g = gs + blk * 64; g < std::min(le, gs + blk * 64 + 64); g++) {
@@ -51,8 +59,8 @@ int emulate(const TiledHost &H, int64_t rows, int64_t cols, const uint32_t *x, u
           const bool takes = (lane & 1) == 0 && lane + 1 < 64 && flagged(g + 1);
           if (pos + 4 > H.p_len) return -11;
           for (int k = 0; k < 4; k++) {
-            T acc = prod(g * 4 + k, k == 0 ? TCOL_MASK : 0xFFFFu);
-            if (takes) acc = SR::add(acc, prod((g + 1) * 4 + k, k == 0 ? TCOL_MASK : 0xFFFFu));
+            T acc = prod(g * 4 + k, k == 0 ? first_mask : 0xFFFFu);
+            if (takes) acc = SR::add(acc, prod((g + 1) * 4 + k, k == 0 ? first_mask : 0xFFFFu));
             P[(size_t)pos + k] = tobits<T>(acc);
           }
           pos += 4;
@@ -127,7 +135,7 @@ int emulate(const TiledHost &H, int64_t rows, int64_t cols, const uint32_t *x, u
   if (stats) {
     stats[0] = H.stream_len; stats[1] = H.light_entries; stats[2] = H.p_len; stats[3] = (int64_t)H.bins.size();
     stats[4] = (int64_t)H.chunks.size(); stats[5] = (int64_t)H.heavy.size(); stats[6] = poison_reads;
-    stats[7] = (cols + TCOLS - 1) / TCOLS;
+    stats[7] = (cols + H.tcols - 1) / H.tcols;
   }
   (void)rows;
   return 0;
@@ -218,6 +226,40 @@ extern "C" int sh_debug_plan_coding(int64_t rows, int64_t cols, int64_t nnz, con
   *distinct = H.vdict.empty() ? 0 : H.vdict_used;
   return 0;
 }
+// The layout the host builder gives a matrix, for the CPU tests that look at it (tests/test_wide_tile_cpu.py):
+// info[0..9] = tile width, tiles, stream_len, light_len, p_len, code bits (0: raw words), words of obase, words of
+// fmask (0: a narrow layout), work items, a 64-bit FNV-1a hash over every array of the layout (two layouts with the
+// same bytes hash alike).  tcol / obase / fmask (each may be NULL) get up to cap_* elements of those arrays; describe
+// (cap_describe bytes) the string sh_csr_describe would print for the layout.  0, or -1: the builder refused.
+extern "C" int sh_debug_plan_layout(int64_t rows, int64_t cols, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
+                                    const sh_plan_options *opt_p, int n_cus, int64_t *info, uint16_t *tcol, int64_t cap_tcol, uint32_t *obase,
+                                    int64_t cap_obase, uint64_t *fmask, int64_t cap_fmask, char *describe, int64_t cap_describe) {
+  sh_plan_options opt;
+  if (opt_p) opt = *opt_p; else sh_plan_options_default(&opt);
+  TiledHost H;
+  if (!build_tiled_plan(rows, cols, nnz, row_ptr, col_idx, (const uint32_t *)val, opt, n_cus, H)) return -1;
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&](const void *p, size_t n) { for (size_t k = 0; k < n; k++) { h ^= ((const uint8_t *)p)[k]; h *= 1099511628211ull; } };
+  mix(H.bins.data(), H.bins.size() * sizeof(RowBin)); mix(H.chunks.data(), H.chunks.size() * sizeof(TileChunk));
+  mix(H.heavy.data(), H.heavy.size() * sizeof(LongRow)); mix(H.tval.data(), H.tval.size() * 4); mix(H.gdest.data(), H.gdest.size() * 4);
+  mix(H.gblk.data(), H.gblk.size() * 4); mix(H.lrp.data(), H.lrp.size() * 4); mix(H.obase.data(), H.obase.size() * 4);
+  mix(H.ptab.data(), H.ptab.size() * 4); mix(H.ptile.data(), H.ptile.size() * 2); mix(H.tcode.data(), H.tcode.size());
+  mix(H.vdict.data(), H.vdict.size() * 4); mix(H.tcol.data(), H.tcol.size() * 2); mix(H.pslot.data(), H.pslot.size() * 2);
+  mix(H.fmask.data(), H.fmask.size() * 8);
+  if (info) {
+    info[0] = H.tcols; info[1] = (cols + H.tcols - 1) / H.tcols; info[2] = H.stream_len; info[3] = H.light_len; info[4] = H.p_len;
+    info[5] = H.vdict.empty() ? 0 : H.code_bits; info[6] = (int64_t)H.obase.size(); info[7] = (int64_t)H.fmask.size();
+    info[8] = (int64_t)H.chunks.size(); info[9] = (int64_t)h;
+  }
+  if (tcol) memcpy(tcol, H.tcol.data(), (size_t)std::min<int64_t>(cap_tcol, (int64_t)H.tcol.size()) * 2);
+  if (obase) memcpy(obase, H.obase.data(), (size_t)std::min<int64_t>(cap_obase, (int64_t)H.obase.size()) * 4);
+  if (fmask) memcpy(fmask, H.fmask.data(), (size_t)std::min<int64_t>(cap_fmask, (int64_t)H.fmask.size()) * 8);
+  if (describe && cap_describe > 0)
+    describe_tiled(describe, (size_t)cap_describe, cols, H.tcols, (int)H.vdict.size(), H.code_bits, H.vdict_used, (long long)H.chunks.size(),
+                   (long long)H.bins.size(), (long long)H.heavy.size(), H.stream_len, H.light_entries, H.p_len,
+                   opt.fold != 0 && (H.tcols != TCOLS || TCOL_FOLD != 0));
+  return 0;
+}
 // The CSR arrays of a matrix on the device as the device builders take them, owned by `own`: NULL, or the HIP call that failed.
 static const char *debug_upload_csr(DevArrays &own, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val,
                                     int32_t **d_rp, int32_t **d_ci, uint32_t **d_val) {
@@ -262,7 +304,7 @@ extern "C" int sh_debug_compare_builds(sh_engine *e, int64_t rows, int64_t cols,
   scalar("heavy_base", hh.heavy_base, hg.heavy_base); scalar("light_entries", hh.light_entries, hg.light_entries);
   scalar("n_partials", hh.n_partials, hg.n_partials); scalar("code_bits", hh.code_bits, hg.code_bits); scalar("vdict_used", hh.vdict_used, hg.vdict_used);
   scalar("n_bins", (long long)hh.bins.size(), (long long)hg.bins.size()); scalar("n_chunks", (long long)hh.chunks.size(), (long long)hg.chunks.size());
-  scalar("n_heavy", (long long)hh.heavy.size(), (long long)hg.heavy.size());
+  scalar("n_heavy", (long long)hh.heavy.size(), (long long)hg.heavy.size()); scalar("tcols", hh.tcols, hg.tcols);
   scalar("tile_fill*1e6", (long long)(hh.tile_fill * 1e6), (long long)(hg.tile_fill * 1e6));
   auto host_bytes = [&](const char *name, const void *a, size_t na, const void *b, size_t nb, size_t elem) {
     if (na != nb) { snprintf(line, sizeof line, "%s: %zu vs %zu bytes\n", name, na, nb); rep += line; diffs++; return; }
@@ -298,6 +340,7 @@ extern "C" int sh_debug_compare_builds(sh_engine *e, int64_t rows, int64_t cols,
   dev_bytes("ptab", hh.ptab.data(), hh.ptab.size() * 4, td.ptab, td.n_ptab, 4);
   dev_bytes("ptile", hh.ptile.data(), hh.ptile.size() * 2, td.ptile, td.n_ptab, 2);
   dev_bytes("obase", hh.obase.data(), hh.obase.size() * 4, td.obase, td.n_obase, 4);
+  dev_bytes("fmask", hh.fmask.data(), hh.fmask.size() * 8, td.fmask, td.n_fmask, 8);
   if (!hip_ok) { rep += "hipMemcpy (download) failed\n"; return finish(-3); }
   return finish(diffs);
 }

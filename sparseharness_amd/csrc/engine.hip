@@ -105,6 +105,8 @@ struct TiledLayout {   // the x-tiled two-phase plan (kernels.hip.h); built when
   uint32_t *d_tval = nullptr, *d_gdest = nullptr, *d_gblk = nullptr, *d_P = nullptr, *d_obase = nullptr;
   int32_t *d_ptab = nullptr;
   uint16_t *d_ptile = nullptr;     // per piece: its column tile
+  int tcols = TCOLS;               // columns per x tile: TCOLS, or TCOLS_WIDE for a wide layout (plan_common.h::pick_tile_cols)
+  uint64_t *d_fmask = nullptr;     // wide layouts: the fold flags, one mask word per block of d_obase
   int32_t *d_ptab_live = nullptr;  // per launch of a semiring with absorbing words: ptab with the pieces of dead tiles marked (tiled_mark_dead)
   uint32_t *d_tile_live = nullptr; // per column tile: phase 1 found a word of x that is not absorbing
   int64_t n_pieces = 0;
@@ -229,6 +231,19 @@ static int plan_array(sh_engine *e, sh_csr *m, T **p, D *&dev, size_t n_dev, con
   m->tiled.dev.adopt(dev, n_dev * sizeof(T) + slack);
   dev = nullptr;
   return SH_OK;
+}
+
+// The describe string of a tiled layout (sh_csr_describe; the tools build also prints it for a layout that was only
+// built on the host).  A wide layout says its tile width; a narrow layout's string is what it always was.
+static void describe_tiled(char *buf, size_t buflen, int64_t cols, int tcols, int n_vdict, int code_bits, int vdict_used, long long chunks,
+                           long long bins, long long heavy_rows, int64_t stream_len, int64_t light_entries, int64_t p_len, bool fold) {
+  char vals[32], tile[24] = "";
+  if (n_vdict) snprintf(vals, sizeof vals, "dict%d(%d)", code_bits, vdict_used);
+  else snprintf(vals, sizeof vals, "raw");
+  if (tcols != TCOLS) snprintf(tile, sizeof tile, " tile=%d", tcols);
+  snprintf(buf, buflen, "tiled values=%s tiles=%lld%s chunks=%lld bins=%lld heavy_rows=%lld stream=%.1fM light=%.1fM products=%.1fM%s", vals,
+           (long long)((cols + tcols - 1) / tcols), tile, chunks, bins, heavy_rows, stream_len / 1e6, light_entries / 1e6, p_len / 1e6,
+           fold ? " folded" : "");
 }
 
 extern "C" {
@@ -477,7 +492,9 @@ int sh_plan_row_work(int64_t rows, int64_t cols, int64_t nnz, const int32_t *row
   sh_plan_options opt;
   if (opt_p) opt = *opt_p; else sh_plan_options_default(&opt);
   const bool tiled = choose_plan(opt, cols, nnz) == PLAN_TILED && nnz > 0;
-  const int CT = (int)std::max<int64_t>(1, (cols + TCOLS - 1) / TCOLS);
+  // (the values are not known here: the tile width a matrix of this size gets unless it needs two-byte codes)
+  const int tcols = pick_tile_cols(true, 8, nnz);
+  const int CT = (int)std::max<int64_t>(1, (cols + tcols - 1) / tcols);
   const int64_t heavy_thr = std::min<int64_t>(TBIN / 4, std::max<int64_t>(512, (int64_t)std::max(1, opt.heavy_per_tile) * CT));
   uint64_t acc = 0;
   work_prefix[0] = 0;
@@ -618,7 +635,7 @@ static int build_tiled_layout(sh_engine *e, sh_csr *m, const HostCsr &h, const s
   if (want_tiled && !*tiled) {   // (tools builds: sh_debug_held_at_host_build)
     g_debug_held_at_host_build = 0;
     for (const void *p : {(const void *)td.tcol, (const void *)td.pslot, (const void *)td.tcode, (const void *)td.tval, (const void *)td.gdest,
-                          (const void *)td.gblk, (const void *)td.obase, (const void *)td.lrp, (const void *)td.ptab, (const void *)td.ptile})
+                          (const void *)td.gblk, (const void *)td.obase, (const void *)td.lrp, (const void *)td.ptab, (const void *)td.ptile, (const void *)td.fmask})
       if (p) g_debug_held_at_host_build++;
   }
 #endif
@@ -637,7 +654,8 @@ static int upload_tiled_layout(sh_engine *e, sh_csr *m, const sh_plan_options &o
   t.stream_len = th.stream_len;
   t.p_len = th.p_len;
   t.light_entries = th.light_entries;
-  t.fold = opt.fold != 0 && TCOL_FOLD != 0;
+  t.tcols = th.tcols;
+  t.fold = opt.fold != 0 && (th.tcols != TCOLS || TCOL_FOLD != 0);
   t.bin_r0.reserve(th.bins.size());
   for (const RowBin &b : th.bins) t.bin_r0.push_back(b.r0);
   RC_TRY(dev_array(e, t.dev, &t.d_bins, th.bins.data(), th.bins.size() * sizeof(RowBin), 0));
@@ -661,11 +679,12 @@ static int upload_tiled_layout(sh_engine *e, sh_csr *m, const sh_plan_options &o
   t.n_pieces = (int64_t)(m->built_on_device ? td.n_ptab : th.ptab.size());
   // dead pieces (launches of a semiring with absorbing words): the marked copy of ptab, the tiles' live words (all live until a launch says otherwise)
   RC_TRY(dev_array(e, t.dev, &t.d_ptab_live, nullptr, (size_t)t.n_pieces * 4, SLACK_WIDE));
-  const size_t ct = (size_t)std::max<int64_t>(1, (m->cols + TCOLS - 1) / TCOLS);
+  const size_t ct = (size_t)std::max<int64_t>(1, (m->cols + t.tcols - 1) / t.tcols);
   RC_TRY(dev_array(e, t.dev, &t.d_tile_live, nullptr, ct * 4, 0));
   HIP_TRY(e, hipMemsetD32Async((hipDeviceptr_t)t.d_tile_live, 1, ct, e->stream));
   RC_TRY(plan_array(e, m, &t.d_pslot, td.pslot, td.n_pslot, th.pslot, SLACK_WIDE));
   RC_TRY(plan_array(e, m, &t.d_obase, td.obase, td.n_obase, th.obase, SLACK_WIDE));
+  if (t.tcols != TCOLS) RC_TRY(plan_array(e, m, &t.d_fmask, td.fmask, td.n_fmask, th.fmask, SLACK_WIDE));
   RC_TRY(dev_array(e, t.dev, &t.d_P, nullptr, (size_t)std::max<int64_t>(t.p_len, 4) * 4, 16));
   RC_TRY(plan_array(e, m, (uint32_t **)&t.d_lrp, td.lrp, td.n_lrp, th.lrp, 16));   // (+16: see plan_gpu.hip)
   if (t.n_tlong) {
@@ -825,7 +844,7 @@ int sh_csr_plan(const sh_csr *m, int32_t *plan, uint64_t *streamed_bytes) {
     const uint64_t vec = 4ull * (m->rows + 1) + 4ull * m->cols + 4ull * m->rows;
     *streamed_bytes = (m->plan == PLAN_TILED)
                           ? (m->tiled.n_vdict ? 2ull : 6ull) * m->tiled.stream_len + (m->tiled.n_vdict ? (uint64_t)m->tiled.stream_len * m->tiled.code_bits / 8 : 0ull) + (uint64_t)(m->tiled.stream_len - m->tiled.light_len) / 4 /* gdest: 4 B per 16-entry strip */ +
-                                (uint64_t)m->tiled.light_len / 64 /* obase: 4 B per 64 groups */ +
+                                (uint64_t)m->tiled.light_len / 64 /* obase: 4 B per 64 groups */ + (m->tiled.d_fmask ? (uint64_t)m->tiled.light_len / 32 /* fmask: 8 B */ : 0ull) +
                                 4ull * m->tiled.p_len /* P written */ + 6ull * m->tiled.p_len + m->tiled.p_len / 6 /* phase 2: P, slot; piece tables ~0.14 B per product */ +
                                 vec /* x once: a tile is re-staged per phase-1 workgroup, but out of its XCD's L2 */
                           : 8ull * m->nnz + vec;
@@ -837,12 +856,9 @@ int sh_csr_describe(const sh_csr *m, char *buf, size_t buflen) {
   if (!m || !buf || buflen == 0)
     return SH_EINVAL;
   if (m->plan == PLAN_TILED) {
-    char vals[32];
-    if (m->tiled.n_vdict) snprintf(vals, sizeof vals, "dict%d(%d)", m->tiled.code_bits, m->tiled.n_vdict_used);
-    else snprintf(vals, sizeof vals, "raw");
-    snprintf(buf, buflen, "tiled values=%s tiles=%lld chunks=%d bins=%d heavy_rows=%d stream=%.1fM light=%.1fM products=%.1fM%s", vals,
-             (long long)((m->cols + TCOLS - 1) / TCOLS), m->tiled.n_chunks, m->tiled.n_bins, m->tiled.n_tlong, m->tiled.stream_len / 1e6,
-             m->tiled.light_entries / 1e6, m->tiled.p_len / 1e6, m->tiled.fold ? " folded" : "");
+    const TiledLayout &t = m->tiled;
+    describe_tiled(buf, buflen, m->cols, t.tcols, t.n_vdict, t.code_bits, t.n_vdict_used, t.n_chunks, t.n_bins, t.n_tlong, t.stream_len,
+                   t.light_entries, t.p_len, t.fold != 0);
   } else if (m->bits_only) {
     snprintf(buf, buflen, "bits-only");
   } else {
@@ -992,14 +1008,24 @@ static int launch_bits_layout(sh_engine *e, const sh_csr *A, const sh_vec *x, co
 }
 
 // Phase 1 of the tiled plan for one way of storing the values: CODE 0 raw words (d_tval), 1 / 2 / 3 dictionary codes of
-// 8 / 4 / 16 bits (d_tcode, d_vdict).
-template <class SR, int CODE>
-static void launch_phase1(sh_engine *e, const sh_csr *A, const sh_vec *x, StepDev st, int32_t skip_dead, uint32_t *tile_live) {
+// 8 / 4 / 16 bits (d_tcode, d_vdict), and for the layout's tile width (WIDE: TCOLS_WIDE columns, fold flags in d_fmask).
+template <class SR, int CODE, bool WIDE>
+static void launch_phase1_as(sh_engine *e, const sh_csr *A, const sh_vec *x, StepDev st, int32_t skip_dead, uint32_t *tile_live) {
   const TiledLayout &t = A->tiled;
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_tiled_phase1<SR, CODE>), dim3((unsigned)t.n_chunks), dim3(TBS), 0, e->stream,
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(spmv_tiled_phase1<SR, CODE, WIDE>), dim3((unsigned)t.n_chunks), dim3(TBS), 0, e->stream,
                      (const TileChunk *)t.d_chunks, CODE ? (const void *)t.d_tcode : (const void *)t.d_tval,
-                     CODE ? (const uint32_t *)t.d_vdict : (const uint32_t *)nullptr, t.d_tcol, t.d_gdest, t.d_obase,
+                     CODE ? (const uint32_t *)t.d_vdict : (const uint32_t *)nullptr, t.d_tcol, t.d_gdest, t.d_obase, (const uint64_t *)t.d_fmask,
                      (const uint32_t *)x->d, (int32_t)A->cols, t.d_P, t.d_tpartial, st.gate, skip_dead, tile_live);
+}
+template <class SR, int CODE>
+static int launch_phase1(sh_engine *e, const sh_csr *A, const sh_vec *x, StepDev st, int32_t skip_dead, uint32_t *tile_live) {
+  const TiledLayout &t = A->tiled;
+  if (t.tcols == TCOLS) { launch_phase1_as<SR, CODE, false>(e, A, x, st, skip_dead, tile_live); return SH_OK; }
+  // (two-byte codes have no wide kernel: their dictionary takes the LDS, and the builders keep such a layout narrow)
+  if constexpr (CODE != 3) {
+    if (t.tcols == TCOLS_WIDE && t.d_fmask) { launch_phase1_as<SR, CODE, true>(e, A, x, st, skip_dead, tile_live); return SH_OK; }
+  }
+  return SH_EINVAL;
 }
 
 template <class SR>
@@ -1018,10 +1044,12 @@ static int launch_tiled(sh_engine *e, const sh_csr *A, const sh_vec *x, const sh
   const bool mark_dead = SR::has_absorbing && skip_dead && t.n_bins > 0 && t.n_pieces > 0;
   uint32_t *tile_live = mark_dead ? t.d_tile_live : nullptr;
   if (t.n_chunks > 0) {
-    if (!t.n_vdict) launch_phase1<SR, 0>(e, A, x, st, skip_dead, tile_live);
-    else if (t.code_bits == 16) launch_phase1<SR, 3>(e, A, x, st, skip_dead, tile_live);
-    else if (t.code_bits == 4) launch_phase1<SR, 2>(e, A, x, st, skip_dead, tile_live);
-    else launch_phase1<SR, 1>(e, A, x, st, skip_dead, tile_live);
+    int rc1;
+    if (!t.n_vdict) rc1 = launch_phase1<SR, 0>(e, A, x, st, skip_dead, tile_live);
+    else if (t.code_bits == 16) rc1 = launch_phase1<SR, 3>(e, A, x, st, skip_dead, tile_live);
+    else if (t.code_bits == 4) rc1 = launch_phase1<SR, 2>(e, A, x, st, skip_dead, tile_live);
+    else rc1 = launch_phase1<SR, 1>(e, A, x, st, skip_dead, tile_live);
+    if (rc1 != SH_OK) return rc1;
     HIP_TRY(e, hipGetLastError());
   }
   if (mark_dead) {

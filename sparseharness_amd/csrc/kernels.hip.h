@@ -678,7 +678,14 @@ __device__ inline void heavy_row_by_wave(const LongRow lr, const uint32_t *__res
 #ifndef SH_TCOLS
 #define SH_TCOLS 32760
 #endif
-constexpr int TCOLS = SH_TCOLS;         // columns per x tile (4 B each in LDS); a multiple of 8, < 32768: a column code has 15 bits
+constexpr int TCOLS = SH_TCOLS;         // columns per x tile (4 B each in LDS) of the NARROW layout; a multiple of 8, < 32768: a column code has 15 bits
+// The WIDE layout (plan_common.h::pick_tile_cols says which matrices get it): the widest multiple of 8 at which the x tile,
+// its identity slot, a 256-word dictionary, the 256 bytes of the workgroup vote and the timeline build's stamp still fit
+// the 160 KiB of LDS a gfx950 workgroup may hold.  Its column codes use all 16 bits; the fold flags travel in fmask[].
+#ifndef SH_TCOLS_WIDE
+#define SH_TCOLS_WIDE 40632
+#endif
+constexpr int TCOLS_WIDE = SH_TCOLS_WIDE;
 constexpr int TBS = 1024;               // threads per phase-1 workgroup
 #ifndef SH_TBIN
 #define SH_TBIN 16384   // 32768: one 1024-thread WG per CU; 16384: two 512-thread WGs (measured 5 % faster)
@@ -700,6 +707,10 @@ constexpr uint16_t TCOL_FOLD = SH_TCOLS < 32768 ? 0x8000 : 0;
 constexpr uint32_t TCOL_MASK = SH_TCOLS < 32768 ? 0x7FFFu : 0xFFFFu;
 constexpr uint16_t TSLOT_PAD = 0xFFFF;     // slot16 marker: padding product
 static_assert(TCOLS % 8 == 0 && TCOLS <= 65528 && TCOL_IDENTITY == TCOLS, "the identity column code indexes the slot behind the x tile; bit 15 is the fold flag when the tile leaves it free");
+static_assert(TCOLS_WIDE % 8 == 0 && TCOLS_WIDE > TCOLS && TCOLS_WIDE <= 65528, "a wide layout's identity column code is its tile width: 16 bits");
+// what a layout of tile width tcols puts into / takes out of a light group's first column code (a wide layout: nothing)
+__host__ __device__ constexpr uint16_t tcol_fold_bit(int tcols) { return tcols == TCOLS ? TCOL_FOLD : (uint16_t)0; }
+__host__ __device__ constexpr uint32_t tcol_first_mask(int tcols) { return tcols == TCOLS ? TCOL_MASK : 0xFFFFu; }
 // Heavy rows: every (row, tile) piece is padded to whole STRIPS of HSTRIP consecutive stream entries.  One
 // lane of phase 1 sums a strip (wide loads, 16 products in stream order); consecutive lanes whose strips
 // belong to the same piece are then combined by a segmented wave scan in DPP, and the last lane of each run
@@ -769,7 +780,10 @@ __device__ __forceinline__ typename SR::T seg_scan_wave(typename SR::T t, const 
 // VC: 0 = raw 4-byte values, 1 = one-byte dictionary codes, 2 = four-bit codes (<= 16 values), 3 = two-byte codes
 // (<= 4096 values: 4 instead of 6 bytes per entry for a matrix with a few hundred or thousand distinct weights, e.g.
 // small integers after the reference's int narrowing, src/sparse_matrix.cpp:107, or 1 / degree weights)
-// xs: [TCOLS + 4] words of LDS, ds: [VDICT] ([VDICT16] for VC = 3).
+// WIDE: the layout's x tile has TCOLS_WIDE columns instead of TCOLS and its fold flags come from fmask[] (one 64-bit
+// word per block of obase[]: bit i = group i of the block folds into the lane in front) instead of bit 15 of a group's
+// first column code.
+// xs: [TW + 4] words of LDS (TW = the tile width), ds: [VDICT] ([VDICT16] for VC = 3).
 SH_STAT(__device__ uint64_t *g_p1_stats;)
 // per workgroup of phase 2 (wave 0 of each role, shader cycles): [0] loader total, [1] loader in vmcnt waits, [2] loader in
 // barriers, [3] bins, [4] reducer total, [5] reducer in barriers, [6] reducer in the reduction proper, [7] bins,
@@ -783,14 +797,16 @@ SH_STAT(__device__ uint64_t g_p2_wave[256 * 12 * 4];)   // per reducer wave: cyc
 #endif
 struct NoHook { __device__ void operator()() const {} };
 // staged(): called by every thread right after the barrier that publishes the x tile (SH_STATS builds stamp it).
-template <class SR, int VC, class Hook = NoHook>
+template <class SR, int VC, bool WIDE, class Hook = NoHook>
 __device__ __forceinline__ void tiled_phase1_chunk(
     const TileChunk ch, uint32_t *xs, uint32_t *ds, const void *__restrict__ tval_or_code,
     const uint32_t *__restrict__ vdict, const uint16_t *__restrict__ tcol,
-    const uint32_t *__restrict__ gdest, const uint32_t *__restrict__ obase, const uint32_t *__restrict__ x, int32_t cols,
+    const uint32_t *__restrict__ gdest, const uint32_t *__restrict__ obase, const uint64_t *__restrict__ fmask,
+    const uint32_t *__restrict__ x, int32_t cols,
     uint32_t *__restrict__ P, uint32_t *__restrict__ partial, const bool skip_dead_tiles, uint32_t *__restrict__ tile_live,
     Hook staged = NoHook()) {
   using T = typename SR::T;
+  constexpr int TW = WIDE ? TCOLS_WIDE : TCOLS;   // columns of the x tile
   constexpr int U = VC ? P1U_VC : P1U;
   // skip_dead_tiles (workgroup-uniform): when every x word of the tile is absorbing (SR::absorbing: an unreached vertex
   // of SSSP, a vertex outside the BFS frontier) all products of the chunk are the identity and are written without
@@ -798,41 +814,41 @@ __device__ __forceinline__ void tiled_phase1_chunk(
   const bool may_skip = SR::has_absorbing && skip_dead_tiles;
   // the value words of one group of 4 entries: 4 values, 4 one-byte codes, or 4 nibbles
   using VWord = typename std::conditional<VC == 0, uint4, typename std::conditional<VC == 1, uint32_t, typename std::conditional<VC == 2, uint16_t, uint2>::type>::type>::type;
-  // xs[TCOLS] holds the identity: a column code of TCOL_IDENTITY (== TCOLS) reads it with no test
+  // xs[TW] holds the identity: the identity column code (== TW) reads it with no test
   const VWord *__restrict__ tval = reinterpret_cast<const VWord *>(tval_or_code);
   const uint2 *__restrict__ tcol2 = reinterpret_cast<const uint2 *>(tcol);
   const int tid = threadIdx.x;
-  const int c0 = ch.tile * TCOLS;
+  const int c0 = ch.tile * TW;
   const uint32_t ident = to_bits<T>(SR::identity());
   if constexpr (VC == 3)
     reinterpret_cast<uint4 *>(ds)[tid] = reinterpret_cast<const uint4 *>(vdict)[tid];   // TBS * 4 == VDICT16 words
   else if (VC && tid < VDICT)
     ds[tid] = vdict[tid];
   if (tid == 0)
-    xs[TCOLS] = ident;
+    xs[TW] = ident;
   // Stage the x tile (cols is arbitrary, x is only guaranteed 4-byte aligned), then request the chunk's
   // first stream batch.  (LDS-DMA staging -- global_load_lds_dwordx4, no VGPR round trip -- was measured
   // neutral on the same box: 494-512 vs 494-497 us per SpMV.)  (Requesting it right behind the staging loads, so that its HBM latency runs
   // under the LDS writes, was measured SLOWER on the same box: 533 vs 508 us per SpMV.)
   auto stage = [&](auto request_first) -> bool {
     bool live_word = false;   // this thread staged a word that is not absorbing
-    if (c0 + TCOLS <= cols && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+    if (c0 + TW <= cols && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
       // full tile, 16-byte aligned: 1 KiB per wave-instruction; every load is issued before the first
       // LDS write (a rolled loop would pay one memory latency per iteration)
-      constexpr int NI = (TCOLS / 4 + TBS - 1) / TBS;
+      constexpr int NI = (TW / 4 + TBS - 1) / TBS;
       uint4 t[NI];
 #pragma unroll
       for (int k = 0; k < NI; k++)
-        t[k] = reinterpret_cast<const uint4 *>(x + c0)[min(tid + k * TBS, TCOLS / 4 - 1)];
+        t[k] = reinterpret_cast<const uint4 *>(x + c0)[min(tid + k * TBS, TW / 4 - 1)];
 #pragma unroll
       for (int k = 0; k < NI; k++) {
-        if (tid + k * TBS < TCOLS / 4)
+        if (tid + k * TBS < TW / 4)
           reinterpret_cast<uint4 *>(xs)[tid + k * TBS] = t[k];
         if (SR::has_absorbing)
           live_word = live_word || !SR::absorbing(t[k].x) || !SR::absorbing(t[k].y) || !SR::absorbing(t[k].z) || !SR::absorbing(t[k].w);
       }
     } else {
-      for (int i = tid; i < TCOLS; i += TBS) {
+      for (int i = tid; i < TW; i += TBS) {
         const uint32_t w = (c0 + i < cols) ? x[c0 + i] : ident;
         xs[i] = w;
         if (SR::has_absorbing) live_word = live_word || !SR::absorbing(w);
@@ -861,8 +877,8 @@ __device__ __forceinline__ void tiled_phase1_chunk(
       v = make_uint4(ds[w.x & 0xFFFFu], ds[w.x >> 16], ds[w.y & 0xFFFFu], ds[w.y >> 16]);
     else
       v = w;
-    // (bit 15 of a group's first column code is the fold flag)
-    pr[0] = SR::mul(from_bits<T>(xs[c.x & TCOL_MASK]), from_bits<T>(v.x));
+    // (narrow layouts: bit 15 of a group's first column code is the fold flag)
+    pr[0] = SR::mul(from_bits<T>(xs[c.x & tcol_first_mask(TW)]), from_bits<T>(v.x));
     pr[1] = SR::mul(from_bits<T>(xs[c.x >> 16]), from_bits<T>(v.y));
     pr[2] = SR::mul(from_bits<T>(xs[c.y & 0xFFFFu]), from_bits<T>(v.z));
     pr[3] = SR::mul(from_bits<T>(xs[c.y >> 16]), from_bits<T>(v.w));
@@ -890,19 +906,21 @@ __device__ __forceinline__ void tiled_phase1_chunk(
   if (ch.hs > ch.s) {
     constexpr int S = TBS * U;
     const int gs = ch.s / 4, last_blk = (le - gs - 1) >> 6, lane = tid & 63;
-    auto load = [&](int gbase, VWord (&vw)[U], uint2 (&c)[U], uint32_t (&ob)[U]) {
+    auto load = [&](int gbase, VWord (&vw)[U], uint2 (&c)[U], uint32_t (&ob)[U], uint64_t (&fk)[WIDE ? U : 1]) {
 #pragma unroll
       for (int k = 0; k < U; k++) {
         const int g = min(gbase + k * TBS, le - 1);
         vw[k] = stream_load(&tval[g]);
         c[k] = stream_load(&tcol2[g]);
         // the wave's 64 groups are one block of obase[] (chunks start on block boundaries): a scalar load
-        ob[k] = obase[ch.ob0 + __builtin_amdgcn_readfirstlane(min((gbase + k * TBS - gs) >> 6, last_blk))];
+        const int blk = ch.ob0 + __builtin_amdgcn_readfirstlane(min((gbase + k * TBS - gs) >> 6, last_blk));
+        ob[k] = obase[blk];
+        if constexpr (WIDE) fk[k] = fmask[blk];   // ... and the block's fold flags: another one
       }
     };
     // (the loop runs per WAVE -- while the wave's first group is inside the chunk -- so that every lane takes part in
     // the DPP moves and ballots; lanes past the end of the chunk neither fold nor store)
-    auto consume = [&](int gbase, const VWord (&vw)[U], const uint2 (&c)[U], const uint32_t (&ob)[U]) {
+    auto consume = [&](int gbase, const VWord (&vw)[U], const uint2 (&c)[U], const uint32_t (&ob)[U], const uint64_t (&fk)[WIDE ? U : 1]) {
 #pragma unroll
       for (int k = 0; k < U; k++) {
         const int g = gbase + k * TBS;
@@ -910,8 +928,13 @@ __device__ __forceinline__ void tiled_phase1_chunk(
           const bool valid = g < le;
           T pr[4];
           products(vw[k], c[k], pr);
-          const bool folds = valid && (c[k].x & TCOL_FOLD) != 0;          // this lane is the B of a pair
-          const uint64_t fm = __ballot(folds), sm = __ballot(valid && !folds);
+          // this lane is the B of a pair.  (Wide: the builder sets flags for groups of the tile's run only, and a
+          // work item ends where the run ends or on a block boundary: no flag beyond le.)
+          bool folds;
+          uint64_t fm;
+          if constexpr (WIDE) { fm = fk[k]; folds = (fm >> lane) & 1u; }
+          else { folds = valid && (c[k].x & TCOL_FOLD) != 0; fm = __ballot(folds); }
+          const uint64_t sm = __ballot(valid && !folds);
           const bool takes = ((fm >> 1) >> lane) & 1u;                   // the lane behind folds into this one
 #pragma unroll
           for (int i = 0; i < 4; i++) {
@@ -937,8 +960,9 @@ __device__ __forceinline__ void tiled_phase1_chunk(
     VWord va[U], vb[U];
     uint2 ca[U], cb[U];
     uint32_t oa[U], obb[U];
+    uint64_t fa[WIDE ? U : 1], fb[WIDE ? U : 1];
     int g0 = gs + tid;
-    const bool live = stage([&]() { load(g0, va, ca, oa); });
+    const bool live = stage([&]() { load(g0, va, ca, oa, fa); });
     if (!live && tile_live != nullptr) {
       // a dead tile whose pieces phase 2 will not read: nothing to write
     } else if (!live) {
@@ -951,12 +975,12 @@ __device__ __forceinline__ void tiled_phase1_chunk(
       }
     } else if (g0 - lane < le) {
       for (;;) {
-        load(g0 + S, vb, cb, obb);
-        consume(g0, va, ca, oa);
+        load(g0 + S, vb, cb, obb, fb);
+        consume(g0, va, ca, oa, fa);
         g0 += S;
         if (g0 - lane >= le) break;
-        load(g0 + S, va, ca, oa);
-        consume(g0, vb, cb, obb);
+        load(g0 + S, va, ca, oa, fa);
+        consume(g0, vb, cb, obb, fb);
         g0 += S;
         if (g0 - lane >= le) break;
       }
@@ -1039,15 +1063,20 @@ __device__ __forceinline__ void tiled_phase1_chunk(
 }
 
 
-template <class SR, int VC>
+template <class SR, int VC, bool WIDE>
 __global__ __launch_bounds__(TBS) void spmv_tiled_phase1(
     const TileChunk *__restrict__ chunks, const void *__restrict__ tval_or_code,
     const uint32_t *__restrict__ vdict, const uint16_t *__restrict__ tcol,
-    const uint32_t *__restrict__ gdest, const uint32_t *__restrict__ obase, const uint32_t *__restrict__ x, int32_t cols,
+    const uint32_t *__restrict__ gdest, const uint32_t *__restrict__ obase, const uint64_t *__restrict__ fmask,
+    const uint32_t *__restrict__ x, int32_t cols,
     uint32_t *__restrict__ P, uint32_t *__restrict__ partial, const int32_t *gate, int32_t skip_dead_tiles,
     uint32_t *__restrict__ tile_live) {
-  __shared__ uint32_t xs[TCOLS + 4];
+  __shared__ uint32_t xs[(WIDE ? TCOLS_WIDE : TCOLS) + 4];
   __shared__ uint32_t ds[VC == 3 ? VDICT16 : (VC ? VDICT : 1)];
+  // LDS budget of a workgroup on gfx950: the tile, the dictionary, 256 bytes of the workgroup vote (__syncthreads_or)
+  // and the timeline build's stamp.  The two-byte dictionary (16 KiB) leaves no room for a wide tile.
+  static_assert(!(WIDE && VC == 3), "two-byte codes keep the narrow tile");
+  static_assert(sizeof(xs) + sizeof(ds) + 256 + 8 <= 160 * 1024, "phase 1 must fit the LDS of one workgroup");
   static_assert(TBS * 4 == VDICT16, "one 16-byte load per thread stages the two-byte dictionary");
   const TileChunk ch = chunks[blockIdx.x];
   if (ch.s >= ch.e || (gate != nullptr && *gate == 0))
@@ -1055,7 +1084,7 @@ __global__ __launch_bounds__(TBS) void spmv_tiled_phase1(
   SH_STAT(const uint64_t st_t0 = __builtin_amdgcn_s_memrealtime(); __shared__ uint64_t st_staged;)
   SH_STAT(auto stamp = [&]() { if (threadIdx.x == 0) st_staged = __builtin_amdgcn_s_memrealtime(); };)
 #ifdef SH_STATS
-  tiled_phase1_chunk<SR, VC>(ch, xs, ds, tval_or_code, vdict, tcol, gdest, obase, x, cols, P, partial, skip_dead_tiles != 0, tile_live, stamp);
+  tiled_phase1_chunk<SR, VC, WIDE>(ch, xs, ds, tval_or_code, vdict, tcol, gdest, obase, fmask, x, cols, P, partial, skip_dead_tiles != 0, tile_live, stamp);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0 && g_p1_stats) {   // per chunk: kind, entries, start, staged, end (100 MHz ticks)
@@ -1063,7 +1092,7 @@ __global__ __launch_bounds__(TBS) void spmv_tiled_phase1(
     S[0] = ch.hs <= ch.s; S[1] = (uint64_t)(ch.e - ch.s); S[2] = st_t0; S[3] = st_staged; S[4] = __builtin_amdgcn_s_memrealtime();
   }
 #else
-  tiled_phase1_chunk<SR, VC>(ch, xs, ds, tval_or_code, vdict, tcol, gdest, obase, x, cols, P, partial, skip_dead_tiles != 0, tile_live);
+  tiled_phase1_chunk<SR, VC, WIDE>(ch, xs, ds, tval_or_code, vdict, tcol, gdest, obase, fmask, x, cols, P, partial, skip_dead_tiles != 0, tile_live);
 #endif
 }
 

@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <thread>
 #include <utility>
@@ -84,6 +85,8 @@ struct TiledHost {
   int vdict_used = 0;
   int code_bits = 0;                 // 8: one code per byte of tcode; 4: two per byte (<= 16 values); 16: two bytes per code (<= 4096 values)
   std::vector<uint16_t> tcol, pslot;
+  int tcols = TCOLS;                 // columns per x tile: TCOLS (narrow layout) or TCOLS_WIDE (pick_tile_cols)
+  std::vector<uint64_t> fmask;       // wide layouts only, beside obase[]: bit i = group i of the block of 64 stream groups folds into the lane in front
   int64_t stream_len = 0, p_len = 0, light_len = 0, heavy_base = 0;   // light_len: light stream entries (padding included); p_len: products in P
   int64_t light_entries = 0;         // light entries of the matrix (no padding)
   int32_t n_partials = 0;
@@ -177,6 +180,25 @@ static inline void decide_value_coding(std::vector<uint32_t> &words, bool overfl
   } else {
     dict.overflow = true;
   }
+}
+
+// Tile width of the layout, from the value coding just decided (coded: dictionary codes of code_bits bits; else raw
+// words) and the stored entries.  The narrow tile (TCOLS columns, 128 KiB of LDS) leaves 31 KiB of a gfx950 workgroup's
+// LDS unused unless the two-byte dictionary (16 KiB) sits beside it; the wide tile (TCOLS_WIDE) takes them: every
+// per-tile cost of an SpMV -- pieces of P, padding, piece tables, heavy partials -- shrinks with the tile count, every
+// work item stages a quarter more of x.  That pays for large matrices only (WIDE_MIN_NNZ); which codings get it by
+// default is what the A/B runs settled.  SH_TILE_COLS=narrow|wide overrides size and default;
+// two-byte codes stay narrow whatever it says.  Both builders ask here, before they tile anything.
+constexpr int64_t WIDE_MIN_NNZ = (int64_t)1 << 22;
+constexpr bool WIDE_FOR_RAW = true, WIDE_FOR_DICT8 = true, WIDE_FOR_DICT4 = true;
+static inline int pick_tile_cols(bool coded, int code_bits, int64_t nnz) {
+  if (coded && code_bits == 16) return TCOLS;
+  if (const char *v = getenv("SH_TILE_COLS")) {
+    if (!strcmp(v, "narrow")) return TCOLS;
+    if (!strcmp(v, "wide")) return TCOLS_WIDE;
+  }
+  const bool by_default = !coded ? WIDE_FOR_RAW : (code_bits == 4 ? WIDE_FOR_DICT4 : WIDE_FOR_DICT8);
+  return by_default && nnz >= WIDE_MIN_NNZ ? TCOLS_WIDE : TCOLS;
 }
 
 // Modelled time of one phase-1 work item, ns: P1_COST_ENTRY per stream entry read, P1_COST_PRODUCT per product written
@@ -379,9 +401,10 @@ struct TiledDevArrays {
   uint16_t *tcol = nullptr, *pslot = nullptr;
   uint8_t *tcode = nullptr;
   uint32_t *tval = nullptr, *gdest = nullptr, *gblk = nullptr, *obase = nullptr, *lrp = nullptr;
+  uint64_t *fmask = nullptr;   // wide layouts only
   int32_t *ptab = nullptr;
   uint16_t *ptile = nullptr;
-  size_t n_tcol = 0, n_pslot = 0, n_tcode = 0, n_tval = 0, n_gdest = 0, n_gblk = 0, n_obase = 0, n_lrp = 0, n_ptab = 0;
+  size_t n_tcol = 0, n_pslot = 0, n_tcode = 0, n_tval = 0, n_gdest = 0, n_gblk = 0, n_obase = 0, n_lrp = 0, n_ptab = 0, n_fmask = 0;
   void release();   // frees what is still set (a builder that failed half-way; the caller after adopting nothing)
 };
 // slack bytes behind the arrays (the host path's DEV_ARRAY calls use the same numbers)

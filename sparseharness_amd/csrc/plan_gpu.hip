@@ -32,7 +32,7 @@
 namespace sh {
 
 void TiledDevArrays::release() {
-  for (void *p : {(void *)tcol, (void *)pslot, (void *)tcode, (void *)tval, (void *)gdest, (void *)gblk, (void *)obase, (void *)lrp, (void *)ptab, (void *)ptile})
+  for (void *p : {(void *)tcol, (void *)pslot, (void *)tcode, (void *)tval, (void *)gdest, (void *)gblk, (void *)obase, (void *)lrp, (void *)ptab, (void *)ptile, (void *)fmask})
     if (p) (void)hipFree(p);
   *this = TiledDevArrays();
 }
@@ -100,12 +100,12 @@ __global__ void k_fill16(uint16_t *__restrict__ v, int64_t n, uint16_t x) {
   if (i < n) v[i] = x;
 }
 // key = row << tb | tile (out-of-range columns: tile 0, as the host's tile_of)
-__global__ void k_keys(const uint32_t *__restrict__ row_of, const int32_t *__restrict__ ci, int64_t n, int64_t cols, int tb,
+__global__ void k_keys(const uint32_t *__restrict__ row_of, const int32_t *__restrict__ ci, int64_t n, int64_t cols, int tcols, int tb,
                        uint64_t *__restrict__ key, uint32_t *__restrict__ val) {
   const int64_t i = GID;
   if (i >= n) return;
   const int32_t c = ci[i];
-  const uint32_t t = ((uint32_t)c < (uint32_t)cols) ? (uint32_t)(c / TCOLS) : 0u;
+  const uint32_t t = ((uint32_t)c < (uint32_t)cols) ? (uint32_t)(c / tcols) : 0u;
   key[i] = ((uint64_t)row_of[i] << tb) | t;
   val[i] = (uint32_t)i;
 }
@@ -250,8 +250,9 @@ __global__ void k_fill_light(int64_t L, const uint32_t *__restrict__ iB, const u
                              const uint32_t *__restrict__ p_spos, const uint32_t *__restrict__ p_off, const uint32_t *__restrict__ binT,
                              const uint32_t *__restrict__ info, const uint32_t *__restrict__ repscan, const uint32_t *__restrict__ jA,
                              const int32_t *__restrict__ ci, const uint32_t *__restrict__ val, const RowBin *__restrict__ bins, int64_t cols,
+                             int tcols, const uint32_t *__restrict__ p_tile, const uint64_t *__restrict__ run_start, const uint64_t *__restrict__ ob0,
                              Coding cd, uint16_t *__restrict__ tcol, uint8_t *__restrict__ code8, uint32_t *__restrict__ tval,
-                             uint16_t *__restrict__ pslot) {
+                             uint16_t *__restrict__ pslot, unsigned long long *__restrict__ fmask) {
   // a dictionary of up to VDICT words is staged in LDS; a larger one (two-byte codes) is searched where it lies (16 KB: cache hits)
   __shared__ uint32_t sw_l[VDICT];
   __shared__ uint16_t sc_l[VDICT];
@@ -293,8 +294,15 @@ __global__ void k_fill_light(int64_t L, const uint32_t *__restrict__ iB, const u
   }
   const uint32_t j = jA[i];
   const int32_t col = ci[j];
-  uint16_t tc = ((uint32_t)col < (uint32_t)cols) ? (uint16_t)(col % TCOLS) : TCOL_IDENTITY;
-  if (fold_flag) tc |= TCOL_FOLD;
+  uint16_t tc = ((uint32_t)col < (uint32_t)cols) ? (uint16_t)(col % tcols) : (uint16_t)tcols;
+  if (fold_flag) {   // narrow layouts: bit 15 of the group's first column code; wide ones: the group's bit in fmask[]
+    if (tcols == TCOLS) tc |= TCOL_FOLD;
+    else {
+      const uint32_t t = p_tile[p];
+      const int64_t g = (q - (int64_t)run_start[t]) / 4;
+      atomicOr(&fmask[(int64_t)ob0[t] + g / 64], 1ull << (g % 64));
+    }
+  }
   tcol[q] = tc;
   if (cd.n_words) {
     const uint16_t code = code_of(sw, sc, cd.n_words, val[j]);
@@ -339,8 +347,9 @@ __global__ void k_gblk_before(const RowBin *__restrict__ bins, int64_t n_bins, u
   }
 }
 // storing groups (no fold flag) of every 64-group block of the light runs: one wave per block
-__global__ void k_block_counts(const uint16_t *__restrict__ tcol, const uint64_t *__restrict__ ob0, const uint64_t *__restrict__ run_start,
-                               const uint64_t *__restrict__ run_len, int CT, int64_t NB, uint32_t *__restrict__ bcnt) {
+__global__ void k_block_counts(const uint16_t *__restrict__ tcol, const unsigned long long *__restrict__ fmask, const uint64_t *__restrict__ ob0,
+                               const uint64_t *__restrict__ run_start, const uint64_t *__restrict__ run_len, int CT, int64_t NB,
+                               uint32_t *__restrict__ bcnt) {
   const int64_t B = GID >> 6;
   const int lane = threadIdx.x & 63;
   if (B >= NB) return;   // (whole waves: PBS is a multiple of 64)
@@ -351,7 +360,9 @@ __global__ void k_block_counts(const uint16_t *__restrict__ tcol, const uint64_t
   }
   const int64_t rel = (B - (int64_t)ob0[lo]) * 256 + lane * 4;
   const bool valid = rel < (int64_t)run_len[lo];
-  const bool stores = valid && !(tcol[(int64_t)run_start[lo] + rel] & TCOL_FOLD);
+  // (fmask != NULL: a wide layout, whose flags are the block's mask word)
+  const bool folds = fmask ? ((fmask[B] >> lane) & 1ull) != 0 : valid && (tcol[(int64_t)run_start[lo] + rel] & TCOL_FOLD) != 0;
+  const bool stores = valid && !folds;
   const uint64_t m = __ballot(stores);
   if (lane == 0) bcnt[B] = (uint32_t)__popcll(m);
 }
@@ -425,7 +436,7 @@ __global__ void k_gdest(const uint64_t *__restrict__ hposT, const uint32_t *__re
 }
 __global__ void k_fill_heavy(int64_t n, const uint8_t *__restrict__ role, const uint32_t *__restrict__ rs, const uint32_t *__restrict__ hscan,
                              const uint64_t *__restrict__ c_glob, int64_t heavy_base, const uint32_t *__restrict__ jA,
-                             const int32_t *__restrict__ ci, const uint32_t *__restrict__ val, int64_t cols, Coding cd,
+                             const int32_t *__restrict__ ci, const uint32_t *__restrict__ val, int64_t cols, int tcols, Coding cd,
                              uint16_t *__restrict__ tcol, uint8_t *__restrict__ code8, uint32_t *__restrict__ tval) {
   // a dictionary of up to VDICT words is staged in LDS; a larger one (two-byte codes) is searched where it lies (16 KB: cache hits)
   __shared__ uint32_t sw_l[VDICT];
@@ -442,7 +453,7 @@ __global__ void k_fill_heavy(int64_t n, const uint8_t *__restrict__ role, const 
   const int64_t q = heavy_base + (int64_t)c_glob[hscan[s]] + ((int64_t)i - s);
   const uint32_t j = jA[i];
   const int32_t col = ci[j];
-  tcol[q] = ((uint32_t)col < (uint32_t)cols) ? (uint16_t)(col % TCOLS) : TCOL_IDENTITY;
+  tcol[q] = ((uint32_t)col < (uint32_t)cols) ? (uint16_t)(col % tcols) : (uint16_t)tcols;
   if (cd.n_words) {
     const uint16_t code = code_of(sw, sc, cd.n_words, val[j]);
     if (cd.bits == 16) reinterpret_cast<uint16_t *>(code8)[q] = code;
@@ -583,14 +594,15 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
   g_debug_fail_device_build = 0;
   if (inject == 1) { why = "injected"; return -1; }
 #endif
-  const int CT = (int)std::max<int64_t>(1, (cols + TCOLS - 1) / TCOLS);
-  if (CT > 65535 || nnz <= 0 || rows <= 0) { why = "not applicable"; return 0; }
-  const bool fold = opt.fold != 0 && TCOL_FOLD != 0;
+  if (nnz <= 0 || rows <= 0) { why = "not applicable"; return 0; }
+  // (set once the value coding is known -- the tile width depends on it; plain variables: the error path is a goto)
+  int tcols = TCOLS, CT = 1, tb = 0;
+  bool fold = false, wide = false;
   const int64_t per_tile = std::max(1, opt.heavy_per_tile);
-  const int64_t heavy_thr = std::min<int64_t>(TBIN / 4, std::max<int64_t>(512, per_tile * CT));
+  int64_t heavy_thr = 0;
   auto is_heavy = [&](int64_t r) { return (int64_t)h_rp[r + 1] - h_rp[r] >= heavy_thr; };
   const int64_t n = nnz;
-  const int tb = bits_for((uint64_t)CT - 1), rb = bits_for((uint64_t)rows - 1);
+  const int rb = bits_for((uint64_t)rows - 1);
 
   DevPool pool;
   pool.stream = stream;
@@ -640,8 +652,7 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
   uint8_t *role = nullptr, *code8 = nullptr;
   int32_t *d_bin_r0 = nullptr;
   RowBin *d_bins = nullptr;
-  std::vector<int64_t> run_len((size_t)CT, 0), run_plen((size_t)CT, 0), run_start((size_t)CT, 0), hrel((size_t)CT, 0), heavy_start((size_t)CT, 0),
-      ob0((size_t)CT + 1, 0);
+  std::vector<int64_t> run_len, run_plen, run_start, hrel, heavy_start, ob0;
   std::vector<uint64_t> h64a, h64b, h64c, h64d;
   int64_t L = 0, NP = 0, NC = 0, n_heavy = 0, n_pieces_total = 0, n_blocks_total = 0, p_off_total = 0, heavy_total = 0, heavy_base = 0;
   // heavy-side arrays
@@ -657,6 +668,70 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
   bool coded = false;
   uint32_t u32tmp = 0;
 
+  // ---- value dictionary, ahead of the tiling: the tile width depends on the coding (plan_common.h::pick_tile_cols)
+  coded = opt.value_coding >= 0;
+  if (coded) {
+    dtable = pool.get<unsigned long long>((size_t)DT, true);
+    dctl = pool.get<uint32_t>(4, true);
+    POOL_OK();
+    hipLaunchKernelGGL(k_distinct, dim3((unsigned)((n + (int64_t)PBS * 64 - 1) / ((int64_t)PBS * 64))), dim3(PBS), 0, stream, d_val, n, dtable, dctl);
+    GT(hipGetLastError());
+    std::vector<unsigned long long> tab((size_t)DT);
+    uint32_t ctl[4] = {0, 0, 0, 0};
+    GT(hipMemcpyAsync(tab.data(), dtable, (size_t)DT * 8, hipMemcpyDeviceToHost, stream));
+    GT(hipMemcpyAsync(ctl, dctl, 16, hipMemcpyDeviceToHost, stream));
+    GT(hipStreamSynchronize(stream));
+    std::vector<uint32_t> words;
+    bool overflow = ctl[1] != 0u || ctl[0] > (uint32_t)VDICT;
+    if (!overflow)
+      for (unsigned long long e : tab) if (e) words.push_back((uint32_t)e);
+    if (overflow && opt.value_coding == 0) {   // more than VDICT words: up to VDICT16 of them still make two-byte codes
+      unsigned long long *dtable16 = pool.get<unsigned long long>((size_t)DT16, true);
+      uint32_t *dctl16 = pool.get<uint32_t>(4, true);
+      POOL_OK();
+      hipLaunchKernelGGL(k_distinct16, dim3((unsigned)((n + (int64_t)PBS * 64 - 1) / ((int64_t)PBS * 64))), dim3(PBS), 0, stream, d_val, n, dtable16, dctl16);
+      GT(hipGetLastError());   // (a launch that failed would read as "no distinct words")
+      std::vector<unsigned long long> tab16((size_t)DT16);
+      GT(hipMemcpyAsync(tab16.data(), dtable16, (size_t)DT16 * 8, hipMemcpyDeviceToHost, stream));
+      GT(hipMemcpyAsync(ctl, dctl16, 16, hipMemcpyDeviceToHost, stream));
+      GT(hipStreamSynchronize(stream));
+      overflow = ctl[1] != 0u || ctl[0] > (uint32_t)VDICT16;
+      if (!overflow)
+        for (unsigned long long e : tab16) if (e) words.push_back((uint32_t)e);
+    }
+    decide_value_coding(words, overflow, opt, H.code_bits, dict);
+    coded = !dict.overflow;
+  }
+  if (coded) {
+    H.vdict = dict.list;
+    H.vdict_used = (int)H.vdict.size();
+    // sorted words and their codes for the device lookup
+    std::vector<std::pair<uint32_t, uint16_t>> wc;
+    for (size_t k = 0; k < dict.list.size(); k++) wc.emplace_back(dict.list[k], (uint16_t)k);
+    std::sort(wc.begin(), wc.end());
+    std::vector<uint32_t> ws; std::vector<uint16_t> cs;
+    for (auto &pr : wc) { ws.push_back(pr.first); cs.push_back(pr.second); }
+    d_words = pool.get<uint32_t>(VDICT16); d_codes = pool.get<uint16_t>(VDICT16);
+    POOL_OK();
+    GT(hipMemcpyAsync(d_words, ws.data(), ws.size() * 4, hipMemcpyHostToDevice, stream));
+    GT(hipMemcpyAsync(d_codes, cs.data(), cs.size() * 2, hipMemcpyHostToDevice, stream));
+    GT(hipStreamSynchronize(stream));
+    cd = Coding{d_words, d_codes, (int)ws.size(), H.code_bits};
+    H.vdict.resize(dict_words(H.code_bits), 0u);
+  }
+
+  PHASE("  dictionary");
+  tcols = pick_tile_cols(coded, H.code_bits, nnz);
+  H.tcols = tcols;
+  wide = tcols != TCOLS;
+  CT = (int)std::max<int64_t>(1, (cols + tcols - 1) / tcols);
+  if (CT > 65535) { why = "not applicable"; return 0; }
+  fold = opt.fold != 0 && (wide || TCOL_FOLD != 0);
+  heavy_thr = std::min<int64_t>(TBIN / 4, std::max<int64_t>(512, per_tile * CT));
+  tb = bits_for((uint64_t)CT - 1);
+  run_len.assign((size_t)CT, 0); run_plen.assign((size_t)CT, 0); run_start.assign((size_t)CT, 0); hrel.assign((size_t)CT, 0);
+  heavy_start.assign((size_t)CT, 0); ob0.assign((size_t)CT + 1, 0);
+
   // ---- A-order: entries by (row, tile), stable
   row_of = pool.get<uint32_t>((size_t)n);
   head = pool.get<uint32_t>((size_t)n, true);
@@ -665,7 +740,7 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
   POOL_OK();
   LAUNCH(k_row_heads, rows, d_rp, rows, head);
   CUB(incl_max(d_temp_storage, temp_storage_bytes, head, row_of, n, stream));
-  LAUNCH(k_keys, n, row_of, d_ci, n, cols, tb, keyA_in, valA_in);
+  LAUNCH(k_keys, n, row_of, d_ci, n, cols, tcols, tb, keyA_in, valA_in);
   CUB(sort_pairs(d_temp_storage, temp_storage_bytes, keyA_in, keyA, valA_in, jA, n, 0, tb + rb, stream));
   PHASE("  A-order sort");
   // runs, roles
@@ -895,59 +970,6 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
   }
 
   PHASE("  heavy cells");
-  // ---- value dictionary
-  coded = opt.value_coding >= 0;
-  if (coded) {
-    dtable = pool.get<unsigned long long>((size_t)DT, true);
-    dctl = pool.get<uint32_t>(4, true);
-    POOL_OK();
-    hipLaunchKernelGGL(k_distinct, dim3((unsigned)((n + (int64_t)PBS * 64 - 1) / ((int64_t)PBS * 64))), dim3(PBS), 0, stream, d_val, n, dtable, dctl);
-    GT(hipGetLastError());
-    std::vector<unsigned long long> tab((size_t)DT);
-    uint32_t ctl[4] = {0, 0, 0, 0};
-    GT(hipMemcpyAsync(tab.data(), dtable, (size_t)DT * 8, hipMemcpyDeviceToHost, stream));
-    GT(hipMemcpyAsync(ctl, dctl, 16, hipMemcpyDeviceToHost, stream));
-    GT(hipStreamSynchronize(stream));
-    std::vector<uint32_t> words;
-    bool overflow = ctl[1] != 0u || ctl[0] > (uint32_t)VDICT;
-    if (!overflow)
-      for (unsigned long long e : tab) if (e) words.push_back((uint32_t)e);
-    if (overflow && opt.value_coding == 0) {   // more than VDICT words: up to VDICT16 of them still make two-byte codes
-      unsigned long long *dtable16 = pool.get<unsigned long long>((size_t)DT16, true);
-      uint32_t *dctl16 = pool.get<uint32_t>(4, true);
-      POOL_OK();
-      hipLaunchKernelGGL(k_distinct16, dim3((unsigned)((n + (int64_t)PBS * 64 - 1) / ((int64_t)PBS * 64))), dim3(PBS), 0, stream, d_val, n, dtable16, dctl16);
-      GT(hipGetLastError());   // (a launch that failed would read as "no distinct words")
-      std::vector<unsigned long long> tab16((size_t)DT16);
-      GT(hipMemcpyAsync(tab16.data(), dtable16, (size_t)DT16 * 8, hipMemcpyDeviceToHost, stream));
-      GT(hipMemcpyAsync(ctl, dctl16, 16, hipMemcpyDeviceToHost, stream));
-      GT(hipStreamSynchronize(stream));
-      overflow = ctl[1] != 0u || ctl[0] > (uint32_t)VDICT16;
-      if (!overflow)
-        for (unsigned long long e : tab16) if (e) words.push_back((uint32_t)e);
-    }
-    decide_value_coding(words, overflow, opt, H.code_bits, dict);
-    coded = !dict.overflow;
-  }
-  if (coded) {
-    H.vdict = dict.list;
-    H.vdict_used = (int)H.vdict.size();
-    // sorted words and their codes for the device lookup
-    std::vector<std::pair<uint32_t, uint16_t>> wc;
-    for (size_t k = 0; k < dict.list.size(); k++) wc.emplace_back(dict.list[k], (uint16_t)k);
-    std::sort(wc.begin(), wc.end());
-    std::vector<uint32_t> ws; std::vector<uint16_t> cs;
-    for (auto &pr : wc) { ws.push_back(pr.first); cs.push_back(pr.second); }
-    d_words = pool.get<uint32_t>(VDICT16); d_codes = pool.get<uint16_t>(VDICT16);
-    POOL_OK();
-    GT(hipMemcpyAsync(d_words, ws.data(), ws.size() * 4, hipMemcpyHostToDevice, stream));
-    GT(hipMemcpyAsync(d_codes, cs.data(), cs.size() * 2, hipMemcpyHostToDevice, stream));
-    GT(hipStreamSynchronize(stream));
-    cd = Coding{d_words, d_codes, (int)ws.size(), H.code_bits};
-    H.vdict.resize(dict_words(H.code_bits), 0u);
-  }
-
-  PHASE("  dictionary");
   // ---- the final arrays
   D.n_tcol = (size_t)H.stream_len;
   D.n_gdest = (size_t)(H.stream_len - heavy_base) / HSTRIP + 1;
@@ -962,6 +984,11 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
   GT(hipMalloc((void **)&D.ptab, D.n_ptab * 4 + SLACK_WIDE));
   GT(hipMalloc((void **)&D.ptile, D.n_ptab * 2 + SLACK_WIDE));
   GT(hipMalloc((void **)&D.obase, D.n_obase * 4 + SLACK_WIDE));
+  if (wide) {   // the fold flags: one mask word per block of obase[]
+    D.n_fmask = D.n_obase;
+    GT(hipMalloc((void **)&D.fmask, D.n_fmask * 8 + SLACK_WIDE));
+    GT(hipMemsetAsync(D.fmask, 0, D.n_fmask * 8, stream));
+  }
   if (coded) {
     D.n_tcode = tcode_bytes(H.code_bits, H.stream_len);
     GT(hipMalloc((void **)&D.tcode, D.n_tcode + SLACK_TCODE));
@@ -972,7 +999,7 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
     GT(hipMalloc((void **)&D.tval, D.n_tval * 4 + SLACK_WIDE));
     GT(hipMemsetAsync(D.tval, 0, D.n_tval * 4, stream));
   }
-  LAUNCH(k_fill16, (int64_t)D.n_tcol, D.tcol, (int64_t)D.n_tcol, TCOL_IDENTITY);
+  LAUNCH(k_fill16, (int64_t)D.n_tcol, D.tcol, (int64_t)D.n_tcol, (uint16_t)tcols);
   GT(hipMemsetAsync(D.gdest, 0, D.n_gdest * 4, stream));
   GT(hipMemsetAsync(D.pslot, 0xFF, D.n_pslot * 2, stream));
   GT(hipMemsetAsync(D.gblk, 0, D.n_gblk * 4, stream));
@@ -982,15 +1009,15 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
   PHASE("  final arrays: malloc + clear");
   // light stream, slots, piece tables
   if (L > 0 && NP > 0) {
-    LAUNCH(k_fill_light, L, L, iB, pid1, p_first, cscan, p_np, p_ns, p_spos, p_off, binT, info, repscan, jA, d_ci, d_val, d_bins, cols, cd,
-           D.tcol, code8, D.tval, D.pslot);
+    LAUNCH(k_fill_light, L, L, iB, pid1, p_first, cscan, p_np, p_ns, p_spos, p_off, binT, info, repscan, jA, d_ci, d_val, d_bins, cols, tcols,
+           p_tile, d_run_start, d_ob0, cd, D.tcol, code8, D.tval, D.pslot, (unsigned long long *)D.fmask);
     LAUNCH(k_piece_tables, NP, pB, offB, p_bin, p_tile, sP, d_bins, NP, D.ptab, D.ptile, D.gblk);
   }
   LAUNCH(k_gblk_before, (int64_t)H.bins.size(), d_bins, (int64_t)H.bins.size(), D.gblk);
   // heavy stream and gdest
   if (NC > 0) {
     LAUNCH(k_gdest, heavy_total / HSTRIP, hposT, cT, c_pos, c_part, NC, heavy_total / HSTRIP, D.gdest);
-    LAUNCH(k_fill_heavy, n, n, role, rs, hscan, c_glob, heavy_base, jA, d_ci, d_val, cols, cd, D.tcol, code8, D.tval);
+    LAUNCH(k_fill_heavy, n, n, role, rs, hscan, c_glob, heavy_base, jA, d_ci, d_val, cols, tcols, cd, D.tcol, code8, D.tval);
   }
   if (coded && H.code_bits == 4) LAUNCH(k_pack_nibbles, (int64_t)D.n_tcode, code8, (int64_t)D.n_tcode, D.tcode);
   PHASE("  fills");
@@ -1000,7 +1027,7 @@ int build_tiled_plan_gpu(hipStream_t stream, int64_t rows, int64_t cols, int64_t
     bcnt = pool.get<uint32_t>((size_t)NB + 1, true); bscan = pool.get<uint32_t>((size_t)NB + 1);
     POOL_OK();
     if (NB > 0) {
-      LAUNCH(k_block_counts, NB * 64, D.tcol, d_ob0, d_run_start, d_run_len, CT, NB, bcnt);
+      LAUNCH(k_block_counts, NB * 64, D.tcol, (const unsigned long long *)D.fmask, d_ob0, d_run_start, d_run_len, CT, NB, bcnt);
       CUB(excl_sum(d_temp_storage, temp_storage_bytes, bcnt, bscan, NB + 1, stream));
       LAUNCH(k_scale4, NB + 1, bscan, NB + 1, D.obase);   // (the entry behind the last block = all products: obase[b + 1] - obase[b] = products of block b)
       // every tile's products must end where the next tile's begin (the host builder's consistency check)

@@ -69,18 +69,55 @@ static void build_schedule(int64_t rows, const int32_t *rp, std::vector<int32_t>
 // aligned in P.
 static bool build_tiled_plan(int64_t rows, int64_t cols, int64_t nnz, const int32_t *rp,
                              const int32_t *ci, const uint32_t *val, const sh_plan_options &opt, int n_cus, TiledHost &H) {
-  const int CT = (int)std::max<int64_t>(1, (cols + TCOLS - 1) / TCOLS);
-  if (CT > 65535) return false;   // (tile numbers travel as 16-bit values in the builder; 2.1 G columns: shard the matrix)
-  const bool fold = opt.fold != 0 && TCOL_FOLD != 0;
   lap(nullptr);
+  const int NT = build_threads(opt);
+  // P0: the value dictionary, ahead of the tiling: it depends on the distinct values alone, and the tile width depends
+  // on it (pick_tile_cols).  <= VDICT distinct bit patterns => the stream carries one-byte codes, <= 16 => four-bit
+  // codes.  Code 0 is the all-zero word (padding) unless exactly 16 finite non-zero values fill the four-bit table,
+  // in which case padding borrows code 0's value: its products are identity (x) finite == identity.
+  // SH_VALCODE=off keeps raw values, SH_VALCODE=8 never packs nibbles.
+  ValSet dict;
+  {
+    bool coded = opt.value_coding >= 0;
+    if (coded) {
+      std::vector<ValSet> part((size_t)NT);
+      parallel_items((nnz + 65535) / 65536, 4, NT, [&](int64_t blk, int th) {
+        ValSet &vs = part[(size_t)th];
+        const int64_t e = std::min<int64_t>(nnz, (blk + 1) * 65536);
+        for (int64_t j = blk * 65536; j < e && !vs.overflow; j++) vs.add(val[j]);
+      });
+      // the distinct words of the data, in ascending bit-pattern order (the same dictionary whatever the
+      // thread count)
+      ValSet all;
+      for (const ValSet &vs : part) {
+        if (vs.overflow) all.overflow = true;
+        for (uint32_t b : vs.list) all.add(b);
+      }
+      std::vector<uint32_t> words(all.list);
+      decide_value_coding(words, all.overflow, opt, H.code_bits, dict);
+      coded = !dict.overflow;
+    }
+    if (coded) H.vdict = dict.list;
+  }
+  const bool coded = !H.vdict.empty();
+  lap("P0 dictionary");
+  // The tile width, and everything that follows from it: the tile count, the identity column code (= the width: the
+  // LDS slot behind the tile), where the fold flag of a light group lives (narrow: bit 15 of its first column code;
+  // wide: fmask[]).
+  const int tcols = pick_tile_cols(coded, H.code_bits, nnz);
+  H.tcols = tcols;
+  const bool wide = tcols != TCOLS;
+  const uint16_t tcol_identity = (uint16_t)tcols;
+  const int CT = (int)std::max<int64_t>(1, (cols + tcols - 1) / tcols);
+  if (CT > 65535) return false;   // (tile numbers travel as 16-bit values in the builder; 2.1 G columns: shard the matrix)
+  const bool fold = opt.fold != 0 && (wide || TCOL_FOLD != 0);
   // A row is "heavy" when it averages >= 8 entries per column tile (or cannot fit a bin): its
   // (row, tile) runs are summed inside phase 1 instead of travelling through P.
   const int64_t per_tile = std::max(1, opt.heavy_per_tile);
   // (capped at TBIN/4 so that a single light row fits a bin even when every entry is padded to 4)
   const int64_t heavy_thr = std::min<int64_t>(TBIN / 4, std::max<int64_t>(512, per_tile * CT));
   auto is_heavy = [&](int64_t r) { return (int64_t)rp[r + 1] - rp[r] >= heavy_thr; };
-  auto tile_of = [&](int32_t c) -> int { return ((uint32_t)c < (uint32_t)cols) ? (c / TCOLS) : 0; };
-  const int NT = build_threads(opt);
+  auto tile_of = [&](int32_t c) -> int { return ((uint32_t)c < (uint32_t)cols) ? (c / tcols) : 0; };
 
   // Per-thread scratch.  ent[]: the light entries of the bin being worked on, as (tile << 32 | local row << 16 ...)
   // would not fit: two parallel arrays sorted by tile with a counting sort (stable: row order, then CSR order).
@@ -181,7 +218,7 @@ static bool build_tiled_plan(int64_t rows, int64_t cols, int64_t nnz, const int3
   //      S2 (sequential)            heavy pieces: hrel[t] is the running position inside tile t, which
   //                                 fixes where the 64-group wave boundaries of phase 1 fall, hence how
   //                                 a heavy (row, tile) piece splits into partials
-  //      P3 (parallel)              value dictionary (per-thread sets, merged)
+  //      (P0, above: the value dictionary)
   //      P4 (parallel, bins)        fill the light stream (entries + fold flags), pslot, the piece tables (gblk, ptab)
   //      P5 (parallel, heavy rows)  fill the heavy stream and gdest
   //      P6 (parallel, tiles)       obase: where in P the products of every 64 stream groups start
@@ -335,36 +372,6 @@ static bool build_tiled_plan(int64_t rows, int64_t cols, int64_t nnz, const int3
     return false; // padding would cost more than 25 %: keep the stream plan
 
   lap("S1 S2 positions");
-  // P3: value dictionary: <= VDICT distinct bit patterns => the stream carries one-byte codes, <= 16 => four-bit
-  // codes.  Code 0 is the all-zero word (padding) unless exactly 16 finite non-zero values fill the four-bit table,
-  // in which case padding borrows code 0's value: its products are identity (x) finite == identity.
-  // SH_VALCODE=off keeps raw values, SH_VALCODE=8 never packs nibbles.
-  ValSet dict;
-  {
-    bool coded = opt.value_coding >= 0;
-    if (coded) {
-      std::vector<ValSet> part((size_t)NT);
-      parallel_items((nnz + 65535) / 65536, 4, NT, [&](int64_t blk, int th) {
-        ValSet &vs = part[(size_t)th];
-        const int64_t e = std::min<int64_t>(nnz, (blk + 1) * 65536);
-        for (int64_t j = blk * 65536; j < e && !vs.overflow; j++) vs.add(val[j]);
-      });
-      // the distinct words of the data, in ascending bit-pattern order (the same dictionary whatever the
-      // thread count)
-      ValSet all;
-      for (const ValSet &vs : part) {
-        if (vs.overflow) all.overflow = true;
-        for (uint32_t b : vs.list) all.add(b);
-      }
-      std::vector<uint32_t> words(all.list);
-      decide_value_coding(words, all.overflow, opt, H.code_bits, dict);
-      coded = !dict.overflow;
-    }
-    if (coded) H.vdict = dict.list;
-  }
-  const bool coded = !H.vdict.empty();
-
-  lap("P3 dictionary");
   // P4 / P5: fill
   if (coded) {
     H.vdict_used = (int)H.vdict.size();
@@ -372,12 +379,28 @@ static bool build_tiled_plan(int64_t rows, int64_t cols, int64_t nnz, const int3
     H.vdict.resize(dict_words(H.code_bits), 0u);
   }
   else H.tval.assign((size_t)H.stream_len, 0u);
-  H.tcol.assign((size_t)H.stream_len, TCOL_IDENTITY);   // padding: the identity column, value word / code 0, no fold flag
+  H.tcol.assign((size_t)H.stream_len, tcol_identity);   // padding: the identity column, value word / code 0, no fold flag
   H.gdest.assign((size_t)(H.stream_len - heavy_base) / HSTRIP + 1, 0u);   // partial slot of every heavy strip
   H.pslot.assign((size_t)H.p_len, TSLOT_PAD);
   H.gblk.assign((size_t)(n_blocks_total + 1) * 4, 0u);
   H.ptab.assign((size_t)n_pieces_total + 1, 0);
   H.ptile.assign((size_t)n_pieces_total + 1, 0);
+  // ob0[t]: the tile's first block of 64 stream groups in obase[] (and, wide layouts, in fmask[])
+  std::vector<int64_t> ob0((size_t)CT + 1, 0);
+  for (int t = 0; t < CT; t++) ob0[(size_t)t + 1] = ob0[(size_t)t] + (((run_len[(size_t)t] + 255) & ~int64_t(255)) / 256);
+  if (wide) H.fmask.assign((size_t)ob0[(size_t)CT] + 1, 0ull);
+  // "the group at stream position q of tile t folds into the lane in front": narrow layouts flag the group's first
+  // column code, wide ones the group's bit in fmask[] (bins of several threads share a mask word: an atomic OR)
+  auto set_fold = [&](int t, int64_t q) {
+    if (!wide) { H.tcol[(size_t)q] |= TCOL_FOLD; return; }
+    const int64_t g = (q - run_start[(size_t)t]) / 4;
+    __atomic_fetch_or(&H.fmask[(size_t)(ob0[(size_t)t] + g / 64)], 1ull << (g % 64), __ATOMIC_RELAXED);
+  };
+  auto folds_at = [&](int t, int64_t q) -> bool {
+    if (!wide) return (H.tcol[(size_t)q] & TCOL_FOLD) != 0;
+    const int64_t g = (q - run_start[(size_t)t]) / 4;
+    return (H.fmask[(size_t)(ob0[(size_t)t] + g / 64)] >> (g % 64)) & 1ull;
+  };
   std::atomic<bool> ok{true};
   auto put_entry = [&](int64_t pos, int32_t j) {
     const int32_t c = ci[j];
@@ -389,7 +412,7 @@ static bool build_tiled_plan(int64_t rows, int64_t cols, int64_t nnz, const int3
       else H.tcode[(size_t)pos] = (uint8_t)code;
     }
     else H.tval[(size_t)pos] = val[j];
-    H.tcol[(size_t)pos] = in_range ? (uint16_t)(c % TCOLS) : TCOL_IDENTITY;
+    H.tcol[(size_t)pos] = in_range ? (uint16_t)(c % tcols) : tcol_identity;
   };
   parallel_items(n_bins, 8, NT, [&](int64_t bi, int th) {
     const RowBin &b = H.bins[(size_t)bi];
@@ -445,7 +468,7 @@ static bool build_tiled_plan(int64_t rows, int64_t cols, int64_t nnz, const int3
             H.pslot[(size_t)(off + o + k)] = slot_of(i);
           }
         }
-        H.tcol[(size_t)q + 4] |= TCOL_FOLD;              // group B folds into the lane in front of it
+        set_fold(pc.tile, q + 4);                        // group B folds into the lane in front of it
         q += 8; o += 4;
       }
       while (sg_left-- > 0) singles_group();
@@ -489,9 +512,7 @@ static bool build_tiled_plan(int64_t rows, int64_t cols, int64_t nnz, const int3
   });
   lap("P5 heavy fill");
   // P6: obase[block] = P position of the first product of the block's 64 stream groups (a group stores 4 products
-  // unless its first entry carries the fold flag).  Read back from the flags just written, so the two cannot disagree.
-  std::vector<int64_t> ob0((size_t)CT + 1, 0);
-  for (int t = 0; t < CT; t++) ob0[(size_t)t + 1] = ob0[(size_t)t] + (((run_len[(size_t)t] + 255) & ~int64_t(255)) / 256);
+  // unless it carries the fold flag).  Read back from the flags just written, so the two cannot disagree.
   H.obase.assign((size_t)ob0[(size_t)CT] + 1, 0u);
   H.obase[(size_t)ob0[(size_t)CT]] = (uint32_t)H.p_len;   // one entry behind the last block: obase[b + 1] - obase[b] = products of block b
   parallel_items(CT, 1, NT, [&](int64_t t, int) {
@@ -499,7 +520,7 @@ static bool build_tiled_plan(int64_t rows, int64_t cols, int64_t nnz, const int3
     const int64_t s0 = run_start[(size_t)t], s1 = s0 + run_len[(size_t)t];
     for (int64_t q = s0; q < s1; q += 4) {
       if (((q - s0) & 255) == 0) H.obase[(size_t)(ob0[(size_t)t] + (q - s0) / 256)] = (uint32_t)pp;
-      if (!(H.tcol[(size_t)q] & TCOL_FOLD)) pp += 4;
+      if (!folds_at((int)t, q)) pp += 4;
       else if (((q - s0) & 255) == 0) ok = false;   // a pair never straddles a block of 64 groups
     }
     if (pp != run_pstart[(size_t)t] + run_plen[(size_t)t]) ok = false;
