@@ -1802,6 +1802,103 @@ int sh_trsv_graph_level(sh_engine *e, sh_trsv_graph *g, sh_vec *level);
 int sh_trsv(sh_engine *e, sh_trsv_graph *g, const sh_vec *b, sh_vec *x, int32_t f32, int32_t thin, int64_t *launches,
             int64_t *runs, int64_t *levels_in_runs, uint64_t *total_ns);
 
+/* ---- incomplete LU factorisation without fill, ILU(0): A ~ L U on the pattern of A, by level sets, float64, one fixed order
+ * (the reference has no counterpart.  It makes the factor that sh_trsv applies: the engine orders (sh_rcm), colours
+ * (sh_color), multiplies (sh_spmv) and solves (sh_trsv); this factorises.  ILU(0): Meijerink, van der Vorst, Math. Comp.
+ * 1977; Saad, Iterative Methods for Sparse Linear Systems, algorithm 10.4 (the row-wise IKJ form); by level sets on
+ * GPUs: Naumov, NVIDIA NVR-2012-003.  No kernel here ever waits for another kernel's write.)
+ *
+ * THE DEFINITION IS PART OF THE ABI.  The pattern is square (rows x rows), given as host CSR (row_ptr, col_idx); the
+ * float32 values come per call, as an sh_vec of nnz elements in the order of the entries.
+ *      SLOTS.  The slots of row r are the distinct columns c with 0 <= c < rows among its entries, in ascending c.  Rows
+ *      need not be sorted; entries with a column outside the matrix take no part; nothing is refused, whatever the
+ *      values.  a[r, c] = the entries (r, c) in the order given, widened to float64 and added left to right from +0.0
+ *      (sh_trsv's rule for d[r]).
+ *      RECURRENCE.  Row-wise IKJ, all in float64:
+ *          w = a[r, :] on the slots of r
+ *          for every slot (r, k) with k < r, ascending k:
+ *              w[k] = w[k] / u[k, k]      (the final value of slot (k, k); +0.0 if row k has no diagonal slot)
+ *              for every slot (k, j) with j > k, ascending j:
+ *                  if (r, j) is a slot: w[j] = w[j] - w[k] * u[k, j]
+ *          row r of the factor = w
+ *      Every product is rounded once and the subtraction is a second rounding: no fused multiply-add.  l[r, k] = w[k] for
+ *      k < r (the unit diagonal of L is not stored), u[r, j] = w[j] for j >= r.  Every slot (r, j) receives its
+ *      subtractions in ascending k, one after the other, so the factor is a function of the pattern and the values alone,
+ *      whatever the tier, the grid or thin.  A zero, missing or non-finite pivot gives what IEEE gives.  With that every
+ *      comparison is ==, a NaN standing where a NaN stands: tests/ilu0_ref.py restates the definition in numpy and
+ *      host/src/ilu0_factor.cpp in C++.
+ *      OUTPUT.  lu is in the positions of the input entries: lu[p] = the slot's value if entry p is the first entry as
+ *      given of its (r, c) group; +0.0 if it is a later entry of the group or its column is outside the matrix.  So
+ *      (row_ptr, col_idx, lu) is a CSR matrix that sh_trsv_graph_create(..., uplo = 0, unit = 1) and (..., uplo = 1,
+ *      unit = 0) read as exactly L and U.  f32 == 1: nnz float32 elements, each rounded once on the way out (what
+ *      sh_trsv_graph_create takes); f32 == 0: 2 * nnz four-byte elements, which is nnz float64, 8-byte aligned.  val and
+ *      lu may be the same vector when f32 == 1.  val is not written otherwise.
+ *      level[r] = 0 for a row without a lower slot, else 1 + the largest level among its lower slots: sh_trsv_graph_level
+ *      of the uplo = 0 handle on the same arrays.
+ *      Per call: *zero_pivots = the rows whose pivot u[r, r] compares == 0.0 (a missing diagonal slot counts as +0.0; a
+ *      NaN pivot does not count), *first_zero = the smallest such row, -1 if there is none.
+ *
+ *      Schedule (csrc/ilu0.hip.h).  sh_ilu0_graph_create builds on the device, once, from the pattern alone: sh_trsv's
+ *      analysis of the lower triangle gives level, order and lstart (gated rounds of atomic decrements, no
+ *      compare-and-swap); the entries inside the matrix are keyed (r << bits | c) with their position riding along, one
+ *      stable sort, the heads of the runs of equal keys are the slots.  Per row: its slots (ptr / col), the diagonal slot
+ *      or -1, the first upper slot, and its share of work; per slot: its entries in the order given; per input position:
+ *      its slot and whether it is the head; one float64 working array w of `entries` elements.
+ *      sh_ilu0: one launch loads w from val (ilu0_load), the levels follow sh_trsv's plan -- one ungated launch per wide
+ *      level (ilu0_level: the grid sized by the level's width, at most 1024 workgroups, a grid-stride loop), one launch of
+ *      ONE workgroup per run of at most 1024 consecutive THIN levels (ilu0_run) with a workgroup barrier between levels
+ *      -- and one launch writes lu from w and counts the zero pivots (ilu0_store).  thin has sh_trsv's meaning and range:
+ *      thin == 0 gives one launch per level; thin < 0 means the default, 256; thin > 65536 is refused.  A wave takes 64
+ *      rows of a level.  A row whose share of work is at most ILU0_LANE_WORK = 256 is eliminated by its lane alone; the
+ *      others are taken one at a time by the whole wave, the lanes striding over the upper slots of row k and bisecting
+ *      row r's sorted columns; distinct j of one row k are distinct slots, so no two lanes write one word.  Both tiers run
+ *      ONE sequence of operations per slot.  One owner per value, no float atomics; w is written and re-read inside a
+ *      launch by plain stores and loads, ordered by the barrier at workgroup scope between levels and by a fence at
+ *      wavefront scope between the steps of the wave tier; no agent fence, no flag, no spin.  ILU0_LANE_WORK = 256 is the
+ *      sweep's choice among 16, 64, 256, 1024 and 4096.
+ *      Worst cases: a dense hub row against long rows k is one wave's work alone (no workgroup tier); a path (a
+ *      tridiagonal matrix) has `rows` levels of one row, and a host loop wins.
+ *      Measured on an MI355X: see DESIGN.md "6r Incomplete LU factorisation" for what was measured and what was not.
+ *
+ * sh_ilu0_graph_create: the handle is made from the host pattern alone (no sh_csr, no values), and one handle serves any
+ * number of sh_ilu0 calls with new values, one at a time: the re-factorisation of a time-stepping or Newton loop.
+ * rows == 0 or nnz == 0 give a valid handle and a call that launches nothing (*zero_pivots = rows then: every pivot is
+ * missing).  Freeing NULL is SH_OK.
+ * sh_ilu0_graph_footprint: device bytes held =
+ *     4 * (rows + 1) + 20 * rows + 12 * nnz + 16 * entries + 4 * (levels + 1) + 20.
+ * (ptr; dslot, up, the rows' work, order and level; slot_of, head and perm per entry as given; col, gstart and the
+ * float64 w per slot, gstart one more; lstart; the figures.)  sh_ilu0_graph_entries: the slots.  _levels, _max_list
+ * (the longest row, in slots), _max_width (the widest level), _missing_diag (rows without a diagonal slot),
+ * _first_missing (the smallest such row, -1 if none), _work (the look-ups of one factorisation: the sum over every
+ * lower slot (r, k) of the upper slots of row k).  sh_ilu0_graph_level: level[r] into an int32 sh_vec of >= rows elements.
+ *
+ * sh_ilu0: *launches = the launches of the call (ilu0_load where there is a slot, the plan's, ilu0_store), *runs = how
+ * many of them were runs, *levels_in_runs = the levels those held (each may be NULL; they are the plan's, known before
+ * anything is launched), *zero_pivots and *first_zero as above (each may be NULL), *total_ns device time (hipEvent) as
+ * elsewhere.  nnz elements (f32) or 2 * nnz elements of lu are written, no more.
+ * SH_EINVAL: f32 outside {0, 1}, thin > 65536 (the scalars are checked first); NULL arguments; a float64 lu not aligned
+ * to 8 bytes; val and lu overlapping without being the same float32 vector; rows < 0, nnz < 0.  SH_ESHAPE: row_ptr[0] != 0,
+ * row_ptr[rows] != nnz or a row_ptr that decreases; val shorter than nnz elements, lu shorter than nnz (f32) or 2 * nnz;
+ * level shorter than rows.  All are reported before any launch, with the buffers untouched.
+ * NOT covered: IC(0), ILU(k), ILUT, pivoting and diagonal shifts; refreshing a sh_trsv handle's values on the device (the
+ * factor goes through the host once per factorisation); a workgroup tier for hub rows; the multi-GPU driver.
+ */
+typedef struct sh_ilu0_graph sh_ilu0_graph;
+int sh_ilu0_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx,
+                         sh_ilu0_graph **out);
+int sh_ilu0_graph_free(sh_engine *e, sh_ilu0_graph *g);
+int sh_ilu0_graph_footprint(const sh_ilu0_graph *g, uint64_t *device_bytes);
+int sh_ilu0_graph_entries(const sh_ilu0_graph *g, int64_t *entries);
+int sh_ilu0_graph_levels(const sh_ilu0_graph *g, int64_t *levels);
+int sh_ilu0_graph_max_list(const sh_ilu0_graph *g, int64_t *entries);
+int sh_ilu0_graph_max_width(const sh_ilu0_graph *g, int64_t *rows);
+int sh_ilu0_graph_missing_diag(const sh_ilu0_graph *g, int64_t *rows);
+int sh_ilu0_graph_first_missing(const sh_ilu0_graph *g, int64_t *row);
+int sh_ilu0_graph_work(const sh_ilu0_graph *g, int64_t *lookups);
+int sh_ilu0_graph_level(sh_engine *e, sh_ilu0_graph *g, sh_vec *level);
+int sh_ilu0(sh_engine *e, sh_ilu0_graph *g, sh_vec *val, sh_vec *lu, int32_t f32, int32_t thin, int64_t *launches,
+            int64_t *runs, int64_t *levels_in_runs, int64_t *zero_pivots, int64_t *first_zero, uint64_t *total_ns);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,19 @@ SIGNATURES = {
     "sh_trsv_graph_first_zero": (_int, [_vp, C.POINTER(_i64)]),
     "sh_trsv_graph_level": (_int, [_vp, _vp, _vp]),
     "sh_trsv": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_u64)]),
+    "sh_ilu0_graph_create": (_int, [_vp, _i64, _i64, _vp, _vp, _pp]),
+    "sh_ilu0_graph_free": (_int, [_vp, _vp]),
+    "sh_ilu0_graph_footprint": (_int, [_vp, C.POINTER(_u64)]),
+    "sh_ilu0_graph_entries": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_ilu0_graph_levels": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_ilu0_graph_max_list": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_ilu0_graph_max_width": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_ilu0_graph_missing_diag": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_ilu0_graph_first_missing": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_ilu0_graph_work": (_int, [_vp, C.POINTER(_i64)]),
+    "sh_ilu0_graph_level": (_int, [_vp, _vp, _vp]),
+    "sh_ilu0": (_int, [_vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
+                       C.POINTER(_i64), C.POINTER(_u64)]),
 }
 
 _lib = None

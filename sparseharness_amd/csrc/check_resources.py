@@ -16,12 +16,13 @@ kernels (match_init / match_bid / match_take / match_clear / match_close, match.
 rcm_begin / rcm_sweep / rcm_claim / rcm_count / rcm_place / rcm_close / rcm_finish / rcm_total, rcm.hip.h), or one of the betweenness
 kernels (bc_in_keys / bc_out_keys / bc_init / bc_expand / bc_count / bc_close / bc_delta, bc.hip.h), or one of the triangular-solve
 kernels (trsv_flag / trsv_keys / trsv_diag / trsv_flip / trsv_seed / trsv_settle / trsv_close / trsv_rank_keys / trsv_order /
-trsv_level / trsv_run, trsv.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
+trsv_level / trsv_run, trsv.hip.h), or one of the incomplete-LU kernels (ilu0_flag / ilu0_keys / ilu0_slots / ilu0_diag /
+ilu0_work / ilu0_load / ilu0_level / ilu0_run / ilu0_store, ilu0.hip.h), uses scratch or spills VGPRs or SGPRs (see the asm-check target of the Makefile)."""
 import re
 import sys
 
 text = open(sys.argv[1]).read()
-bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core, seen_truss, seen_gcol, seen_msf, seen_match, seen_rcm, seen_bc, seen_trsv = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
+bad, seen, seen_multi, seen_bits, seen_frontier, seen_bfs, seen_sssp, seen_scc, seen_wcc, seen_tri, seen_core, seen_truss, seen_gcol, seen_msf, seen_match, seen_rcm, seen_bc, seen_trsv, seen_ilu0 = [], 0, set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set(), set()
 BFS_KERNELS = ("bfs_init", "bfs_topdown", "bfs_bottomup", "bfs_queue_from_bitmap", "bfs_decide", "bfs_parents")
 SSSP_KERNELS = ("sssp_init", "sssp_relax", "sssp_split", "sssp_decide", "sssp_preds")
 SCC_KERNELS = ("scc_init", "scc_trim", "scc_pick", "scc_seed", "scc_propagate", "scc_claim", "scc_label", "scc_decide")
@@ -34,6 +35,7 @@ RCM_KERNELS = ("rcm_init", "rcm_begin", "rcm_sweep", "rcm_claim", "rcm_count", "
 BC_KERNELS = ("bc_in_keys", "bc_out_keys", "bc_init", "bc_expand", "bc_count", "bc_close", "bc_delta")
 TRSV_KERNELS = ("trsv_flag", "trsv_keys", "trsv_diag", "trsv_flip", "trsv_seed", "trsv_settle", "trsv_close", "trsv_rank_keys",
                 "trsv_order", "trsv_level", "trsv_run")
+ILU0_KERNELS = ("ilu0_flag", "ilu0_keys", "ilu0_slots", "ilu0_diag", "ilu0_work", "ilu0_load", "ilu0_level", "ilu0_run", "ilu0_store")
 MSF_KERNELS = ("msf_weights", "msf_init", "msf_find", "msf_pick", "msf_link", "msf_jump", "msf_close", "msf_top", "msf_label")
 WCC_KERNELS = ("wcc_init", "wcc_sample", "wcc_compact", "wcc_full", "wcc_jump", "wcc_decide", "wcc_label")
 for blk in text.split("remark: Function Name: ")[1:]:
@@ -54,9 +56,12 @@ for blk in text.split("remark: Function Name: ")[1:]:
     rcm = any(k in name for k in RCM_KERNELS)
     bc = any(k in name for k in BC_KERNELS)
     trsv = any(k in name for k in TRSV_KERNELS)
-    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core and not truss and not gcol and not msf and not match and not rcm and not bc and not trsv:
+    ilu0 = any(k in name for k in ILU0_KERNELS)
+    if "spmv_tiled" not in name and not multi and not packed and not frontier and not bfs and not sssp and not scc and not wcc and not tri and not core and not truss and not gcol and not msf and not match and not rcm and not bc and not trsv and not ilu0:
         continue
-    if trsv:
+    if ilu0:
+        seen_ilu0.add(name)
+    elif trsv:
         seen_trsv.add(name)
     elif bc:
         seen_bc.add(name)
@@ -156,7 +161,10 @@ if len(seen_bc) != len(BC_KERNELS):
 # the eleven kernels of sh_trsv, under the limits of the BFS kernels
 if len(seen_trsv) != len(TRSV_KERNELS):
     sys.exit(f"expected {len(TRSV_KERNELS)} triangular-solve kernels in the remarks, found {len(seen_trsv)}: {sorted(seen_trsv)}")
+# the nine kernels of sh_ilu0, under the limits of the BFS kernels
+if len(seen_ilu0) != len(ILU0_KERNELS):
+    sys.exit(f"expected {len(ILU0_KERNELS)} incomplete-LU kernels in the remarks, found {len(seen_ilu0)}: {sorted(seen_ilu0)}")
 for b in bad:
     print("resource check FAILED: %s scratch=%d vgpr_spill=%d vgprs=%d sgpr_spill=%d" % b)
-print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle, {len(seen_core)} core-number, {len(seen_truss)} truss, {len(seen_gcol)} colouring, {len(seen_msf)} spanning-forest, {len(seen_match)} matching, {len(seen_rcm)} ordering, {len(seen_trsv)} triangular-solve and {len(seen_bc)} betweenness kernels checked, {len(bad)} offenders")
+print(f"{seen} tiled, {len(seen_multi)} multi-vector, {len(seen_bits)} packed-bit, {len(seen_frontier)} frontier, {len(seen_bfs)} BFS, {len(seen_sssp)} SSSP, {len(seen_scc)} SCC, {len(seen_wcc)} WCC, {len(seen_tri)} triangle, {len(seen_core)} core-number, {len(seen_truss)} truss, {len(seen_gcol)} colouring, {len(seen_msf)} spanning-forest, {len(seen_match)} matching, {len(seen_rcm)} ordering, {len(seen_ilu0)} incomplete-LU, {len(seen_trsv)} triangular-solve and {len(seen_bc)} betweenness kernels checked, {len(bad)} offenders")
 sys.exit(1 if bad else 0)

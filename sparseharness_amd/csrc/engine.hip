@@ -24,6 +24,7 @@
 #include "rcm.hip.h"
 #include "bc.hip.h"
 #include "trsv.hip.h"
+#include "ilu0.hip.h"
 #include "plan_common.h"
 #include "plan_host.h"
 #include "dev_arrays.h"
@@ -4352,6 +4353,251 @@ int sh_trsv(sh_engine *e, sh_trsv_graph *g, const sh_vec *b, sh_vec *x, int32_t 
   uint64_t ns = 0;
   HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
   if (total_ns) *total_ns = ns;
+  return SH_OK;
+}
+
+} // extern "C"
+
+// ---- incomplete LU factorisation without fill by level sets, in float64 (ilu0.hip.h) ----------------------------------------
+// d_ptr / d_col: the slots of every row in ascending column; d_dslot / d_up / d_rwork per row; d_gstart / d_perm: the
+// entries of every slot in the order given; d_slot_of / d_head per input position; d_w: the float64 working array of a
+// call; d_order / d_lstart the level sets and d_level the level of every row, as sh_trsv's analysis of the lower
+// triangle left them; d_fig: the figures a kernel counts.  The keys and scans of the build are temporaries.
+struct sh_ilu0_graph : GraphBase {
+  int64_t levels = 0, max_list = 0, max_width = 0, missing_diag = 0, first_missing = -1, work = 0;
+  int32_t *d_ptr = nullptr, *d_col = nullptr, *d_dslot = nullptr, *d_up = nullptr, *d_rwork = nullptr, *d_level = nullptr;
+  int32_t *d_slot_of = nullptr, *d_gstart = nullptr;
+  uint32_t *d_head = nullptr, *d_perm = nullptr, *d_order = nullptr, *d_lstart = nullptr, *d_fig = nullptr;
+  double *d_w = nullptr;
+  std::vector<uint32_t> lstart;   // levels + 1 words: what the plan of a call is made from
+};
+// sh_ilu0_graph_footprint: ptr (4 bytes per row + 1); dslot, up, rwork, order and level (4 per row each); slot_of, head
+// and perm (4 per entry as given each); col and gstart (4 per slot, gstart one more) and w (8 per slot); lstart (4 per
+// level + 1); the figures
+static_assert(ILU0_FIG_BYTES == 16, "the header states 4 * (rows + 1) + 20 * rows + 12 * nnz + 16 * entries + 4 * (levels + 1) + 20");
+static_assert(ILU0_THIN == TRSV_THIN && ILU0_THIN_MAX == TRSV_THIN_MAX, "thin has sh_trsv's meaning and range");
+static constexpr const char *ILU0_CREATE = "sh_ilu0_graph_create";
+
+// The slots and the level sets of an ILU(0) handle from the host CSR pattern.  Returns with the stream synchronised.
+static int build_ilu0(sh_engine *e, sh_ilu0_graph *g, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx) {
+  g->rows = rows; g->nnz = nnz;
+  DevArrays &own = g->dev;
+  HIP_TRY(e, own.alloc(&g->d_level, rows * 4));
+  HIP_TRY(e, own.alloc(&g->d_order, rows * 4));
+  {   // the level sets: sh_trsv's analysis of the lower triangle, unit diagonal (it reads no value: the columns stand in)
+    sh_trsv_graph t;
+    t.uplo = 0; t.unit = 1;
+    RC_TRY(build_trsv(e, &t, rows, nnz, row_ptr, col_idx, col_idx));
+    g->levels = t.levels; g->max_width = t.max_width;
+    g->lstart = t.lstart;
+    if (rows > 0) {
+      HIP_TRY(e, hipMemcpyAsync(g->d_level, t.d_level, (size_t)rows * 4, hipMemcpyDeviceToDevice, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(g->d_order, t.d_order, (size_t)rows * 4, hipMemcpyDeviceToDevice, e->stream));
+      HIP_TRY(e, hipStreamSynchronize(e->stream));
+    }
+  }   // (its lists, diagonal and control block go here)
+  DevArrays tmp;
+  int32_t *t_rp = nullptr, *t_ci = nullptr;
+  uint32_t *t_flag = nullptr, *t_pos = nullptr, *t_word = nullptr, *t_max = nullptr;
+  uint64_t *t_key = nullptr, *t_sorted = nullptr;
+  int64_t S = 0, E = 0;
+  const int bits = 32 - __builtin_clz((unsigned)std::max<int64_t>(rows - 1, 1));   // (rows <= 2^31 - 256)
+  const dim3 blk(WL_BS);
+  const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
+  HIP_TRY(e, own.alloc(&g->d_ptr, (rows + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_dslot, rows * 4));
+  HIP_TRY(e, own.alloc(&g->d_up, rows * 4));
+  HIP_TRY(e, own.alloc(&g->d_rwork, rows * 4));
+  HIP_TRY(e, own.alloc(&g->d_slot_of, nnz * 4));
+  HIP_TRY(e, own.alloc(&g->d_head, nnz * 4));
+  HIP_TRY(e, own.alloc(&g->d_perm, nnz * 4));
+  HIP_TRY(e, own.alloc(&g->d_lstart, (g->levels + 1) * 4));
+  HIP_TRY(e, own.alloc(&g->d_fig, ILU0_FIG_BYTES));
+  HIP_TRY(e, hipMemcpyAsync(g->d_lstart, g->lstart.data(), (size_t)(g->levels + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_ptr, 0, (size_t)(rows + 1) * 4, e->stream));
+  const uint32_t fig0[4] = {0u, 0xFFFFFFFFu, 0u, 0u};
+  HIP_TRY(e, hipMemcpyAsync(g->d_fig, fig0, ILU0_FIG_BYTES, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, tmp.alloc(&t_max, 4));
+  HIP_TRY(e, hipMemsetAsync(t_max, 0, 4, e->stream));
+  if (rows > 0 && nnz > 0) {
+    HIP_TRY(e, tmp.alloc(&t_rp, (rows + 1) * 4));
+    HIP_TRY(e, tmp.alloc(&t_ci, nnz * 4));
+    HIP_TRY(e, tmp.alloc(&t_flag, (nnz + 1) * 4));
+    HIP_TRY(e, tmp.alloc(&t_pos, (nnz + 1) * 4));
+    HIP_TRY(e, hipMemcpyAsync(t_rp, row_ptr, (size_t)(rows + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(t_ci, col_idx, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemsetAsync(g->d_slot_of, 0xFF, (size_t)nnz * 4, e->stream));
+    HIP_TRY(e, hipMemsetAsync(g->d_head, 0, (size_t)nnz * 4, e->stream));
+    hipLaunchKernelGGL(ilu0_flag, grid_for(nnz + 1), blk, 0, e->stream, t_ci, nnz, (int32_t)rows, t_flag);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_exclusive_sum_u32(e->stream, t_flag, t_pos, nnz + 1));
+    uint32_t n = 0;
+    HIP_TRY(e, hipMemcpy(&n, t_pos + nnz, 4, hipMemcpyDeviceToHost));
+    S = (int64_t)n;
+  }
+  if (S > 0) {   // key, one stable sort, heads, slots
+    uint32_t *t_head = nullptr, *t_hpos = nullptr;
+    HIP_TRY(e, tmp.alloc(&t_key, S * 8));
+    HIP_TRY(e, tmp.alloc(&t_sorted, S * 8));
+    HIP_TRY(e, tmp.alloc(&t_word, S * 4));
+    HIP_TRY(e, tmp.alloc(&t_head, (S + 1) * 4));
+    HIP_TRY(e, tmp.alloc(&t_hpos, (S + 1) * 4));
+    hipLaunchKernelGGL(ilu0_keys, grid_for(nnz), blk, 0, e->stream, t_rp, t_ci, t_flag, t_pos, nnz, (int32_t)rows, bits, t_key, t_word);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_sort_pairs_u64_u32(e->stream, t_key, t_sorted, t_word, g->d_perm, S, 2 * bits));
+    hipLaunchKernelGGL(wl_run_heads, grid_for(S + 1), blk, 0, e->stream, t_sorted, S, t_head);
+    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, device_exclusive_sum_u32(e->stream, t_head, t_hpos, S + 1));
+    uint32_t n = 0;
+    HIP_TRY(e, hipMemcpy(&n, t_hpos + S, 4, hipMemcpyDeviceToHost));
+    E = (int64_t)n;
+    HIP_TRY(e, own.alloc(&g->d_col, E * 4));
+    HIP_TRY(e, own.alloc(&g->d_gstart, (E + 1) * 4));
+    HIP_TRY(e, own.alloc(&g->d_w, E * 8));
+    hipLaunchKernelGGL(ilu0_slots, grid_for(S + 1), blk, 0, e->stream, (const uint64_t *)t_sorted, (const uint32_t *)t_head,
+                       (const uint32_t *)t_hpos, (const uint32_t *)g->d_perm, S, g->d_slot_of, g->d_head, t_key, g->d_gstart);
+    HIP_TRY(e, hipGetLastError());   // (t_key holds the slots' keys from here on)
+    hipLaunchKernelGGL(wl_forward_lists, grid_for(std::max(E, rows + 1)), blk, 0, e->stream, t_key, E, rows, bits, g->d_ptr, g->d_col);
+    HIP_TRY(e, hipGetLastError());
+    const dim3 mgrid((unsigned)std::max(1, std::min(e->n_cus * 4, ILU0_MAX_BLOCKS)));
+    hipLaunchKernelGGL(wl_max_len, mgrid, blk, 0, e->stream, g->d_ptr, rows, t_max);
+    HIP_TRY(e, hipGetLastError());
+  } else {
+    HIP_TRY(e, own.alloc(&g->d_col, 0));
+    HIP_TRY(e, own.alloc(&g->d_gstart, 4));
+    HIP_TRY(e, own.alloc(&g->d_w, 0));
+    HIP_TRY(e, hipMemsetAsync(g->d_gstart, 0, 4, e->stream));
+  }
+  g->edges = E;
+  if (rows > 0) {
+    hipLaunchKernelGGL(ilu0_diag, grid_for(rows), blk, 0, e->stream, (const int32_t *)g->d_ptr, (const int32_t *)g->d_col, (int32_t)rows,
+                       g->d_dslot, g->d_up, g->d_fig);
+    HIP_TRY(e, hipGetLastError());
+    hipLaunchKernelGGL(ilu0_work, grid_for(rows), blk, 0, e->stream, (const int32_t *)g->d_ptr, (const int32_t *)g->d_col,
+                       (const int32_t *)g->d_up, (int32_t)rows, g->d_rwork, (unsigned long long *)(g->d_fig + 2));
+    HIP_TRY(e, hipGetLastError());
+  }
+  uint32_t longest = 0, fig[4] = {0u, 0u, 0u, 0u};
+  HIP_TRY(e, hipMemcpyAsync(&longest, t_max, 4, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(fig, g->d_fig, ILU0_FIG_BYTES, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  g->max_list = (int64_t)longest;
+  g->missing_diag = (int64_t)fig[0];
+  g->first_missing = fig[0] ? (int64_t)fig[1] : -1;
+  g->work = (int64_t)(((uint64_t)fig[3] << 32) | (uint64_t)fig[2]);
+  return SH_OK;   // (the keys and the scans go with tmp)
+}
+
+extern "C" {
+
+int sh_ilu0_graph_create(sh_engine *e, int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, sh_ilu0_graph **out) {
+  // (the pattern alone: check_host_csr's `val` is what a matrix with entries must bring, and here that is its columns)
+  return create_graph_handle<sh_ilu0_graph>(e, ILU0_CREATE, rows, nnz, row_ptr, col_idx, col_idx, out,
+                                            [&](sh_ilu0_graph *g) -> int { return build_ilu0(e, g, rows, nnz, row_ptr, col_idx); });
+}
+
+int sh_ilu0_graph_free(sh_engine *e, sh_ilu0_graph *g) { return free_handle(e, g); }
+
+int sh_ilu0_graph_footprint(const sh_ilu0_graph *g, uint64_t *device_bytes) { return HANDLE_GET(g, device_bytes, (uint64_t)g->dev.bytes); }
+
+int sh_ilu0_graph_entries(const sh_ilu0_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->edges); }
+
+int sh_ilu0_graph_levels(const sh_ilu0_graph *g, int64_t *levels) { return HANDLE_GET(g, levels, g->levels); }
+
+int sh_ilu0_graph_max_list(const sh_ilu0_graph *g, int64_t *entries) { return HANDLE_GET(g, entries, g->max_list); }
+
+int sh_ilu0_graph_max_width(const sh_ilu0_graph *g, int64_t *rows) { return HANDLE_GET(g, rows, g->max_width); }
+
+int sh_ilu0_graph_missing_diag(const sh_ilu0_graph *g, int64_t *rows) { return HANDLE_GET(g, rows, g->missing_diag); }
+
+int sh_ilu0_graph_first_missing(const sh_ilu0_graph *g, int64_t *row) { return HANDLE_GET(g, row, g->first_missing); }
+
+int sh_ilu0_graph_work(const sh_ilu0_graph *g, int64_t *lookups) { return HANDLE_GET(g, lookups, g->work); }
+
+int sh_ilu0_graph_level(sh_engine *e, sh_ilu0_graph *g, sh_vec *level) {
+  if (!e || !g || !level)
+    return fail(e, SH_EINVAL, "sh_ilu0_graph_level: NULL argument (engine, graph or level)");
+  if (level->n < g->rows)
+    return fail(e, SH_ESHAPE, "sh_ilu0_graph_level: level is shorter than the graph's %lld rows", (long long)g->rows);
+  if (g->rows == 0)
+    return SH_OK;
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipMemcpyAsync(level->d, g->d_level, (size_t)g->rows * 4, hipMemcpyDeviceToDevice, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  return SH_OK;
+}
+
+int sh_ilu0(sh_engine *e, sh_ilu0_graph *g, sh_vec *val, sh_vec *lu, int32_t f32, int32_t thin, int64_t *launches, int64_t *runs,
+            int64_t *levels_in_runs, int64_t *zero_pivots, int64_t *first_zero, uint64_t *total_ns) {
+  // what the scalars alone decide comes first: no handle is needed to be told
+  if (f32 != 0 && f32 != 1)
+    return fail(e, SH_EINVAL, "sh_ilu0: f32 = %d, must be 0 (lu is float64) or 1 (float32)", (int)f32);
+  if (thin > ILU0_THIN_MAX)
+    return fail(e, SH_EINVAL, "sh_ilu0: thin = %d, must be at most %d (negative: the default, %d)", (int)thin, ILU0_THIN_MAX, ILU0_THIN);
+  if (!e || !g || !val || !lu)
+    return fail(e, SH_EINVAL, "sh_ilu0: NULL argument (engine, graph, val or lu)");
+  const int64_t rows = g->rows, nnz = g->nnz, per = f32 ? 1 : 2;
+  if (val->n < nnz)
+    return fail(e, SH_ESHAPE, "sh_ilu0: val holds fewer elements than the graph's %lld entries", (long long)nnz);
+  if (lu->n < per * nnz)
+    return fail(e, SH_ESHAPE, "sh_ilu0: lu holds fewer than %d elements for each of the graph's %lld entries", (int)per, (long long)nnz);
+  if (!f32 && ((uintptr_t)lu->d & 7u))
+    return fail(e, SH_EINVAL, "sh_ilu0: lu is not aligned to 8 bytes");
+  if (nnz > 0 && (val->d != lu->d || !f32)) {
+    const char *pv = (const char *)val->d, *pl = (const char *)lu->d;
+    if (pv < pl + nnz * 4 * per && pl < pv + nnz * 4)
+      return fail(e, SH_EINVAL, "sh_ilu0: val and lu overlap without being the same float32 vector");
+  }
+  if (thin < 0) thin = ILU0_THIN;
+  std::vector<TrsvLaunch> plan;
+  trsv_plan(g->lstart, thin, ILU0_RUN, plan);
+  const bool any = rows > 0 && nnz > 0;   // (without entries every lu is nothing and every pivot +0.0: the host says so)
+  if (!any) plan.clear();
+  int64_t n_runs = 0, in_runs = 0;
+  for (const TrsvLaunch &l : plan) { n_runs += l.n > 0; in_runs += l.n; }
+  if (launches) *launches = any ? (int64_t)plan.size() + (g->edges > 0) + 1 : 0;   // (ilu0_load, the plan, ilu0_store)
+  if (runs) *runs = n_runs;
+  if (levels_in_runs) *levels_in_runs = in_runs;
+  if (total_ns) *total_ns = 0;
+  if (!any) {
+    if (zero_pivots) *zero_pivots = rows;
+    if (first_zero) *first_zero = rows > 0 ? 0 : -1;
+    return SH_OK;
+  }
+  HIP_TRY(e, hipSetDevice(e->device));
+  const Ilu0Lists T{g->d_ptr, g->d_col, g->d_dslot, g->d_up, g->d_rwork, g->d_order, g->d_w};
+  const dim3 block(WL_BS);
+  const auto grid_for = [](int64_t n) { return dim3((unsigned)((n + WL_BS - 1) / WL_BS)); };
+  HIP_TRY(e, hipMemsetAsync(g->d_fig, 0, 4, e->stream));
+  HIP_TRY(e, hipMemsetAsync(g->d_fig + 1, 0xFF, 4, e->stream));
+  HIP_TRY(e, hipEventRecord(e->ev0, e->stream));
+  if (g->edges > 0) {
+    hipLaunchKernelGGL(ilu0_load, grid_for(g->edges), block, 0, e->stream, (const int32_t *)g->d_gstart, (const uint32_t *)g->d_perm,
+                       (const float *)val->d, g->edges, g->d_w);
+    HIP_TRY(e, hipGetLastError());
+  }
+  for (const TrsvLaunch &l : plan) {
+    if (l.n > 0) {
+      hipLaunchKernelGGL(ilu0_run, dim3(1), block, 0, e->stream, l.L0, l.n, (const uint32_t *)g->d_lstart, T);
+    } else {
+      const uint32_t a = g->lstart[l.L0], z = g->lstart[l.L0 + 1];
+      const dim3 grid((unsigned)std::min<int64_t>(((int64_t)(z - a) + WL_BS - 1) / WL_BS, ILU0_MAX_BLOCKS));
+      hipLaunchKernelGGL(ilu0_level, grid, block, 0, e->stream, a, z, T);
+    }
+    HIP_TRY(e, hipGetLastError());
+  }
+  hipLaunchKernelGGL(ilu0_store, grid_for(std::max(nnz, rows)), block, 0, e->stream, (const int32_t *)g->d_slot_of,
+                     (const uint32_t *)g->d_head, (const int32_t *)g->d_dslot, (const double *)g->d_w, nnz, (int32_t)rows, f32, lu->d, g->d_fig);
+  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, hipEventRecord(e->ev1, e->stream));
+  uint32_t fig[2] = {0u, 0u};
+  HIP_TRY(e, hipMemcpyAsync(fig, g->d_fig, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(e, hipStreamSynchronize(e->stream));
+  uint64_t ns = 0;
+  HIP_TRY(e, ms_between(e->ev0, e->ev1, &ns));
+  if (total_ns) *total_ns = ns;
+  if (zero_pivots) *zero_pivots = (int64_t)fig[0];
+  if (first_zero) *first_zero = fig[0] ? (int64_t)fig[1] : -1;
   return SH_OK;
 }
 

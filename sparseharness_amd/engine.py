@@ -653,6 +653,28 @@ class Engine:
                                      C.byref(runs), C.byref(in_runs), C.byref(total)))
         return launches.value, runs.value, in_runs.value, total.value
 
+    # ---- incomplete LU factorisation without fill by level sets, float64, one fixed order
+    def ilu0_graph(self, row_ptr, col_idx):
+        """The handle Engine.ilu0 needs (ilu0.Ilu0Graph), from the CSR pattern of a square matrix alone: no values."""
+        from .ilu0 import Ilu0Graph   # (ilu0.py imports this module)
+        row_ptr, col_idx, _ = _csr_args(row_ptr, col_idx, col_idx)
+        h = C.c_void_p()
+        self._chk(abi.load().sh_ilu0_graph_create(self.h, len(row_ptr) - 1, len(col_idx), _ptr(row_ptr), _ptr(col_idx), C.byref(h)))
+        return Ilu0Graph(self, h, len(row_ptr) - 1)
+
+    def ilu0(self, G, val, lu, f32=1, thin=None):
+        """-> (launches, runs, levels_in_runs, zero_pivots, first_zero, total_ns): the launches of the call, how many of
+        them were runs of thin levels inside one workgroup, the levels those held, the rows whose pivot == 0.0 (a missing
+        diagonal counts, a NaN does not), the smallest of them or -1, device ns.  val: a float32 vector of >= nnz elements
+        in the order of the entries; lu: >= nnz float32 (f32 = 1; may be val), or >= 2 * nnz 4-byte elements (nnz float64,
+        8-byte aligned).  lu[p] = the factor's value at the first entry of its (row, column) group, +0.0 elsewhere: with
+        the handle's row_ptr / col_idx it is L (trsv_graph(uplo=0, unit=1)) and U (uplo=1, unit=0) in one matrix.  thin:
+        as Engine.trsv's.  lu does not depend on thin."""
+        launches, runs, in_runs, zero, first, total = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_uint64()
+        self._chk(abi.load().sh_ilu0(self.h, G.h, val.h, lu.h, f32, -1 if thin is None else int(thin), C.byref(launches),
+                                     C.byref(runs), C.byref(in_runs), C.byref(zero), C.byref(first), C.byref(total)))
+        return launches.value, runs.value, in_runs.value, zero.value, first.value, total.value
+
     # ---- several vectors per launch (element i of vector j at i * width + j; the matrix uploaded with plan=1)
     def spmm(self, semiring, A, X, Y, alpha, beta, Out, width, timed=False):
         dt = elem_dtype(semiring)

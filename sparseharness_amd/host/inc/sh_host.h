@@ -131,6 +131,19 @@ int sh_trsv_solve(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32
  * beyond); 1: the one-lane formula where n <= 8; 2: the pieces for any n.  The tiers are one function. */
 double sh_trsv_list_sum(const double *t, int64_t n, int32_t tier);
 
+/* The incomplete LU factorisation without fill, ILU(0), of a square CSR matrix by the row-wise IKJ recurrence
+ * (single-threaded): the gold for sh_ilu0.  The slots of row r are the distinct columns 0 <= c < rows among its entries;
+ * a[r, c] = its entries in the order given, widened to float64 and added left to right from +0.0; rows need not be
+ * sorted and columns out of range take no part.  Every product and every subtraction is rounded once, in the order that
+ * include/sparseharness_hip.h fixes, so lu equals sh_ilu0's bit for bit.  lu is in the positions of the entries: the
+ * slot's value at the first entry of its (r, c) group, +0.0 at every other position; f32 1: nnz floats, rounded once on
+ * the way out; 0: nnz doubles.  val and lu may be the same array when f32.  level[r] (rows words, may be NULL) = 0 for a
+ * row without a lower slot, else 1 + the largest level among its lower slots.  figures (9 words, may be NULL): slots,
+ * levels, the longest row in slots, the widest level, the rows without a diagonal slot, the smallest such row or -1, the
+ * look-ups (work), the rows whose pivot == 0.0, the smallest such row or -1.  Return 0, -1 bad argument. */
+int sh_ilu0_factor(int64_t rows, int64_t nnz, const int32_t *row_ptr, const int32_t *col_idx, const void *val, int32_t f32, void *lu,
+                   int32_t *level, int64_t *figures);
+
 /* MatrixMarket -> CSR with the reference's semantics (SparseMatrix<T>,
  * src/sparse_matrix.cpp:11-119): see host/inc/sparse_matrix.h.  elem_is_int
  * selects SparseMatrix<int> (BFS) instead of SparseMatrix<float>.

@@ -3,7 +3,7 @@ loader (host/src/sparse_matrix.cpp), the seeded synthetic generators
 (host/src/synth.cpp) that define the benchmark configs of BASELINE.json, and the
 host golds of sh_scc (host/src/scc_labels.cpp), sh_wcc (host/src/wcc_labels.cpp), sh_tri
 (host/src/triangle_counts.cpp), sh_core (host/src/core_numbers.cpp), sh_truss (host/src/truss_numbers.cpp), sh_color
-(host/src/greedy_colors.cpp), sh_msf (host/src/msf_edges.cpp), sh_match (host/src/greedy_matching.cpp), sh_rcm (host/src/rcm_order.cpp), sh_bc (host/src/bc_scores.cpp) and sh_trsv (host/src/trsv_solve.cpp)."""
+(host/src/greedy_colors.cpp), sh_msf (host/src/msf_edges.cpp), sh_match (host/src/greedy_matching.cpp), sh_rcm (host/src/rcm_order.cpp), sh_bc (host/src/bc_scores.cpp), sh_trsv (host/src/trsv_solve.cpp) and sh_ilu0 (host/src/ilu0_factor.cpp)."""
 import ctypes as C
 import os
 import subprocess
@@ -44,6 +44,7 @@ SIGNATURES = {
     "sh_bc_scores": (C.c_int, _csr + [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sh_trsv_solve": (C.c_int, _csr + [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "sh_trsv_list_sum": (C.c_double, [_vp, _i64, C.c_int32]),
+    "sh_ilu0_factor": (C.c_int, _csr + [C.c_int32, _vp, _vp, _vp]),
     "sh_mm_load": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.POINTER(_HostCsr)]),
     "sh_mm_load_ex": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(_HostCsr)]),
     "sh_host_csr_release": (None, [C.POINTER(_HostCsr)]),
@@ -280,6 +281,21 @@ def trsv_list_sum(terms, tier=0):
     terms; 2: the pieces)."""
     t = np.ascontiguousarray(terms, np.float64)
     return float(load().sh_trsv_list_sum(_p(t), len(t), int(tier)))
+
+
+def ilu0_factor(row_ptr, col_idx, val, f32=1):
+    """-> (lu, level, figures): lu (float32 when f32, else float64) = the ILU(0) factor of the square matrix in the
+    positions of its entries (Engine.ilu0's lu: the slot's value at the first entry of its (r, c) group, +0.0 at a later
+    one or at a column outside the matrix), level[r] (int32) = 0 for a row without a lower slot, else 1 + the largest level
+    among its lower slots, and figures = dict(entries, levels, max_list, max_width, missing_diag, first_missing, work,
+    zero_pivots, first_zero) (the getters of ilu0.Ilu0Graph and the figures of a call), by the row-wise IKJ recurrence on
+    the host in the order include/sparseharness_hip.h fixes: the results are sh_ilu0's bit for bit."""
+    n = len(row_ptr) - 1
+    lu = np.zeros(max(len(col_idx), 1), np.float32 if f32 else np.float64)
+    level, fig = np.zeros(max(n, 1), np.int32), np.zeros(9, np.int64)
+    _gold("sh_ilu0_factor", row_ptr, col_idx, val, int(f32), _p(lu), _p(level), _p(fig))
+    names = ("entries", "levels", "max_list", "max_width", "missing_diag", "first_missing", "work", "zero_pivots", "first_zero")
+    return lu[:len(col_idx)], level[:n], dict(zip(names, (int(v) for v in fig)))
 
 
 NORM_NONE, NORM_PAGERANK, NORM_SCC = 0, 1, 2
